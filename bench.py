@@ -1,10 +1,16 @@
 #!/usr/bin/env python3
-"""bench.py -- skinned vertices/sec of the deformation hot path on MI355X, with the HBM roofline of
-the dominant kernel and the reference CPU path timed beside it.
+"""bench.py -- skinned vertices/sec of the deformation hot path on MI355X; with --full also the HBM
+roofline of the dominant kernel and the reference CPU path timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (value, ms_per_step and the
+step-level roofline derived from them).  --full adds every other figure: the cold start, the deform
+kernel alone, a changing morph state, per-kernel events, copy / fill / store ceilings, plainly
+allocated outputs, the CPU baseline and the other BASELINE workloads.  --dump-outputs DIR writes what
+the last timed step computed, for comparing two builds output for output.
 
 Workload (BASELINE.json configs[2]/[3], SURVEY.md section 8d "config 3/4"): a crowd of 1024 instances PER GPU
 of the synthetic 50 000-vertex / 300-bone / 200-morph model, per-instance bone palettes resident in
@@ -15,7 +21,7 @@ with no data-path collective ("scaling": "weak"); torch.distributed (gloo) is us
 start/stop barriers and the max-over-ranks reduction of the elapsed time.
 
 The config-2 (single 50k model, latency) and config-5 (256k verts, fp16 positions) figures ride
-along under "other_workloads"; they are not the headline value.
+along under "other_workloads" with --full; they are not the headline value.
 """
 from __future__ import annotations
 
@@ -31,6 +37,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3 TB/s measured copy
+DUMP_BUDGET = 48 << 20     # bytes --dump-outputs writes at most
+DUMP_SEED = 20240601       # fixes which instances --dump-outputs samples
 
 
 def algorithmic_bytes_config3(nv, nb, nm, ne, ni, n1, n2, n4):
@@ -86,8 +94,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--instances-per-gpu", type=int, default=1024)
     ap.add_argument("--layout", choices=["soa", "vertex32"], default="soa")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else this benchmark measures: the cold figure, the deform kernel alone, "
+                         "a changing morph state, per-kernel events, copy / fill / store ceilings, plainly allocated outputs, the "
+                         "recorded PMC traffic, the CPU baseline and the other BASELINE workloads (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32): the output arrays "
+                         "of a fixed, seeded sample of the instances, at most %d MiB in all" % (DUMP_BUDGET >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out the other BASELINE workloads")
     ap.add_argument("--plain-alloc", action="store_true", help="plain hipMalloc for the output arrays")
     ap.add_argument("--shop-alloc", type=int, default=128, metavar="TRIES",
                     help="let mmdx_crowd_output_alloc try up to TRIES placements of the output arrays (bounded: ~5 ms per try, "
@@ -96,6 +111,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous, sharding and the JSON line only -- no GPU work (CPU test of the N>1 plumbing)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # N > 1 without a launcher: decided before the product library is loaded or any HIP call is made.
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -198,17 +215,19 @@ def main():
     # measurement taken cold reports the transient, not the sustained rate.  Untimed batches of 20 steps until two
     # consecutive batches agree within 1.5 % and stop improving (at most 600 steps, ~0.15 s), then the contract's
     # W warm-up steps and the K timed steps.
-    # ---- cold figure first: the contract's W warm-up steps and K timed steps taken right after set-up, BEFORE any settle
-    # batch -- what a caller gets who starts stepping at once (reported as cold_ms_per_step next to the headline) ------------
-    for _ in range(args.warmup):
-        step()
-    device_synchronize()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    device_synchronize()
-    cold_ms = rv.max(time.perf_counter() - t0) / args.steps * 1e3
+    # ---- cold figure first (--full): the contract's W warm-up steps and K timed steps taken right after set-up, BEFORE any
+    # settle batch -- what a caller gets who starts stepping at once (reported as cold_ms_per_step next to the headline) -----
+    cold_ms = None
+    if args.full:
+        for _ in range(args.warmup):
+            step()
+        device_synchronize()
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        device_synchronize()
+        cold_ms = rv.max(time.perf_counter() - t0) / args.steps * 1e3
     settle_batches = []
     if not args.no_settle:
         for _ in range(30):
@@ -243,27 +262,10 @@ def main():
     elapsed = time.perf_counter() - t0
     barrier()
     elapsed = rv.max(elapsed)
-    # ---- the dominant kernel, live: K back-to-back launches of the deform kernel ALONE between two HIP events on
-    # its stream (MMDX_MORPH_UNCHANGED: the shared morph state did not change, the morph pass is skipped) -- the
-    # kernel's duration in an uninstrumented stream, which is what a rocprofv3 kernel trace of this run shows too.
-    # Three batches of K, the median is reported (one batch now and then catches a clock or placement hiccup: 0.2275 vs 0.2185-0.2198 ms
-    # on otherwise identical runs); all three are kept in roofline.kernel_only_batches_ms.
     pass_stats = dm.morph_pass_stats()      # (walks, device-side skips, host-side skips) up to the end of the timed region
-    kernel_batches = [timed_batch(kernel_only_step, args.steps) for _ in range(3)]
-    kernel_ms = sorted(kernel_batches)[1]
-    # ---- the same K steps with a morph state that CHANGES every step (two rate sets taking turns): flatten + walk + deform -----
-    timed_batch(changing_step, 5)
-    changing_ms = sorted(timed_batch(changing_step, args.steps) for _ in range(3))[1]
-    step()                                  # leave the headline's morph state behind
-    # ---- the old figure, kept as a named extra: events around every kernel of K more steps ---------------------
-    dm.profile_enable(True)
-    for _ in range(args.steps):
-        step()
-    ncalls, skin_total, morph_total = dm.profile_collect()
-    dm.profile_enable(False)
-    skin_avg = skin_total / ncalls
-    morph_avg = morph_total / ncalls
-
+    # ---- what the last timed step computed, copied out before anything else writes the output arrays ----------------------
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_a, d_b, layout, ni, model.nv, rank, world)
     # cached non-temporal stores into arrays the placement probe found fast, write-through stores otherwise (mmdx.h,
     # MMDX_OUT_STORES_*): what the library chose for these arrays
     placement = dict(placement, store_policy=dm.last_store_policy())
@@ -280,26 +282,20 @@ def main():
     if layout == api.OUT_VERTEX32:
         deform_bytes += ni * model.nv * 8 + model.nv * 8        # 32 B out + uv in
         step_bytes += ni * model.nv * 8 + model.nv * 8
-    achieved = deform_bytes / (kernel_ms * 1e-3) / 1e9
 
     result = {
         "metric": "skinned vertices/sec (instance-sharded crowd); achieved HBM GB/s vs roofline",
         "value": value, "unit": "vertices/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": ms_per_step, "cold_ms_per_step": cold_ms, "plain_alloc_ms_per_step": None,
         "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
         "config": {"workload": "config3: 1024-instance crowd per GPU of the 50k-vert/300-bone/200-morph "
                                "model, shared morph state, per-instance palettes in HBM",
                    "instances_per_gpu": ni, "vertices": model.nv, "bones": model.nb, "morphs": model.nm,
                    "morph_entries": int(info.n_entries), "out_layout": args.layout,
                    "sharding": f"instances/{world} ranks, no collective"},
-        "roofline": {"bound": "hbm", "kernel": "deform_kernel (skinning + write-out)",
-                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                     "algorithmic_bytes_per_launch": deform_bytes, "avg_kernel_ms": kernel_ms,
-                     "avg_kernel_ms_how": f"median of 3 batches of {args.steps} back-to-back launches of the kernel alone, each batch "
-                                          "between two HIP events on its stream (rank 0)",
-                     "kernel_only_batches_ms": [round(x, 5) for x in kernel_batches],
+        # the step-level figures come from the timed steps alone; the kernel-level ones need runs of their own (--full)
+        "roofline": {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      # the whole step (morph pass + deform kernel) against the same peak, from the driver-checkable
                      # ms_per_step: kernel and step figures must tell one story
                      "step_algorithmic_bytes": step_bytes,
@@ -311,119 +307,148 @@ def main():
                                     "pass launched every step and skipped its walk")),
                      "morph_pass_stats_at_end_of_timed_region": {"walks": pass_stats[0], "device_skips": pass_stats[1],
                                                                  "host_skips": pass_stats[2]},
-                     # the morph state changes on every step (two rate sets in turn): flatten + walk + deform, median of 3 x K
-                     "changing_morph_state": {"ms_per_step": changing_ms, "step_algorithmic_bytes": walk_step_bytes,
-                                              "step_frac": walk_step_bytes / (changing_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                     # W warm-up + K steps right after set-up, no settle batches in front (max over ranks, wall clock)
-                     "cold": {"ms_per_step": cold_ms, "step_frac": step_bytes / (cold_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                     # per-kernel events on every launch (round 1's headline; flatters the kernel, see above)
-                     "event_bracketed_kernel_ms": skin_avg, "event_bracketed_morph_pass_ms": morph_avg,
-                     "event_bracketed_frac": deform_bytes / (skin_avg * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     # deform-kernel launches after the timed region, oldest first (trace post-processing)
-                     "trace_segments": [["timed", args.steps], ["kernel_only", args.steps], ["kernel_only", args.steps],
-                                        ["kernel_only", args.steps], ["changing_morph_state", 5 + 3 * args.steps + 1],
-                                        ["event_bracketed", args.steps]],
+                     # deform-kernel launches from the timed region on, oldest first (trace post-processing)
+                     "trace_segments": [["timed", args.steps]],
                      "output_placement": placement,
                      "kernel_source_sha": kernel_source_sha(),
                      # the binary's own word on what it was built from, next to the hash of the tree (bench refuses a mismatch)
                      "library_source_sha": stamp["library_source_sha"], "tree_source_sha": stamp["tree_source_sha"],
                      "settle_batches_step_ms": [round(x, 4) for x in settle_batches]},
     }
-
-    if world > 1:       # every rank placed its own output arrays: how many tries each took and what it got
-        tries = rv.gather_u64([int(placement.get("tries", 0)), int(placement.get("store_GBs", 0.0))])
-        if rank == 0:
-            result["roofline"]["output_placement_per_rank"] = tries
     if rank == 0:
-        result["roofline"].update(pmc_traffic(layout == api.OUT_SOA, ni, model.nv, placement.get("store_policy", "nt")))
         result["device"] = device_name(local_rank % ndev)
-        # practical ceilings on this box (SURVEY.md section 8d asks for them next to the spec peak)
-        nb_ceiling = 1 << 30
-        src, dst = DeviceBuffer(nb_ceiling), DeviceBuffer(nb_ceiling)
-        src.memset(1)
-        import ctypes as C
-        ms = C.c_float(0)
-        api.check(api.lib().mmdx_bench_copy(dst.ptr, src.ptr, nb_ceiling, 10, C.byref(ms)))
-        result["roofline"]["measured_copy_GBs"] = 2 * nb_ceiling / (ms.value * 1e-3) / 1e9
-        api.check(api.lib().mmdx_bench_fill(dst.ptr, nb_ceiling, 10, C.byref(ms)))
-        result["roofline"]["measured_fill_GBs"] = nb_ceiling / (ms.value * 1e-3) / 1e9
-        src.free()
-        dst.free()
-        if layout == api.OUT_SOA and model.nv % 4 == 0:
-            api.check(api.lib().mmdx_bench_store_pattern(d_a.ptr, d_b.ptr, model.nv, ni, 10, C.byref(ms)))
-            result["roofline"]["measured_store_pattern_GBs"] = ni * model.nv * 24 / (ms.value * 1e-3) / 1e9
-            step()      # leave real results in the output buffers
-            result["roofline"]["trace_segments"].append(["trailing", 1])
-        # What a caller sees who simply hipMallocs the output arrays (first placement, no probing): the same K steps
-        # into plainly allocated arrays, next to the headline's placement-probed ones.  On MI355X about six placements
-        # in seven store ~25 % slower for this two-array pattern; the headline says how many
-        # tries its placement took.
-        if not args.plain_alloc and placement.get("tries", 1) >= 1:
-            p_a, p_b, p_info = dm.alloc_outputs(layout, ni, 1)
-
-            def plain_step():
-                # (no hint: these arrays were not probed, the library's default for unknown arrays applies)
-                dm.deform_batched_raw(ni, d_w.ptr, d_pal.ptr, p_a.ptr, p_b.ptr if p_b else None, layout,
-                                      base_flags | p_info.get("store_flags", 0), pos_scale)
-            timed_batch(plain_step, 20)
-            pl_ms = timed_batch(plain_step, args.steps)
-            pl = {"ms_per_step": pl_ms, "vertices_per_s": ni * model.nv / (pl_ms * 1e-3),
-                  "step_frac": step_bytes / (pl_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "store_policy": dm.last_store_policy()}
+    if args.full:
+        # ---- the dominant kernel, live: K back-to-back launches of the deform kernel ALONE between two HIP events on
+        # its stream (MMDX_MORPH_UNCHANGED: the shared morph state did not change, the morph pass is skipped) -- the
+        # kernel's duration in an uninstrumented stream, which is what a rocprofv3 kernel trace of this run shows too.
+        # Three batches of K, the median is reported (one batch now and then catches a clock or placement hiccup: 0.2275 vs
+        # 0.2185-0.2198 ms on otherwise identical runs); all three are kept in roofline.kernel_only_batches_ms.
+        kernel_batches = [timed_batch(kernel_only_step, args.steps) for _ in range(3)]
+        kernel_ms = sorted(kernel_batches)[1]
+        # ---- the same K steps with a morph state that CHANGES every step (two rate sets taking turns): flatten + walk + deform
+        timed_batch(changing_step, 5)
+        changing_ms = sorted(timed_batch(changing_step, args.steps) for _ in range(3))[1]
+        step()                                  # leave the headline's morph state behind
+        # ---- the old figure, kept as a named extra: events around every kernel of K more steps -----------------
+        dm.profile_enable(True)
+        for _ in range(args.steps):
+            step()
+        ncalls, skin_total, morph_total = dm.profile_collect()
+        dm.profile_enable(False)
+        skin_avg = skin_total / ncalls
+        morph_avg = morph_total / ncalls
+        achieved = deform_bytes / (kernel_ms * 1e-3) / 1e9
+        result["roofline"].update({
+            "kernel": "deform_kernel (skinning + write-out)",
+            "achieved": achieved, "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+            "algorithmic_bytes_per_launch": deform_bytes, "avg_kernel_ms": kernel_ms,
+            "avg_kernel_ms_how": f"median of 3 batches of {args.steps} back-to-back launches of the kernel alone, each batch "
+                                 "between two HIP events on its stream (rank 0)",
+            "kernel_only_batches_ms": [round(x, 5) for x in kernel_batches],
+            # the morph state changes on every step (two rate sets in turn): flatten + walk + deform, median of 3 x K
+            "changing_morph_state": {"ms_per_step": changing_ms, "step_algorithmic_bytes": walk_step_bytes,
+                                     "step_frac": walk_step_bytes / (changing_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
+            # W warm-up + K steps right after set-up, no settle batches in front (max over ranks, wall clock)
+            "cold": {"ms_per_step": cold_ms, "step_frac": step_bytes / (cold_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
+            # per-kernel events on every launch (round 1's headline; flatters the kernel, see above)
+            "event_bracketed_kernel_ms": skin_avg, "event_bracketed_morph_pass_ms": morph_avg,
+            "event_bracketed_frac": deform_bytes / (skin_avg * 1e-3) / 1e9 / HBM_PEAK_GBS})
+        result["roofline"]["trace_segments"] += [["kernel_only", args.steps], ["kernel_only", args.steps],
+                                                 ["kernel_only", args.steps], ["changing_morph_state", 5 + 3 * args.steps + 1],
+                                                 ["event_bracketed", args.steps]]
+        if world > 1:       # every rank placed its own output arrays: how many tries each took and what it got
+            tries = rv.gather_u64([int(placement.get("tries", 0)), int(placement.get("store_GBs", 0.0))])
+            if rank == 0:
+                result["roofline"]["output_placement_per_rank"] = tries
+        if rank == 0:
+            result["roofline"].update(pmc_traffic(layout == api.OUT_SOA, ni, model.nv, placement.get("store_policy", "nt")))
+            # practical ceilings of this device (SURVEY.md section 8d asks for them next to the spec peak)
+            nb_ceiling = 1 << 30
+            src, dst = DeviceBuffer(nb_ceiling), DeviceBuffer(nb_ceiling)
+            src.memset(1)
+            import ctypes as C
+            ms = C.c_float(0)
+            api.check(api.lib().mmdx_bench_copy(dst.ptr, src.ptr, nb_ceiling, 10, C.byref(ms)))
+            result["roofline"]["measured_copy_GBs"] = 2 * nb_ceiling / (ms.value * 1e-3) / 1e9
+            api.check(api.lib().mmdx_bench_fill(dst.ptr, nb_ceiling, 10, C.byref(ms)))
+            result["roofline"]["measured_fill_GBs"] = nb_ceiling / (ms.value * 1e-3) / 1e9
+            src.free()
+            dst.free()
             if layout == api.OUT_SOA and model.nv % 4 == 0:
-                api.check(api.lib().mmdx_bench_store_pattern(p_a.ptr, p_b.ptr, model.nv, ni, 10, C.byref(ms)))
-                pl["store_pattern_GBs"] = ni * model.nv * 24 / (ms.value * 1e-3) / 1e9
-            result["roofline"]["plain_alloc"] = pl
-            result["plain_alloc_ms_per_step"] = pl_ms
-            result["roofline"]["trace_segments"].append(["plain_alloc", 20 + args.steps])
-            p_a.free()
-            if p_b:
-                p_b.free()
+                api.check(api.lib().mmdx_bench_store_pattern(d_a.ptr, d_b.ptr, model.nv, ni, 10, C.byref(ms)))
+                result["roofline"]["measured_store_pattern_GBs"] = ni * model.nv * 24 / (ms.value * 1e-3) / 1e9
+                step()      # leave real results in the output buffers
+                result["roofline"]["trace_segments"].append(["trailing", 1])
+            # What a caller sees who simply hipMallocs the output arrays (first placement, no probing): the same K steps
+            # into plainly allocated arrays, next to the headline's placement-probed ones.  On MI355X about six placements
+            # in seven store ~25 % slower for this two-array pattern; the headline says how many
+            # tries its placement took.
+            if not args.plain_alloc and placement.get("tries", 1) >= 1:
+                p_a, p_b, p_info = dm.alloc_outputs(layout, ni, 1)
 
-    # ---- CPU baseline: rank 0, N=1 only ------------------------------------------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        from oracle.pyoracle import Oracle, Reference, reference_available   # checker, CPU leg only
-        reps = 24                                   # ~11 s of single-thread CPU work
-        if reference_available():
-            ref = Reference(model, normalize=True)
-            secs = sum(ref.time_crowd(rates, pals) for _ in range(reps))
-            ref.close()
-            kind = "reference"
-            what = "libmmd Poser (g++ -O2): 1 morph pass + 1024 x {palette inject, Deform()}"
-        else:
-            orc = Oracle()
-            secs = sum(orc.time_crowd(model, rates, pals) for _ in range(reps))
-            kind = "port"
-            what = "C restatement (gcc -O2): 1 morph pass + 1024 x skinning pass"
-        result["cpu_baseline"] = {"value": reps * ni * model.nv / secs, "unit": "vertices/s", "cores": 1,
-                                  "kind": kind,
-                                  "sample": f"{reps} x the full config-3 crowd step ({what}), "
-                                            f"{secs:.1f} s of CPU work, single thread as the reference runs"}
-        # The same baseline on all host cores (one independent Poser per thread, the crowd's
-        # instances split among them) -- an extra, the contract's cpu_baseline stays the single-thread figure.
-        try:
+                def plain_step():
+                    # (no hint: these arrays were not probed, the library's default for unknown arrays applies)
+                    dm.deform_batched_raw(ni, d_w.ptr, d_pal.ptr, p_a.ptr, p_b.ptr if p_b else None, layout,
+                                          base_flags | p_info.get("store_flags", 0), pos_scale)
+                timed_batch(plain_step, 20)
+                pl_ms = timed_batch(plain_step, args.steps)
+                pl = {"ms_per_step": pl_ms, "vertices_per_s": ni * model.nv / (pl_ms * 1e-3),
+                      "step_frac": step_bytes / (pl_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "store_policy": dm.last_store_policy()}
+                if layout == api.OUT_SOA and model.nv % 4 == 0:
+                    api.check(api.lib().mmdx_bench_store_pattern(p_a.ptr, p_b.ptr, model.nv, ni, 10, C.byref(ms)))
+                    pl["store_pattern_GBs"] = ni * model.nv * 24 / (ms.value * 1e-3) / 1e9
+                result["roofline"]["plain_alloc"] = pl
+                result["plain_alloc_ms_per_step"] = pl_ms
+                result["roofline"]["trace_segments"].append(["plain_alloc", 20 + args.steps])
+                p_a.free()
+                if p_b:
+                    p_b.free()
+
+        # ---- CPU baseline: rank 0, N=1 only ------------------------------------------------------------
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            from oracle.pyoracle import Oracle, Reference, reference_available   # checker, CPU leg only
+            reps = 24                                   # ~11 s of single-thread CPU work
             if reference_available():
-                import concurrent.futures as cf
-                import time as _t
-                cores = min(len(os.sched_getaffinity(0)), 16)
-                per = ni // cores
-                with cf.ThreadPoolExecutor(cores) as ex:          # ctypes releases the GIL inside libmmd
-                    refs = list(ex.map(lambda _: Reference(model, normalize=True), range(cores)))
-                    t0 = _t.perf_counter()
-                    list(ex.map(lambda k: [refs[k].time_crowd(rates, pals[k * per:(k + 1) * per]) for _ in range(40)],
-                                range(cores)))
-                    wall = _t.perf_counter() - t0
-                for r_ in refs:
-                    r_.close()
-                result["cpu_baseline_all_cores"] = {
-                    "value": 40 * cores * per * model.nv / wall, "unit": "vertices/s", "cores": cores, "kind": "reference",
-                    "sample": f"40 x the config-3 crowd step, {cores} threads x {per} instances each with its own libmmd "
-                              f"Poser (every thread repeats the shared morph pass), {wall:.1f} s wall"}
-        except Exception as e:                               # pragma: no cover - reporting only
-            result["cpu_baseline_all_cores"] = {"error": repr(e)}
+                ref = Reference(model, normalize=True)
+                secs = sum(ref.time_crowd(rates, pals) for _ in range(reps))
+                ref.close()
+                kind = "reference"
+                what = "libmmd Poser (g++ -O2): 1 morph pass + 1024 x {palette inject, Deform()}"
+            else:
+                orc = Oracle()
+                secs = sum(orc.time_crowd(model, rates, pals) for _ in range(reps))
+                kind = "port"
+                what = "C restatement (gcc -O2): 1 morph pass + 1024 x skinning pass"
+            result["cpu_baseline"] = {"value": reps * ni * model.nv / secs, "unit": "vertices/s", "cores": 1,
+                                      "kind": kind,
+                                      "sample": f"{reps} x the full config-3 crowd step ({what}), "
+                                                f"{secs:.1f} s of CPU work, single thread as the reference runs"}
+            # The same baseline on all host cores (one independent Poser per thread, the crowd's
+            # instances split among them) -- an extra, the contract's cpu_baseline stays the single-thread figure.
+            try:
+                if reference_available():
+                    import concurrent.futures as cf
+                    import time as _t
+                    cores = min(len(os.sched_getaffinity(0)), 16)
+                    per = ni // cores
+                    with cf.ThreadPoolExecutor(cores) as ex:          # ctypes releases the GIL inside libmmd
+                        refs = list(ex.map(lambda _: Reference(model, normalize=True), range(cores)))
+                        t0 = _t.perf_counter()
+                        list(ex.map(lambda k: [refs[k].time_crowd(rates, pals[k * per:(k + 1) * per]) for _ in range(40)],
+                                    range(cores)))
+                        wall = _t.perf_counter() - t0
+                    for r_ in refs:
+                        r_.close()
+                    result["cpu_baseline_all_cores"] = {
+                        "value": 40 * cores * per * model.nv / wall, "unit": "vertices/s", "cores": cores, "kind": "reference",
+                        "sample": f"40 x the config-3 crowd step, {cores} threads x {per} instances each with its own libmmd "
+                                  f"Poser (every thread repeats the shared morph pass), {wall:.1f} s wall"}
+            except Exception as e:                               # pragma: no cover - reporting only
+                result["cpu_baseline_all_cores"] = {"error": repr(e)}
 
-    # ---- other BASELINE configs (rank 0, N=1): reported, not the headline --------------------------
-    if rank == 0 and world == 1 and not args.no_extras:
-        result["other_workloads"] = extras(api, synth, DeformModel, DeviceBuffer, dm, model)
+        # ---- other BASELINE configs (rank 0, N=1): reported, not the headline --------------------------
+        if rank == 0 and world == 1 and not args.no_extras:
+            result["other_workloads"] = extras(api, synth, DeformModel, DeviceBuffer, dm, model)
 
     d_pal.free(); d_w.free(); d_w2.free(); d_a.free()
     if d_b:
@@ -432,6 +457,29 @@ def main():
     rv.close()
     if rank == 0:
         print(json.dumps(result))
+
+
+def dump_outputs(out_dir: str, d_a, d_b, layout: int, ni: int, nv: int, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs: the crowd's output arrays as the last timed step left them, for the instances of a fixed sample (seeded,
+    the same for the same arguments, sorted), whole rows of NV vertices, float32 -- as many instances as fit in DUMP_BUDGET.
+    SoA layout: positions.npy and normals.npy [k, NV, 3]; vertex32 layout: vertices.npy [k, NV, 8] (pos, normal, uv).
+    Under several ranks every rank writes its own instances into its share of the budget, the file names carry _rank<r>."""
+    from simple_mmd_renderer_amd import _capi as api
+    if layout == api.OUT_SOA:
+        arrays = [("positions", d_a, 3), ("normals", d_b, 3)]
+    elif layout == api.OUT_VERTEX32:
+        arrays = [("vertices", d_a, 8)]
+    else:
+        raise ValueError(f"--dump-outputs: no dump for output layout {layout}")
+    row_bytes = nv * 4 * sum(w for _n, _b, w in arrays)
+    k = max(1, min(ni, DUMP_BUDGET // world // row_bytes))
+    sample = np.sort(np.random.default_rng(DUMP_SEED).choice(ni, k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, buf, width in arrays:
+        out = np.empty((k, nv, width), np.float32)
+        for j, i in enumerate(sample):
+            out[j] = buf.download((nv, width), np.float32, offset=int(i) * nv * width * 4)
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), out)
 
 
 def kernel_source_sha() -> str:

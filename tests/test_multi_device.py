@@ -92,7 +92,7 @@ def test_ranks_run_the_hip_path_on_their_own_devices(oracle, tmp_path, world):
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher (the driver's command shape): one JSON line, n_gpus 2."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--instances-per-gpu", "64", "--no-cpu-baseline", "--no-extras", "--plain-alloc"]
+           "--instances-per-gpu", "64", "--full", "--no-cpu-baseline", "--no-extras", "--plain-alloc"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout + r.stderr

@@ -6,7 +6,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
 for kv in "$@"; do export "$kv"; done
-B="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras --no-settle --plain-alloc"
+B="python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-extras --no-settle --plain-alloc"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LEVEL_WAVES --kernel-trace --output-format csv -d $out/pmc_crowd_sq1 -o sq1 -- $B > /dev/null 2>&1
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVES --kernel-trace --output-format csv -d $out/pmc_crowd_sq2 -o sq2 -- $B > /dev/null 2>&1
 python3 - $out <<'PY'

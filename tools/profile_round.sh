@@ -14,8 +14,8 @@ mkdir -p $out
 export TMPDIR=/tmp
 export MMDX_BENCH_NO_GRAPH=1     # rocprofv3's tracer segfaults on hipStreamBeginCapture (ROCm 7.2): the graph leg of the extras is left out
 if [ "$from" -le 1 ]; then
-env -u MMDX_BENCH_NO_GRAPH python3 bench.py --steps 50 --warmup 5 > $out/bench.json
-B="python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
+env -u MMDX_BENCH_NO_GRAPH python3 bench.py --steps 50 --warmup 5 --full > $out/bench.json
+B="python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -o kt -- $B > $out/bench_under_rocprof.json 2> $out/rocprof.log
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/pmc_fetch -o fetch -- $B > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/pmc_write -o write -- $B > /dev/null 2>&1
@@ -23,7 +23,7 @@ rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_AC
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVES --kernel-trace --output-format csv -d $out/pmc_sq2 -o sq2 -- $B > /dev/null 2>&1
 echo "crowd passes done" >&2
 fi
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_all -o all -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline > /dev/null 2> $out/rocprof_all.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_all -o all -- python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline > /dev/null 2> $out/rocprof_all.log
 echo "all-workloads trace done" >&2
 F="python3 tools/fused_bench.py c2 c5 c3p --iters 10"
 $F > $out/fused_plain.txt
