@@ -55,7 +55,10 @@ extern "C" {
 /* 2: mmdx_skeleton_desc.create_flags (was reserved0), the physics seam and graph entry points, unknown flag bits are
  *    rejected, bench / debug entry points moved to mmdx_bench.h (same library). */
 /* 3: mmdx_placement_info.store_flags (the library keeps no table of array addresses any more: the caller carries the probe's
- *    verdict into mmdx_deform_args.flags); shared morph rates that did not change are detected by the library itself. */
+ *    verdict into mmdx_deform_args.flags); shared morph rates that did not change are detected by the library itself.
+ *    Added later without a version change (additive, same struct sizes): MMDX_OUT_PITCHED with
+ *    mmdx_deform_args.out_instance_pitch (was reserved0), mmdx_model_output_pitch, mmdx_crowd_output_alloc_pitched.  A library
+ *    without them rejects the flag bit as unknown, so a caller that needs pitched outputs fails loudly there. */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -169,7 +172,15 @@ enum {
        is made from the call's arguments alone: the library remembers nothing about array addresses.  Results are
        identical either way; kernels without a write-through flavour ignore the hint; the two exclude each other.   */
     MMDX_OUT_STORES_WRITE_THROUGH = 1u << 5,
-    MMDX_OUT_STORES_CACHED = 1u << 6
+    MMDX_OUT_STORES_CACHED = 1u << 6,
+    /* Instance pitch: instance i of out_a and out_b starts at element i * out_instance_pitch instead of i * NV, counted in
+       vertices of the layout (12 / 12 bytes for MMDX_OUT_SOA, 32 for MMDX_OUT_VERTEX32, 6 / 12 for MMDX_OUT_SOA_POS16), so
+       the arrays hold [NI][pitch] vertices.  out_instance_pitch >= NV.  THE GAP IS NEVER WRITTEN: the bytes of vertices
+       [NV, pitch) of every instance keep whatever they held, on every output path (device, page-locked host, pageable
+       host).  A pitch from mmdx_model_output_pitch starts every instance on a 64-byte boundary -- the layout a renderer
+       needs to bind instances of one vertex buffer at aligned offsets, and the one whose crowd stores run the fast
+       copy-out for any vertex count.  Without the flag out_instance_pitch is not read. */
+    MMDX_OUT_PITCHED = 1u << 7
 };
 
 typedef struct mmdx_deform_args {
@@ -183,7 +194,8 @@ typedef struct mmdx_deform_args {
     void *out_b;
     float pos_scale; /* positions are multiplied by this AFTER the transform, as a separate f32
                         multiply (main.cpp:848-850 uses 0.1f); 1.0f = leave as pose_image          */
-    uint32_t reserved0;
+    uint32_t out_instance_pitch; /* with MMDX_OUT_PITCHED: vertices from one instance's output to the next's
+                                    (>= NV); read only with that flag                              */
 } mmdx_deform_args;
 
 typedef struct mmdx_model_info {
@@ -313,6 +325,20 @@ typedef struct mmdx_placement_info {
 MMDX_API mmdx_status mmdx_crowd_output_alloc(mmdx_model_t model, uint32_t n_instances, int32_t out_layout,
                                              uint32_t max_tries, void **out_a_device, void **out_b_device,
                                              mmdx_placement_info *info /* may be NULL */);
+/* The smallest instance pitch >= NV (in vertices, see MMDX_OUT_PITCHED) that starts every instance of `out_layout` on a
+ * 64-byte boundary: NV rounded up to a multiple of 16 for MMDX_OUT_SOA, of 32 for MMDX_OUT_SOA_POS16, of 2 for
+ * MMDX_OUT_VERTEX32 (at most 31 vertices of gap per instance).  Any pitch that keeps instances 16-byte aligned (a multiple of
+ * 4 / 8 / 1) already takes the kernel's 16-byte copy-out; the 64-byte one is also as fast as a dense crowd whose vertex count is
+ * a multiple of 16.  Plain arithmetic on the model: works on MMDX_CREATE_HOST_ONLY models.  MMDX_OUT_SOA_POS16
+ * goes with MMDX_CREATE_F16_POSITIONS models only (MMDX_ERR_UNSUPPORTED otherwise, as in mmdx_deform_batched). */
+MMDX_API mmdx_status mmdx_model_output_pitch(mmdx_model_t model, int32_t out_layout, uint32_t *pitch);
+/* mmdx_crowd_output_alloc for pitched outputs: the arrays hold [n_instances][pitch] vertices of `out_layout` (pitch >= NV)
+ * and the placement probe replays the pitched store pattern.  With a pitch that keeps every instance 16-byte aligned (one
+ * from mmdx_model_output_pitch) the probe runs for any vertex count.  Pass the same pitch, with MMDX_OUT_PITCHED and
+ * info->store_flags, to the mmdx_deform_batched calls that write these arrays. */
+MMDX_API mmdx_status mmdx_crowd_output_alloc_pitched(mmdx_model_t model, uint32_t n_instances, int32_t out_layout,
+                                                     uint32_t pitch, uint32_t max_tries, void **out_a_device,
+                                                     void **out_b_device, mmdx_placement_info *info /* may be NULL */);
 
 /* ---- PMX 2.0 loader (the data format on the input side of the path) --------------------------- */
 /* From-scratch parser for the fields the deformation path consumes; replaces, for those fields,

@@ -20,6 +20,7 @@ CREATE_NORMALIZE, CREATE_HOST_ONLY, CREATE_F16_POSITIONS, CREATE_FAST_MATH, CREA
 OUT_SOA, OUT_VERTEX32, OUT_SOA_POS16 = 0, 1, 2
 PALETTE_ON_DEVICE, WEIGHTS_ON_DEVICE, OUT_ON_DEVICE, WEIGHTS_SHARED, MORPH_UNCHANGED = 1, 2, 4, 8, 16
 OUT_STORES_WRITE_THROUGH, OUT_STORES_CACHED = 32, 64
+OUT_PITCHED = 128        # mmdx_deform_args.out_instance_pitch is read: instance i of the outputs starts at vertex i * pitch
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
@@ -42,7 +43,7 @@ class DeformArgs(C.Structure):
                 ("n_instances", C.c_uint32), ("out_layout", C.c_uint32),
                 ("morph_weights", C.c_void_p), ("palettes", C.c_void_p),
                 ("out_a", C.c_void_p), ("out_b", C.c_void_p),
-                ("pos_scale", C.c_float), ("reserved0", C.c_uint32)]
+                ("pos_scale", C.c_float), ("out_instance_pitch", C.c_uint32)]
 
 
 class ModelInfo(C.Structure):
@@ -110,6 +111,9 @@ SIGNATURES = {
     "mmdx_pmx_get_name": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint32, C.c_char_p, C.c_size_t]),
     "mmdx_crowd_output_alloc": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p),
                                             C.POINTER(C.c_void_p), C.c_void_p]),
+    "mmdx_model_output_pitch": (C.c_int32, [C.c_void_p, C.c_int32, _u32p]),
+    "mmdx_crowd_output_alloc_pitched": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,
+                                                    C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
     "mmdx_vmd_parse": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "mmdx_vmd_load_file": (C.c_int32, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "mmdx_vmd_destroy": (None, [C.c_void_p]),

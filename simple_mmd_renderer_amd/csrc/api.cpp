@@ -492,7 +492,7 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
     const uint32_t ni = a->n_instances, layout = a->out_layout;
     if (ni == 0) return fail(MMDX_ERR_INVALID_ARGUMENT, "n_instances must be >= 1");
     if (a->flags & ~uint32_t(MMDX_PALETTE_ON_DEVICE | MMDX_WEIGHTS_ON_DEVICE | MMDX_OUT_ON_DEVICE | MMDX_WEIGHTS_SHARED | MMDX_MORPH_UNCHANGED |
-                             MMDX_OUT_STORES_WRITE_THROUGH | MMDX_OUT_STORES_CACHED))
+                             MMDX_OUT_STORES_WRITE_THROUGH | MMDX_OUT_STORES_CACHED | MMDX_OUT_PITCHED))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown bits in mmdx_deform_args.flags");
     if ((a->flags & MMDX_OUT_STORES_WRITE_THROUGH) && (a->flags & MMDX_OUT_STORES_CACHED))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "MMDX_OUT_STORES_WRITE_THROUGH and MMDX_OUT_STORES_CACHED exclude each other");
@@ -504,6 +504,13 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
         return fail(MMDX_ERR_INVALID_ARGUMENT, "palettes / out_a / out_b is NULL");
     if (p.ns && !a->morph_weights && !(a->flags & MMDX_MORPH_UNCHANGED))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "morph_weights is NULL");
+    // instance pitch of the outputs (vertices from one instance to the next); dense outputs: NV
+    const bool pitched = (a->flags & MMDX_OUT_PITCHED) != 0;
+    const uint32_t pitch = pitched ? a->out_instance_pitch : p.nv;
+    if (pitched && pitch < p.nv)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_deform_args.out_instance_pitch is smaller than the model's vertex count");
+    if (pitched && (uint64_t(ni) - 1) * pitch + p.nv > uint64_t(SIZE_MAX) / 32)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_deform_args.out_instance_pitch: the output span overflows");
     // host arguments: what kind of memory they are (device memory without its *_ON_DEVICE flag is a caller's
     // mistake that would otherwise end in a CPU memcpy from / to a device address)
     void *map_a = nullptr, *map_b = nullptr, *map_unused = nullptr;
@@ -668,6 +675,8 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
     // Small outputs bound for pageable memory (a frame of one model) take the same route into a page-locked
     // bounce buffer of the model's and are copied out by the CPU after the wait: the copy command into pageable
     // memory is the one piece of the per-frame call whose cost varies by 100 us between hosts.
+    // Pitched outputs: the kernel writes them pitched where it writes the caller's arrays (device, page-locked host); the
+    // staging and bounce buffers stay dense and the copy out of them spreads the instances (the gap is never written).
     bool out_direct = false, out_bounce = false;
     constexpr size_t kBounceMax = size_t(4) << 20;
     const size_t off_b = (bytes_a + 63) & ~size_t(63);
@@ -699,6 +708,7 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
         }
     }
     dp.out_aligned = ((reinterpret_cast<uintptr_t>(dp.out_a) | reinterpret_cast<uintptr_t>(dp.out_b)) & 15) == 0;
+    dp.pitch = out_dev || out_direct ? pitch : p.nv;
 
     // ---- workgroup shape ------------------------------------------------------------------------------
     // 256 threads / two vertex slots per lane everywhere except the per-instance-morph path: there one slot
@@ -812,12 +822,27 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
     }
 
     if (!out_dev) {
+        // one instance's bytes in the dense staging / bounce buffer and in the caller's pitched arrays
+        const size_t row_a = out_bytes_a(layout, p.nv), row_b = out_bytes_b(layout, p.nv);
+        const size_t pitch_a = out_bytes_a(layout, pitch), pitch_b = out_bytes_b(layout, pitch);
+        const bool spread = pitch != p.nv && ni > 1;
         if (!out_direct && !out_bounce) {
-            HIP_TRY(hipMemcpyAsync(a->out_a, dp.out_a, bytes_a, hipMemcpyDeviceToHost, st));
-            if (bytes_b) HIP_TRY(hipMemcpyAsync(a->out_b, dp.out_b, bytes_b, hipMemcpyDeviceToHost, st));
+            if (spread) {
+                HIP_TRY(hipMemcpy2DAsync(a->out_a, pitch_a, dp.out_a, row_a, row_a, ni, hipMemcpyDeviceToHost, st));
+                if (bytes_b) HIP_TRY(hipMemcpy2DAsync(a->out_b, pitch_b, dp.out_b, row_b, row_b, ni, hipMemcpyDeviceToHost, st));
+            } else {
+                HIP_TRY(hipMemcpyAsync(a->out_a, dp.out_a, bytes_a, hipMemcpyDeviceToHost, st));
+                if (bytes_b) HIP_TRY(hipMemcpyAsync(a->out_b, dp.out_b, bytes_b, hipMemcpyDeviceToHost, st));
+            }
         }
         HIP_TRY(wait_stream(st));
-        if (out_bounce) {
+        if (out_bounce && spread) {
+            const unsigned char *sa = static_cast<const unsigned char *>(m->bounce), *sb = sa + off_b;
+            for (uint32_t i = 0; i < ni; ++i) {
+                std::memcpy(static_cast<unsigned char *>(a->out_a) + i * pitch_a, sa + i * row_a, row_a);
+                if (bytes_b) std::memcpy(static_cast<unsigned char *>(a->out_b) + i * pitch_b, sb + i * row_b, row_b);
+            }
+        } else if (out_bounce) {
             std::memcpy(a->out_a, m->bounce, bytes_a);
             if (bytes_b) std::memcpy(a->out_b, static_cast<unsigned char *>(m->bounce) + off_b, bytes_b);
         }
@@ -1105,8 +1130,27 @@ mmdx_status mmdx_device_synchronize(void) {
 
 
 
-mmdx_status mmdx_crowd_output_alloc(mmdx_model_t m, uint32_t n_instances, int32_t out_layout, uint32_t max_tries,
-                                    void **out_a, void **out_b, mmdx_placement_info *info) {
+mmdx_status mmdx_model_output_pitch(mmdx_model_t m, int32_t out_layout, uint32_t *pitch) {
+    if (!m || !pitch) return fail(MMDX_ERR_INVALID_ARGUMENT, "model / pitch is NULL");
+    if (out_layout < MMDX_OUT_SOA || out_layout > MMDX_OUT_SOA_POS16) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown out_layout");
+    if (m->plan.f16 != (out_layout == MMDX_OUT_SOA_POS16))
+        return fail(MMDX_ERR_UNSUPPORTED, "MMDX_OUT_SOA_POS16 goes with MMDX_CREATE_F16_POSITIONS models (and only with them)");
+    // Every instance of every array of the layout starts on a 64-byte boundary: 12-byte SoA rows need a multiple of 16 vertices,
+    // the 6-byte f16 rows 32, 32-byte vertices 2.  (16-byte boundaries -- multiples of 4 / 8 / 1 -- already give the kernel its
+    // 16-byte copy-out, but measured on the config-3 crowd at NV = 50 003 in one pair of arrays: 0.935 of dense NV = 50 000's rate
+    // at a 16-byte pitch, 1.005 at a 64-byte one, 0.990 at 128; with write-through stores 0.755 against 0.941 --
+    // profiles/pitch/pitch_ab.txt.  Stores of an instance that starts inside a 64-byte line split that line with its neighbour.)
+    const uint64_t align = out_layout == MMDX_OUT_SOA ? 16u : (out_layout == MMDX_OUT_SOA_POS16 ? 32u : 2u);
+    const uint64_t pv = (uint64_t(m->plan.nv) + align - 1) / align * align;
+    if (pv > UINT32_MAX) return fail(MMDX_ERR_INVALID_ARGUMENT, "the aligned pitch does not fit in 32 bits");
+    *pitch = uint32_t(pv);
+    return MMDX_OK;
+}
+
+namespace {
+// mmdx_crowd_output_alloc(_pitched): [n_instances][pitch] vertices, the probe replays the (pitched) store pattern
+mmdx_status crowd_output_alloc(mmdx_model_t m, uint32_t n_instances, int32_t out_layout, uint32_t pitch, uint32_t max_tries,
+                               void **out_a, void **out_b, mmdx_placement_info *info) {
     if (!m || !out_a || !out_b || !n_instances) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
     if (m->device < 0) return fail(MMDX_ERR_NO_DEVICE, "host-only model");
     if (info && info->struct_size != sizeof(mmdx_placement_info))
@@ -1118,13 +1162,18 @@ mmdx_status mmdx_crowd_output_alloc(mmdx_model_t m, uint32_t n_instances, int32_
     case MMDX_OUT_SOA_POS16: bpva = 6; bpvb = 12; break;
     default: return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown out_layout");
     }
+    const uint32_t nv = m->plan.nv;
+    if (pitch < nv) return fail(MMDX_ERR_INVALID_ARGUMENT, "pitch is smaller than the model's vertex count");
+    if (uint64_t(n_instances) * pitch > uint64_t(SIZE_MAX) / 32)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "n_instances * pitch overflows");
     *out_a = *out_b = nullptr;
     HIP_TRY(hipSetDevice(m->device));
-    const uint32_t nv = m->plan.nv;
-    const size_t bytes_a = std::max<size_t>(size_t(n_instances) * nv * bpva, 16);
-    const size_t bytes_b = bpvb ? std::max<size_t>(size_t(n_instances) * nv * bpvb, 16) : 0;
-    // the replay needs every piece 16-byte aligned; otherwise (odd vertex counts) allocate without probing
-    const bool can_probe = max_tries > 1 && nv && (size_t(nv) * bpva) % 16 == 0 && (size_t(nv) * bpvb) % 16 == 0;
+    const size_t bytes_a = std::max<size_t>(size_t(n_instances) * pitch * bpva, 16);
+    const size_t bytes_b = bpvb ? std::max<size_t>(size_t(n_instances) * pitch * bpvb, 16) : 0;
+    // bytes the replay (and a crowd call) actually writes: NV vertices per instance, never the gap of a pitched layout
+    const size_t written = size_t(n_instances) * nv * (bpva + bpvb);
+    // the replay needs every instance's piece 16-byte aligned; otherwise (odd dense vertex counts) allocate without probing
+    const bool can_probe = max_tries > 1 && nv && (size_t(pitch) * bpva) % 16 == 0 && (size_t(pitch) * bpvb) % 16 == 0;
     struct Cand { void *a = nullptr, *b = nullptr; float gbs = 0.f; };
     std::vector<Cand> parked;
     Cand best;
@@ -1159,9 +1208,9 @@ mmdx_status mmdx_crowd_output_alloc(mmdx_model_t m, uint32_t n_instances, int32_
             (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
             if (e == hipSuccess && ms > 0.f) fill_gbs = float(double(bytes_a) * 5 / (ms * 1e-3) / 1e9);
         }
-        if (e == hipSuccess) e = time_store_pattern(c.a, c.b, nv, n_instances, bpva, bpvb, 5, &ms);
+        if (e == hipSuccess) e = time_store_pattern(c.a, c.b, nv, n_instances, bpva, bpvb, 5, &ms, pitch);
         if (e != hipSuccess) { release(c); st = hip_fail(e, "probing a placement of the crowd output arrays"); break; }
-        c.gbs = float(double(bytes_a + bytes_b) / (ms * 1e-3) / 1e9);
+        c.gbs = float(double(written) / (ms * 1e-3) / 1e9);
         if (launch_overrides().placement_log)
             std::fprintf(stderr, "mmdx placement try %u: a=%p b=%p store %.0f GB/s (fill %.0f)\n", tries, c.a, c.b, c.gbs, fill_gbs);
         // measured (tools/archive/probes/shop_probe.py): about one placement in seven is fast either way; freeing a rejected
@@ -1189,8 +1238,8 @@ mmdx_status mmdx_crowd_output_alloc(mmdx_model_t m, uint32_t n_instances, int32_
     // measured, so the caller's first launches already see a quiet memory system (bounded: ~0.25 s).
     for (int i = 0; freed_any && can_probe && i < 150; ++i) {
         float ms = 0.f;
-        if (time_store_pattern(best.a, best.b, nv, n_instances, bpva, bpvb, 5, &ms) != hipSuccess) break;
-        if (double(bytes_a + bytes_b) / (ms * 1e-3) / 1e9 >= 0.98 * best.gbs) break;
+        if (time_store_pattern(best.a, best.b, nv, n_instances, bpva, bpvb, 5, &ms, pitch) != hipSuccess) break;
+        if (double(written) / (ms * 1e-3) / 1e9 >= 0.98 * best.gbs) break;
     }
     HIP_TRY(hipDeviceSynchronize());
     *out_a = best.a;
@@ -1206,6 +1255,17 @@ mmdx_status mmdx_crowd_output_alloc(mmdx_model_t m, uint32_t n_instances, int32_
                                                         : 0u;
     }
     return MMDX_OK;
+}
+}  // namespace
+
+mmdx_status mmdx_crowd_output_alloc(mmdx_model_t m, uint32_t n_instances, int32_t out_layout, uint32_t max_tries,
+                                    void **out_a, void **out_b, mmdx_placement_info *info) {
+    return crowd_output_alloc(m, n_instances, out_layout, m ? m->plan.nv : 0u, max_tries, out_a, out_b, info);
+}
+
+mmdx_status mmdx_crowd_output_alloc_pitched(mmdx_model_t m, uint32_t n_instances, int32_t out_layout, uint32_t pitch,
+                                            uint32_t max_tries, void **out_a, void **out_b, mmdx_placement_info *info) {
+    return crowd_output_alloc(m, n_instances, out_layout, pitch, max_tries, out_a, out_b, info);
 }
 
 }  // extern "C"

@@ -68,7 +68,8 @@ LaunchOverrides read_launch_overrides();
 LaunchOverrides &launch_overrides();
 int env_int(const char *name, int dflt);
 // average ms of `iters` store-pattern launches on the default stream (after one warm-up launch); bench_api.cpp
-hipError_t time_store_pattern(void *a, void *b, uint32_t nv, uint32_t ni, uint32_t bpva, uint32_t bpvb, int iters, float *avg_ms);
+hipError_t time_store_pattern(void *a, void *b, uint32_t nv, uint32_t ni, uint32_t bpva, uint32_t bpvb, int iters, float *avg_ms,
+                              uint32_t pitch = 0);   // pitch: vertices from one instance to the next (0 = nv)
 
 }  // namespace mmdx
 

@@ -8,15 +8,15 @@ using namespace mmdx;
 
 // average ms of `iters` store-pattern launches on the default stream (after one warm-up launch)
 hipError_t mmdx::time_store_pattern(void *a, void *b, uint32_t nv, uint32_t ni, uint32_t bpva, uint32_t bpvb, int iters,
-                              float *avg_ms) {
+                              float *avg_ms, uint32_t pitch) {
     hipEvent_t e0, e1;
     hipError_t e = hipEventCreate(&e0);
     if (e != hipSuccess) return e;
     e = hipEventCreate(&e1);
     if (e != hipSuccess) { (void)hipEventDestroy(e0); return e; }
-    e = launch_pattern_fill(a, b, nv, ni, bpva, bpvb, nullptr);
+    e = launch_pattern_fill(a, b, nv, ni, bpva, bpvb, nullptr, pitch);
     if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
-    for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch_pattern_fill(a, b, nv, ni, bpva, bpvb, nullptr);
+    for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch_pattern_fill(a, b, nv, ni, bpva, bpvb, nullptr, pitch);
     if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
     if (e == hipSuccess) e = hipEventSynchronize(e1);
     float ms = 0.f;

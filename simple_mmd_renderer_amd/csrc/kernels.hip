@@ -677,7 +677,7 @@ template <int THREADS, int LAYOUT, int VPT, bool TILE, bool ALL_FAST, bool WT = 
 __device__ __forceinline__ void skin_instance(const DeformParams &p, const Slot (&sl)[VPT], const float4 *P,
                                               unsigned char *img, uint32_t inst, uint32_t v0, uint32_t nvt,
                                               const v2f (&cxy)[VPT], const float (&cz)[VPT], int tid, Hook after_barrier = Hook()) {
-    const size_t vbase = size_t(inst) * p.nv + v0;  // first output vertex of this tile
+    const size_t vbase = size_t(inst) * p.pitch + v0;  // first output vertex of this tile
     const bool al = p.out_aligned != 0;
     const uint32_t sh4 = al ? uint32_t((vbase * 3) & 3) : 0u;
     const uint32_t sh8 = al ? uint32_t((vbase * 3) & 7) : 0u;
@@ -856,10 +856,11 @@ __global__ __launch_bounds__(THREADS) void deform_kernel(const DeformParams p) {
     __syncthreads();
 
     uint32_t buf = 0;
-    // Every output piece of this workgroup starts on a 16-byte boundary and the tile is full (all but the last tile of a model
-    // whose vertex count is a multiple of 4 -- 8 for the f16 layout): decided once, the instance loop below is instantiated twice.
+    // Every output piece of this workgroup starts on a 16-byte boundary and the tile is full (all but the last tile when the
+    // instance pitch -- NV for dense outputs -- is a multiple of 4, 8 for the f16 layout): decided once, the instance loop below
+    // is instantiated twice.
     constexpr uint32_t kAlignVerts = LAYOUT == MMDX_OUT_SOA_POS16 ? 8u : (LAYOUT == MMDX_OUT_SOA ? 4u : 1u);
-    const bool all_fast = !TILE && p.out_aligned != 0 && nvt == kTileVerts && p.nv % kAlignVerts == 0 && v0 % kAlignVerts == 0;
+    const bool all_fast = !TILE && p.out_aligned != 0 && nvt == kTileVerts && p.pitch % kAlignVerts == 0 && v0 % kAlignVerts == 0;
     auto instances = [&](auto all_fast_tag) {
     constexpr bool kAllFast = decltype(all_fast_tag)::value;
     // the image is double buffered: the next instance writes the other one, so one barrier per instance is enough
@@ -1167,7 +1168,7 @@ __global__ __launch_bounds__(kPkThreads, PK_WAVES) void pack_kernel(const Deform
     const bool wreg = wstride <= uint32_t(kPkThreads);
     constexpr uint32_t kAlignVerts = LAYOUT == MMDX_OUT_SOA_POS16 ? 8u : 4u;
     const bool al = p.out_aligned != 0;
-    const bool fast = al && nvt == kTileVerts && p.nv % kAlignVerts == 0 && v0 % kAlignVerts == 0;
+    const bool fast = al && nvt == kTileVerts && p.pitch % kAlignVerts == 0 && v0 % kAlignVerts == 0;
     __syncthreads();
 
 #ifdef PK_STAMPS
@@ -1262,7 +1263,7 @@ __global__ __launch_bounds__(kPkThreads, PK_WAVES) void pack_kernel(const Deform
         auto instance = [&](const uint32_t j, auto last_tag) {
             constexpr bool kLast = decltype(last_tag)::value;       // the pack's fourth instance: the next walk's row head goes out with it
             const uint32_t inst = first_instance(g0) + j;
-            const size_t vbase = size_t(inst) * p.nv + v0;
+            const size_t vbase = size_t(inst) * p.pitch + v0;
             const uint32_t sh4 = al ? uint32_t((vbase * 3) & 3) : 0u, sh8 = al ? uint32_t((vbase * 3) & 7) : 0u;
             unsigned char *ia = mp + j * kPkRegion, *ib = imgB + buf * kSoaImgBytes;
             // (in place: the values stay in their registers, the compiler merely stops treating them as loop invariants -- whose
@@ -1555,13 +1556,15 @@ __global__ __launch_bounds__(kThreads) void fill_kernel(float4 *dst, size_t n) {
 // and as the probe of mmdx_crowd_output_alloc().
 __global__ __launch_bounds__(kThreads) void pattern_fill_kernel(float4 *a, float4 *b, uint32_t nv,
                                                                 uint32_t ni, uint32_t ntiles, uint32_t bpva,
-                                                                uint32_t bpvb) {
+                                                                uint32_t bpvb, uint32_t pitch) {
     const uint32_t tile = blockIdx.x % ntiles, grp = blockIdx.x / ntiles;
     const uint32_t v0 = tile * kTileVerts, nvt = min(kTileVerts, nv - v0);
-    const uint32_t pa = nvt * bpva / 16, pb = nvt * bpvb / 16;   // callers keep nv * bytes-per-vertex % 16 == 0
+    // callers keep pitch * bytes-per-vertex % 16 == 0; the 16-byte pieces of a ragged last tile are rounded down (never past
+    // the instance's NV vertices)
+    const uint32_t pa = nvt * bpva / 16, pb = nvt * bpvb / 16;
     const float4 v = make_float4(1.f, 2.f, 3.f, 4.f);
     for (uint32_t g = grp * 16; g < min(ni, grp * 16 + 16); ++g) {
-        const size_t base_a = (size_t(g) * nv + v0) * bpva / 16, base_b = (size_t(g) * nv + v0) * bpvb / 16;
+        const size_t base_a = (size_t(g) * pitch + v0) * bpva / 16, base_b = (size_t(g) * pitch + v0) * bpvb / 16;
         for (uint32_t q = threadIdx.x; q < pa + pb; q += kThreads) {
             store16(q < pa ? a + base_a + q : b + base_b + (q - pa), v);      // the deform kernel's store instruction (policy and all)
         }
@@ -1794,10 +1797,11 @@ hipError_t MMDX_K(launch_morph_apply)(bool f16, const DeformParams &p, const Fla
 
 #ifndef MMDX_FAST_MATH
 hipError_t launch_pattern_fill(void *a, void *b, uint32_t nv, uint32_t ni, uint32_t bpva, uint32_t bpvb,
-                               hipStream_t stream) {
+                               hipStream_t stream, uint32_t pitch) {
     const uint32_t ntiles = (nv + kTileVerts - 1) / kTileVerts;
     hipLaunchKernelGGL(pattern_fill_kernel, dim3(ntiles * ((ni + 15) / 16)), dim3(kThreads), 0, stream,
-                       reinterpret_cast<float4 *>(a), reinterpret_cast<float4 *>(b), nv, ni, ntiles, bpva, bpvb);
+                       reinterpret_cast<float4 *>(a), reinterpret_cast<float4 *>(b), nv, ni, ntiles, bpva, bpvb,
+                       pitch ? pitch : nv);
     return hipGetLastError();
 }
 

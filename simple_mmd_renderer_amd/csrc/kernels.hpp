@@ -50,7 +50,10 @@ struct DeformParams {
     uint32_t nm;
     void *out_a;
     void *out_b;
-    uint32_t nv, nb, ns, ni;
+    // pitch: output vertices from one instance to the next (MMDX_OUT_PITCHED; = nv for dense outputs).  It sits where nv sat
+    // before it existed, and nv (read by the morph pass only) at the end: the kernels that write outputs see the same
+    // kernel-argument layout as the dense-only build and compile to the same registers
+    uint32_t pitch, nb, ns, ni;
     uint32_t group;              // instances per workgroup (multiple of 4 for kMorphFused4)
     uint32_t ntiles, ngroups, rem_per_xcd;  // filled by launch_deform (XCD-aware work mapping)
     uint32_t pal_stride;         // float4 per instance in LDS (= max_tile_bones * 3)
@@ -70,6 +73,7 @@ struct DeformParams {
     unsigned long long *stamps;  // diagnostic builds of pack_kernel only (PK_STAMPS): per-wave cycle counters; nullptr in the product
     uint32_t *morph_seen;        // kMorphFused1 crowds: the handle's RatesSeen record; a launch that overwrites `morphed` clears its
                                  // valid word (the record no longer describes what `morphed` holds)
+    uint32_t nv;                 // vertices of the model
 };
 
 // Device-side record of the morph rates the `morphed` buffer of a handle was last computed from (shared morph pass of a crowd):
@@ -113,8 +117,9 @@ hipError_t launch_frame(int threads, int layout, int morph, bool f16, const Defo
 hipError_t launch_morph_apply(bool f16, const DeformParams &p, const FlattenParams *fused,
                               hipStream_t stream);
 constexpr uint32_t kMaxFusedSlots = 8192;
+// pitch: vertices from one instance's piece to the next (0 = nv)
 hipError_t launch_pattern_fill(void *a, void *b, uint32_t nv, uint32_t ni, uint32_t bpva, uint32_t bpvb,
-                               hipStream_t stream);
+                               hipStream_t stream, uint32_t pitch = 0);
 hipError_t launch_flatten(const FlattenParams &p, hipStream_t stream);
 hipError_t launch_morph_track_eval(const MorphTrackParams &t, hipStream_t stream);
 hipError_t launch_copy(void *dst, const void *src, size_t bytes, hipStream_t stream);

@@ -253,16 +253,25 @@ class DeformModel:
                                                  C.c_float(pos_scale), out.ctypes.data))
         return out
 
-    def out_sizes(self, layout: int, ni: int) -> Tuple[int, int]:
-        nvi = ni * self.nv
+    def output_pitch(self, layout: int) -> int:
+        """mmdx_model_output_pitch: the smallest instance pitch >= NV (in vertices) that starts every instance of `layout` on a
+        16-byte boundary -- what alloc_outputs(..., pitch=) and deform_batched*(..., pitch=) take."""
+        p = C.c_uint32(0)
+        api.check(api.lib().mmdx_model_output_pitch(self.h, layout, C.byref(p)))
+        return p.value
+
+    def out_sizes(self, layout: int, ni: int, pitch: int = 0) -> Tuple[int, int]:
+        """Bytes of the two output arrays of `ni` instances, [ni][pitch] vertices when a pitch is given, else [ni][NV]."""
+        nvi = ni * (pitch or self.nv)
         if layout == api.OUT_SOA:
             return nvi * 12, nvi * 12
         if layout == api.OUT_VERTEX32:
             return nvi * 32, 0
         return nvi * 6, nvi * 12
 
-    def alloc_outputs(self, layout: int, ni: int, max_tries: int = 16):
-        """The crowd's output arrays through mmdx_crowd_output_alloc (placement-aware on MI355X).
+    def alloc_outputs(self, layout: int, ni: int, max_tries: int = 16, pitch: int = 0):
+        """The crowd's output arrays through mmdx_crowd_output_alloc (placement-aware on MI355X); with a pitch through
+        mmdx_crowd_output_alloc_pitched ([ni][pitch] vertices, for calls with the same pitch).
         Returns (a, b or None, info dict); info["store_flags"] is the MMDX_OUT_STORES_* hint to OR into the flags of the crowd
         calls that write these arrays (the library itself remembers nothing about them)."""
         class _Info(C.Structure):
@@ -271,18 +280,26 @@ class DeformModel:
         info = _Info()
         info.struct_size = C.sizeof(_Info)
         pa, pb = C.c_void_p(), C.c_void_p()
-        api.check(api.lib().mmdx_crowd_output_alloc(self.h, ni, layout, max_tries, C.byref(pa), C.byref(pb),
-                                                    C.byref(info)))
-        sa, sb = self.out_sizes(layout, ni)
+        if pitch:
+            api.check(api.lib().mmdx_crowd_output_alloc_pitched(self.h, ni, layout, pitch, max_tries, C.byref(pa), C.byref(pb),
+                                                                C.byref(info)))
+        else:
+            api.check(api.lib().mmdx_crowd_output_alloc(self.h, ni, layout, max_tries, C.byref(pa), C.byref(pb),
+                                                        C.byref(info)))
+        sa, sb = self.out_sizes(layout, ni, pitch)
         a = DeviceBuffer.adopt(pa.value, sa)
         b = DeviceBuffer.adopt(pb.value, sb) if pb.value else None
         return a, b, {"tries": info.tries, "probed": bool(info.probed), "store_GBs": info.store_GBs,
                       "fill_GBs": info.fill_GBs, "store_flags": int(info.store_flags)}
 
     def deform_batched_raw(self, ni: int, weights_ptr, palettes_ptr, out_a_ptr, out_b_ptr, layout: int,
-                           flags: int, pos_scale: float = 1.0) -> None:
+                           flags: int, pos_scale: float = 1.0, pitch: int = 0) -> None:
+        """pitch: instance pitch of the outputs in vertices (MMDX_OUT_PITCHED); 0 = dense [ni][NV]."""
         a = api.DeformArgs()
         a.struct_size = C.sizeof(api.DeformArgs)
+        if pitch:
+            flags |= api.OUT_PITCHED
+            a.out_instance_pitch = pitch
         a.flags, a.n_instances, a.out_layout = flags, ni, layout
         a.morph_weights, a.palettes = weights_ptr, palettes_ptr
         a.out_a, a.out_b = out_a_ptr, out_b_ptr
@@ -290,26 +307,31 @@ class DeformModel:
         api.check(api.lib().mmdx_deform_batched(self.h, C.byref(a)))
 
     def deform_batched(self, weights, palettes, layout: int = api.OUT_SOA, shared_weights: bool = False,
-                       pos_scale: float = 1.0):
+                       pos_scale: float = 1.0, pitch: int = 0):
         """Host arrays in, host arrays out (copies + sync inside the call).
-        weights [NI,NM] (or [NM] with shared_weights); palettes [NI,NB,16]."""
+        weights [NI,NM] (or [NM] with shared_weights); palettes [NI,NB,16].  pitch: the call writes [NI][pitch]-vertex host
+        arrays (MMDX_OUT_PITCHED); the [:, :NV] views of them are returned."""
         pal = _c(palettes, np.float32).reshape(-1, self.nb, 16)
         ni = pal.shape[0]
         w = _c(weights, np.float32)
         if self.nm:
             w = w.reshape(self.nm) if shared_weights else w.reshape(ni, self.nm)
         flags = api.WEIGHTS_SHARED if shared_weights else 0
+        rows = pitch or self.nv
         if layout == api.OUT_SOA:
-            oa = np.empty((ni, self.nv, 3), np.float32)
-            ob = np.empty((ni, self.nv, 3), np.float32)
+            oa = np.empty((ni, rows, 3), np.float32)
+            ob = np.empty((ni, rows, 3), np.float32)
         elif layout == api.OUT_VERTEX32:
-            oa = np.empty((ni, self.nv, 8), np.float32)
+            oa = np.empty((ni, rows, 8), np.float32)
             ob = None
         else:
-            oa = np.empty((ni, self.nv, 3), np.float16)
-            ob = np.empty((ni, self.nv, 3), np.float32)
+            oa = np.empty((ni, rows, 3), np.float16)
+            ob = np.empty((ni, rows, 3), np.float32)
         self.deform_batched_raw(ni, w.ctypes.data if w.size else None, pal.ctypes.data, oa.ctypes.data,
-                                ob.ctypes.data if ob is not None else None, layout, flags, pos_scale)
+                                ob.ctypes.data if ob is not None else None, layout, flags, pos_scale, pitch)
+        if pitch:
+            oa = oa[:, :self.nv]
+            ob = ob[:, :self.nv] if ob is not None else None
         return (oa, ob) if ob is not None else oa
 
     def sync(self) -> None:

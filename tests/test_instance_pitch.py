@@ -1,0 +1,404 @@
+"""Instance pitch of the crowd outputs (MMDX_OUT_PITCHED, mmdx_deform_args.out_instance_pitch): instance i of out_a / out_b
+starts at vertex i * pitch instead of i * NV, on every crowd path, and the bytes between vertex NV and vertex pitch of an
+instance are never written.  CPU: the ABI (header, exports, struct size) and mmdx_model_output_pitch on host-only models.
+GPU: bit-exact against the oracle for ragged sizes, every layout and morph mode, tile order, all four output paths, the
+graph replay, fast math within its tolerance, and the full-size crowd in the benchmark's call form."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from simple_mmd_renderer_amd import _capi as api
+from simple_mmd_renderer_amd import synth
+from simple_mmd_renderer_amd.engine import DeformModel, DeviceBuffer, PinnedArray, device_count
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "mmdx.h")
+
+BPV = {api.OUT_SOA: (12, 12), api.OUT_VERTEX32: (32, 0), api.OUT_SOA_POS16: (6, 12)}   # bytes per vertex of out_a, out_b
+TAIL = 64                                                                            # sentinel bytes behind the last instance
+
+
+# ---- CPU: the ABI --------------------------------------------------------------------------------------------------------------
+def test_header_declares_pitch_and_library_exports_it(hip_lib):
+    text = open(HEADER).read()
+    assert re.search(r"MMDX_OUT_PITCHED\s*=\s*1u\s*<<\s*7", text)
+    assert re.search(r"uint32_t\s+out_instance_pitch\s*;", text)
+    for name in ("mmdx_model_output_pitch", "mmdx_crowd_output_alloc_pitched"):
+        assert re.search(r"MMDX_API\s+mmdx_status\s+" + name + r"\s*\(", text), name
+        assert hasattr(hip_lib, name), name
+        assert name in api.SIGNATURES
+    assert api.OUT_PITCHED == 1 << 7
+    assert "#define MMDX_ABI_VERSION 3u" in text
+
+
+def test_deform_args_keeps_its_size_and_names_the_pitch():
+    assert C.sizeof(api.DeformArgs) == 56
+    names = [f[0] for f in api.DeformArgs._fields_]
+    assert names[-1] == "out_instance_pitch" and "reserved0" not in names
+    assert api.DeformArgs.out_instance_pitch.offset == 52
+
+
+def _round_up(n, k):
+    return (n + k - 1) // k * k
+
+
+@pytest.mark.parametrize("nv", [1, 3, 4, 5, 50000, 50001, 50002, 50003])
+def test_output_pitch_on_host_only_models(hip_lib, nv):
+    m = synth.make_model(nv, 1 if nv == 1 else 17, 3, min(nv, 40), seed=300 + nv)
+    with DeformModel(m, host_only=True) as dm, DeformModel(m, host_only=True, f16_positions=True) as d16:
+        # every instance of every array starts on a 64-byte boundary, with the least padding that does it
+        assert dm.output_pitch(api.OUT_SOA) == _round_up(nv, 16)
+        assert dm.output_pitch(api.OUT_VERTEX32) == _round_up(nv, 2)
+        assert d16.output_pitch(api.OUT_SOA_POS16) == _round_up(nv, 32)
+        for layout, model in ((api.OUT_SOA, dm), (api.OUT_VERTEX32, dm), (api.OUT_SOA_POS16, d16)):
+            p = model.output_pitch(layout)
+            assert nv <= p < nv + 32 and all((p * b) % 64 == 0 for b in BPV[layout])
+            assert not all(((p - 1) * b) % 64 == 0 for b in BPV[layout]) or p - 1 < nv
+        with pytest.raises(api.MmdxError) as e:
+            dm.output_pitch(api.OUT_SOA_POS16)                  # f16 layout on an f32 model: as mmdx_deform_batched
+        assert e.value.status == 6
+        with pytest.raises(api.MmdxError) as e:
+            d16.output_pitch(api.OUT_SOA)
+        assert e.value.status == 6
+        with pytest.raises(api.MmdxError) as e:
+            dm.output_pitch(7)
+        assert e.value.status == 1
+
+
+# ---- GPU helpers ---------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def _gpu(hip_lib):
+    assert device_count() >= 1, "no HIP device visible: the GPU tests must run on the MI355X box"
+
+
+def _no_morphs(m):
+    m.morph_type = np.zeros(0, np.int32)
+    m.morph_off = np.zeros(1, np.uint32)
+    m.morph_index = np.zeros(0, np.uint32)
+    m.morph_value = np.zeros((0, 3), np.float32)
+    return m
+
+
+def _quantised(m):
+    q = m.copy()
+    q.positions = m.positions.astype(np.float16).astype(np.float32)
+    q.morph_value = m.morph_value.astype(np.float16).astype(np.float32)
+    return q
+
+
+class Expect:
+    """Oracle results of one model per (rates row, palette row), as the bytes of one instance of each layout."""
+
+    def __init__(self, oracle, m, order=None):
+        self.o, self.m, self.q = oracle, m, _quantised(m)
+        self.skin, self.qskin = oracle.normalize(m), oracle.normalize(self.q)
+        self.order = order          # engine_to_original of a tile-order model
+        self.memo = {}
+
+    def rows(self, layout, rates, pal, scale):
+        key = (layout, rates.tobytes(), pal.tobytes(), scale)
+        if key not in self.memo:
+            o, m = self.o, self.m
+            if layout == api.OUT_SOA_POS16:
+                p, n = o.skin(self.q, pal, o.morph(self.q, rates), self.qskin)
+                a, b = p.astype(np.float16), n
+            else:
+                p, n = o.skin(m, pal, o.morph(m, rates), self.skin)
+                a, b = (p, n) if layout == api.OUT_SOA else (o.repack32(m, p, n, scale), None)
+            if self.order is not None:
+                a = a[self.order]
+                b = b[self.order] if b is not None else None
+            self.memo[key] = (np.ascontiguousarray(a).view(np.uint8).reshape(-1),
+                              np.ascontiguousarray(b).view(np.uint8).reshape(-1) if b is not None else None)
+        return self.memo[key]
+
+
+def _check(buf, want_rows, ni, nv, pitch, bpv, what):
+    """buf: bytes of one output array ([ni][pitch] vertices + TAIL).  Every instance equals its expected bytes, every gap byte
+    and every tail byte is still the 0xFF sentinel."""
+    span = ni * pitch * bpv
+    assert buf.size == span + TAIL
+    rows = buf[:span].reshape(ni, pitch * bpv)
+    for i in range(ni):
+        got, want = rows[i, :nv * bpv], want_rows[i]
+        if not np.array_equal(got, want):
+            bad = np.flatnonzero(got != want)
+            raise AssertionError(f"{what}: instance {i}: {bad.size} of {got.size} bytes differ, first at vertex {bad[0] // bpv}")
+    gap = rows[:, nv * bpv:]
+    assert (gap == 0xFF).all(), f"{what}: {(gap != 0xFF).sum()} gap bytes written (instance {np.argwhere(gap != 0xFF)[0][0]})"
+    assert (buf[span:] == 0xFF).all(), f"{what}: bytes behind the last instance written"
+
+
+def _call(dm, path, layout, ni, rates, pals, shared, pitch, scale, flags=0):
+    """One pitched call through `path` (device | mapped | pageable); returns the two output arrays' bytes (b: None)."""
+    ba, bb = BPV[layout]
+    na, nb = ni * pitch * ba + TAIL, (ni * pitch * bb + TAIL if bb else 0)
+    fl = flags | (api.WEIGHTS_SHARED if shared else 0)
+    w = np.ascontiguousarray(rates[0] if shared else rates, np.float32)
+    pal = np.ascontiguousarray(pals, np.float32)
+    if path == "device":
+        d_a, d_b = DeviceBuffer(na), (DeviceBuffer(nb) if nb else None)
+        d_pal, d_w = DeviceBuffer.from_numpy(pal), DeviceBuffer.from_numpy(w if w.size else np.zeros(1, np.float32))
+        for x in (d_a, d_b):
+            if x is not None:
+                x.memset(0xFF)
+        fl |= api.PALETTE_ON_DEVICE | api.WEIGHTS_ON_DEVICE | api.OUT_ON_DEVICE
+        dm.deform_batched_raw(ni, d_w.ptr, d_pal.ptr, d_a.ptr, d_b.ptr if d_b else None, layout, fl, scale, pitch)
+        dm.sync()
+        a = d_a.download((na,), np.uint8)
+        b = d_b.download((nb,), np.uint8) if d_b else None
+        for x in (d_a, d_b, d_pal, d_w):
+            if x is not None:
+                x.free()
+        return a, b
+    if path == "mapped":
+        pa, pb = PinnedArray((na,), np.uint8), (PinnedArray((nb,), np.uint8) if nb else None)
+        for x in (pa, pb):
+            if x is not None:
+                x.array[:] = 0xFF
+        dm.deform_batched_raw(ni, w.ctypes.data if w.size else None, pal.ctypes.data, pa.ptr, pb.ptr if pb else None, layout, fl,
+                              scale, pitch)
+        a, b = pa.array.copy(), (pb.array.copy() if pb else None)
+        for x in (pa, pb):
+            if x is not None:
+                x.free()
+        return a, b
+    a = np.full(na, 0xFF, np.uint8)
+    b = np.full(nb, 0xFF, np.uint8) if nb else None
+    dm.deform_batched_raw(ni, w.ctypes.data if w.size else None, pal.ctypes.data, a.ctypes.data,
+                          b.ctypes.data if b is not None else None, layout, fl, scale, pitch)
+    return a, b
+
+
+def _verify(exp, a, b, layout, ni, rates, pals, shared, pitch, scale, what):
+    nv = exp.m.nv
+    wa, wb = zip(*[exp.rows(layout, rates[0] if shared else rates[i], pals[i], scale) for i in range(ni)])
+    ba, bb = BPV[layout]
+    _check(a, wa, ni, nv, pitch, ba, what + " out_a")
+    if bb:
+        _check(b, wb, ni, nv, pitch, bb, what + " out_b")
+
+
+@pytest.fixture
+def set_env(monkeypatch, hip_lib):
+    def _set(**env):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        hip_lib.mmdx_debug_reload_env()
+    yield _set
+    monkeypatch.delenv("MMDX_FUSED_PACK", raising=False)
+    hip_lib.mmdx_debug_reload_env()
+
+
+# ---- GPU: ragged sizes x layouts x morph modes, device outputs --------------------------------------------------------------------
+# (mode, instances, shared rates, MMDX_FUSED_PACK): no morphs; shared rates with the crowd's separate morph pass (NI > 8); shared
+# rates gathered inside the kernel (NI <= 8); per-instance weights in the deform kernel and in the pack kernel
+MODES = [("none", 6, False, "0"), ("shared pass", 11, True, "0"), ("shared gathered", 5, True, "0"),
+         ("per-instance", 11, False, "0"), ("per-instance pack", 11, False, "1")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tile_order", [False, True], ids=["file-order", "tile-order"])
+@pytest.mark.parametrize("nv", [1, 63, 513, 1000, 4099])
+def test_ragged_pitched_every_layout_and_morph_mode(_gpu, oracle, set_env, nv, tile_order):
+    nb = 1 if nv == 1 else 17
+    base = synth.make_model(nv, nb, 5, min(nv, 60), seed=4100 + nv)
+    bare = _no_morphs(synth.make_model(nv, nb, 1, 1, seed=4100 + nv))
+    for mname, ni, shared, pack in MODES:
+        set_env(MMDX_FUSED_PACK=pack)
+        m = bare if mname == "none" else base
+        rates = synth.morph_weights(m.nm, np.arange(ni) * 7 + 2) if m.nm else np.zeros((ni, 0), np.float32)
+        pals = synth.make_palettes(m, np.arange(ni) * 3 + 1)
+        with DeformModel(m, tile_order=tile_order) as dm, DeformModel(m, tile_order=tile_order, f16_positions=True) as d16:
+            exps = {id(x): Expect(oracle, m, x.vertex_order()[0] if tile_order else None) for x in (dm, d16)}
+            for layout, model in ((api.OUT_SOA, dm), (api.OUT_VERTEX32, dm), (api.OUT_SOA_POS16, d16)):
+                exp = exps[id(model)]
+                scale = 0.1 if layout == api.OUT_VERTEX32 else 1.0
+                for pitch in (model.output_pitch(layout), nv + 13):
+                    what = f"nv={nv} {mname} layout={layout} pitch={pitch}{' tile' if tile_order else ''}"
+                    a, b = _call(model, "device", layout, ni, rates, pals, shared, pitch, scale)
+                    _verify(exp, a, b, layout, ni, rates, pals, shared, pitch, scale, what)
+
+
+# ---- GPU: the four output paths keep the gap --------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("nv", [63, 1000, 4099])
+def test_gap_untouched_on_every_output_path(_gpu, oracle, nv):
+    """Device arrays, page-locked mapped host arrays (written by the kernel over PCIe), pageable host arrays through the
+    staging buffer (outputs > 4 MB: 2D copy out) and through the bounce buffer (small outputs: one copy per instance)."""
+    m = synth.make_model(nv, 17, 5, min(nv, 60), seed=5200 + nv)
+    with DeformModel(m) as dm, DeformModel(m, f16_positions=True) as d16:
+        exp = Expect(oracle, m)
+        for path, ni in (("device", 9), ("mapped", 9), ("pageable", 5), ("pageable", 4 * 1024 * 1024 // (18 * nv) + 2)):
+            rates = synth.morph_weights(m.nm, np.arange(ni) * 5 + 1)
+            pals = synth.make_palettes(m, np.arange(ni) * 2 + 3)
+            for layout, model in ((api.OUT_SOA, dm), (api.OUT_VERTEX32, dm), (api.OUT_SOA_POS16, d16)):
+                scale = 0.1 if layout == api.OUT_VERTEX32 else 1.0
+                for pitch in (model.output_pitch(layout), nv + 13):
+                    for shared in (False, True):
+                        what = f"{path} ni={ni} nv={nv} layout={layout} pitch={pitch} shared={shared}"
+                        a, b = _call(model, path, layout, ni, rates, pals, shared, pitch, scale)
+                        _verify(exp, a, b, layout, ni, rates, pals, shared, pitch, scale, what)
+
+
+@pytest.mark.gpu
+def test_deform_batched_returns_views_of_pitched_host_arrays(_gpu, oracle):
+    m = synth.make_model(1000, 17, 5, 60, seed=77)
+    ni = 7
+    rates = synth.morph_weights(m.nm, np.arange(ni))
+    pals = synth.make_palettes(m, np.arange(ni) * 2)
+    with DeformModel(m) as dm:
+        pos, nrm = dm.deform_batched(rates, pals)
+        ppos, pnrm = dm.deform_batched(rates, pals, pitch=1013)
+        assert ppos.shape == (ni, m.nv, 3) and ppos.base is not None and ppos.base.shape == (ni, 1013, 3)
+        assert np.array_equal(ppos.view(np.uint32), pos.view(np.uint32)) and np.array_equal(pnrm.view(np.uint32), nrm.view(np.uint32))
+        v32 = dm.deform_batched(rates, pals, layout=api.OUT_VERTEX32, pos_scale=0.1, pitch=1001)
+        assert np.array_equal(v32.view(np.uint32), dm.deform_batched(rates, pals, layout=api.OUT_VERTEX32, pos_scale=0.1).view(np.uint32))
+
+
+# ---- GPU: pitch == NV, invalid pitches -----------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("nv", [513, 4099])
+def test_pitch_equal_to_nv_is_the_dense_call_and_short_pitches_are_rejected(_gpu, nv):
+    m = synth.make_model(nv, 17, 5, 60, seed=900 + nv)
+    ni = 9
+    rates = synth.morph_weights(m.nm, np.arange(ni))
+    pals = synth.make_palettes(m, np.arange(ni) * 4)
+    with DeformModel(m) as dm:
+        for layout in (api.OUT_SOA, api.OUT_VERTEX32):
+            for shared in (False, True):
+                a0, b0 = _call(dm, "device", layout, ni, rates, pals, shared, nv, 1.0)          # flag + pitch = NV
+                fl = api.PALETTE_ON_DEVICE | api.WEIGHTS_ON_DEVICE | api.OUT_ON_DEVICE | (api.WEIGHTS_SHARED if shared else 0)
+                sa, sb = dm.out_sizes(layout, ni)
+                d_a, d_b = DeviceBuffer(sa + TAIL), DeviceBuffer(max(sb, 16) + TAIL)
+                d_a.memset(0xFF); d_b.memset(0xFF)
+                d_pal, d_w = DeviceBuffer.from_numpy(pals), DeviceBuffer.from_numpy(rates[0] if shared else rates)
+                dm.deform_batched_raw(ni, d_w.ptr, d_pal.ptr, d_a.ptr, d_b.ptr, layout, fl)     # no flag
+                dm.sync()
+                assert np.array_equal(a0, d_a.download((sa + TAIL,), np.uint8))
+                if sb:
+                    assert np.array_equal(b0, d_b.download((sb + TAIL,), np.uint8))
+                for bad in (nv - 1, 0):
+                    with pytest.raises(api.MmdxError) as e:
+                        dm.deform_batched_raw(ni, d_w.ptr, d_pal.ptr, d_a.ptr, d_b.ptr, layout, fl, 1.0, bad) if bad else \
+                            dm.deform_batched_raw(ni, d_w.ptr, d_pal.ptr, d_a.ptr, d_b.ptr, layout, fl | api.OUT_PITCHED)
+                    assert e.value.status == 1 and "pitch" in str(e.value)
+                for x in (d_a, d_b, d_pal, d_w):
+                    x.free()
+        # the field is not read without the flag: garbage there changes nothing
+        a = api.DeformArgs()
+        a.struct_size = C.sizeof(api.DeformArgs)
+        pos = np.empty((ni, nv, 3), np.float32)
+        nrm = np.empty((ni, nv, 3), np.float32)
+        a.flags, a.n_instances, a.out_layout, a.out_instance_pitch = 0, ni, api.OUT_SOA, 1
+        a.morph_weights, a.palettes, a.out_a, a.out_b, a.pos_scale = rates.ctypes.data, pals.ctypes.data, pos.ctypes.data, nrm.ctypes.data, 1.0
+        api.check(api.lib().mmdx_deform_batched(dm.h, C.byref(a)))
+        want_p, want_n = dm.deform_batched(rates, pals)
+        assert np.array_equal(pos.view(np.uint32), want_p.view(np.uint32)) and np.array_equal(nrm.view(np.uint32), want_n.view(np.uint32))
+
+
+# ---- GPU: fast math -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("nv", [63, 4099])
+def test_fast_math_pitched_within_tolerance(_gpu, oracle, nv):
+    """Tolerance of tests/test_fast_math.py: |x - x_ref| <= 1e-5 (1 + |x_ref|) per position, 2e-6 per normal component."""
+    m = synth.make_model(nv, 17, 5, min(nv, 60), seed=6600 + nv)
+    skin = oracle.normalize(m)
+    for ni, shared in ((9, False), (11, True), (5, True)):
+        rates = synth.morph_weights(m.nm, np.arange(ni) * 3 + 4)
+        pals = synth.make_palettes(m, np.arange(ni) * 5)
+        with DeformModel(m, fast_math=True) as fm:
+            for pitch in (fm.output_pitch(api.OUT_SOA), nv + 13):
+                a, b = _call(fm, "device", api.OUT_SOA, ni, rates, pals, shared, pitch, 1.0)
+                for arr in (a, b):
+                    rows = arr[:ni * pitch * 12].reshape(ni, pitch * 12)
+                    assert (rows[:, nv * 12:] == 0xFF).all() and (arr[ni * pitch * 12:] == 0xFF).all()
+                pos = a[:ni * pitch * 12].view(np.float32).reshape(ni, pitch, 3)[:, :nv]
+                nrm = b[:ni * pitch * 12].view(np.float32).reshape(ni, pitch, 3)[:, :nv]
+                for i in range(ni):
+                    ep, en = oracle.skin(m, pals[i], oracle.morph(m, rates[0] if shared else rates[i]), skin)
+                    assert np.all(np.abs(pos[i].astype(np.float64) - ep) <= 1e-5 * (1 + np.abs(ep.astype(np.float64)))), i
+                    assert np.all(np.abs(nrm[i].astype(np.float64) - en) <= 2e-6), i
+
+
+# ---- GPU: graph replay ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_pitched_call_recorded_in_a_graph_matches_the_direct_call(_gpu, oracle):
+    m = synth.make_model(4099, 40, 6, 200, seed=41)
+    ni, pitch = 12, 4099 + 13
+    rates = synth.morph_weights(m.nm, 9)[0]
+    pals = [synth.make_palettes(m, np.arange(ni) * 3 + k) for k in (0, 50, 90)]
+    flags = api.PALETTE_ON_DEVICE | api.WEIGHTS_ON_DEVICE | api.OUT_ON_DEVICE | api.WEIGHTS_SHARED
+    with DeformModel(m) as dm:
+        exp = Expect(oracle, m)
+        d_pal, d_w = DeviceBuffer.from_numpy(pals[0]), DeviceBuffer.from_numpy(rates)
+        n = ni * pitch * 12 + TAIL
+        d_a, d_b = DeviceBuffer(n), DeviceBuffer(n)
+        dm.deform_batched_raw(ni, d_w.ptr, d_pal.ptr, d_a.ptr, d_b.ptr, api.OUT_SOA, flags, 1.0, pitch)   # sizes the scratch
+        dm.sync()
+        dm.graph_begin()
+        dm.deform_batched_raw(ni, d_w.ptr, d_pal.ptr, d_a.ptr, d_b.ptr, api.OUT_SOA, flags, 1.0, pitch)
+        g = dm.graph_end()
+        for k, p in enumerate(pals):
+            d_pal.upload(p)
+            d_a.memset(0xFF); d_b.memset(0xFF)
+            g.launch()
+            dm.sync()
+            ra, rb = d_a.download((n,), np.uint8), d_b.download((n,), np.uint8)
+            da, db = _call(dm, "device", api.OUT_SOA, ni, rates[None], p, True, pitch, 1.0)
+            assert np.array_equal(ra, da) and np.array_equal(rb, db), f"replay {k} differs from the direct call"
+            _verify(exp, ra, rb, api.OUT_SOA, ni, rates[None], p, True, pitch, 1.0, f"replay {k}")
+        g.close()
+        for x in (d_pal, d_w, d_a, d_b):
+            x.free()
+
+
+# ---- GPU: full size, the benchmark's call form ---------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("nv", [50001, 50003])
+def test_full_size_crowd_pitched_bench_call_form(_gpu, oracle, nv):
+    """Config-3-shaped crowd with a vertex count that is not a multiple of 4: 1 024 instances, crowd_frames palettes, shared
+    rates, arrays from alloc_outputs(pitch=output_pitch) with the probe's store flags, every resident in HBM.  The pitched
+    allocation is probed (the dense one of an unaligned NV is not); the first, the last and four inner instances equal the
+    oracle at every vertex and their gaps keep the sentinel."""
+    from simple_mmd_renderer_amd.crowd import crowd_frames
+    m = synth.make_model(nv, 300, 200, 2048, seed=50002)
+    ni = 1024
+    pals = synth.make_palettes(m, crowd_frames(0, ni))
+    rates = synth.morph_weights(m.nm, 12)[0]
+    d_pal, d_w = DeviceBuffer.from_numpy(pals), DeviceBuffer.from_numpy(rates)
+    exp = Expect(oracle, m)
+    with DeformModel(m) as dm, DeformModel(m, f16_positions=True) as d16:
+        for layout, model in ((api.OUT_SOA, dm), (api.OUT_VERTEX32, dm), (api.OUT_SOA_POS16, d16)):
+            pitch = model.output_pitch(layout)
+            ba, bb = BPV[layout]
+            if layout != api.OUT_VERTEX32:                   # dense rows of an odd NV start off 16-byte boundaries: no probe
+                a0, b0, info0 = model.alloc_outputs(layout, ni, 4)
+                assert not info0["probed"] and info0["store_flags"] == 0
+                for x in (a0, b0):
+                    x.free()
+            d_a, d_b, info = model.alloc_outputs(layout, ni, 4, pitch=pitch)
+            assert info["probed"] and info["store_flags"] in (api.OUT_STORES_CACHED, api.OUT_STORES_WRITE_THROUGH), info
+            assert d_a.nbytes == ni * pitch * ba and (d_b is None or d_b.nbytes == ni * pitch * bb)
+            for x in (d_a, d_b):
+                if x is not None:
+                    x.memset(0xFF)
+            scale = 0.1 if layout == api.OUT_VERTEX32 else 1.0
+            flags = api.PALETTE_ON_DEVICE | api.WEIGHTS_ON_DEVICE | api.OUT_ON_DEVICE | api.WEIGHTS_SHARED | info["store_flags"]
+            model.deform_batched_raw(ni, d_w.ptr, d_pal.ptr, d_a.ptr, d_b.ptr if d_b else None, layout, flags, scale, pitch)
+            model.sync()
+            for i in (0, 1, 255, 512, 777, ni - 1):
+                wa, wb = exp.rows(layout, rates, pals[i], scale)
+                for buf, bpv, want, name in ((d_a, ba, wa, "a"), (d_b, bb, wb, "b")):
+                    if not bpv:
+                        continue
+                    row = buf.download((pitch * bpv,), np.uint8, offset=i * pitch * bpv)
+                    assert np.array_equal(row[:nv * bpv], want), f"nv={nv} layout={layout} instance {i} out_{name}"
+                    assert (row[nv * bpv:] == 0xFF).all(), f"nv={nv} layout={layout} instance {i} out_{name}: gap written"
+            for x in (d_a, d_b):
+                if x is not None:
+                    x.free()
+    d_pal.free(); d_w.free()

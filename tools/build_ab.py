@@ -28,6 +28,8 @@ from simple_mmd_renderer_amd.engine import DeformModel, DeviceBuffer  # noqa: E4
 def load(path):
     l = C.CDLL(path)
     for name, (res, args) in api.SIGNATURES.items():
+        if not hasattr(l, name):          # an older build (entry points added since, e.g. the instance-pitch ones)
+            continue
         fn = getattr(l, name)
         fn.restype, fn.argtypes = res, args
     assert l.mmdx_abi_version() == api.ABI_VERSION
