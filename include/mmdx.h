@@ -419,6 +419,7 @@ typedef struct mmdx_vmd_bone_key {            /* one 111-byte VMD bone record mi
 } mmdx_vmd_bone_key;
 
 enum { MMDX_FRAMES_ON_DEVICE = 1u << 0 };     /* with MMDX_OUT_ON_DEVICE for mmdx_morph_motion_eval  */
+enum { MMDX_TIMES_ON_DEVICE = MMDX_FRAMES_ON_DEVICE };   /* the same bit, for the *_time entry points     */
 
 MMDX_API mmdx_status mmdx_vmd_parse(const void *data, size_t size, mmdx_vmd_t *out_vmd);
 MMDX_API mmdx_status mmdx_vmd_load_file(const char *path, mmdx_vmd_t *out_vmd);
@@ -443,6 +444,27 @@ MMDX_API mmdx_status mmdx_morph_motion_get_info(mmdx_morph_motion_t motion, uint
 MMDX_API mmdx_status mmdx_morph_motion_eval(mmdx_morph_motion_t motion, mmdx_model_t model,
                                             uint32_t n_instances, const uint32_t *frames,
                                             uint32_t flags, float *out_weights);
+/* Time-based evaluation: MotionPlayer::SeekTime(double time) (L/motion/poser_impl.inl:548-555), i.e.
+ * Motion::GetMorphPose(name, double time) (L/motion/motion_impl.inl:426-465) and GetBonePose(name, double
+ * time) (:321-380) -- NOT the frame path at frame floor(time * 30):
+ *   1. dframe = time * 30.0 in double; the clamps compare the key frames as doubles: the first key when
+ *      first >= dframe, the last key when last <= dframe;
+ *   2. the bracket is upper_bound(size_t(dframe)) (truncation);
+ *   3. bary = (float)((dframe - left) / (right - left)), a double subtraction and division rounded once to
+ *      float (the frame path: float(frame - left) / float(right - left) in f32);
+ *   4. no exact-hit shortcut: at dframe == a key's frame the left key is interpolated at bary 0 (a curved
+ *      key's first presample, the translation lerp and the renormalising NLerp still run; a morph weight next
+ *      to an infinite one gives NaN), so SeekTime(k / 30.0) may differ from SeekFrame(k) in the last bits;
+ *   5. dframe just below a key can round bary up to 1.0f: the curve's last sample and NLerp's right key;
+ *   6. negative times and -inf give the first key, times past the end and +inf the last key.  NaN is
+ *      undefined in the reference: host times that are NaN are rejected (MMDX_ERR_INVALID_ARGUMENT); device
+ *      times that are NaN take the first key.
+ * times[n_instances] are seconds, one per instance; flags, stream, device and graph rules as for the frame
+ * entry points, MMDX_TIMES_ON_DEVICE (= MMDX_FRAMES_ON_DEVICE) for device times.  Unknown flag bits are
+ * rejected.  out_weights[i][m] = rate of model morph m at times[i]. */
+MMDX_API mmdx_status mmdx_morph_motion_eval_time(mmdx_morph_motion_t motion, mmdx_model_t model,
+                                                 uint32_t n_instances, const double *times,
+                                                 uint32_t flags, float *out_weights);
 MMDX_API void mmdx_morph_motion_destroy(mmdx_morph_motion_t motion);
 
 
@@ -477,6 +499,12 @@ MMDX_API mmdx_status mmdx_bone_motion_get_info(mmdx_bone_motion_t motion, uint32
 MMDX_API mmdx_status mmdx_bone_motion_eval(mmdx_bone_motion_t motion, mmdx_model_t model,
                                            uint32_t n_instances, const uint32_t *frames,
                                            uint32_t flags, float *out_poses);
+/* out_poses[i][b][MMDX_POSE_FLOATS] = local pose of model bone b at times[i] seconds (Motion::GetBonePose(name,
+ * double time), L/motion/motion_impl.inl:321-380; points 1-6 at mmdx_morph_motion_eval_time).  flags:
+ * MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE. */
+MMDX_API mmdx_status mmdx_bone_motion_eval_time(mmdx_bone_motion_t motion, mmdx_model_t model,
+                                                uint32_t n_instances, const double *times,
+                                                uint32_t flags, float *out_poses);
 MMDX_API void mmdx_bone_motion_destroy(mmdx_bone_motion_t motion);
 
 enum {                                        /* bits of the PMX bone flag word the skeleton reads    */
@@ -565,6 +593,12 @@ MMDX_API mmdx_status mmdx_skeleton_solve(mmdx_skeleton_t skeleton, mmdx_model_t 
 MMDX_API mmdx_status mmdx_skeleton_solve_motion(mmdx_skeleton_t skeleton, mmdx_bone_motion_t motion, mmdx_model_t model,
                                                 uint32_t n_instances, const uint32_t *frames, uint32_t flags,
                                                 float *out_palettes);
+/* The same at times[i] seconds: bit for bit mmdx_bone_motion_eval_time followed by mmdx_skeleton_solve (MotionPlayer::SeekTime,
+ * L/motion/poser_impl.inl:548-555; points 1-6 at mmdx_morph_motion_eval_time).  One launch on parallel-FK skeletons of up to
+ * 2 048 bones, else the two launches.  flags: MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE; recordable into a graph. */
+MMDX_API mmdx_status mmdx_skeleton_solve_motion_time(mmdx_skeleton_t skeleton, mmdx_bone_motion_t motion, mmdx_model_t model,
+                                                     uint32_t n_instances, const double *times, uint32_t flags,
+                                                     float *out_palettes);
 /* The same with bone morphs applied first: morph_weights[i][n_morphs] (or one shared row with
  * MMDX_WEIGHTS_SHARED; device pointer with MMDX_WEIGHTS_ON_DEVICE) are the raw per-frame morph rates, the
  * ones mmdx_deform_batched takes.  Bone-morph rotations go through SLerp, i.e. through the device's double

@@ -890,9 +890,10 @@ mmdx_status mmdx_sync(mmdx_model_t m) {
 
 
 // ---- VMD morph motion: device-side evaluation ----------------------------------------------------
-mmdx_status mmdx_morph_motion_eval(mmdx_morph_motion_t mm, mmdx_model_t model, uint32_t n_instances,
-                                   const uint32_t *frames, uint32_t flags, float *out_weights) {
-    if (!mm || !frames || !out_weights || !n_instances)
+// mmdx_morph_motion_eval / _eval_time: frames (uint32_t) or, with `time`, seconds (double)
+static mmdx_status morph_motion_eval(mmdx_morph_motion_t mm, mmdx_model_t model, uint32_t n_instances, const void *clock, bool time,
+                                     uint32_t flags, float *out_weights) {
+    if (!mm || !clock || !out_weights || !n_instances)
         return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
     if (tl_recording_depth > 0 && (flags & (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) != (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory");
@@ -925,19 +926,22 @@ mmdx_status mmdx_morph_motion_eval(mmdx_morph_motion_t mm, mmdx_model_t model, u
     t.key_frames = static_cast<const uint32_t *>(d.frames);
     t.key_weights = static_cast<const float *>(d.weights);
     t.nm = h.nm; t.ni = n_instances;
-    if (flags & MMDX_FRAMES_ON_DEVICE) {
-        t.frames = frames;
-    } else {
-        if (d.frames_in_bytes < size_t(n_instances) * 4) {
+    t.frames = nullptr; t.times = nullptr;
+    const void *dev_clock = clock;
+    if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
+        const size_t clock_bytes = size_t(n_instances) * (time ? 8 : 4);
+        if (d.frames_in_bytes < clock_bytes) {      // grows to 8 bytes per instance: room for frames or times
             if (graph_pinned(&d.pin)) return hip_fail(hipErrorIllegalState, "morph motion frame scratch");
             if (d.frames_in) (void)hipFree(d.frames_in);
             d.frames_in = nullptr; d.frames_in_bytes = 0;
-            HIP_TRY(hipMalloc(&d.frames_in, size_t(n_instances) * 4));
-            d.frames_in_bytes = size_t(n_instances) * 4;
+            HIP_TRY(hipMalloc(&d.frames_in, size_t(n_instances) * 8));
+            d.frames_in_bytes = size_t(n_instances) * 8;
         }
-        HIP_TRY(hipMemcpyAsync(d.frames_in, frames, size_t(n_instances) * 4, hipMemcpyHostToDevice, st));
-        t.frames = static_cast<const uint32_t *>(d.frames_in);
+        HIP_TRY(hipMemcpyAsync(d.frames_in, clock, clock_bytes, hipMemcpyHostToDevice, st));
+        dev_clock = d.frames_in;
     }
+    if (time) t.times = static_cast<const double *>(dev_clock);
+    else t.frames = static_cast<const uint32_t *>(dev_clock);
     const size_t out_bytes = size_t(n_instances) * h.nm * 4;
     if (flags & MMDX_OUT_ON_DEVICE) {
         t.out = out_weights;
@@ -956,9 +960,22 @@ mmdx_status mmdx_morph_motion_eval(mmdx_morph_motion_t mm, mmdx_model_t model, u
         if (out_bytes) HIP_TRY(hipMemcpyAsync(out_weights, t.out, out_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(wait_stream(st));
     } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
-        HIP_TRY(wait_stream(st));   // borrowed host frames must be consumed before returning
+        HIP_TRY(wait_stream(st));   // borrowed host frames / times must be consumed before returning
     }
     return MMDX_OK;
+}
+
+mmdx_status mmdx_morph_motion_eval(mmdx_morph_motion_t mm, mmdx_model_t model, uint32_t n_instances,
+                                   const uint32_t *frames, uint32_t flags, float *out_weights) {
+    return morph_motion_eval(mm, model, n_instances, frames, false, flags, out_weights);
+}
+
+mmdx_status mmdx_morph_motion_eval_time(mmdx_morph_motion_t mm, mmdx_model_t model, uint32_t n_instances,
+                                        const double *times, uint32_t flags, float *out_weights) {
+    if (!mm || !times || !out_weights || !n_instances)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    if (mmdx_status r = check_time_args(times, n_instances, flags, MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) return r;
+    return morph_motion_eval(mm, model, n_instances, times, true, flags, out_weights);
 }
 
 mmdx_status mmdx_graph_begin(mmdx_model_t m) {

@@ -21,6 +21,7 @@
 //   HBM-bound: ~24-32 B written per vertex-instance against ~100 VALU ops; no MFMA (gather of small
 //   mat x vec, <= 3 flop/B).
 #include "kernels.hpp"
+#include "motion_clock.hpp"
 
 #include <type_traits>
 #ifdef PK_STAMPS
@@ -1507,28 +1508,33 @@ __global__ __launch_bounds__(kThreads) void flatten_kernel(const FlattenParams f
 // One thread per (instance, model morph): clamp to the first / last key, exact hit, else the linear
 // blend l*(1-t) + r*t with t = float(frame-left)/float(right-left) (IEEE division: hipcc keeps f32
 // division correctly rounded by default).  A morph without a track keeps rate 0, as after ResetPosing.
+// With a TimeClock: GetMorphPose(name, double time), :426-465 (motion_clock.hpp) -- no exact-hit shortcut,
+// so a key hit still goes through the blend (an infinite neighbour gives NaN there).
+template <class Clock>
 __global__ __launch_bounds__(kThreads) void morph_track_eval_kernel(const MorphTrackParams t) {
     const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
     if (idx >= size_t(t.ni) * t.nm) return;
     const uint32_t i = uint32_t(idx / t.nm), m = uint32_t(idx - size_t(i) * t.nm);
-    const uint32_t b = t.key_off[m], e = t.key_off[m + 1], frame = t.frames[i];
+    const uint32_t b = t.key_off[m], e = t.key_off[m + 1];
+    const Clock clk = clock_of<Clock>(t.frames, t.times, i);
     float w = 0.f;
     if (e > b) {
-        if (t.key_frames[b] >= frame) {
+        if (clk.at_or_before_first(t.key_frames[b])) {
             w = t.key_weights[b];
-        } else if (t.key_frames[e - 1] <= frame) {
+        } else if (clk.at_or_after_last(t.key_frames[e - 1])) {
             w = t.key_weights[e - 1];
         } else {
-            uint32_t lo = b, hi = e - 1;               // key_frames[lo] < frame < key_frames[hi]
+            const uint32_t frame = clk.search();
+            uint32_t lo = b, hi = e - 1;               // key_frames[lo] <= frame < key_frames[hi]
             while (hi - lo > 1) {                      // first key whose frame is > `frame`
                 const uint32_t mid = (lo + hi) / 2;
                 if (t.key_frames[mid] > frame) hi = mid; else lo = mid;
             }
             const uint32_t lf = t.key_frames[lo], rf = t.key_frames[hi];
-            if (lf == frame) {
+            if (clk.exact(lf)) {
                 w = t.key_weights[lo];
             } else {
-                const float bary = float(frame - lf) / float(rf - lf);
+                const float bary = clk.bary(lf, rf);
                 w = t.key_weights[lo] * (1.0f - bary) + t.key_weights[hi] * bary;
             }
         }
@@ -1817,8 +1823,9 @@ hipError_t launch_flatten(const FlattenParams &f, hipStream_t stream) {
 hipError_t launch_morph_track_eval(const MorphTrackParams &t, hipStream_t stream) {
     const size_t n = size_t(t.ni) * t.nm;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(morph_track_eval_kernel, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads),
-                       0, stream, t);
+    const dim3 grid(uint32_t((n + kThreads - 1) / kThreads));
+    if (t.times) hipLaunchKernelGGL(morph_track_eval_kernel<TimeClock>, grid, dim3(kThreads), 0, stream, t);
+    else hipLaunchKernelGGL(morph_track_eval_kernel<FrameClock>, grid, dim3(kThreads), 0, stream, t);
     return hipGetLastError();
 }
 

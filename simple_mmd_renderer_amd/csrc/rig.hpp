@@ -42,6 +42,7 @@ struct BoneTrackParams {
     const uint32_t *frames;                     // [ni]
     float *out;                                 // [ni][nb][8]: t.xyz, 0, q.xyzw
     uint32_t nb, ni;
+    const double *times;                        // [ni] seconds instead of frames (MotionPlayer::SeekTime), or nullptr
 };
 
 // ---- skeleton: local poses -> skinning palette --------------------------------------------------

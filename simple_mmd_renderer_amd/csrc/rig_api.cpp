@@ -112,9 +112,24 @@ static BoneTrackParams motion_params(mmdx_bone_motion_t m, uint32_t n_instances)
     p.key_rot = static_cast<const float *>(m->key_rot.ptr);
     p.key_curve = static_cast<const uint32_t *>(m->key_curve.ptr);
     p.lut = static_cast<const float *>(m->lut.ptr);
-    p.frames = nullptr; p.out = nullptr;
+    p.frames = nullptr; p.out = nullptr; p.times = nullptr;
     p.nb = m->host.nb; p.ni = n_instances;
     return p;
+}
+// the instant of every instance -> the kernel parameters: frame numbers (uint32_t) or, with `time`, seconds (double).  Host
+// operands go through the motion's scratch, sized 8 bytes per instance whenever it grows (room for either).
+static mmdx_status motion_clock_in(mmdx_bone_motion_t m, const void *clock, bool time, uint32_t n_instances, uint32_t flags,
+                                   hipStream_t st, BoneTrackParams &p) {
+    const void *dev = clock;
+    if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
+        const size_t bytes = size_t(n_instances) * (time ? 8 : 4);
+        if (m->frames_in.bytes < bytes) HIP_TRY(m->frames_in.ensure(size_t(n_instances) * 8));
+        HIP_TRY(hipMemcpyAsync(m->frames_in.ptr, clock, bytes, hipMemcpyHostToDevice, st));
+        dev = m->frames_in.ptr;
+    }
+    if (time) p.times = static_cast<const double *>(dev);
+    else p.frames = static_cast<const uint32_t *>(dev);
+    return MMDX_OK;
 }
 static mmdx_status skeleton_to_device(mmdx_skeleton_t s, int device) {
     if (s->device == device) return MMDX_OK;
@@ -143,6 +158,10 @@ static mmdx_status skeleton_to_device(mmdx_skeleton_t s, int device) {
 static mmdx_status skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
                                   const float *morph_weights, uint32_t flags, float *out_palettes, uint32_t passes,
                                   const mmdx_physics_overrides *ov);
+static mmdx_status bone_motion_eval(mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances, const void *clock, bool time,
+                                    uint32_t flags, float *out_poses);
+static mmdx_status skeleton_solve_motion(mmdx_skeleton_t s, mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
+                                         const void *clock, bool time, uint32_t flags, float *out_palettes);
 
 extern "C" {
 
@@ -173,42 +192,17 @@ mmdx_status mmdx_bone_motion_get_info(mmdx_bone_motion_t m, uint32_t *n_bones, u
 
 mmdx_status mmdx_bone_motion_eval(mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
                                   const uint32_t *frames, uint32_t flags, float *out_poses) {
-    if (!m || !frames || !out_poses || !n_instances)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
-    int device;
-    hipStream_t st;
-    if (mmdx_status s = resolve_stream(model, &device, &st)) return s;
-    const BoneMotionHost &h = m->host;
-    if (graph_recording() && ((flags & (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) != (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE) ||
-                              m->device != device))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory and the "
-                                               "motion must have run on this device before");
-    if (mmdx_status r = motion_to_device(m, device)) return r;
-    graph_note_handle(model, &m->pin);
-    BoneTrackParams p = motion_params(m, n_instances);
-    if (flags & MMDX_FRAMES_ON_DEVICE) {
-        p.frames = frames;
-    } else {
-        HIP_TRY(m->frames_in.ensure(size_t(n_instances) * 4));
-        HIP_TRY(hipMemcpyAsync(m->frames_in.ptr, frames, size_t(n_instances) * 4, hipMemcpyHostToDevice, st));
-        p.frames = static_cast<const uint32_t *>(m->frames_in.ptr);
-    }
-    const size_t out_bytes = size_t(n_instances) * h.nb * MMDX_POSE_FLOATS * sizeof(float);
-    if (flags & MMDX_OUT_ON_DEVICE) {
-        p.out = out_poses;
-    } else {
-        HIP_TRY(m->out.ensure(out_bytes));
-        p.out = static_cast<float *>(m->out.ptr);
-    }
-    HIP_TRY(launch_bone_track_eval(p, st));
-    if (!(flags & MMDX_OUT_ON_DEVICE)) {
-        if (out_bytes) HIP_TRY(hipMemcpyAsync(out_poses, p.out, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
-        HIP_TRY(wait_stream(st));   // borrowed host frames must be consumed before returning
-    }
-    return MMDX_OK;
+    return bone_motion_eval(m, model, n_instances, frames, false, flags, out_poses);
 }
+
+mmdx_status mmdx_bone_motion_eval_time(mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
+                                       const double *times, uint32_t flags, float *out_poses) {
+    if (!m || !times || !out_poses || !n_instances)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    if (mmdx_status r = check_time_args(times, n_instances, flags, MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) return r;
+    return bone_motion_eval(m, model, n_instances, times, true, flags, out_poses);
+}
+
 
 void mmdx_bone_motion_destroy(mmdx_bone_motion_t m) {
     if (!m) return;
@@ -257,68 +251,15 @@ mmdx_status mmdx_skeleton_get_info(mmdx_skeleton_t s, mmdx_skeleton_info *info) 
 
 mmdx_status mmdx_skeleton_solve_motion(mmdx_skeleton_t s, mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
                                        const uint32_t *frames, uint32_t flags, float *out_palettes) {
-    if (!s || !m || !frames || !out_palettes || !n_instances)
+    return skeleton_solve_motion(s, m, model, n_instances, frames, false, flags, out_palettes);
+}
+
+mmdx_status mmdx_skeleton_solve_motion_time(mmdx_skeleton_t s, mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
+                                            const double *times, uint32_t flags, float *out_palettes) {
+    if (!s || !m || !times || !out_palettes || !n_instances)
         return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
-    if (m->host.nb != s->plan.nb)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "the motion was bound to " + std::to_string(m->host.nb) + " bones, the skeleton has " +
-                                               std::to_string(s->plan.nb));
-    int device;
-    hipStream_t st;
-    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
-    const SkeletonPlan &pl = s->plan;
-    const size_t pose_bytes = size_t(n_instances) * pl.nb * MMDX_POSE_FLOATS * sizeof(float);
-    if (pl.serial || size_t(pl.nb) * 32 > kMotionFkMaxLds) {
-        // append bones / IK (the ordered solver) or a skeleton too large for the LDS pose table: the two launches, the poses in the
-        // motion's scratch buffer
-        if (graph_recording() && m->out.bytes < pose_bytes)
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "run the call once before recording: it sizes the motion's pose buffer");
-        if (mmdx_status r = motion_to_device(m, device)) return r;
-        HIP_TRY(m->out.ensure(pose_bytes));
-        if (mmdx_status r = mmdx_bone_motion_eval(m, model, n_instances, frames, (flags & MMDX_FRAMES_ON_DEVICE) | MMDX_OUT_ON_DEVICE,
-                                                  static_cast<float *>(m->out.ptr)))
-            return r;
-        return mmdx_skeleton_solve(s, model, n_instances, static_cast<const float *>(m->out.ptr),
-                                   MMDX_POSES_ON_DEVICE | (flags & MMDX_OUT_ON_DEVICE), out_palettes);
-    }
-    if (graph_recording() && ((flags & (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) != (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE) ||
-                              m->device != device || s->device != device))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory and the motion "
-                                               "and the skeleton must have run on this device before");
-    if (mmdx_status r = motion_to_device(m, device)) return r;
-    if (mmdx_status r = skeleton_to_device(s, device)) return r;
-    graph_note_handle(model, &m->pin);
-    graph_note_handle(model, &s->pin);
-    BoneTrackParams tp = motion_params(m, n_instances);
-    if (flags & MMDX_FRAMES_ON_DEVICE) {
-        tp.frames = frames;
-    } else {
-        HIP_TRY(m->frames_in.ensure(size_t(n_instances) * 4));
-        HIP_TRY(hipMemcpyAsync(m->frames_in.ptr, frames, size_t(n_instances) * 4, hipMemcpyHostToDevice, st));
-        tp.frames = static_cast<const uint32_t *>(m->frames_in.ptr);
-    }
-    const size_t out_bytes = size_t(n_instances) * pl.nb * 16 * sizeof(float);
-    SkeletonParams fp;
-    fp.morph = nullptr;
-    fp.poses = nullptr;
-    if (flags & MMDX_OUT_ON_DEVICE) {
-        fp.out = out_palettes;
-    } else {
-        HIP_TRY(s->out.ensure(out_bytes));
-        fp.out = static_cast<float *>(s->out.ptr);
-    }
-    fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
-    fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
-    fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
-    fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
-    fp.nb = pl.nb; fp.ni = n_instances;
-    HIP_TRY(launch_motion_fk(tp, fp, st));
-    if (!(flags & MMDX_OUT_ON_DEVICE)) {
-        HIP_TRY(hipMemcpyAsync(out_palettes, fp.out, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
-        HIP_TRY(wait_stream(st));                    // the borrowed host frame numbers must be consumed before returning
-    }
-    return MMDX_OK;
+    if (mmdx_status r = check_time_args(times, n_instances, flags, MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) return r;
+    return skeleton_solve_motion(s, m, model, n_instances, times, true, flags, out_palettes);
 }
 
 mmdx_status mmdx_skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
@@ -494,4 +435,99 @@ extern "C" void mmdx_skeleton_destroy(mmdx_skeleton_t s) {
     if (s->device >= 0) (void)hipSetDevice(s->device);
     s->release_all();
     delete s;
+}
+
+// mmdx_bone_motion_eval / _eval_time: frames (uint32_t) or, with `time`, seconds (double)
+static mmdx_status bone_motion_eval(mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances, const void *clock, bool time,
+                                    uint32_t flags, float *out_poses) {
+    if (!m || !clock || !out_poses || !n_instances)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    int device;
+    hipStream_t st;
+    if (mmdx_status s = resolve_stream(model, &device, &st)) return s;
+    const BoneMotionHost &h = m->host;
+    if (graph_recording() && ((flags & (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) != (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE) ||
+                              m->device != device))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory and the "
+                                               "motion must have run on this device before");
+    if (mmdx_status r = motion_to_device(m, device)) return r;
+    graph_note_handle(model, &m->pin);
+    BoneTrackParams p = motion_params(m, n_instances);
+    if (mmdx_status r = motion_clock_in(m, clock, time, n_instances, flags, st, p)) return r;
+    const size_t out_bytes = size_t(n_instances) * h.nb * MMDX_POSE_FLOATS * sizeof(float);
+    if (flags & MMDX_OUT_ON_DEVICE) {
+        p.out = out_poses;
+    } else {
+        HIP_TRY(m->out.ensure(out_bytes));
+        p.out = static_cast<float *>(m->out.ptr);
+    }
+    HIP_TRY(launch_bone_track_eval(p, st));
+    if (!(flags & MMDX_OUT_ON_DEVICE)) {
+        if (out_bytes) HIP_TRY(hipMemcpyAsync(out_poses, p.out, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(wait_stream(st));
+    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
+        HIP_TRY(wait_stream(st));   // borrowed host frames / times must be consumed before returning
+    }
+    return MMDX_OK;
+}
+
+// mmdx_skeleton_solve_motion / _time: frames (uint32_t) or, with `time`, seconds (double)
+static mmdx_status skeleton_solve_motion(mmdx_skeleton_t s, mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
+                                         const void *clock, bool time, uint32_t flags, float *out_palettes) {
+    if (!s || !m || !clock || !out_palettes || !n_instances)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    if (m->host.nb != s->plan.nb)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "the motion was bound to " + std::to_string(m->host.nb) + " bones, the skeleton has " +
+                                               std::to_string(s->plan.nb));
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const SkeletonPlan &pl = s->plan;
+    const size_t pose_bytes = size_t(n_instances) * pl.nb * MMDX_POSE_FLOATS * sizeof(float);
+    if (pl.serial || size_t(pl.nb) * 32 > kMotionFkMaxLds) {
+        // append bones / IK (the ordered solver) or a skeleton too large for the LDS pose table: the two launches, the poses in the
+        // motion's scratch buffer
+        if (graph_recording() && m->out.bytes < pose_bytes)
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "run the call once before recording: it sizes the motion's pose buffer");
+        if (mmdx_status r = motion_to_device(m, device)) return r;
+        HIP_TRY(m->out.ensure(pose_bytes));
+        if (mmdx_status r = bone_motion_eval(m, model, n_instances, clock, time, (flags & MMDX_FRAMES_ON_DEVICE) | MMDX_OUT_ON_DEVICE,
+                                             static_cast<float *>(m->out.ptr)))
+            return r;
+        return mmdx_skeleton_solve(s, model, n_instances, static_cast<const float *>(m->out.ptr),
+                                   MMDX_POSES_ON_DEVICE | (flags & MMDX_OUT_ON_DEVICE), out_palettes);
+    }
+    if (graph_recording() && ((flags & (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) != (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE) ||
+                              m->device != device || s->device != device))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory and the motion "
+                                               "and the skeleton must have run on this device before");
+    if (mmdx_status r = motion_to_device(m, device)) return r;
+    if (mmdx_status r = skeleton_to_device(s, device)) return r;
+    graph_note_handle(model, &m->pin);
+    graph_note_handle(model, &s->pin);
+    BoneTrackParams tp = motion_params(m, n_instances);
+    if (mmdx_status r = motion_clock_in(m, clock, time, n_instances, flags, st, tp)) return r;
+    const size_t out_bytes = size_t(n_instances) * pl.nb * 16 * sizeof(float);
+    SkeletonParams fp;
+    fp.morph = nullptr;
+    fp.poses = nullptr;
+    if (flags & MMDX_OUT_ON_DEVICE) {
+        fp.out = out_palettes;
+    } else {
+        HIP_TRY(s->out.ensure(out_bytes));
+        fp.out = static_cast<float *>(s->out.ptr);
+    }
+    fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
+    fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
+    fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
+    fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
+    fp.nb = pl.nb; fp.ni = n_instances;
+    HIP_TRY(launch_motion_fk(tp, fp, st));
+    if (!(flags & MMDX_OUT_ON_DEVICE)) {
+        HIP_TRY(hipMemcpyAsync(out_palettes, fp.out, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(wait_stream(st));
+    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
+        HIP_TRY(wait_stream(st));                    // the borrowed host frame numbers / times must be consumed before returning
+    }
+    return MMDX_OK;
 }

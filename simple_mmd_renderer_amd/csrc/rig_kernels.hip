@@ -1,10 +1,11 @@
 // rig_kernels.hip -- per-frame producers of the bone palette, gfx950.
-//   bone_track_eval_kernel : VMD bone tracks -> local poses, one thread per (instance, bone)
+//   bone_track_eval_kernel : VMD bone tracks -> local poses, one thread per (instance, bone), at frames or at times (motion_clock.hpp)
 //   skeleton_fk_kernel     : local poses -> float[16] skinning palettes, one thread per (instance, bone)
 // Both follow the reference's float operation order exactly (file built with -ffp-contract=off), so the
 // palettes are bit-identical to libmmd's and the deform kernel downstream stays bit-exact end to end.
 #include <hip/hip_runtime.h>
 
+#include "motion_clock.hpp"
 #include "rig.hpp"
 #include "rig_kernels.hpp"
 
@@ -29,28 +30,32 @@ __device__ __forceinline__ float curve_at(const float *lut, uint32_t id, float x
     return t[kCurveSamples - 1];
 }
 
-// Motion::GetBonePose(name, frame), L/motion/motion_impl.inl:255-319: the local pose (translation, rotation) of one bone at one frame.
-__device__ __forceinline__ void eval_bone_pose(const BoneTrackParams &p, uint32_t bone, uint32_t frame, float4 &t_out, float4 &q_out) {
+// Motion::GetBonePose(name, frame), L/motion/motion_impl.inl:255-319: the local pose (translation, rotation) of one bone at one
+// frame; with a TimeClock GetBonePose(name, time), :321-380 (motion_clock.hpp: the clamps, the search key, no exact-hit shortcut,
+// bary in double).  The curve lookup and the NLerp are the same code for both.
+template <class Clock>
+__device__ __forceinline__ void eval_bone_pose(const BoneTrackParams &p, uint32_t bone, const Clock clk, float4 &t_out, float4 &q_out) {
     const uint32_t b = p.key_off[bone], e = p.key_off[bone + 1];
     const float4 *tr = reinterpret_cast<const float4 *>(p.key_tr);
     const float4 *rot = reinterpret_cast<const float4 *>(p.key_rot);
     float4 t = make_float4(0.f, 0.f, 0.f, 0.f), q = make_float4(0.f, 0.f, 0.f, 1.f);   // Poser::ResetPosing
     if (e > b) {
-        if (p.key_frame[b] >= frame) {
+        if (clk.at_or_before_first(p.key_frame[b])) {
             t = tr[b]; q = rot[b];
-        } else if (p.key_frame[e - 1] <= frame) {
+        } else if (clk.at_or_after_last(p.key_frame[e - 1])) {
             t = tr[e - 1]; q = rot[e - 1];
         } else {
+            const uint32_t frame = clk.search();
             uint32_t lo = b, hi = e - 1;                   // key_frame[lo] <= frame < key_frame[hi]
             while (hi - lo > 1) {
                 const uint32_t mid = (lo + hi) / 2;
                 if (p.key_frame[mid] > frame) hi = mid; else lo = mid;
             }
             const uint32_t lf = p.key_frame[lo], rf = p.key_frame[hi];
-            if (lf == frame) {
+            if (clk.exact(lf)) {
                 t = tr[lo]; q = rot[lo];
             } else {
-                const float bary = float(frame - lf) / float(rf - lf);
+                const float bary = clk.bary(lf, rf);
                 const uint4 cv = reinterpret_cast<const uint4 *>(p.key_curve)[lo];   // the LEFT key's curves
                 const float4 lt = tr[lo], rt = tr[hi], lq = rot[lo], rq = rot[hi];
                 float lam = curve_at(p.lut, cv.x, bary);
@@ -88,12 +93,13 @@ __device__ __forceinline__ void eval_bone_pose(const BoneTrackParams &p, uint32_
     q_out = q;
 }
 
+template <class Clock>
 __global__ __launch_bounds__(kRigThreads) void bone_track_eval_kernel(const BoneTrackParams p) {
     const size_t idx = size_t(blockIdx.x) * kRigThreads + threadIdx.x;
     if (idx >= size_t(p.ni) * p.nb) return;
     const uint32_t i = uint32_t(idx / p.nb), bone = uint32_t(idx - size_t(i) * p.nb);
     float4 t, q;
-    eval_bone_pose(p, bone, p.frames[i], t, q);
+    eval_bone_pose(p, bone, clock_of<Clock>(p.frames, p.times, i), t, q);
     float4 *out = reinterpret_cast<float4 *>(p.out) + idx * 2;
     out[0] = t;
     out[1] = q;
@@ -192,13 +198,15 @@ __global__ __launch_bounds__(kRigThreads) void skeleton_fk_kernel(const Skeleton
 // threads evaluate the bones' local poses at the instance's frame into LDS (eval_bone_pose: what bone_track_eval_kernel writes to
 // HBM), one barrier, then every thread rebuilds its bones' matrices from those poses (fk_bone: what skeleton_fk_kernel does from
 // HBM).  The same two functions, so the same bits; the [NI][NB][8] pose array never leaves the chip (it is still written out when
-// the caller asks for it: t.out != nullptr).
+// the caller asks for it: t.out != nullptr).  The instance's clock (frame, or time * 30.0) is read once per workgroup.
+template <class Clock>
 __global__ __launch_bounds__(1024) void motion_fk_kernel(const BoneTrackParams t, const SkeletonParams p) {
     extern __shared__ float4 pose_lds[];                 // [nb][2]
-    const uint32_t i = blockIdx.x, frame = t.frames[i];
+    const uint32_t i = blockIdx.x;
+    const Clock clk = clock_of<Clock>(t.frames, t.times, i);
     for (uint32_t b = threadIdx.x; b < p.nb; b += blockDim.x) {   // one bone per thread up to 1 024 bones: one latency chain, not several
         float4 tr, q;
-        eval_bone_pose(t, b, frame, tr, q);
+        eval_bone_pose(t, b, clk, tr, q);
         pose_lds[2 * b] = tr;
         pose_lds[2 * b + 1] = q;
         if (t.out) {
@@ -1182,8 +1190,9 @@ hipError_t launch_physics_override(const PhysicsParams &p, hipStream_t stream) {
 hipError_t launch_bone_track_eval(const BoneTrackParams &p, hipStream_t stream) {
     const size_t n = size_t(p.ni) * p.nb;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(bone_track_eval_kernel, dim3(uint32_t((n + kRigThreads - 1) / kRigThreads)),
-                       dim3(kRigThreads), 0, stream, p);
+    const dim3 grid(uint32_t((n + kRigThreads - 1) / kRigThreads));
+    if (p.times) hipLaunchKernelGGL(bone_track_eval_kernel<TimeClock>, grid, dim3(kRigThreads), 0, stream, p);
+    else hipLaunchKernelGGL(bone_track_eval_kernel<FrameClock>, grid, dim3(kRigThreads), 0, stream, p);
     return hipGetLastError();
 }
 
@@ -1200,7 +1209,8 @@ hipError_t launch_motion_fk(const BoneTrackParams &t, const SkeletonParams &p, h
     const size_t lds = size_t(p.nb) * 32;
     if (lds > kMotionFkMaxLds) return hipErrorInvalidValue;                  // callers check: the two-launch path takes over
     const uint32_t threads = std::min<uint32_t>(1024u, (p.nb + 63u) / 64u * 64u);
-    hipLaunchKernelGGL(motion_fk_kernel, dim3(p.ni), dim3(threads), lds, stream, t, p);
+    if (t.times) hipLaunchKernelGGL(motion_fk_kernel<TimeClock>, dim3(p.ni), dim3(threads), lds, stream, t, p);
+    else hipLaunchKernelGGL(motion_fk_kernel<FrameClock>, dim3(p.ni), dim3(threads), lds, stream, t, p);
     return hipGetLastError();
 }
 

@@ -277,3 +277,11 @@ void mmdx_morph_motion_destroy(mmdx_morph_motion_t mm) {
 }
 
 }  // extern "C"
+
+mmdx_status mmdx::check_time_args(const double *times, uint32_t n_instances, uint32_t flags, uint32_t allowed) {
+    if (flags & ~allowed) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    if (!(flags & MMDX_TIMES_ON_DEVICE))
+        for (uint32_t i = 0; i < n_instances; ++i)
+            if (times[i] != times[i]) return fail(MMDX_ERR_INVALID_ARGUMENT, "times[" + std::to_string(i) + "] is NaN");
+    return MMDX_OK;
+}

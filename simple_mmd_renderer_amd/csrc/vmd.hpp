@@ -21,7 +21,8 @@ struct MorphMotionHost {          // keyframes of every model morph, model-morph
 
 struct MorphMotionDevice {        // owned by api.cpp (hipMalloc / hipFree)
     void *key_off = nullptr, *frames = nullptr, *weights = nullptr;
-    void *frames_in = nullptr, *out = nullptr;   // per-call scratch for host-pointer callers
+    void *frames_in = nullptr, *out = nullptr;   // per-call scratch for host-pointer callers (frames_in: 8 bytes per instance,
+                                                 // room for the double times of mmdx_morph_motion_eval_time)
     size_t frames_in_bytes = 0, out_bytes = 0;
     int device = -1;
     GraphPin pin;                 // recorded graphs that hold these addresses
@@ -38,12 +39,17 @@ struct VmdBoneTracks {            // views into a parsed motion, valid until mmd
 };
 VmdBoneTracks vmd_bone_tracks(const mmdx_vmd_s *v);
 
+// The argument checks the *_time entry points share beyond NULL / n_instances: flag bits outside `allowed`, and NaN in
+// host-resident times (size_t(NaN) is undefined behaviour in the reference; device times that are NaN take the first key).
+mmdx_status check_time_args(const double *times, uint32_t n_instances, uint32_t flags, uint32_t allowed);
+
 struct MorphTrackParams {
     const uint32_t *key_off, *key_frames;
     const float *key_weights;
     const uint32_t *frames;       // [ni] frame number of every instance
     float *out;                   // [ni][nm]
     uint32_t nm, ni;
+    const double *times;          // [ni] seconds instead of frames (MotionPlayer::SeekTime), or nullptr
 };
 
 }  // namespace mmdx

@@ -282,8 +282,8 @@ private:
 };
 
 // = mmd::MotionPlayer: associates the motion's tracks with the poser's bones and morphs by name at
-// construction; SeekFrame evaluates every track at `frame` (on the device) and hands the results to the
-// poser through SetMorphPose / SetBonePose, like the reference's loop over its name maps.
+// construction; SeekFrame / SeekTime evaluate every track at `frame` / `time` seconds (on the device) and hand the results to
+// the poser through SetMorphPose / SetBonePose, like the reference's loop over its name maps.
 class MotionPlayer {
 public:
     MotionPlayer(const Motion &motion, Poser &poser) : poser_(poser) {
@@ -310,6 +310,15 @@ public:
             check(mmdx_morph_motion_eval(morphs_, poser_.handle(), 1, &f, 0, poser_.morph_rates().data()));
         if (poser_.bone_count())
             check(mmdx_bone_motion_eval(bones_, poser_.handle(), 1, &f, 0, poser_.bone_poses().data()));
+    }
+    // = MotionPlayer::SeekTime (L/motion/poser_impl.inl:548-555): every track at `time` seconds, interpolated at the fractional
+    // frame time * 30 the way the reference's GetMorphPose / GetBonePose(name, double time) do (include/mmdx.h,
+    // mmdx_morph_motion_eval_time).  Not SeekFrame(size_t(time * 30)): that steps at 30 fps whatever the display rate.
+    void SeekTime(double time) {
+        if (poser_.morph_count())
+            check(mmdx_morph_motion_eval_time(morphs_, poser_.handle(), 1, &time, 0, poser_.morph_rates().data()));
+        if (poser_.bone_count())
+            check(mmdx_bone_motion_eval_time(bones_, poser_.handle(), 1, &time, 0, poser_.bone_poses().data()));
     }
     uint32_t mapped_bones() const { return mapped_bones_; }
 

@@ -1,7 +1,8 @@
 // motion_example.cpp -- the reference's whole per-frame sequence (main.cpp:1786-1825) from files, without
 // libmmd: model + rig from a .pmx / .pmd, motion from a .vmd, every step on the GPU behind the C ABI.
 //   g++ -std=c++17 -O2 motion_example.cpp -I../../include -L.. -lmmdx -Wl,-rpath,'$ORIGIN/..' -o motion_example
-//   ./motion_example model.pmx motion.vmd [frames]
+//   ./motion_example model.pmx motion.vmd [frames [hz]]
+// With `hz` the loop runs at that display rate: step n seeks to n / hz seconds (MotionPlayer::SeekTime) instead of frame n.
 // Prints per-run checksums so tests can compare with the Python path over the same C ABI.
 #include <cstdio>
 #include <cstdlib>
@@ -16,17 +17,19 @@ static uint64_t checksum(const void *p, size_t n) {
 }
 
 int main(int argc, char **argv) {
-    if (argc < 3) { std::printf("usage: %s model.pmx|.pmd motion.vmd [frames]\n", argv[0]); return 64; }
+    if (argc < 3) { std::printf("usage: %s model.pmx|.pmd motion.vmd [frames [hz]]\n", argv[0]); return 64; }
     try {
         std::unique_ptr<mmdx::Poser> poser(mmdx::Poser::FromFile(argv[1]));
         mmdx::Motion motion(argv[2]);
         mmdx::MotionPlayer player(motion, *poser);
         const size_t frames = argc > 3 ? size_t(std::atoi(argv[3])) : motion.GetLength() + 1;
+        const double hz = argc > 4 ? std::atof(argv[4]) : 0.0;
         std::vector<mmdx::Vertex> vertices;
         uint64_t h = 0;
         for (size_t frame = 0; frame < frames; ++frame) {
             poser->ResetPosing();                 // main.cpp:1788
-            player.SeekFrame(frame);              // :1795
+            if (hz > 0.0) player.SeekTime(double(frame) / hz);   // a display-rate loop: the time, not a frame number
+            else player.SeekFrame(frame);         // :1795
             poser->PrePhysicsPosing();            // :1801  (physics would React() here and overwrite its bones)
             poser->PostPhysicsPosing();           // :1810
             poser->Deform();                      // :1821

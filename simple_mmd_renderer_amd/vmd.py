@@ -144,6 +144,19 @@ class MorphMotion:
         api.check(api.lib().mmdx_morph_motion_eval(self.h, model.h if model is not None else None, n_instances,
                                                    frames_ptr, 1 | api.OUT_ON_DEVICE, out_ptr))
 
+    def eval_time(self, times, model=None) -> np.ndarray:
+        """Host convenience: times in seconds f64 [NI] -> rates f32 [NI, NM] (MotionPlayer::SeekTime's morph half)."""
+        t = np.ascontiguousarray(times, np.float64).reshape(-1)
+        out = np.empty((t.size, self.nm), np.float32)
+        api.check(api.lib().mmdx_morph_motion_eval_time(self.h, model.h if model is not None else None, t.size,
+                                                        t.ctypes.data, 0, out.ctypes.data))
+        return out
+
+    def eval_time_device(self, n_instances: int, times_ptr, out_ptr, model=None) -> None:
+        """times f64[NI] (seconds) and out f32[NI][NM] resident in HBM; asynchronous on the model's stream."""
+        api.check(api.lib().mmdx_morph_motion_eval_time(self.h, model.h if model is not None else None, n_instances,
+                                                        times_ptr, TIMES_ON_DEVICE | api.OUT_ON_DEVICE, out_ptr))
+
     def close(self):
         if getattr(self, "h", None):
             api.lib().mmdx_morph_motion_destroy(self.h)
@@ -157,6 +170,7 @@ class MorphMotion:
 
 
 FRAMES_ON_DEVICE = 1 << 0
+TIMES_ON_DEVICE = FRAMES_ON_DEVICE       # the same bit for the *_time entry points
 POSES_ON_DEVICE = 1 << 4
 POSE_FLOATS = 8
 
@@ -187,6 +201,19 @@ class BoneMotion:
         """frames u32[NI] and out f32[NI][NB][8] resident in HBM; asynchronous on the model's stream."""
         api.check(api.lib().mmdx_bone_motion_eval(self.h, model.h if model is not None else None, n_instances,
                                                   frames_ptr, FRAMES_ON_DEVICE | api.OUT_ON_DEVICE, out_ptr))
+
+    def eval_time(self, times, model=None) -> np.ndarray:
+        """Host convenience: times in seconds f64 [NI] -> poses f32 [NI, NB, 8] (Motion::GetBonePose(name, double time))."""
+        t = np.ascontiguousarray(times, np.float64).reshape(-1)
+        out = np.empty((t.size, self.nb, POSE_FLOATS), np.float32)
+        api.check(api.lib().mmdx_bone_motion_eval_time(self.h, model.h if model is not None else None, t.size,
+                                                       t.ctypes.data, 0, out.ctypes.data))
+        return out
+
+    def eval_time_device(self, n_instances: int, times_ptr, out_ptr, model=None) -> None:
+        """times f64[NI] (seconds) and out f32[NI][NB][8] resident in HBM; asynchronous on the model's stream."""
+        api.check(api.lib().mmdx_bone_motion_eval_time(self.h, model.h if model is not None else None, n_instances,
+                                                       times_ptr, TIMES_ON_DEVICE | api.OUT_ON_DEVICE, out_ptr))
 
     def close(self):
         if getattr(self, "h", None):
@@ -337,6 +364,19 @@ class Skeleton:
         """Frame numbers and palettes resident in HBM; asynchronous on the model's stream."""
         api.check(api.lib().mmdx_skeleton_solve_motion(self.h, motion.h, model.h if model is not None else None, n_instances,
                                                        frames_ptr, FRAMES_ON_DEVICE | api.OUT_ON_DEVICE, out_ptr))
+
+    def solve_motion_time(self, motion: "BoneMotion", times, model=None) -> np.ndarray:
+        """Host convenience: times in seconds f64 [NI] -> palettes f32 [NI, NB, 16] (= solve(motion.eval_time(times)))."""
+        t = np.ascontiguousarray(times, np.float64).reshape(-1)
+        out = np.empty((t.size, self.nb, 16), np.float32)
+        api.check(api.lib().mmdx_skeleton_solve_motion_time(self.h, motion.h, model.h if model is not None else None, t.size,
+                                                            t.ctypes.data, 0, out.ctypes.data))
+        return out
+
+    def solve_motion_time_device(self, motion: "BoneMotion", n_instances: int, times_ptr, out_ptr, model=None) -> None:
+        """Times (f64 seconds) and palettes resident in HBM; asynchronous on the model's stream."""
+        api.check(api.lib().mmdx_skeleton_solve_motion_time(self.h, motion.h, model.h if model is not None else None, n_instances,
+                                                            times_ptr, TIMES_ON_DEVICE | api.OUT_ON_DEVICE, out_ptr))
 
     def solve_device(self, n_instances: int, poses_ptr, out_ptr, model=None, weights_ptr=None, shared=False) -> None:
         """poses, palettes (and morph rates) resident in HBM; asynchronous on the model's stream."""

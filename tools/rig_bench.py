@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
 """The palette producers alone (bone tracks -> poses -> palettes for 1024 instances x 300 bones): FK rig, append rig, IK rig.
+Every rig also as one call at times in seconds (mmdx_skeleton_solve_motion_time, MotionPlayer::SeekTime) next to the frame leg.
 Small enough to run under rocprofv3 (tools/profile_round.sh)."""
 import os
 import sys
@@ -31,6 +32,7 @@ rigs["ik40"] = vmdmod.Skeleton(*rig40)
 # quarter of the SIMDs -- what does the solver do when the chip is filled?); RIG_ONLY=ik restricts the rigs
 for ni in [int(x) for x in os.environ.get("RIG_NI", "1024").split(",")]:
     d_fr = DeviceBuffer.from_numpy(((np.arange(ni) * 7) % 600).astype(np.uint32))
+    d_t = DeviceBuffer.from_numpy(((np.arange(ni) * 7) % 600) / 30.0 + (np.arange(ni) % 5) / 144.0)   # the same, sub-frame offsets
     d_pose, d_pal = DeviceBuffer(ni * m.nb * 32), DeviceBuffer(ni * m.nb * 64)
     for name, sk in rigs.items():
         if os.environ.get("RIG_ONLY") and name not in os.environ["RIG_ONLY"].split(","):
@@ -39,7 +41,9 @@ for ni in [int(x) for x in os.environ.get("RIG_NI", "1024").split(",")]:
         ms = bench.time_calls(dm, lambda: (bm.eval_device(ni, d_fr.ptr, d_pose.ptr, dm), sk.solve_device(ni, d_pose.ptr, d_pal.ptr, dm)),
                               iters)
         ms1 = bench.time_calls(dm, lambda: sk.solve_motion_device(bm, ni, d_fr.ptr, d_pal.ptr, dm), iters)
+        mst = bench.time_calls(dm, lambda: sk.solve_motion_time_device(bm, ni, d_t.ptr, d_pal.ptr, dm), iters)
         print(f"{name:7s} rig: poses + palettes of {ni:6d} x {m.nb} bones  {ms * 1e3:9.1f} us   as one call {ms1 * 1e3:9.1f} us   "
+              f"at times {mst * 1e3:9.1f} us ({(mst / ms1 - 1) * 100:+5.1f} %)   "
               f"{ni * 1e-6 / (ms * 1e-3):8.2f} M palettes/s   solver {sk.info['solver']} rounds {sk.info['n_solve_rounds']}", flush=True)
-    for b in (d_fr, d_pose, d_pal):
+    for b in (d_fr, d_t, d_pose, d_pal):
         b.free()
