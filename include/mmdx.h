@@ -58,7 +58,8 @@ extern "C" {
  *    verdict into mmdx_deform_args.flags); shared morph rates that did not change are detected by the library itself.
  *    Added later without a version change (additive, same struct sizes): MMDX_OUT_PITCHED with
  *    mmdx_deform_args.out_instance_pitch (was reserved0), mmdx_model_output_pitch, mmdx_crowd_output_alloc_pitched.  A library
- *    without them rejects the flag bit as unknown, so a caller that needs pitched outputs fails loudly there. */
+ *    without them rejects the flag bit as unknown, so a caller that needs pitched outputs fails loudly there.
+ *    mmdx_deform_batched_bounds (a new entry point; mmdx_deform_args unchanged). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -282,6 +283,23 @@ MMDX_API mmdx_status mmdx_deform_vertex32(mmdx_model_t model, const float *morph
 /* General / crowd form.  Asynchronous on the handle's stream when every pointer is a device pointer;
  * otherwise returns after the copies have completed. */
 MMDX_API mmdx_status mmdx_deform_batched(mmdx_model_t model, const mmdx_deform_args *args);
+/* mmdx_deform_batched plus where every instance ended up, for culling, LOD and shadow-frustum fitting without reading the
+ * vertices back or passing over them again: out_bounds[i][6] = {min x, min y, min z, max x, max y, max z} of instance i.
+ * Everything else is exactly mmdx_deform_batched(model, args): same flags, layouts, pitch, morph modes, output paths, graph
+ * recording and validation (unknown flag bits included); the outputs are bit-identical.
+ * Contract:
+ *  - bounds are taken over the positions AS WRITTEN: vertices [0, NV) of the instance, never the pitch gap; pos_scale applied;
+ *    for MMDX_OUT_SOA_POS16 the binary16 values widened to f32.  So every bound is a value that occurs in the output.
+ *  - comparisons follow IEEE rules: NaN coordinates are skipped, a component that is NaN at every vertex gives NaN, +-inf take
+ *    part, -0.0 and +0.0 compare equal (which of the two is returned is unspecified).
+ *  - out_bounds lives where the outputs live: a device pointer (4-byte aligned) with MMDX_OUT_ON_DEVICE, written in the
+ *    model's stream order like the outputs; otherwise a host pointer, filled when the call returns.  NULL is
+ *    MMDX_ERR_INVALID_ARGUMENT.
+ * Routes: a single frame that mmdx_deform_batched gives to its one-frame kernel (MMDX_FRAME_KERNEL) and per-instance weights
+ * under the opt-in MMDX_FUSED_PACK=1 run the crowd kernel's bounds flavour instead.  That flavour stores cached: a bounds call
+ * accepts MMDX_OUT_STORES_WRITE_THROUGH and ignores it.  The per-(instance, tile) partial bounds live in a per-call scratch
+ * buffer of the handle, which a recorded graph pins like the others (see the graph section). */
+MMDX_API mmdx_status mmdx_deform_batched_bounds(mmdx_model_t model, const mmdx_deform_args *args, float *out_bounds /*[NI][6]*/);
 MMDX_API mmdx_status mmdx_sync(mmdx_model_t model);
 
 /* ---- plain device-memory helpers (thin hipMalloc / hipMemcpy wrappers) ----------------------- */

@@ -80,6 +80,7 @@ SIGNATURES = {
     "mmdx_deform": (C.c_int32, [C.c_void_p, _f32p, _f32p, _f32p, _f32p]),
     "mmdx_deform_vertex32": (C.c_int32, [C.c_void_p, _f32p, _f32p, C.c_float, C.c_void_p]),
     "mmdx_deform_batched": (C.c_int32, [C.c_void_p, C.POINTER(DeformArgs)]),
+    "mmdx_deform_batched_bounds": (C.c_int32, [C.c_void_p, C.POINTER(DeformArgs), C.c_void_p]),
     "mmdx_sync": (C.c_int32, [C.c_void_p]),
     "mmdx_timer_start": (C.c_int32, [C.c_void_p]),
     "mmdx_timer_stop": (C.c_int32, [C.c_void_p, _f32p]),

@@ -200,7 +200,7 @@ void free_model(mmdx_model_s *m) {
         for (DevBuf *b : {&m->tiles, &m->spos, &m->snrm, &m->suv, &m->perm, &m->skin1, &m->skin2_ids,
                           &m->skin2_w, &m->skin4_ids, &m->skin4_w, &m->bone_list, &m->ell,
                           &m->entries, &m->slot_top, &m->chain_off, &m->chain_rate, &m->pal, &m->rates,
-                          &m->wslot, &m->morphed, &m->seen, &m->out_a, &m->out_b})
+                          &m->wslot, &m->morphed, &m->seen, &m->out_a, &m->out_b, &m->bnd})
             b->release();
         if (m->bounce) (void)hipHostFree(m->bounce);
         if (m->bounce_in) (void)hipHostFree(m->bounce_in);
@@ -481,7 +481,8 @@ mmdx_status mmdx_model_set_stream(mmdx_model_t m, void *hip_stream) {
     return MMDX_OK;
 }
 
-mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
+// mmdx_deform_batched and, with out_bounds != nullptr, mmdx_deform_batched_bounds
+static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, float *out_bounds) {
     if (!m || !a) return fail(MMDX_ERR_INVALID_ARGUMENT, "model / args is NULL");
     if (a->struct_size != sizeof(mmdx_deform_args))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_deform_args.struct_size mismatch");
@@ -527,6 +528,12 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
             return fail(MMDX_ERR_INVALID_ARGUMENT, "out_a / out_b points to device memory: pass MMDX_OUT_ON_DEVICE");
         if (!host_direct_enabled()) map_a = map_b = nullptr;
     }
+    // bounds live where the outputs live
+    const bool bounds = out_bounds != nullptr;
+    if (bounds && (a->flags & MMDX_OUT_ON_DEVICE) && (reinterpret_cast<uintptr_t>(out_bounds) & 3))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "device out_bounds must be 4-byte aligned");
+    if (bounds && !(a->flags & MMDX_OUT_ON_DEVICE) && classify_pointer(out_bounds, &map_unused) == PtrKind::Device)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "out_bounds points to device memory: pass MMDX_OUT_ON_DEVICE");
     if (m->capturing) {
         if (mmdx_status rst = recording_thread_check(m)) return rst;
         const uint32_t need = MMDX_PALETTE_ON_DEVICE | MMDX_OUT_ON_DEVICE | (p.ns ? uint32_t(MMDX_WEIGHTS_ON_DEVICE) : 0u);
@@ -724,7 +731,8 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
     }
     // ---- store flavour: only where the launch shape has the write-through flavour, and only for outputs in device memory (stores
     // into mapped host memory cross PCIe whatever their cache bits say) ------------------------------------------------------------
-    dp.write_through = out_dev && deform_has_write_through(threads, int(layout), morph, p.f16, dp.tile_order != 0) &&
+    // (the bounds flavour has no write-through variant: its calls store cached whatever the hint says)
+    dp.write_through = !bounds && out_dev && deform_has_write_through(threads, int(layout), morph, p.f16, dp.tile_order != 0) &&
                        write_through_for(bytes_a + bytes_b, a->flags) ? 1u : 0u;
     m->last_write_through = dp.write_through != 0;
     // ---- group size (instances per workgroup) from the LDS budget ---------------------------------
@@ -762,7 +770,9 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
     // the walk and the skinning of one CU do not overlap in either kernel (walk alone 132 us + skinning alone 254 us), and packs of 4
     // walk the table twice as often as packs of 8.  Kept for the A/B, not the default.  Two-array layouts in original vertex order.
     // The group: as many instances (multiple of 4, up to 16) as keep three workgroups on a CU, else as fit two.
-    bool pack = morph == kMorphFused4 && ov.fused_pack != 0 && kTileVerts == 512 && !dp.tile_order && layout != MMDX_OUT_VERTEX32 && !ov.threads;
+    // (bounds calls keep deform_kernel's bounds flavour: the pack kernel, an archived A/B, has none)
+    bool pack = !bounds && morph == kMorphFused4 && ov.fused_pack != 0 && kTileVerts == 512 && !dp.tile_order && layout != MMDX_OUT_VERTEX32 &&
+                !ov.threads;
     size_t lds = 0;
     if (pack) {
         uint32_t so, wo, mo;
@@ -787,6 +797,20 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
     if (!pack) {
         dp.group = group;
         lds = deform_lds_bytes(threads, layout, morph, group, p.max_tile_bones, p.ns, &dp.stage_off, &dp.w_off, dp.tile_order != 0);
+        if (bounds && !dp.tile_order) {
+            dp.bounds_off = uint32_t(lds);
+            lds += kBoundsLdsBytes;
+        }
+    }
+    // bounds: the kernel's partials, then the reduce into the caller's device array -- or into the tail of the same scratch, copied
+    // out to the host array next to the outputs
+    const uint32_t bounds_units = bounds ? deform_bounds_units(threads, p.ntiles, dp.tile_order != 0) : 0u;
+    float *bounds_dev = nullptr;
+    if (bounds) {
+        const size_t part = size_t(ni) * bounds_units * 24;
+        HIP_TRY(m->bnd.ensure(part + (out_dev ? 0 : size_t(ni) * 24)));
+        dp.bounds = static_cast<float *>(m->bnd.ptr);
+        bounds_dev = out_dev ? out_bounds : reinterpret_cast<float *>(static_cast<unsigned char *>(m->bnd.ptr) + part);
     }
     if (lds > 160 * 1024)
         return fail(MMDX_ERR_UNSUPPORTED, "tile needs " + std::to_string(lds) + " bytes of LDS (> 160 KiB): "
@@ -801,7 +825,8 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
     // Outputs in mapped host memory keep the tile kernel: its 16-byte coalesced stores are what crosses PCIe well.
     // Models with fewer tiles than the chip has CUs only (config 2: 6.3 us against the tile kernel's 6.9); a large model fills the
     // chip with whole tiles and is better off with their coalesced stores (config 5: 14.9 us against 15.2).
-    const bool frame = one_frame && !out_direct && !out_bounce && (ov.frame_kernel == 2 || (ov.frame_kernel == 1 && p.ntiles < 256));
+    // (bounds calls take the tile kernel's bounds flavour: the frame kernel has none)
+    const bool frame = !bounds && one_frame && !out_direct && !out_bounce && (ov.frame_kernel == 2 || (ov.frame_kernel == 1 && p.ntiles < 256));
     if (frame) {
         DeformParams fp = dp;
         fp.morphed = nullptr;                                  // nothing reads a single frame's morphed positions later
@@ -813,6 +838,7 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
         HIP_TRY((fast ? launch_pack_fast : launch_pack)(int(layout), p.f16, dp, p.ntiles, lds, st));
     } else {
         HIP_TRY((fast ? launch_deform_fast : launch_deform)(threads, int(layout), morph, p.f16, dp, p.ntiles, lds, st));
+        if (bounds) HIP_TRY(launch_bounds_reduce(dp.bounds, bounds_units, ni, bounds_dev, st));
     }
     if (pev) {
         HIP_TRY(hipEventRecord(pev[1], st));
@@ -835,6 +861,7 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
                 if (bytes_b) HIP_TRY(hipMemcpyAsync(a->out_b, dp.out_b, bytes_b, hipMemcpyDeviceToHost, st));
             }
         }
+        if (bounds) HIP_TRY(hipMemcpyAsync(out_bounds, bounds_dev, size_t(ni) * 24, hipMemcpyDeviceToHost, st));
         HIP_TRY(wait_stream(st));
         if (out_bounce && spread) {
             const unsigned char *sa = static_cast<const unsigned char *>(m->bounce), *sb = sa + off_b;
@@ -852,6 +879,13 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) {
         HIP_TRY(wait_stream(st));
     }
     return MMDX_OK;
+}
+
+mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) { return deform_batched(m, a, nullptr); }
+
+mmdx_status mmdx_deform_batched_bounds(mmdx_model_t m, const mmdx_deform_args *a, float *out_bounds) {
+    if (!out_bounds) return fail(MMDX_ERR_INVALID_ARGUMENT, "out_bounds is NULL");
+    return deform_batched(m, a, out_bounds);
 }
 
 mmdx_status mmdx_deform(mmdx_model_t m, const float *w, const float *palette, float *out_pos,

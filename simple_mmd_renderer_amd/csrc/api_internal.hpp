@@ -92,6 +92,7 @@ struct mmdx_model_s {
     // per-call scratch (grown on demand, reused)
     mmdx::DevBuf pal, rates, wslot, morphed, out_a, out_b;
     mmdx::DevBuf seen;              // RatesSeen record (kernels.hpp): the rates `morphed` was last computed from, device side
+    mmdx::DevBuf bnd;               // mmdx_deform_batched_bounds: partial bounds, then (host bounds) the [NI][6] result
     bool morphed_valid = false;     // `morphed` holds the result of a shared morph pass (MMDX_MORPH_UNCHANGED)
     std::vector<float> host_rates;  // ... and the host's copy of those rates when they came from host memory
     bool host_rates_valid = false;
@@ -103,7 +104,7 @@ struct mmdx_model_s {
     bool rec_poisoned = false;          // one of them was destroyed before mmdx_graph_end: the recording cannot become a graph
     bool last_write_through = false;          // store flavour of the last crowd launch (mmdx_debug_last_store_policy)
     mmdx_model_s() {
-        for (mmdx::DevBuf *b : {&pal, &rates, &wslot, &morphed, &out_a, &out_b}) b->pin = &pin;
+        for (mmdx::DevBuf *b : {&pal, &rates, &wslot, &morphed, &out_a, &out_b, &bnd}) b->pin = &pin;
     }
     // page-locked bounce buffer for small outputs bound for pageable host memory (see mmdx_deform_batched)
     void *bounce = nullptr, *bounce_dev = nullptr;  // host address, device-side address

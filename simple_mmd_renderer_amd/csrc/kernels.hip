@@ -668,20 +668,81 @@ __device__ __forceinline__ M12 skin_matrix(const Slot &q, const float4 *P) {
     return m;
 }
 
+// ---- per-instance bounds (mmdx_deform_batched_bounds) ------------------------------------------------------------------------
+// min / max with IEEE minNum / maxNum (v_min_f32 / v_max_f32, IEEE mode): a NaN operand is skipped, so NaN is the identity and a
+// component that is NaN everywhere stays NaN; the result is always one of the operands (bit for bit, up to NaN payloads).
+template <bool MAX>
+__device__ __forceinline__ float bound_op(float a, float b) { return MAX ? fmaxf(a, b) : fminf(a, b); }
+// Across lanes the comparison runs on ordered integer keys (signed order of the keys = numeric order of the floats, -0 just below
+// +0; key2f(f2key(x)) == x bit for bit): an integer min / max takes its DPP operand directly, where the float one would first have
+// to quiet the moved value (a v_max_f32 x, x per step) -- a third of the instructions.
+__device__ __forceinline__ int f2key(float x) { const int b = __float_as_int(x); return b ^ ((b >> 31) & 0x7fffffff); }
+__device__ __forceinline__ float key2f(int k) { return __int_as_float(k ^ ((k >> 31) & 0x7fffffff)); }
+template <bool MAX>
+__device__ __forceinline__ int key_op(int a, int b) { return MAX ? max(a, b) : min(a, b); }
+template <int CTRL>
+__device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, false); }
+// one DPP step of the six keys at once (independent chains: they fill each other's DPP wait states)
+template <int CTRL>
+__device__ __forceinline__ void dpp_step6(int (&k)[6]) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) k[c] = c < 3 ? key_op<false>(k[c], dpp_i<CTRL>(k[c])) : key_op<true>(k[c], dpp_i<CTRL>(k[c]));
+}
+// Lane c < 6 of the calling wave gets component c of {min x, min y, min z, max x, max y, max z} over the wave's lanes, NaN lanes
+// skipped (NaN when every lane holds NaN): four DPP steps inside each row of 16 lanes (none of them reads outside its row), then
+// the four row results through readlane.
+__device__ __forceinline__ float wave_bounds6(const float (&mn)[3], const float (&mx)[3], uint32_t lane) {
+    int k[6];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {                           // a NaN lane's key loses against every value
+        k[c] = mn[c] != mn[c] ? INT_MAX : f2key(mn[c]);
+        k[3 + c] = mx[c] != mx[c] ? INT_MIN : f2key(mx[c]);
+    }
+    dpp_step6<0xb1>(k);        // quad_perm [1,0,3,2]
+    dpp_step6<0x4e>(k);        // quad_perm [2,3,0,1]
+    dpp_step6<0x141>(k);       // row_half_mirror
+    dpp_step6<0x140>(k);       // row_mirror: every lane of a row holds the row's result
+    int r[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        const int a = __builtin_amdgcn_readlane(k[c], 0), b = __builtin_amdgcn_readlane(k[c], 16);
+        const int d = __builtin_amdgcn_readlane(k[c], 32), e = __builtin_amdgcn_readlane(k[c], 48);
+        r[c] = c < 3 ? key_op<false>(key_op<false>(a, b), key_op<false>(d, e)) : key_op<true>(key_op<true>(a, b), key_op<true>(d, e));
+    }
+    const int s = lane == 0 ? r[0] : lane == 1 ? r[1] : lane == 2 ? r[2] : lane == 3 ? r[3] : lane == 4 ? r[4] : r[5];
+    return s == (lane < 3 ? INT_MAX : INT_MIN) ? __builtin_nanf("") : key2f(s);
+}
+
+// Where one instance's bounds go in a bounds launch: `lds` = the combine words of the instance's image parity (image path: one
+// group of 6 per wave), `out` = its partial(s) in p.bounds -- one group of 6 per tile, or per wave of a tile for tile-order outputs.
+struct BoundsOut {
+    float *lds;
+    float *out;
+};
+
 // One instance: skin the thread's slots with the palette at P (LDS), scatter the results to the LDS image `img`
 // (undoing the class sort), ONE workgroup barrier, then write the image out with coalesced 16-byte stores.
 // `inst` = the instance's index in the output arrays, cxy / cz = the (morphed) positions of the thread's slots.
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
 // `after_barrier`: called between the barrier and the copy-out -- whatever it requests from memory is in the queue IN FRONT of this
 // instance's stores (vmcnt is in order: a load issued behind them would wait for their drain).
-template <int THREADS, int LAYOUT, int VPT, bool TILE, bool ALL_FAST, bool WT = false, typename Hook = NoHook>
+// BOUNDS: also the min / max of the positions as written (pos_scale applied, binary16 widened back), reduced over the wave in
+// registers, then over the workgroup through `bo.lds` across the barrier the image already needs (tile order: no barrier, one
+// partial per wave).
+template <int THREADS, int LAYOUT, int VPT, bool TILE, bool ALL_FAST, bool WT = false, bool BOUNDS = false, typename Hook = NoHook>
 __device__ __forceinline__ void skin_instance(const DeformParams &p, const Slot (&sl)[VPT], const float4 *P,
                                               unsigned char *img, uint32_t inst, uint32_t v0, uint32_t nvt,
-                                              const v2f (&cxy)[VPT], const float (&cz)[VPT], int tid, Hook after_barrier = Hook()) {
+                                              const v2f (&cxy)[VPT], const float (&cz)[VPT], int tid, Hook after_barrier = Hook(),
+                                              BoundsOut bo = BoundsOut{nullptr, nullptr}) {
     const size_t vbase = size_t(inst) * p.pitch + v0;  // first output vertex of this tile
     const bool al = p.out_aligned != 0;
     const uint32_t sh4 = al ? uint32_t((vbase * 3) & 3) : 0u;
     const uint32_t sh8 = al ? uint32_t((vbase * 3) & 7) : 0u;
+    float bmn[3], bmx[3];
+    if constexpr (BOUNDS) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) bmn[c] = bmx[c] = __builtin_nanf("");
+    }
 #pragma unroll
     for (int k = 0; k < VPT; ++k) {
         const Slot &q = sl[k];
@@ -694,6 +755,15 @@ __device__ __forceinline__ void skin_instance(const DeformParams &p, const Slot 
         // pos_scale is a separate multiply after the transform (main.cpp:848-850); x*1.0f == x
         oxy = oxy * p.pos_scale;
         oz = oz * p.pos_scale;
+        if constexpr (BOUNDS) {
+            float w[3] = {oxy.x, oxy.y, oz};
+            if constexpr (LAYOUT == MMDX_OUT_SOA_POS16) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) w[c] = h2f(f2h(w[c]));      // the value as stored
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { bmn[c] = bound_op<false>(bmn[c], w[c]); bmx[c] = bound_op<true>(bmx[c], w[c]); }
+        }
         if constexpr (TILE) {
             // MMDX_CREATE_TILE_ORDER (a compile-time variant: the default kernels' code is untouched by it): the vertex keeps its sorted slot in the output -- consecutive lanes write consecutive
             // vertices (12 / 32 / 6 bytes apart) straight from registers: no image, no barrier, no wave waits for another
@@ -734,9 +804,25 @@ __device__ __forceinline__ void skin_instance(const DeformParams &p, const Slot 
             B[0] = rxy.x; B[1] = rxy.y; B[2] = rz;
         }
     }
+    if constexpr (BOUNDS) {
+        const uint32_t lane = uint32_t(tid) & 63u, wave = uint32_t(tid) >> 6;
+        const float v = wave_bounds6(bmn, bmx, lane);
+        if (lane < 6) (TILE ? bo.out : bo.lds)[wave * 6 + lane] = v;
+    }
     if constexpr (TILE) return;
     __syncthreads();
     after_barrier();
+    if constexpr (BOUNDS) {
+        // the waves' partials -> this (instance, tile)'s.  The words of this parity are rewritten two instances later, after the
+        // next instance's barrier, which no wave passes before these reads are done.
+        if (tid < 6) {
+            float r = bo.lds[tid];
+#pragma unroll
+            for (int w = 1; w < THREADS / 64; ++w)
+                r = tid < 3 ? bound_op<false>(r, bo.lds[w * 6 + tid]) : bound_op<true>(r, bo.lds[w * 6 + tid]);
+            bo.out[tid] = r;
+        }
+    }
     // ALL_FAST: the kernel found, once per workgroup, that every instance of this full tile starts on a 16-byte boundary; the
     // generic copy-out is then not even compiled into the instance loop (1-2 % of the crowd step: measured)
     const bool fast = ALL_FAST || (al && nvt == kTileVerts && sh4 == 0 && sh8 == 0);
@@ -800,7 +886,12 @@ __device__ __forceinline__ void fused4_walk(const void *entries, uint32_t rb, ui
 
 // ---- the deformation kernel ----------------------------------------------------------------------
 // THREADS = 512: one sorted slot per lane, 8 waves per workgroup; THREADS = 256: two slots per lane.
-template <int THREADS, int LAYOUT, int MORPH, bool F16, bool TILE, bool WT = false>
+// BOUNDS: the flavour of mmdx_deform_batched_bounds -- the same outputs, bit for bit, plus 6 floats of partial bounds per (instance,
+// tile), per (instance, tile, wave) for tile-order outputs, in p.bounds, which bounds_reduce_kernel folds into [NI][6].  Only with
+// WT = false: bounds calls store cached (api.cpp), no write-through bounds variant is built.
+// (A template parameter of this kernel, not a device function shared by two kernels: that wrapping alone moved the register
+// allocation of the per-instance-morph kernels by +-2 VGPRs; this way BOUNDS = false is the previous kernel's code.)
+template <int THREADS, int LAYOUT, int MORPH, bool F16, bool TILE, bool WT = false, bool BOUNDS = false>
 __global__ __launch_bounds__(THREADS) void deform_kernel(const DeformParams p) {
     constexpr int VPT = int(kTileVerts) / THREADS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -866,8 +957,14 @@ __global__ __launch_bounds__(THREADS) void deform_kernel(const DeformParams p) {
     constexpr bool kAllFast = decltype(all_fast_tag)::value;
     // the image is double buffered: the next instance writes the other one, so one barrier per instance is enough
     auto run_instance = [&](uint32_t g, const v2f (&cxy)[VPT], const float (&cz)[VPT], auto hook) {
-        skin_instance<THREADS, LAYOUT, VPT, TILE, kAllFast, WT>(p, sl, pal + size_t(g) * p.pal_stride, stage + buf * kStage,
-                                                           inst0 + g * istep, v0, nvt, cxy, cz, tid, hook);
+        BoundsOut bo{nullptr, nullptr};
+        if constexpr (BOUNDS) {
+            constexpr uint32_t kUnits = TILE ? uint32_t(THREADS) / 64u : 1u;    // partials per (instance, tile)
+            bo.lds = reinterpret_cast<float *>(smem + p.bounds_off) + buf * 48u;
+            bo.out = p.bounds + (size_t(inst0 + g * istep) * p.ntiles + tile) * kUnits * 6u;
+        }
+        skin_instance<THREADS, LAYOUT, VPT, TILE, kAllFast, WT, BOUNDS>(p, sl, pal + size_t(g) * p.pal_stride, stage + buf * kStage,
+                                                                   inst0 + g * istep, v0, nvt, cxy, cz, tid, hook, bo);
         buf ^= 1u;
     };
 
@@ -1035,6 +1132,7 @@ __global__ __launch_bounds__(THREADS) void deform_kernel(const DeformParams p) {
         else instances(std::false_type{});
     }
 }
+
 
 // ---- per-instance morph weights, second shape (round 4): packs of 4 instances, walk and skinning in SEPARATE phases -------------
 // deform_kernel<512, ., kMorphFused4> holds, at the same time, the walk's accumulators for 8 instances, the entries in flight, the
@@ -1577,39 +1675,74 @@ __global__ __launch_bounds__(kThreads) void pattern_fill_kernel(float4 *a, float
     }
 }
 
+// ---- per-instance bounds from the partials of deform_kernel<..., BOUNDS>: one wave per instance, out[i][6] -----------------------
+// (min / max only: the same kernel serves fast-math models)
+__global__ __launch_bounds__(64) void bounds_reduce_kernel(const float *part, float *out, uint32_t units) {
+    const uint32_t lane = threadIdx.x;
+    const float *src = part + size_t(blockIdx.x) * units * 6;
+    float mn[3], mx[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) mn[c] = mx[c] = __builtin_nanf("");
+    for (uint32_t u = lane; u < units; u += 64) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            mn[c] = bound_op<false>(mn[c], src[size_t(u) * 6 + c]);
+            mx[c] = bound_op<true>(mx[c], src[size_t(u) * 6 + 3 + c]);
+        }
+    }
+    const float v = wave_bounds6(mn, mx, lane);
+    if (lane < 6) out[size_t(blockIdx.x) * 6 + lane] = v;
+}
+
 #endif  // !MMDX_FAST_MATH
 
 using KernelFn = void (*)(const DeformParams);
 
-template <int THREADS, int LAYOUT, bool F16, bool TILE>
+template <int THREADS, int LAYOUT, bool F16, bool TILE, bool BOUNDS>
 KernelFn pick_morph(int morph) {
-    switch (morph) {
-    case kMorphNone: return deform_kernel<THREADS, LAYOUT, kMorphNone, F16, TILE>;
-    case kMorphShared: return deform_kernel<THREADS, LAYOUT, kMorphShared, F16, TILE>;
-    case kMorphFused1: return deform_kernel<THREADS, LAYOUT, kMorphFused1, F16, TILE>;
-    default: return deform_kernel<THREADS, LAYOUT, kMorphFused4, F16, TILE>;
+    if constexpr (BOUNDS) {
+        switch (morph) {
+        case kMorphNone: return deform_kernel<THREADS, LAYOUT, kMorphNone, F16, TILE, false, true>;
+        case kMorphShared: return deform_kernel<THREADS, LAYOUT, kMorphShared, F16, TILE, false, true>;
+        case kMorphFused1: return deform_kernel<THREADS, LAYOUT, kMorphFused1, F16, TILE, false, true>;
+        default: return deform_kernel<THREADS, LAYOUT, kMorphFused4, F16, TILE, false, true>;
+        }
+    } else {
+        switch (morph) {
+        case kMorphNone: return deform_kernel<THREADS, LAYOUT, kMorphNone, F16, TILE>;
+        case kMorphShared: return deform_kernel<THREADS, LAYOUT, kMorphShared, F16, TILE>;
+        case kMorphFused1: return deform_kernel<THREADS, LAYOUT, kMorphFused1, F16, TILE>;
+        default: return deform_kernel<THREADS, LAYOUT, kMorphFused4, F16, TILE>;
+        }
     }
 }
 
-template <int THREADS, bool TILE>
+template <int THREADS, bool TILE, bool BOUNDS>
 KernelFn pick_t(int layout, int morph, bool f16) {
-    if (f16) return layout == MMDX_OUT_SOA_POS16 ? pick_morph<THREADS, MMDX_OUT_SOA_POS16, true, TILE>(morph) : nullptr;
-    if (layout == MMDX_OUT_SOA) return pick_morph<THREADS, MMDX_OUT_SOA, false, TILE>(morph);
-    if (layout == MMDX_OUT_VERTEX32) return pick_morph<THREADS, MMDX_OUT_VERTEX32, false, TILE>(morph);
+    if (f16) return layout == MMDX_OUT_SOA_POS16 ? pick_morph<THREADS, MMDX_OUT_SOA_POS16, true, TILE, BOUNDS>(morph) : nullptr;
+    if (layout == MMDX_OUT_SOA) return pick_morph<THREADS, MMDX_OUT_SOA, false, TILE, BOUNDS>(morph);
+    if (layout == MMDX_OUT_VERTEX32) return pick_morph<THREADS, MMDX_OUT_VERTEX32, false, TILE, BOUNDS>(morph);
     return nullptr;
+}
+
+template <bool BOUNDS>
+KernelFn pick_b(int threads, int layout, int morph, bool f16, bool tile) {
+#if MMDX_TILE >= 512
+    if (threads != 256) return tile ? pick_t<512, true, BOUNDS>(layout, morph, f16) : pick_t<512, false, BOUNDS>(layout, morph, f16);
+#endif
+    return tile ? pick_t<256, true, BOUNDS>(layout, morph, f16) : pick_t<256, false, BOUNDS>(layout, morph, f16);
 }
 
 // tile = outputs in the engine's vertex order (MMDX_CREATE_TILE_ORDER): the direct-store variants.
 // wt = write-through stores (CopyFast): instantiated where it was measured to pay -- the SoA f32 crowd kernels (256 threads, no
 // morphs or shared morphs, original vertex order); every other shape keeps its nt stores whatever the hint says.
-KernelFn pick(int threads, int layout, int morph, bool f16, bool tile, bool wt = false) {
+// bounds = the BOUNDS flavour (mmdx_deform_batched_bounds): every shape, nt stores only.
+KernelFn pick(int threads, int layout, int morph, bool f16, bool tile, bool wt = false, bool bounds = false) {
+    if (bounds) return pick_b<true>(threads, layout, morph, f16, tile);
     if (wt && deform_has_write_through(threads, layout, morph, f16, tile))
         return morph == kMorphNone ? deform_kernel<256, MMDX_OUT_SOA, kMorphNone, false, false, true>
                                    : deform_kernel<256, MMDX_OUT_SOA, kMorphShared, false, false, true>;
-#if MMDX_TILE >= 512
-    if (threads != 256) return tile ? pick_t<512, true>(layout, morph, f16) : pick_t<512, false>(layout, morph, f16);
-#endif
-    return tile ? pick_t<256, true>(layout, morph, f16) : pick_t<256, false>(layout, morph, f16);
+    return pick_b<false>(threads, layout, morph, f16, tile);
 }
 
 }  // namespace
@@ -1728,8 +1861,8 @@ hipError_t MMDX_K(prepare_kernels)() {
     for (int threads = 256; threads <= 512; threads += 256)
       for (int f16 = 0; f16 < 2; ++f16)
         for (int layout = 0; layout < 3; ++layout)
-            for (int morph = 0; morph < 8; ++morph) {
-                KernelFn fn = pick(threads, layout, morph & 3, f16 != 0, morph >= 4);
+            for (int morph = 0; morph < 16; ++morph) {
+                KernelFn fn = pick(threads, layout, morph & 3, f16 != 0, (morph & 4) != 0, false, morph >= 8);
                 if (!fn) continue;
                 hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1756,7 +1889,7 @@ hipError_t MMDX_K(prepare_kernels)() {
 
 hipError_t MMDX_K(launch_deform)(int threads, int layout, int morph, bool f16, const DeformParams &p,
                          uint32_t ntiles, size_t lds_bytes, hipStream_t stream) {
-    KernelFn fn = pick(threads, layout, morph, f16, p.tile_order != 0, p.write_through != 0);
+    KernelFn fn = pick(threads, layout, morph, f16, p.tile_order != 0, p.write_through != 0, p.bounds != nullptr);
     if (!fn) return hipErrorInvalidValue;
     DeformParams q = p;
     q.ntiles = ntiles;
@@ -1808,6 +1941,11 @@ hipError_t launch_pattern_fill(void *a, void *b, uint32_t nv, uint32_t ni, uint3
     hipLaunchKernelGGL(pattern_fill_kernel, dim3(ntiles * ((ni + 15) / 16)), dim3(kThreads), 0, stream,
                        reinterpret_cast<float4 *>(a), reinterpret_cast<float4 *>(b), nv, ni, ntiles, bpva, bpvb,
                        pitch ? pitch : nv);
+    return hipGetLastError();
+}
+
+hipError_t launch_bounds_reduce(const float *partials, uint32_t units, uint32_t ni, float *out, hipStream_t stream) {
+    hipLaunchKernelGGL(bounds_reduce_kernel, dim3(ni), dim3(64), 0, stream, partials, out, units);
     return hipGetLastError();
 }
 

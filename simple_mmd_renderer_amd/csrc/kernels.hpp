@@ -74,7 +74,19 @@ struct DeformParams {
     uint32_t *morph_seen;        // kMorphFused1 crowds: the handle's RatesSeen record; a launch that overwrites `morphed` clears its
                                  // valid word (the record no longer describes what `morphed` holds)
     uint32_t nv;                 // vertices of the model
+    // mmdx_deform_batched_bounds (behind every field the other kernels read, so their argument layout does not move):
+    uint32_t bounds_off;         // byte offset in dynamic LDS of the combine words (kBoundsLdsBytes; image path only)
+    float *bounds;               // partial bounds, 6 floats per deform_bounds_units(); nullptr = the plain deform_kernel
 };
+
+// Partial bounds (6 floats) per instance of a bounds launch: one per tile, or one per wave of a tile for tile-order outputs (no
+// per-instance barrier there to combine the waves' partials).  `threads` as passed to launch_deform.
+inline uint32_t deform_bounds_units(int threads, uint32_t ntiles, bool tile_order) {
+    return tile_order ? ntiles * ((threads == 256 || kTileVerts < 512) ? 256u : 512u) / 64u : ntiles;
+}
+constexpr uint32_t kBoundsLdsBytes = 2 * 8 * 6 * 4;     // combine words: 2 instance parities x up to 8 waves x 6 floats
+// out[i][6] = bounds of instance i from the partials ([ni][units][6]), on `stream` behind the bounds launch
+hipError_t launch_bounds_reduce(const float *partials, uint32_t units, uint32_t ni, float *out, hipStream_t stream);
 
 // Device-side record of the morph rates the `morphed` buffer of a handle was last computed from (shared morph pass of a crowd):
 // morph_apply_kernel compares the call's rates with it, bit for bit, and skips its walk when they are equal -- the automatic form of

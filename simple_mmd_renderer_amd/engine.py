@@ -293,8 +293,10 @@ class DeformModel:
                       "fill_GBs": info.fill_GBs, "store_flags": int(info.store_flags)}
 
     def deform_batched_raw(self, ni: int, weights_ptr, palettes_ptr, out_a_ptr, out_b_ptr, layout: int,
-                           flags: int, pos_scale: float = 1.0, pitch: int = 0) -> None:
-        """pitch: instance pitch of the outputs in vertices (MMDX_OUT_PITCHED); 0 = dense [ni][NV]."""
+                           flags: int, pos_scale: float = 1.0, pitch: int = 0, bounds_ptr=None) -> None:
+        """pitch: instance pitch of the outputs in vertices (MMDX_OUT_PITCHED); 0 = dense [ni][NV].
+        bounds_ptr: f32 [ni][6] {min xyz, max xyz} of every instance's written positions (mmdx_deform_batched_bounds), where the
+        outputs live: a device pointer with OUT_ON_DEVICE, else a host pointer."""
         a = api.DeformArgs()
         a.struct_size = C.sizeof(api.DeformArgs)
         if pitch:
@@ -304,13 +306,17 @@ class DeformModel:
         a.morph_weights, a.palettes = weights_ptr, palettes_ptr
         a.out_a, a.out_b = out_a_ptr, out_b_ptr
         a.pos_scale = pos_scale
-        api.check(api.lib().mmdx_deform_batched(self.h, C.byref(a)))
+        if bounds_ptr is None:
+            api.check(api.lib().mmdx_deform_batched(self.h, C.byref(a)))
+        else:
+            api.check(api.lib().mmdx_deform_batched_bounds(self.h, C.byref(a), bounds_ptr))
 
     def deform_batched(self, weights, palettes, layout: int = api.OUT_SOA, shared_weights: bool = False,
-                       pos_scale: float = 1.0, pitch: int = 0):
+                       pos_scale: float = 1.0, pitch: int = 0, bounds: bool = False):
         """Host arrays in, host arrays out (copies + sync inside the call).
         weights [NI,NM] (or [NM] with shared_weights); palettes [NI,NB,16].  pitch: the call writes [NI][pitch]-vertex host
-        arrays (MMDX_OUT_PITCHED); the [:, :NV] views of them are returned."""
+        arrays (MMDX_OUT_PITCHED); the [:, :NV] views of them are returned.  bounds: one more result, f32 [NI,6] = {min x,
+        min y, min z, max x, max y, max z} of each instance's positions as written (mmdx_deform_batched_bounds)."""
         pal = _c(palettes, np.float32).reshape(-1, self.nb, 16)
         ni = pal.shape[0]
         w = _c(weights, np.float32)
@@ -327,12 +333,15 @@ class DeformModel:
         else:
             oa = np.empty((ni, rows, 3), np.float16)
             ob = np.empty((ni, rows, 3), np.float32)
+        bnd = np.empty((ni, 6), np.float32) if bounds else None
         self.deform_batched_raw(ni, w.ctypes.data if w.size else None, pal.ctypes.data, oa.ctypes.data,
-                                ob.ctypes.data if ob is not None else None, layout, flags, pos_scale, pitch)
+                                ob.ctypes.data if ob is not None else None, layout, flags, pos_scale, pitch,
+                                bnd.ctypes.data if bounds else None)
         if pitch:
             oa = oa[:, :self.nv]
             ob = ob[:, :self.nv] if ob is not None else None
-        return (oa, ob) if ob is not None else oa
+        out = (oa, ob) if ob is not None else (oa,)
+        return out + (bnd,) if bounds else (out if ob is not None else oa)
 
     def sync(self) -> None:
         api.check(api.lib().mmdx_sync(self.h))
