@@ -59,7 +59,8 @@ extern "C" {
  *    Added later without a version change (additive, same struct sizes): MMDX_OUT_PITCHED with
  *    mmdx_deform_args.out_instance_pitch (was reserved0), mmdx_model_output_pitch, mmdx_crowd_output_alloc_pitched.  A library
  *    without them rejects the flag bit as unknown, so a caller that needs pitched outputs fails loudly there.
- *    mmdx_deform_batched_bounds (a new entry point; mmdx_deform_args unchanged). */
+ *    mmdx_deform_batched_bounds (a new entry point; mmdx_deform_args unchanged).
+ *    mmdx_deform_batched_select with mmdx_instance_select (a new entry point and structure; mmdx_deform_args unchanged). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -300,6 +301,47 @@ MMDX_API mmdx_status mmdx_deform_batched(mmdx_model_t model, const mmdx_deform_a
  * accepts MMDX_OUT_STORES_WRITE_THROUGH and ignores it.  The per-(instance, tile) partial bounds live in a per-call scratch
  * buffer of the handle, which a recorded graph pins like the others (see the graph section). */
 MMDX_API mmdx_status mmdx_deform_batched_bounds(mmdx_model_t model, const mmdx_deform_args *args, float *out_bounds /*[NI][6]*/);
+
+/* ---- deforming a subset of a crowd: an instance list and a count that may live in device memory -------------------------------
+ * For a renderer that has decided ON THE GPU (from mmdx_deform_batched_bounds' result, say) which instances are in view:
+ * no read-back, no re-packing of palettes, every instance keeps its slot of the vertex buffer. */
+enum { MMDX_SELECT_ON_DEVICE = 1u << 0 };   /* ids and count are device pointers (else host memory, copied per call) */
+typedef struct mmdx_instance_select {
+    uint32_t struct_size;   /* = sizeof(mmdx_instance_select)                                                        */
+    uint32_t flags;         /* MMDX_SELECT_*; unknown bits are MMDX_ERR_INVALID_ARGUMENT                              */
+    const uint32_t *ids;    /* [n_ids] instance indices into the call's arrays, any order                            */
+    const uint32_t *count;  /* optional: how many leading ids are in use; NULL = n_ids; lives where ids lives        */
+    uint32_t n_ids;         /* capacity of ids; the launch is sized from it                                          */
+    uint32_t reserved0;     /* 0                                                                                     */
+} mmdx_instance_select;
+/* mmdx_deform_batched (out_bounds == NULL) or mmdx_deform_batched_bounds (out_bounds != NULL) for the listed instances only.
+ *  1. `args` means what it means for mmdx_deform_batched: n_instances = NI is the extent of palettes, morph_weights, out_a, out_b
+ *     (and out_bounds); instance i reads row i and writes at i * NV or i * out_instance_pitch.  The list only says which i take part.
+ *  2. For every listed i < NI the bytes written to out_a, out_b and out_bounds[i] are identical to what mmdx_deform_batched /
+ *     mmdx_deform_batched_bounds write for that instance with the same args: every layout, pos_scale, dense and pitched, shared /
+ *     per-instance / no morph weights, MMDX_MORPH_UNCHANGED and the automatic morph skip, tile-order and fast-math models.  The
+ *     store hints MMDX_OUT_STORES_* are accepted and ignored (select launches store cached).
+ *  3. Nothing else is written: outputs and bounds rows of instances that are not listed keep what they held, as does every
+ *     instance's pitch gap.  Palettes and per-instance weights of unlisted instances may hold anything (uninitialised memory,
+ *     NaN): if they are read at all they influence no written byte.
+ *  4. The first min(*count, n_ids) ids are used.  *count == 0 or n_ids == 0 is a valid call that writes no instance; the shared
+ *     morph pass and its skip record behave as in the plain call, so a later MMDX_MORPH_UNCHANGED call is legal.
+ *  5. An id >= NI: in a host list the call fails with MMDX_ERR_INVALID_ARGUMENT before anything is launched; in a device list the
+ *     entry is skipped on the device (nothing read or written for it).  An id that occurs twice is allowed and costs twice (both
+ *     writers store the same bytes).
+ *  6. The GPU-resident crowd form only: MMDX_PALETTE_ON_DEVICE | MMDX_OUT_ON_DEVICE are required, and MMDX_WEIGHTS_ON_DEVICE when
+ *     morph_weights is passed; out_bounds is then a device pointer.  Anything else is MMDX_ERR_INVALID_ARGUMENT (the staging and
+ *     bounce copies of host operands move whole arrays and cannot honour rule 3).  A host-resident list is supported (a host-side
+ *     culler can use the call too): it is copied to a scratch buffer of the handle in stream order, and the call returns after
+ *     its work has completed, like every call that borrows host memory.
+ *  7. With a device list the call is asynchronous on the handle's stream like the plain device call and records into a graph
+ *     (mmdx_graph_begin / mmdx_graph_end; a host list is refused while recording).  A replay uses whatever ids / *count hold in
+ *     device memory at replay time.  ids and count are 4-byte aligned.
+ *  8. select == NULL is MMDX_ERR_INVALID_ARGUMENT: callers who want every instance call the plain entry points.
+ * The launch is sized from n_ids: workgroups whose list positions lie behind *count return at once, so a capacity far above the
+ * usual count costs little, but keep n_ids to what the list can hold. */
+MMDX_API mmdx_status mmdx_deform_batched_select(mmdx_model_t model, const mmdx_deform_args *args,
+                                                const mmdx_instance_select *select, float *out_bounds /* [NI][6] or NULL */);
 MMDX_API mmdx_status mmdx_sync(mmdx_model_t model);
 
 /* ---- plain device-memory helpers (thin hipMalloc / hipMemcpy wrappers) ----------------------- */

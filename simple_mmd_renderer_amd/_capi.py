@@ -21,6 +21,7 @@ OUT_SOA, OUT_VERTEX32, OUT_SOA_POS16 = 0, 1, 2
 PALETTE_ON_DEVICE, WEIGHTS_ON_DEVICE, OUT_ON_DEVICE, WEIGHTS_SHARED, MORPH_UNCHANGED = 1, 2, 4, 8, 16
 OUT_STORES_WRITE_THROUGH, OUT_STORES_CACHED = 32, 64
 OUT_PITCHED = 128        # mmdx_deform_args.out_instance_pitch is read: instance i of the outputs starts at vertex i * pitch
+SELECT_ON_DEVICE = 1     # mmdx_instance_select.flags: ids and count are device pointers
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
@@ -44,6 +45,13 @@ class DeformArgs(C.Structure):
                 ("morph_weights", C.c_void_p), ("palettes", C.c_void_p),
                 ("out_a", C.c_void_p), ("out_b", C.c_void_p),
                 ("pos_scale", C.c_float), ("out_instance_pitch", C.c_uint32)]
+
+
+class InstanceSelect(C.Structure):
+    """mmdx_instance_select: which instances a mmdx_deform_batched_select call deforms."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32),
+                ("ids", C.c_void_p), ("count", C.c_void_p),
+                ("n_ids", C.c_uint32), ("reserved0", C.c_uint32)]
 
 
 class ModelInfo(C.Structure):
@@ -81,6 +89,7 @@ SIGNATURES = {
     "mmdx_deform_vertex32": (C.c_int32, [C.c_void_p, _f32p, _f32p, C.c_float, C.c_void_p]),
     "mmdx_deform_batched": (C.c_int32, [C.c_void_p, C.POINTER(DeformArgs)]),
     "mmdx_deform_batched_bounds": (C.c_int32, [C.c_void_p, C.POINTER(DeformArgs), C.c_void_p]),
+    "mmdx_deform_batched_select": (C.c_int32, [C.c_void_p, C.POINTER(DeformArgs), C.POINTER(InstanceSelect), C.c_void_p]),
     "mmdx_sync": (C.c_int32, [C.c_void_p]),
     "mmdx_timer_start": (C.c_int32, [C.c_void_p]),
     "mmdx_timer_stop": (C.c_int32, [C.c_void_p, _f32p]),

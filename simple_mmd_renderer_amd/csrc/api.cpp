@@ -200,7 +200,7 @@ void free_model(mmdx_model_s *m) {
         for (DevBuf *b : {&m->tiles, &m->spos, &m->snrm, &m->suv, &m->perm, &m->skin1, &m->skin2_ids,
                           &m->skin2_w, &m->skin4_ids, &m->skin4_w, &m->bone_list, &m->ell,
                           &m->entries, &m->slot_top, &m->chain_off, &m->chain_rate, &m->pal, &m->rates,
-                          &m->wslot, &m->morphed, &m->seen, &m->out_a, &m->out_b, &m->bnd})
+                          &m->wslot, &m->morphed, &m->seen, &m->out_a, &m->out_b, &m->bnd, &m->sel})
             b->release();
         if (m->bounce) (void)hipHostFree(m->bounce);
         if (m->bounce_in) (void)hipHostFree(m->bounce_in);
@@ -248,7 +248,8 @@ LaunchOverrides mmdx::read_launch_overrides() {
     return {env_int("MMDX_INTERLEAVE", 1), env_int("MMDX_THREADS", 0), env_int("MMDX_LDS_TARGET", 0),
             env_int("MMDX_GROUP", 0), env_int("MMDX_PLACEMENT_LOG", 0), env_int("MMDX_PLACEMENT_PARK", 0),
             env_int("MMDX_FRAME_KERNEL", 1), env_int("MMDX_FRAME_THREADS", 256), env_int("MMDX_SHARED_FUSED", 1),
-            env_int("MMDX_STORE_WT", -1), env_int("MMDX_MORPH_AUTOSKIP", 1), env_int("MMDX_FUSED_PACK", 0), env_int("MMDX_STAGGER", 0)};
+            env_int("MMDX_STORE_WT", -1), env_int("MMDX_MORPH_AUTOSKIP", 1), env_int("MMDX_FUSED_PACK", 0), env_int("MMDX_STAGGER", 0),
+            env_int("MMDX_SELECT_INTERLEAVE", 1)};
 }
 LaunchOverrides &mmdx::launch_overrides() {
     static LaunchOverrides o = read_launch_overrides();
@@ -481,8 +482,10 @@ mmdx_status mmdx_model_set_stream(mmdx_model_t m, void *hip_stream) {
     return MMDX_OK;
 }
 
-// mmdx_deform_batched and, with out_bounds != nullptr, mmdx_deform_batched_bounds
-static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, float *out_bounds) {
+// mmdx_deform_batched and, with out_bounds != nullptr, mmdx_deform_batched_bounds; with sel != nullptr mmdx_deform_batched_select
+// (out_bounds optional there)
+static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, float *out_bounds,
+                                  const mmdx_instance_select *sel = nullptr) {
     if (!m || !a) return fail(MMDX_ERR_INVALID_ARGUMENT, "model / args is NULL");
     if (a->struct_size != sizeof(mmdx_deform_args))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_deform_args.struct_size mismatch");
@@ -505,6 +508,41 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
         return fail(MMDX_ERR_INVALID_ARGUMENT, "palettes / out_a / out_b is NULL");
     if (p.ns && !a->morph_weights && !(a->flags & MMDX_MORPH_UNCHANGED))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "morph_weights is NULL");
+    // ---- the instance list of a select call: validated in full before anything is enqueued ------------------------------------
+    uint32_t sel_live_host = 0;             // host lists: how many leading ids are in use
+    if (sel) {
+        if (sel->struct_size != sizeof(mmdx_instance_select))
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.struct_size mismatch");
+        if (sel->flags & ~uint32_t(MMDX_SELECT_ON_DEVICE))
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown bits in mmdx_instance_select.flags");
+        if (sel->reserved0 != 0) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.reserved0 must be 0");
+        if (sel->n_ids && !sel->ids) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids is NULL");
+        // the GPU-resident crowd form only: a staging or bounce copy of the outputs moves whole arrays and cannot leave the
+        // instances outside a list untouched
+        const uint32_t need = MMDX_PALETTE_ON_DEVICE | MMDX_OUT_ON_DEVICE |
+                              (p.ns && a->morph_weights ? uint32_t(MMDX_WEIGHTS_ON_DEVICE) : 0u);
+        if ((a->flags & need) != need)
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_deform_batched_select takes device operands only: pass MMDX_PALETTE_ON_DEVICE | "
+                                                   "MMDX_OUT_ON_DEVICE, and MMDX_WEIGHTS_ON_DEVICE with morph_weights");
+        if (sel->flags & MMDX_SELECT_ON_DEVICE) {
+            if ((reinterpret_cast<uintptr_t>(sel->ids) | reinterpret_cast<uintptr_t>(sel->count)) & 3)
+                return fail(MMDX_ERR_INVALID_ARGUMENT, "device ids / count of mmdx_instance_select must be 4-byte aligned");
+        } else {
+            if (m->capturing)
+                return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded the instance list must be in device memory "
+                                                       "(MMDX_SELECT_ON_DEVICE)");
+            void *unused = nullptr;
+            if ((sel->n_ids && classify_pointer(sel->ids, &unused) == PtrKind::Device) ||
+                (sel->count && classify_pointer(sel->count, &unused) == PtrKind::Device))
+                return fail(MMDX_ERR_INVALID_ARGUMENT, "ids / count of mmdx_instance_select point to device memory: pass "
+                                                       "MMDX_SELECT_ON_DEVICE");
+            sel_live_host = sel->count ? std::min(*sel->count, sel->n_ids) : sel->n_ids;
+            for (uint32_t j = 0; j < sel_live_host; ++j)
+                if (sel->ids[j] >= ni)
+                    return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids[" + std::to_string(j) + "] = " +
+                                                           std::to_string(sel->ids[j]) + " is not below n_instances");
+        }
+    }
     // instance pitch of the outputs (vertices from one instance to the next); dense outputs: NV
     const bool pitched = (a->flags & MMDX_OUT_PITCHED) != 0;
     const uint32_t pitch = pitched ? a->out_instance_pitch : p.nv;
@@ -580,6 +618,26 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
     dp.interleave = uint32_t(ov.interleave);
     dp.tile_order = (p.flags & MMDX_CREATE_TILE_ORDER) ? 1u : 0u;
 
+    // ---- instance list (select calls): device lists are used in place -- a recorded graph reads them afresh at every replay; host
+    // lists go to a scratch of the handle in stream order, count word first -------------------------------------------------
+    const uint32_t nwork = sel ? sel->n_ids : ni;       // instances the launch is sized for
+    if (sel) {
+        dp.sel_n = sel->n_ids;
+        dp.sel_interleave = ov.select_interleave != 0 ? 1u : 0u;
+        if (sel->flags & MMDX_SELECT_ON_DEVICE) {
+            dp.sel_ids = sel->ids; dp.sel_count = sel->count;
+        } else if (sel->n_ids) {
+            HIP_TRY(m->sel.ensure((size_t(sel->n_ids) + 1) * 4));
+            m->sel_host.resize(size_t(sel->n_ids) + 1);
+            m->sel_host[0] = sel_live_host;
+            std::memcpy(m->sel_host.data() + 1, sel->ids, size_t(sel->n_ids) * 4);
+            // (pageable source: the copy has left the host vector when the call returns)
+            HIP_TRY(hipMemcpyAsync(m->sel.ptr, m->sel_host.data(), m->sel_host.size() * 4, hipMemcpyHostToDevice, st));
+            dp.sel_count = static_cast<const uint32_t *>(m->sel.ptr);
+            dp.sel_ids = dp.sel_count + 1;
+        }
+    }
+
     // ---- palettes -------------------------------------------------------------------------------
     const size_t pal_bytes = size_t(ni) * p.nb * 64;
     if (a->flags & MMDX_PALETTE_ON_DEVICE) {
@@ -615,10 +673,13 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
         unchanged = true;
         ++m->host_skips;
     }
-    const bool gather_in_kernel = ni == 1 || (p.ns <= kMaxFusedSlots && !unchanged && (sf == 2 || (sf == 1 && ni <= 8)));
+    // (a select call with an empty list launches no deform kernel: its shared rates take the morph pass, so that the positions
+    // later MMDX_MORPH_UNCHANGED calls rely on are there)
+    const bool gather_in_kernel = ni == 1 || (p.ns <= kMaxFusedSlots && !unchanged && (sf == 2 || (sf == 1 && ni <= 8)) &&
+                                              !(sel && sel->n_ids == 0));
     if (p.ns) morph = shared ? (gather_in_kernel ? kMorphFused1 : kMorphShared) : kMorphFused4;
     if (morph != kMorphNone) {
-        const uint32_t niw = shared ? 1u : ni;
+        const uint32_t niw = shared ? 1u : nwork;           // (select, per-instance rates: one row per list position)
         const float *rates_dev;
         if ((a->flags & MMDX_WEIGHTS_ON_DEVICE) || unchanged) {
             rates_dev = a->morph_weights;                     // (unchanged: never read)
@@ -627,7 +688,7 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
             HIP_TRY(copy_in(m, m->rates.ptr, a->morph_weights, kind_w, size_t(niw) * p.nm * 4, kBounceInBytes / 2, st));
             rates_dev = static_cast<const float *>(m->rates.ptr);
         }
-        FlattenParams f;
+        FlattenParams f{};
         f.rates = rates_dev;
         f.slot_top = static_cast<const uint32_t *>(m->slot_top.ptr);
         f.chain_off = static_cast<const uint32_t *>(m->chain_off.ptr);
@@ -635,6 +696,7 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
         f.nm = p.nm; f.ns = p.ns; f.niw = niw;
         f.quad = morph == kMorphFused4 ? 1u : 0u;
         f.seen = nullptr;
+        if (sel && !shared) { f.sel_ids = dp.sel_ids; f.sel_count = dp.sel_count; f.sel_ni = ni; }
         const size_t rows = f.quad ? size_t((niw + 3) / 4) * 4 : niw;
         HIP_TRY(m->wslot.ensure(rows * (size_t(p.ns) + 1) * 4));
         f.out = static_cast<float *>(m->wslot.ptr);
@@ -722,7 +784,7 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
     // per lane (512 threads) leaves the registers to serve 8 instances per walk over a morph row.
     // A single frame (one instance) is latency-bound: one slot per lane and twice the waves per tile finish sooner
     // (config 2: 8.4 -> 6.9 us, config 5: 16.9 -> 14.9 us).
-    const bool one_frame = ni == 1 && (morph == kMorphNone || morph == kMorphFused1);
+    const bool one_frame = ni == 1 && nwork <= 1 && (morph == kMorphNone || morph == kMorphFused1);
     // (tile-order outputs: no LDS image, 80 VGPRs with one slot per lane -- 512 threads measured 215.5 vs 219.1 us on the crowd)
     int threads = (ov.threads ? ov.threads : (morph == kMorphFused4 || one_frame || dp.tile_order ? 512 : 256)) == 512 ? 512 : 256;
     if (morph == kMorphFused4 && threads == 512) {   // tiles with hundreds of bones: 8 palettes do not fit, 4 may
@@ -732,7 +794,8 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
     // ---- store flavour: only where the launch shape has the write-through flavour, and only for outputs in device memory (stores
     // into mapped host memory cross PCIe whatever their cache bits say) ------------------------------------------------------------
     // (the bounds flavour has no write-through variant: its calls store cached whatever the hint says)
-    dp.write_through = !bounds && out_dev && deform_has_write_through(threads, int(layout), morph, p.f16, dp.tile_order != 0) &&
+    // (nor has the select flavour)
+    dp.write_through = !bounds && !sel && out_dev && deform_has_write_through(threads, int(layout), morph, p.f16, dp.tile_order != 0) &&
                        write_through_for(bytes_a + bytes_b, a->flags) ? 1u : 0u;
     m->last_write_through = dp.write_through != 0;
     // ---- group size (instances per workgroup) from the LDS budget ---------------------------------
@@ -751,10 +814,10 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
         // pair 16 wins (204 vs 211): profiles/r03/shape_sweep_write_through*.txt
         if (dp.write_through) g = std::min(g, 8u);
         g = std::max(g / gmin * gmin, gmin);
-        const uint32_t ni_up = (ni + gmin - 1) / gmin * gmin;
+        const uint32_t ni_up = (std::max(nwork, 1u) + gmin - 1) / gmin * gmin;
         g = std::min(g, ni_up);
         // keep the grid large enough to fill 256 CUs several times over
-        while (g > gmin && uint64_t(p.ntiles) * ((ni + g - 1) / g) < 2048) {
+        while (g > gmin && uint64_t(p.ntiles) * ((nwork + g - 1) / g) < 2048) {
             const uint32_t half = std::max((g / 2) / gmin * gmin, gmin);
             if (half == g) break;
             g = half;
@@ -771,7 +834,7 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
     // walk the table twice as often as packs of 8.  Kept for the A/B, not the default.  Two-array layouts in original vertex order.
     // The group: as many instances (multiple of 4, up to 16) as keep three workgroups on a CU, else as fit two.
     // (bounds calls keep deform_kernel's bounds flavour: the pack kernel, an archived A/B, has none)
-    bool pack = !bounds && morph == kMorphFused4 && ov.fused_pack != 0 && kTileVerts == 512 && !dp.tile_order && layout != MMDX_OUT_VERTEX32 &&
+    bool pack = !bounds && !sel && morph == kMorphFused4 && ov.fused_pack != 0 && kTileVerts == 512 && !dp.tile_order && layout != MMDX_OUT_VERTEX32 &&
                 !ov.threads;
     size_t lds = 0;
     if (pack) {
@@ -807,7 +870,7 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
     const uint32_t bounds_units = bounds ? deform_bounds_units(threads, p.ntiles, dp.tile_order != 0) : 0u;
     float *bounds_dev = nullptr;
     if (bounds) {
-        const size_t part = size_t(ni) * bounds_units * 24;
+        const size_t part = size_t(nwork) * bounds_units * 24;         // (select: partials by list position)
         HIP_TRY(m->bnd.ensure(part + (out_dev ? 0 : size_t(ni) * 24)));
         dp.bounds = static_cast<float *>(m->bnd.ptr);
         bounds_dev = out_dev ? out_bounds : reinterpret_cast<float *>(static_cast<unsigned char *>(m->bnd.ptr) + part);
@@ -826,7 +889,7 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
     // Models with fewer tiles than the chip has CUs only (config 2: 6.3 us against the tile kernel's 6.9); a large model fills the
     // chip with whole tiles and is better off with their coalesced stores (config 5: 14.9 us against 15.2).
     // (bounds calls take the tile kernel's bounds flavour: the frame kernel has none)
-    const bool frame = !bounds && one_frame && !out_direct && !out_bounce && (ov.frame_kernel == 2 || (ov.frame_kernel == 1 && p.ntiles < 256));
+    const bool frame = !bounds && !sel && one_frame && !out_direct && !out_bounce && (ov.frame_kernel == 2 || (ov.frame_kernel == 1 && p.ntiles < 256));
     if (frame) {
         DeformParams fp = dp;
         fp.morphed = nullptr;                                  // nothing reads a single frame's morphed positions later
@@ -836,9 +899,13 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
         HIP_TRY((fast ? launch_frame_fast : launch_frame)(ov.frame_threads, int(layout), morph, p.f16, fp, p.ntiles, flds, st));
     } else if (pack) {
         HIP_TRY((fast ? launch_pack_fast : launch_pack)(int(layout), p.f16, dp, p.ntiles, lds, st));
+    } else if (sel && sel->n_ids == 0) {
+        // an empty list: no instance to write (the shared morph pass above has run as in the plain call)
     } else {
         HIP_TRY((fast ? launch_deform_fast : launch_deform)(threads, int(layout), morph, p.f16, dp, p.ntiles, lds, st));
-        if (bounds) HIP_TRY(launch_bounds_reduce(dp.bounds, bounds_units, ni, bounds_dev, st));
+        if (bounds && sel)
+            HIP_TRY(launch_bounds_reduce_select(dp.bounds, bounds_units, ni, bounds_dev, dp.sel_ids, dp.sel_count, dp.sel_n, st));
+        else if (bounds) HIP_TRY(launch_bounds_reduce(dp.bounds, bounds_units, ni, bounds_dev, st));
     }
     if (pev) {
         HIP_TRY(hipEventRecord(pev[1], st));
@@ -874,7 +941,8 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
             if (bytes_b) std::memcpy(a->out_b, static_cast<unsigned char *>(m->bounce) + off_b, bytes_b);
         }
     } else if (!(a->flags & MMDX_PALETTE_ON_DEVICE) ||
-               (morph != kMorphNone && !(a->flags & MMDX_WEIGHTS_ON_DEVICE))) {
+               (morph != kMorphNone && !(a->flags & MMDX_WEIGHTS_ON_DEVICE)) ||
+               (sel && !(sel->flags & MMDX_SELECT_ON_DEVICE) && sel->n_ids)) {
         // borrowed host inputs must be consumed before we return
         HIP_TRY(wait_stream(st));
     }
@@ -886,6 +954,11 @@ mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) { ret
 mmdx_status mmdx_deform_batched_bounds(mmdx_model_t m, const mmdx_deform_args *a, float *out_bounds) {
     if (!out_bounds) return fail(MMDX_ERR_INVALID_ARGUMENT, "out_bounds is NULL");
     return deform_batched(m, a, out_bounds);
+}
+
+mmdx_status mmdx_deform_batched_select(mmdx_model_t m, const mmdx_deform_args *a, const mmdx_instance_select *select, float *out_bounds) {
+    if (!select) return fail(MMDX_ERR_INVALID_ARGUMENT, "select is NULL (mmdx_deform_batched / mmdx_deform_batched_bounds deform every instance)");
+    return deform_batched(m, a, out_bounds, select);
 }
 
 mmdx_status mmdx_deform(mmdx_model_t m, const float *w, const float *palette, float *out_pos,

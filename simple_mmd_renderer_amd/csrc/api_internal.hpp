@@ -63,6 +63,8 @@ struct LaunchOverrides {
     int fused_pack;     // MMDX_FUSED_PACK: 0 = per-instance morph weights run deform_kernel<512, ., kMorphFused4> (default),
                         // 1 = pack_kernel (round 4's higher-occupancy shape: measured slower, kept for the A/B)
     int stagger;        // MMDX_STAGGER: start offset between the workgroups of a CU, in units of 64 cycles per residency slot (A/B)
+    int select_interleave;   // MMDX_SELECT_INTERLEAVE: 1 = select launches deal list positions interleaved over the workgroups like the
+                             // plain crowd call (default, measured faster); 0 = blocked (A/B)
 };
 LaunchOverrides read_launch_overrides();
 LaunchOverrides &launch_overrides();
@@ -93,6 +95,8 @@ struct mmdx_model_s {
     mmdx::DevBuf pal, rates, wslot, morphed, out_a, out_b;
     mmdx::DevBuf seen;              // RatesSeen record (kernels.hpp): the rates `morphed` was last computed from, device side
     mmdx::DevBuf bnd;               // mmdx_deform_batched_bounds: partial bounds, then (host bounds) the [NI][6] result
+    mmdx::DevBuf sel;               // mmdx_deform_batched_select with a host list: {live count, ids[n_ids]}
+    std::vector<uint32_t> sel_host; // ... and its image on the host, the source of the upload
     bool morphed_valid = false;     // `morphed` holds the result of a shared morph pass (MMDX_MORPH_UNCHANGED)
     std::vector<float> host_rates;  // ... and the host's copy of those rates when they came from host memory
     bool host_rates_valid = false;
@@ -104,7 +108,7 @@ struct mmdx_model_s {
     bool rec_poisoned = false;          // one of them was destroyed before mmdx_graph_end: the recording cannot become a graph
     bool last_write_through = false;          // store flavour of the last crowd launch (mmdx_debug_last_store_policy)
     mmdx_model_s() {
-        for (mmdx::DevBuf *b : {&pal, &rates, &wslot, &morphed, &out_a, &out_b, &bnd}) b->pin = &pin;
+        for (mmdx::DevBuf *b : {&pal, &rates, &wslot, &morphed, &out_a, &out_b, &bnd, &sel}) b->pin = &pin;
     }
     // page-locked bounce buffer for small outputs bound for pageable host memory (see mmdx_deform_batched)
     void *bounce = nullptr, *bounce_dev = nullptr;  // host address, device-side address

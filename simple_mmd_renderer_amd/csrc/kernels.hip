@@ -497,6 +497,14 @@ __device__ __forceinline__ void load_slot(const DeformParams &p, const TileHdr &
     }
 }
 
+// A word of the instance list of a select launch (the live count, the id of a workgroup's current instance) at a wave-uniform
+// address, read through the constant address space: the list is never written while the kernel runs, and said this way the load
+// is a scalar one (s_load_dword) wherever it stands -- behind the stagger's sleep or the previous instance's stores the compiler
+// would otherwise take a vector load plus readfirstlane.
+__device__ __forceinline__ uint32_t uniform_u32(const uint32_t *q) {
+    return *reinterpret_cast<const __attribute__((address_space(4))) uint32_t *>(reinterpret_cast<uintptr_t>(q));
+}
+
 // bone palettes of `count` instances (first one `inst0`, then every `istep`-th) -> LDS: only the tile's bones,
 // in the pair layout load_m12 reads.  One wave-instruction fetches ONE bone for 16 instances (lane = instance x
 // matrix row: sixteen 64-byte pieces); the bone id is wave-uniform, so it comes through the scalar cache and the
@@ -504,7 +512,9 @@ __device__ __forceinline__ void load_slot(const DeformParams &p, const TileHdr &
 // set-up phase that runs while the CU's memory pipeline is full of other workgroups' stores.
 // `qstep` != 0: the group is made of instance QUADS qstep quads apart (pack_kernel's interleaved mapping): group instance g is
 // instance inst0 + (g >> 2) * 4 * qstep + (g & 3); instances past the crowd's end are left out.
-template <int THREADS>
+// SEL (select launches): inst0 / istep are list positions, the instance is p.sel_ids[position] (one load per lane, in front of the
+// palette rows it addresses: set-up only); ids >= p.ni are left out like instances past the crowd's end.
+template <int THREADS, bool SEL = false>
 __device__ __forceinline__ void stage_palettes(const DeformParams &p, const TileHdr &th, float4 *pal, uint32_t inst0,
                                                uint32_t istep, uint32_t count, int tid, uint32_t qstep = 0u) {
     const uint32_t nbt = th.nbt;
@@ -515,8 +525,9 @@ __device__ __forceinline__ void stage_palettes(const DeformParams &p, const Tile
         const uint32_t g = g0 + gl;
         uint32_t inst = inst0 + (g < count ? g : 0u) * istep;
         if (qstep) inst = inst0 + (g >> 2) * 4u * qstep + (g & 3u);
+        if constexpr (SEL) inst = p.sel_ids[inst];          // (g >= count reads position inst0: inside the live prefix)
         const bool on = g < count && inst < p.ni;
-        const float *src = p.palettes + size_t(on ? inst : inst0) * p.nb * 16 + r * 4;
+        const float *src = p.palettes + size_t(on ? inst : inst0) * p.nb * 16 + r * 4;     // (off: never dereferenced)
         float *dst = reinterpret_cast<float *>(pal + size_t(g) * p.pal_stride);
 #pragma unroll 4
         for (uint32_t lb = wave; lb < nbt; lb += THREADS / 64) {
@@ -541,7 +552,8 @@ __device__ __forceinline__ void stage_palettes(const DeformParams &p, const Tile
 // thread is handled this way; what does not fit (large groups, thousands of slots) follows in plain loops.
 constexpr int kPalBatch = 4, kWgtBatch = 4;
 
-template <int THREADS, int LAYOUT, int MORPH, bool F16, int VPT, uint32_t BH>
+// SEL (select launches): inst0 / istep are list positions; a row of an id >= p.ni is staged as zeros (its instance is never skinned).
+template <int THREADS, int LAYOUT, int MORPH, bool F16, int VPT, uint32_t BH, bool SEL = false>
 __device__ __forceinline__ void setup_fused1(const DeformParams &p, const TileHdr &th, float4 *pal, float *wl, uint32_t inst0,
                                              uint32_t istep, uint32_t gcount, int tid, uint32_t slot_base, Slot (&sl)[VPT],
                                              RowHead<F16, BH> (&hd)[VPT]) {
@@ -552,7 +564,12 @@ __device__ __forceinline__ void setup_fused1(const DeformParams &p, const TileHd
     // palette row e = (instance g of the group, tile bone lb, matrix row r): e = (g * nbt + lb) * 4 + r
     auto row_src = [&](uint32_t e, uint32_t bone) {
         const uint32_t g = gcount == 1 ? 0u : e / nb4;
-        return reinterpret_cast<const float4 *>(p.palettes + size_t(inst0 + g * istep) * p.nb * 16 + size_t(bone) * 16 + (e & 3u) * 4);
+        uint32_t inst = inst0 + g * istep;
+        if constexpr (SEL) {
+            inst = p.sel_ids[inst];
+            if (inst >= p.ni) inst = 0u;                     // a skipped id: any readable row, never used
+        }
+        return reinterpret_cast<const float4 *>(p.palettes + size_t(inst) * p.nb * 16 + size_t(bone) * 16 + (e & 3u) * 4);
     };
     auto row_put = [&](uint32_t e, const float4 row) {
         const uint32_t g = gcount == 1 ? 0u : e / nb4, rem = e - g * nb4, lb = rem >> 2, r = rem & 3u;
@@ -891,8 +908,21 @@ __device__ __forceinline__ void fused4_walk(const void *entries, uint32_t rb, ui
 // WT = false: bounds calls store cached (api.cpp), no write-through bounds variant is built.
 // (A template parameter of this kernel, not a device function shared by two kernels: that wrapping alone moved the register
 // allocation of the per-instance-morph kernels by +-2 VGPRs; this way BOUNDS = false is the previous kernel's code.)
-template <int THREADS, int LAYOUT, int MORPH, bool F16, bool TILE, bool WT = false, bool BOUNDS = false>
+// SELECT: the flavour of mmdx_deform_batched_select -- the workgroup's instances come from a list in device memory: list position j
+// -> instance p.sel_ids[j] for the palette staging, the output base and nothing else (slot weights and partial bounds are indexed
+// by j).  The live count is one word (scalar load, once per workgroup); a workgroup whose positions lie behind it returns before
+// it stages anything; an id >= p.ni is skipped.  List positions are dealt over the workgroups like the instances of the plain
+// crowd call: interleaved (g*ngroups + grp) with p.sel_interleave, else blocked (grp*group + g; always for per-instance rates,
+// whose slot weights are packed by quads of positions).  Interleaved is the default: a short live prefix then keeps every
+// workgroup of the grid busy with a few instances, and re-reading the tile's static streams per few instances (they stay in the
+// XCD's L2) measured cheaper than running a quarter of the workgroups with full groups.
+// Like BOUNDS a compile-time flavour, so that without it the kernel is the previous kernel's code.  It travels as a bit of the
+// morph-mode argument (kMorphSelect), not as one more template parameter: the names of the existing instantiations, which the
+// resource listings and their checks go by, stay what they were.
+template <int THREADS, int LAYOUT, int MORPH_MODE, bool F16, bool TILE, bool WT = false, bool BOUNDS = false>
 __global__ __launch_bounds__(THREADS) void deform_kernel(const DeformParams p) {
+    constexpr int MORPH = MORPH_MODE & 3;
+    constexpr bool SELECT = (MORPH_MODE & kMorphSelect) != 0;
     constexpr int VPT = int(kTileVerts) / THREADS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
@@ -905,11 +935,27 @@ __global__ __launch_bounds__(THREADS) void deform_kernel(const DeformParams p) {
     // so that the workgroups running at the same time (neighbouring grp) write NEIGHBOURING instances:
     // chip-wide the stores then sweep a few contiguous megabytes of each output array, like a linear
     // fill, instead of 8+ streams 9.6 MB apart.
-    const bool ilv = (MORPH == kMorphNone || MORPH == kMorphShared || MORPH == kMorphFused1) && p.interleave != 0;
+    // (SELECT: inst0 / istep / gcount count list positions of the live prefix)
+    const bool ilv = (MORPH == kMorphNone || MORPH == kMorphShared || MORPH == kMorphFused1) &&
+                     (SELECT ? p.sel_interleave != 0 : p.interleave != 0);
     const uint32_t inst0 = ilv ? grp : grp * p.group;
     const uint32_t istep = ilv ? p.ngroups : 1u;
-    const uint32_t gcount = ilv ? (p.ni > grp ? min(p.group, (p.ni - grp + p.ngroups - 1) / p.ngroups) : 0u)
-                                : min(p.group, p.ni - inst0);
+    uint32_t gcount;
+    if constexpr (SELECT) {
+        const uint32_t nlive = p.sel_count ? min(uniform_u32(p.sel_count), p.sel_n) : p.sel_n;
+        // (no "a < b ? min(g, b - a) : 0" here: this compiler turns it into a saturating subtraction whose scalar form wraps)
+        const uint32_t end = min(inst0 + p.group, nlive);       // blocked: the first position behind this workgroup's live ones
+        gcount = ilv ? min(p.group, (nlive + p.ngroups - 1u - grp) / p.ngroups)       // grp < ngroups: no wrap; 0 when nlive <= grp
+                     : (end > inst0 ? end - inst0 : 0u);
+    } else {
+        gcount = ilv ? (p.ni > grp ? min(p.group, (p.ni - grp + p.ngroups - 1) / p.ngroups) : 0u)
+                     : min(p.group, p.ni - inst0);
+    }
+    if constexpr (SELECT) {
+        // nothing live here.  (A small crowd with shared rates walks its morphs in this kernel and workgroup 0 of every tile
+        // keeps the morphed positions for later MMDX_MORPH_UNCHANGED calls: those stay, with no instance to write.)
+        if (gcount == 0 && !(MORPH == kMorphFused1 && grp == 0 && p.morphed)) return;
+    }
     float4 *pal = reinterpret_cast<float4 *>(smem);
     unsigned char *stage = smem + p.stage_off;
     constexpr uint32_t kStage = stage_bytes(LAYOUT);
@@ -931,11 +977,11 @@ __global__ __launch_bounds__(THREADS) void deform_kernel(const DeformParams p) {
     if constexpr (MORPH == kMorphFused1) {
         // palettes, slot weights (ONE set of morph rates for the whole launch; group morphs flattened in here when the raw
         // rates are passed), static vertex data and the heads of the morph rows, in latency order
-        setup_fused1<THREADS, LAYOUT, kMorphFused1, F16, VPT, BH>(p, th, pal, reinterpret_cast<float *>(smem + p.w_off), inst0, istep,
+        setup_fused1<THREADS, LAYOUT, kMorphFused1, F16, VPT, BH, SELECT>(p, th, pal, reinterpret_cast<float *>(smem + p.w_off), inst0, istep,
                                                                    gcount, tid, 0u, sl, hd);
     } else {
         // 1. bone palettes of the group's instances -> LDS: only the tile's bones, in the pair layout
-        stage_palettes<THREADS>(p, th, pal, inst0, istep, gcount, tid);
+        stage_palettes<THREADS, SELECT>(p, th, pal, inst0, istep, gcount, tid);
         // 2. morph slot weights of the first pack -> LDS
         if constexpr (MORPH == kMorphFused4) {
             float4 *wq0 = reinterpret_cast<float4 *>(smem + p.w_off);
@@ -957,12 +1003,27 @@ __global__ __launch_bounds__(THREADS) void deform_kernel(const DeformParams p) {
     constexpr bool kAllFast = decltype(all_fast_tag)::value;
     // the image is double buffered: the next instance writes the other one, so one barrier per instance is enough
     auto run_instance = [&](uint32_t g, const v2f (&cxy)[VPT], const float (&cz)[VPT], auto hook) {
+        uint32_t sel_inst = 0u;
+        if constexpr (SELECT) {
+            sel_inst = uniform_u32(p.sel_ids + (inst0 + g * istep));
+            // An id outside the call's arrays: skipped by the whole workgroup (no barrier missed).  (Per-instance rates: a pack
+            // made of skipped ids only passes no instance barrier, so a fast wave may replace the pack's slot weights while a slow
+            // one still walks with them -- into accumulators that no instance will read.)
+            if (sel_inst >= p.ni) {
+                hook();
+                return;
+            }
+        }
         BoundsOut bo{nullptr, nullptr};
         if constexpr (BOUNDS) {
             constexpr uint32_t kUnits = TILE ? uint32_t(THREADS) / 64u : 1u;    // partials per (instance, tile)
             bo.lds = reinterpret_cast<float *>(smem + p.bounds_off) + buf * 48u;
             bo.out = p.bounds + (size_t(inst0 + g * istep) * p.ntiles + tile) * kUnits * 6u;
         }
+        if constexpr (SELECT)
+            skin_instance<THREADS, LAYOUT, VPT, TILE, kAllFast, WT, BOUNDS>(p, sl, pal + size_t(g) * p.pal_stride, stage + buf * kStage,
+                                                                       sel_inst, v0, nvt, cxy, cz, tid, hook, bo);
+        else
         skin_instance<THREADS, LAYOUT, VPT, TILE, kAllFast, WT, BOUNDS>(p, sl, pal + size_t(g) * p.pal_stride, stage + buf * kStage,
                                                                    inst0 + g * istep, v0, nvt, cxy, cz, tid, hook, bo);
         buf ^= 1u;
@@ -1602,6 +1663,23 @@ __global__ __launch_bounds__(kThreads) void flatten_kernel(const FlattenParams f
     else f.out[idx] = out;
 }
 
+// The same for a select launch (mmdx_deform_batched_select): output row j = the slot weights of instance f.sel_ids[j]; rows behind the
+// live count or with an id >= f.sel_ni are zeros (their instances are never written).  A kernel of its own: flatten_kernel stays as is.
+__global__ __launch_bounds__(kThreads) void flatten_select_kernel(const FlattenParams f) {
+    const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
+    const uint32_t rows = f.quad ? ((f.niw + 3) / 4) * 4 : f.niw, cols = f.ns + 1;
+    if (idx >= size_t(rows) * cols) return;
+    const uint32_t j = uint32_t(idx / cols), s = uint32_t(idx - size_t(j) * cols);
+    const uint32_t live = f.sel_count ? min(*f.sel_count, f.niw) : f.niw;
+    float out = 0.f;
+    if (j < live && s < f.ns) {
+        const uint32_t i = f.sel_ids[j];
+        if (i < f.sel_ni) out = slot_weight(f.rates + size_t(i) * f.nm, f.slot_top, f.chain_off, f.chain_rate, s);
+    }
+    if (f.quad) f.out[(size_t(j / 4) * cols + s) * 4 + (j & 3)] = out;
+    else f.out[idx] = out;
+}
+
 // ---- VMD morph tracks -> per-instance morph rates (Motion::GetMorphPose, motion_impl.inl:382-424) ---
 // One thread per (instance, model morph): clamp to the first / last key, exact hit, else the linear
 // blend l*(1-t) + r*t with t = float(frame-left)/float(right-left) (IEEE division: hipcc keeps f32
@@ -1694,13 +1772,44 @@ __global__ __launch_bounds__(64) void bounds_reduce_kernel(const float *part, fl
     if (lane < 6) out[size_t(blockIdx.x) * 6 + lane] = v;
 }
 
+
+// The same behind a select launch: partials by list position, block j writes row ids[j] -- live positions with an id inside the
+// call's arrays only, every other row of `out` keeps what it held.
+__global__ __launch_bounds__(64) void bounds_reduce_select_kernel(const float *part, float *out, uint32_t units, uint32_t ni,
+                                                                  const uint32_t *ids, const uint32_t *count, uint32_t n_ids) {
+    const uint32_t lane = threadIdx.x, j = blockIdx.x;
+    if (j >= (count ? min(*count, n_ids) : n_ids)) return;
+    const uint32_t inst = ids[j];
+    if (inst >= ni) return;
+    const float *src = part + size_t(j) * units * 6;
+    float mn[3], mx[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) mn[c] = mx[c] = __builtin_nanf("");
+    for (uint32_t u = lane; u < units; u += 64) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            mn[c] = bound_op<false>(mn[c], src[size_t(u) * 6 + c]);
+            mx[c] = bound_op<true>(mx[c], src[size_t(u) * 6 + 3 + c]);
+        }
+    }
+    const float v = wave_bounds6(mn, mx, lane);
+    if (lane < 6) out[size_t(inst) * 6 + lane] = v;
+}
+
 #endif  // !MMDX_FAST_MATH
 
 using KernelFn = void (*)(const DeformParams);
 
-template <int THREADS, int LAYOUT, bool F16, bool TILE, bool BOUNDS>
+template <int THREADS, int LAYOUT, bool F16, bool TILE, bool BOUNDS, bool SELECT = false>
 KernelFn pick_morph(int morph) {
-    if constexpr (BOUNDS) {
+    if constexpr (SELECT) {
+        switch (morph) {
+        case kMorphNone: return deform_kernel<THREADS, LAYOUT, kMorphNone | kMorphSelect, F16, TILE, false, BOUNDS>;
+        case kMorphShared: return deform_kernel<THREADS, LAYOUT, kMorphShared | kMorphSelect, F16, TILE, false, BOUNDS>;
+        case kMorphFused1: return deform_kernel<THREADS, LAYOUT, kMorphFused1 | kMorphSelect, F16, TILE, false, BOUNDS>;
+        default: return deform_kernel<THREADS, LAYOUT, kMorphFused4 | kMorphSelect, F16, TILE, false, BOUNDS>;
+        }
+    } else if constexpr (BOUNDS) {
         switch (morph) {
         case kMorphNone: return deform_kernel<THREADS, LAYOUT, kMorphNone, F16, TILE, false, true>;
         case kMorphShared: return deform_kernel<THREADS, LAYOUT, kMorphShared, F16, TILE, false, true>;
@@ -1717,27 +1826,30 @@ KernelFn pick_morph(int morph) {
     }
 }
 
-template <int THREADS, bool TILE, bool BOUNDS>
+template <int THREADS, bool TILE, bool BOUNDS, bool SELECT = false>
 KernelFn pick_t(int layout, int morph, bool f16) {
-    if (f16) return layout == MMDX_OUT_SOA_POS16 ? pick_morph<THREADS, MMDX_OUT_SOA_POS16, true, TILE, BOUNDS>(morph) : nullptr;
-    if (layout == MMDX_OUT_SOA) return pick_morph<THREADS, MMDX_OUT_SOA, false, TILE, BOUNDS>(morph);
-    if (layout == MMDX_OUT_VERTEX32) return pick_morph<THREADS, MMDX_OUT_VERTEX32, false, TILE, BOUNDS>(morph);
+    if (f16) return layout == MMDX_OUT_SOA_POS16 ? pick_morph<THREADS, MMDX_OUT_SOA_POS16, true, TILE, BOUNDS, SELECT>(morph) : nullptr;
+    if (layout == MMDX_OUT_SOA) return pick_morph<THREADS, MMDX_OUT_SOA, false, TILE, BOUNDS, SELECT>(morph);
+    if (layout == MMDX_OUT_VERTEX32) return pick_morph<THREADS, MMDX_OUT_VERTEX32, false, TILE, BOUNDS, SELECT>(morph);
     return nullptr;
 }
 
-template <bool BOUNDS>
+template <bool BOUNDS, bool SELECT = false>
 KernelFn pick_b(int threads, int layout, int morph, bool f16, bool tile) {
 #if MMDX_TILE >= 512
-    if (threads != 256) return tile ? pick_t<512, true, BOUNDS>(layout, morph, f16) : pick_t<512, false, BOUNDS>(layout, morph, f16);
+    if (threads != 256)
+        return tile ? pick_t<512, true, BOUNDS, SELECT>(layout, morph, f16) : pick_t<512, false, BOUNDS, SELECT>(layout, morph, f16);
 #endif
-    return tile ? pick_t<256, true, BOUNDS>(layout, morph, f16) : pick_t<256, false, BOUNDS>(layout, morph, f16);
+    return tile ? pick_t<256, true, BOUNDS, SELECT>(layout, morph, f16) : pick_t<256, false, BOUNDS, SELECT>(layout, morph, f16);
 }
 
 // tile = outputs in the engine's vertex order (MMDX_CREATE_TILE_ORDER): the direct-store variants.
 // wt = write-through stores (CopyFast): instantiated where it was measured to pay -- the SoA f32 crowd kernels (256 threads, no
 // morphs or shared morphs, original vertex order); every other shape keeps its nt stores whatever the hint says.
 // bounds = the BOUNDS flavour (mmdx_deform_batched_bounds): every shape, nt stores only.
-KernelFn pick(int threads, int layout, int morph, bool f16, bool tile, bool wt = false, bool bounds = false) {
+// select = the SELECT flavour (mmdx_deform_batched_select): every shape, with and without bounds, nt stores only.
+KernelFn pick(int threads, int layout, int morph, bool f16, bool tile, bool wt = false, bool bounds = false, bool select = false) {
+    if (select) return bounds ? pick_b<true, true>(threads, layout, morph, f16, tile) : pick_b<false, true>(threads, layout, morph, f16, tile);
     if (bounds) return pick_b<true>(threads, layout, morph, f16, tile);
     if (wt && deform_has_write_through(threads, layout, morph, f16, tile))
         return morph == kMorphNone ? deform_kernel<256, MMDX_OUT_SOA, kMorphNone, false, false, true>
@@ -1861,8 +1973,8 @@ hipError_t MMDX_K(prepare_kernels)() {
     for (int threads = 256; threads <= 512; threads += 256)
       for (int f16 = 0; f16 < 2; ++f16)
         for (int layout = 0; layout < 3; ++layout)
-            for (int morph = 0; morph < 16; ++morph) {
-                KernelFn fn = pick(threads, layout, morph & 3, f16 != 0, (morph & 4) != 0, false, morph >= 8);
+            for (int morph = 0; morph < 32; ++morph) {
+                KernelFn fn = pick(threads, layout, morph & 3, f16 != 0, (morph & 4) != 0, false, (morph & 8) != 0, morph >= 16);
                 if (!fn) continue;
                 hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1889,11 +2001,13 @@ hipError_t MMDX_K(prepare_kernels)() {
 
 hipError_t MMDX_K(launch_deform)(int threads, int layout, int morph, bool f16, const DeformParams &p,
                          uint32_t ntiles, size_t lds_bytes, hipStream_t stream) {
-    KernelFn fn = pick(threads, layout, morph, f16, p.tile_order != 0, p.write_through != 0, p.bounds != nullptr);
+    const bool select = p.sel_ids != nullptr;
+    if (select && p.sel_n == 0) return hipSuccess;       // an empty list: nothing to launch
+    KernelFn fn = pick(threads, layout, morph, f16, p.tile_order != 0, p.write_through != 0, p.bounds != nullptr, select);
     if (!fn) return hipErrorInvalidValue;
     DeformParams q = p;
     q.ntiles = ntiles;
-    q.ngroups = (p.ni + p.group - 1) / p.group;
+    q.ngroups = ((select ? p.sel_n : p.ni) + p.group - 1) / p.group;     // select: the grid covers the list's capacity
     q.rem_per_xcd = ((ntiles & 7u) * q.ngroups + 7u) / 8u;
     const dim3 grid(8u * ((ntiles >> 3) * q.ngroups + q.rem_per_xcd));
     hipLaunchKernelGGL(fn, grid, dim3((threads == 256 || kTileVerts < 512) ? 256 : 512), lds_bytes, stream, q);
@@ -1949,11 +2063,18 @@ hipError_t launch_bounds_reduce(const float *partials, uint32_t units, uint32_t 
     return hipGetLastError();
 }
 
+hipError_t launch_bounds_reduce_select(const float *partials, uint32_t units, uint32_t ni, float *out, const uint32_t *ids,
+                                       const uint32_t *count, uint32_t n_ids, hipStream_t stream) {
+    if (n_ids == 0) return hipSuccess;
+    hipLaunchKernelGGL(bounds_reduce_select_kernel, dim3(n_ids), dim3(64), 0, stream, partials, out, units, ni, ids, count, n_ids);
+    return hipGetLastError();
+}
+
 hipError_t launch_flatten(const FlattenParams &f, hipStream_t stream) {
     const uint32_t rows = f.quad ? ((f.niw + 3) / 4) * 4 : f.niw;
     const size_t n = size_t(rows) * (f.ns + 1);
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(flatten_kernel, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads),
+    hipLaunchKernelGGL(f.sel_ids ? flatten_select_kernel : flatten_kernel, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads),
                        0, stream, f);
     return hipGetLastError();
 }

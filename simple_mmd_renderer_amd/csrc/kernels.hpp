@@ -17,7 +17,9 @@ enum : int {
                         // with one shared facial state: the morph pass runs once per call)
     kMorphFused1 = 2,   // ONE set of morph rates for the launch, gathered inside the deform kernel: a single-model frame,
                         // or a crowd with a shared facial state (every workgroup repeats its tile's walk)
-    kMorphFused4 = 3    // per-instance weights, 4 instances share one pass over a CSR row
+    kMorphFused4 = 3,   // per-instance weights, 4 instances share one pass over a CSR row
+    kMorphSelect = 16   // kernels.hip only: ORed into deform_kernel's morph-mode template argument for the flavour of
+                        // mmdx_deform_batched_select (modes 16..19 in kernel listings)
 };
 
 struct DeformParams {
@@ -77,6 +79,13 @@ struct DeformParams {
     // mmdx_deform_batched_bounds (behind every field the other kernels read, so their argument layout does not move):
     uint32_t bounds_off;         // byte offset in dynamic LDS of the combine words (kBoundsLdsBytes; image path only)
     float *bounds;               // partial bounds, 6 floats per deform_bounds_units(); nullptr = the plain deform_kernel
+    // mmdx_deform_batched_select (again behind everything the other kernels read): the SELECT flavour of deform_kernel takes its
+    // instances from a list in device memory.  `ni` stays the extent of the call's arrays (ids >= ni are skipped); the grid is
+    // sized from sel_n; partial bounds are indexed by list position.
+    const uint32_t *sel_ids;     // [sel_n] instance indices; nullptr = not a select launch
+    const uint32_t *sel_count;   // live prefix of sel_ids (clamped to sel_n); nullptr = all of them
+    uint32_t sel_n;
+    uint32_t sel_interleave;     // list position = g*ngroups + grp (default) instead of grp*group + g; never with kMorphFused4
 };
 
 // Partial bounds (6 floats) per instance of a bounds launch: one per tile, or one per wave of a tile for tile-order outputs (no
@@ -87,6 +96,9 @@ inline uint32_t deform_bounds_units(int threads, uint32_t ntiles, bool tile_orde
 constexpr uint32_t kBoundsLdsBytes = 2 * 8 * 6 * 4;     // combine words: 2 instance parities x up to 8 waves x 6 floats
 // out[i][6] = bounds of instance i from the partials ([ni][units][6]), on `stream` behind the bounds launch
 hipError_t launch_bounds_reduce(const float *partials, uint32_t units, uint32_t ni, float *out, hipStream_t stream);
+// select launches: partials are [sel_n][units][6] by list position; block j writes out[ids[j]] when j is live and ids[j] < ni
+hipError_t launch_bounds_reduce_select(const float *partials, uint32_t units, uint32_t ni, float *out, const uint32_t *ids,
+                                       const uint32_t *count, uint32_t n_ids, hipStream_t stream);
 
 // Device-side record of the morph rates the `morphed` buffer of a handle was last computed from (shared morph pass of a crowd):
 // morph_apply_kernel compares the call's rates with it, bit for bit, and skips its walk when they are equal -- the automatic form of
@@ -101,6 +113,10 @@ struct FlattenParams {
     uint32_t nm, ns, niw;
     uint32_t quad;               // 1: write float4 [ceil(NIw/4)][NS] instance quads (pad lanes = 0)
     uint32_t *seen;              // morph_apply with the flatten fused in: the handle's RatesSeen record (nullptr: always walk)
+    // select launches (behind everything the other kernels read): row j of the output comes from rates[sel_ids[j]]; rows behind
+    // the live count and rows whose id is >= sel_ni are written as zeros.  niw = sel_n then.
+    const uint32_t *sel_ids, *sel_count;
+    uint32_t sel_ni;
 };
 
 // Bytes of dynamic LDS the deform kernel needs for (layout, morph mode, group).

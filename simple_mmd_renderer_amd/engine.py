@@ -293,10 +293,14 @@ class DeformModel:
                       "fill_GBs": info.fill_GBs, "store_flags": int(info.store_flags)}
 
     def deform_batched_raw(self, ni: int, weights_ptr, palettes_ptr, out_a_ptr, out_b_ptr, layout: int,
-                           flags: int, pos_scale: float = 1.0, pitch: int = 0, bounds_ptr=None) -> None:
+                           flags: int, pos_scale: float = 1.0, pitch: int = 0, bounds_ptr=None, select_ptr=None,
+                           select_count_ptr=None, n_select=None, select_on_device: bool = True) -> None:
         """pitch: instance pitch of the outputs in vertices (MMDX_OUT_PITCHED); 0 = dense [ni][NV].
         bounds_ptr: f32 [ni][6] {min xyz, max xyz} of every instance's written positions (mmdx_deform_batched_bounds), where the
-        outputs live: a device pointer with OUT_ON_DEVICE, else a host pointer."""
+        outputs live: a device pointer with OUT_ON_DEVICE, else a host pointer.
+        n_select (not None): mmdx_deform_batched_select -- only the instances listed in the u32 array at select_ptr (capacity
+        n_select; the first *select_count_ptr of them when a count is given) are deformed, everything else keeps its bytes;
+        device operands only.  select_on_device: the list and the count are device pointers (else host pointers)."""
         a = api.DeformArgs()
         a.struct_size = C.sizeof(api.DeformArgs)
         if pitch:
@@ -306,7 +310,13 @@ class DeformModel:
         a.morph_weights, a.palettes = weights_ptr, palettes_ptr
         a.out_a, a.out_b = out_a_ptr, out_b_ptr
         a.pos_scale = pos_scale
-        if bounds_ptr is None:
+        if n_select is not None:
+            s = api.InstanceSelect()
+            s.struct_size = C.sizeof(api.InstanceSelect)
+            s.flags = api.SELECT_ON_DEVICE if select_on_device else 0
+            s.ids, s.count, s.n_ids = select_ptr, select_count_ptr, n_select
+            api.check(api.lib().mmdx_deform_batched_select(self.h, C.byref(a), C.byref(s), bounds_ptr))
+        elif bounds_ptr is None:
             api.check(api.lib().mmdx_deform_batched(self.h, C.byref(a)))
         else:
             api.check(api.lib().mmdx_deform_batched_bounds(self.h, C.byref(a), bounds_ptr))
@@ -342,6 +352,18 @@ class DeformModel:
             ob = ob[:, :self.nv] if ob is not None else None
         out = (oa, ob) if ob is not None else (oa,)
         return out + (bnd,) if bounds else (out if ob is not None else oa)
+
+    def deform_batched_select(self, ni: int, ids, weights_ptr, palettes_ptr, out_a_ptr, out_b_ptr, layout: int, flags: int,
+                              pos_scale: float = 1.0, pitch: int = 0, bounds_ptr=None, count=None) -> None:
+        """mmdx_deform_batched_select with the list in host memory: `ids` (any integer sequence, converted to u32) names the
+        instances of the `ni`-instance device arrays to deform, `count` (optional) how many leading ids are in use.  Every other
+        operand is a device pointer as in deform_batched_raw; returns when the work has completed."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        cnt = C.c_uint32(count) if count is not None else None
+        self.deform_batched_raw(ni, weights_ptr, palettes_ptr, out_a_ptr, out_b_ptr, layout, flags, pos_scale, pitch, bounds_ptr,
+                                select_ptr=ids.ctypes.data if ids.size else None,
+                                select_count_ptr=C.addressof(cnt) if cnt is not None else None, n_select=int(ids.size),
+                                select_on_device=False)
 
     def sync(self) -> None:
         api.check(api.lib().mmdx_sync(self.h))
