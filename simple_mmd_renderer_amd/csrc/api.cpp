@@ -62,19 +62,6 @@ struct mmdx_graph_s {
 
 namespace {
 std::mutex g_graph_mu;          // graph <-> handle links (rare operations: record, destroy)
-
-// Store flavour of a crowd launch (kernels.hip CopyFast), decided from the CALL alone -- no table of addresses, no state behind the
-// boundary: the caller's hint first (mmdx_placement_info.store_flags hands it the probe's verdict for arrays from
-// mmdx_crowd_output_alloc), then MMDX_STORE_WT=0 / 1 (A/B runs), then the default for arrays nothing is known about: outputs large
-// enough to stream through the caches (>= 512 MB per call) are written through, because six plain allocations in seven are not in
-// the fast store mode (expected cost of the wrong guess: 2 % on a fast pair against 4.6-5 % on the others).
-bool write_through_for(size_t out_bytes, uint32_t flags) {
-    if (flags & MMDX_OUT_STORES_WRITE_THROUGH) return true;
-    if (flags & MMDX_OUT_STORES_CACHED) return false;
-    const int env = launch_overrides().store_wt;
-    if (env == 0 || env == 1) return env == 1;
-    return out_bytes >= (size_t(512) << 20);
-}
 }
 void mmdx::graph_note_handle(mmdx_model_s *model, GraphPin *pin) {
     if (!model || !model->capturing || !pin) return;
@@ -392,8 +379,8 @@ mmdx_status mmdx_model_create(const mmdx_model_desc *desc, mmdx_model_t *out_mod
     auto bail = [&](mmdx_status s) { free_model(m); return s; };
     if ((e = hipSetDevice(m->device)) != hipSuccess) return bail(hip_fail(e, "hipSetDevice"));
     std::call_once(g_prepare_once[m->device], [&] {
-        hipError_t pe = prepare_kernels();
-        g_prepare_status[m->device] = pe != hipSuccess ? pe : prepare_kernels_fast();
+        hipError_t pe = kernel_set(false).prepare();
+        g_prepare_status[m->device] = pe != hipSuccess ? pe : kernel_set(true).prepare();
     });
     if (g_prepare_status[m->device] != hipSuccess)
         return bail(hip_fail(g_prepare_status[m->device], "hipFuncSetAttribute(dynamic LDS)"));
@@ -482,10 +469,63 @@ mmdx_status mmdx_model_set_stream(mmdx_model_t m, void *hip_stream) {
     return MMDX_OK;
 }
 
-// mmdx_deform_batched and, with out_bounds != nullptr, mmdx_deform_batched_bounds; with sel != nullptr mmdx_deform_batched_select
-// (out_bounds optional there)
-static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, float *out_bounds,
-                                  const mmdx_instance_select *sel = nullptr) {
+// ---- mmdx_deform_batched, _bounds (out_bounds != nullptr) and _select (sel != nullptr; out_bounds optional there) ------------------
+// deform_batched() at the end of this section reads as the list of steps; each step is one function here.
+
+// What validation learns about the call's host pointers, for the steps that stage and route them
+struct CallPointers {
+    PtrKind kind_pal = PtrKind::Pageable, kind_w = PtrKind::Pageable;
+    void *map_a = nullptr, *map_b = nullptr;    // device-side addresses of page-locked host outputs (nullptr: pageable)
+    uint32_t sel_live_host = 0;                 // host lists: how many leading ids are in use
+    uint32_t pitch = 0;                         // instance pitch of the outputs (vertices from one instance to the next); dense outputs: NV
+};
+
+// Where the kernel writes and how the results reach the caller's arrays
+struct OutputRoute {
+    bool out_dev = false;                       // the caller's device arrays
+    bool direct = false, bounce = false;        // page-locked host memory: the caller's own, or the handle's bounce buffer
+    size_t bytes_a = 0, bytes_b = 0, off_b = 0; // the two arrays; the second one's offset in the bounce buffer
+};
+
+// the instance list of a select call: validated in full before anything is enqueued
+static mmdx_status validate_select(mmdx_model_t m, const mmdx_deform_args *a, const mmdx_instance_select *sel, uint32_t &live_host) {
+    const Plan &p = m->plan;
+    if (sel->struct_size != sizeof(mmdx_instance_select))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.struct_size mismatch");
+    if (sel->flags & ~uint32_t(MMDX_SELECT_ON_DEVICE))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown bits in mmdx_instance_select.flags");
+    if (sel->reserved0 != 0) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.reserved0 must be 0");
+    if (sel->n_ids && !sel->ids) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids is NULL");
+    // the GPU-resident crowd form only: a staging or bounce copy of the outputs moves whole arrays and cannot leave the
+    // instances outside a list untouched
+    const uint32_t need = MMDX_PALETTE_ON_DEVICE | MMDX_OUT_ON_DEVICE |
+                          (p.ns && a->morph_weights ? uint32_t(MMDX_WEIGHTS_ON_DEVICE) : 0u);
+    if ((a->flags & need) != need)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_deform_batched_select takes device operands only: pass MMDX_PALETTE_ON_DEVICE | "
+                                               "MMDX_OUT_ON_DEVICE, and MMDX_WEIGHTS_ON_DEVICE with morph_weights");
+    if (sel->flags & MMDX_SELECT_ON_DEVICE) {
+        if ((reinterpret_cast<uintptr_t>(sel->ids) | reinterpret_cast<uintptr_t>(sel->count)) & 3)
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "device ids / count of mmdx_instance_select must be 4-byte aligned");
+        return MMDX_OK;
+    }
+    if (m->capturing)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded the instance list must be in device memory "
+                                               "(MMDX_SELECT_ON_DEVICE)");
+    void *unused = nullptr;
+    if ((sel->n_ids && classify_pointer(sel->ids, &unused) == PtrKind::Device) ||
+        (sel->count && classify_pointer(sel->count, &unused) == PtrKind::Device))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "ids / count of mmdx_instance_select point to device memory: pass "
+                                               "MMDX_SELECT_ON_DEVICE");
+    live_host = sel->count ? std::min(*sel->count, sel->n_ids) : sel->n_ids;
+    for (uint32_t j = 0; j < live_host; ++j)
+        if (sel->ids[j] >= a->n_instances)
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids[" + std::to_string(j) + "] = " +
+                                                   std::to_string(sel->ids[j]) + " is not below n_instances");
+    return MMDX_OK;
+}
+
+static mmdx_status validate_call(mmdx_model_t m, const mmdx_deform_args *a, const float *out_bounds, const mmdx_instance_select *sel,
+                                 CallPointers &cp) {
     if (!m || !a) return fail(MMDX_ERR_INVALID_ARGUMENT, "model / args is NULL");
     if (a->struct_size != sizeof(mmdx_deform_args))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_deform_args.struct_size mismatch");
@@ -508,69 +548,34 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
         return fail(MMDX_ERR_INVALID_ARGUMENT, "palettes / out_a / out_b is NULL");
     if (p.ns && !a->morph_weights && !(a->flags & MMDX_MORPH_UNCHANGED))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "morph_weights is NULL");
-    // ---- the instance list of a select call: validated in full before anything is enqueued ------------------------------------
-    uint32_t sel_live_host = 0;             // host lists: how many leading ids are in use
-    if (sel) {
-        if (sel->struct_size != sizeof(mmdx_instance_select))
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.struct_size mismatch");
-        if (sel->flags & ~uint32_t(MMDX_SELECT_ON_DEVICE))
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown bits in mmdx_instance_select.flags");
-        if (sel->reserved0 != 0) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.reserved0 must be 0");
-        if (sel->n_ids && !sel->ids) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids is NULL");
-        // the GPU-resident crowd form only: a staging or bounce copy of the outputs moves whole arrays and cannot leave the
-        // instances outside a list untouched
-        const uint32_t need = MMDX_PALETTE_ON_DEVICE | MMDX_OUT_ON_DEVICE |
-                              (p.ns && a->morph_weights ? uint32_t(MMDX_WEIGHTS_ON_DEVICE) : 0u);
-        if ((a->flags & need) != need)
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_deform_batched_select takes device operands only: pass MMDX_PALETTE_ON_DEVICE | "
-                                                   "MMDX_OUT_ON_DEVICE, and MMDX_WEIGHTS_ON_DEVICE with morph_weights");
-        if (sel->flags & MMDX_SELECT_ON_DEVICE) {
-            if ((reinterpret_cast<uintptr_t>(sel->ids) | reinterpret_cast<uintptr_t>(sel->count)) & 3)
-                return fail(MMDX_ERR_INVALID_ARGUMENT, "device ids / count of mmdx_instance_select must be 4-byte aligned");
-        } else {
-            if (m->capturing)
-                return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded the instance list must be in device memory "
-                                                       "(MMDX_SELECT_ON_DEVICE)");
-            void *unused = nullptr;
-            if ((sel->n_ids && classify_pointer(sel->ids, &unused) == PtrKind::Device) ||
-                (sel->count && classify_pointer(sel->count, &unused) == PtrKind::Device))
-                return fail(MMDX_ERR_INVALID_ARGUMENT, "ids / count of mmdx_instance_select point to device memory: pass "
-                                                       "MMDX_SELECT_ON_DEVICE");
-            sel_live_host = sel->count ? std::min(*sel->count, sel->n_ids) : sel->n_ids;
-            for (uint32_t j = 0; j < sel_live_host; ++j)
-                if (sel->ids[j] >= ni)
-                    return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids[" + std::to_string(j) + "] = " +
-                                                           std::to_string(sel->ids[j]) + " is not below n_instances");
-        }
-    }
-    // instance pitch of the outputs (vertices from one instance to the next); dense outputs: NV
+    if (sel)
+        if (mmdx_status sst = validate_select(m, a, sel, cp.sel_live_host)) return sst;
     const bool pitched = (a->flags & MMDX_OUT_PITCHED) != 0;
-    const uint32_t pitch = pitched ? a->out_instance_pitch : p.nv;
+    const uint32_t pitch = cp.pitch = pitched ? a->out_instance_pitch : p.nv;
     if (pitched && pitch < p.nv)
         return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_deform_args.out_instance_pitch is smaller than the model's vertex count");
     if (pitched && (uint64_t(ni) - 1) * pitch + p.nv > uint64_t(SIZE_MAX) / 32)
         return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_deform_args.out_instance_pitch: the output span overflows");
     // host arguments: what kind of memory they are (device memory without its *_ON_DEVICE flag is a caller's
     // mistake that would otherwise end in a CPU memcpy from / to a device address)
-    void *map_a = nullptr, *map_b = nullptr, *map_unused = nullptr;
-    PtrKind kind_pal = PtrKind::Pageable, kind_w = PtrKind::Pageable, kind_a = PtrKind::Pageable, kind_b = PtrKind::Pageable;
-    if (!(a->flags & MMDX_PALETTE_ON_DEVICE) && (kind_pal = classify_pointer(a->palettes, &map_unused)) == PtrKind::Device)
+    void *map_unused = nullptr;
+    if (!(a->flags & MMDX_PALETTE_ON_DEVICE) && (cp.kind_pal = classify_pointer(a->palettes, &map_unused)) == PtrKind::Device)
         return fail(MMDX_ERR_INVALID_ARGUMENT, "palettes points to device memory: pass MMDX_PALETTE_ON_DEVICE");
     if (p.ns && !(a->flags & MMDX_WEIGHTS_ON_DEVICE) &&
-        (kind_w = classify_pointer(a->morph_weights, &map_unused)) == PtrKind::Device)
+        (cp.kind_w = classify_pointer(a->morph_weights, &map_unused)) == PtrKind::Device)
         return fail(MMDX_ERR_INVALID_ARGUMENT, "morph_weights points to device memory: pass MMDX_WEIGHTS_ON_DEVICE");
     if (!(a->flags & MMDX_OUT_ON_DEVICE)) {
-        kind_a = classify_pointer(a->out_a, &map_a);
-        if (layout != MMDX_OUT_VERTEX32) kind_b = classify_pointer(a->out_b, &map_b);
+        PtrKind kind_b = PtrKind::Pageable;
+        const PtrKind kind_a = classify_pointer(a->out_a, &cp.map_a);
+        if (layout != MMDX_OUT_VERTEX32) kind_b = classify_pointer(a->out_b, &cp.map_b);
         if (kind_a == PtrKind::Device || kind_b == PtrKind::Device)
             return fail(MMDX_ERR_INVALID_ARGUMENT, "out_a / out_b points to device memory: pass MMDX_OUT_ON_DEVICE");
-        if (!host_direct_enabled()) map_a = map_b = nullptr;
+        if (!host_direct_enabled()) cp.map_a = cp.map_b = nullptr;
     }
     // bounds live where the outputs live
-    const bool bounds = out_bounds != nullptr;
-    if (bounds && (a->flags & MMDX_OUT_ON_DEVICE) && (reinterpret_cast<uintptr_t>(out_bounds) & 3))
+    if (out_bounds && (a->flags & MMDX_OUT_ON_DEVICE) && (reinterpret_cast<uintptr_t>(out_bounds) & 3))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "device out_bounds must be 4-byte aligned");
-    if (bounds && !(a->flags & MMDX_OUT_ON_DEVICE) && classify_pointer(out_bounds, &map_unused) == PtrKind::Device)
+    if (out_bounds && !(a->flags & MMDX_OUT_ON_DEVICE) && classify_pointer(out_bounds, &map_unused) == PtrKind::Device)
         return fail(MMDX_ERR_INVALID_ARGUMENT, "out_bounds points to device memory: pass MMDX_OUT_ON_DEVICE");
     if (m->capturing) {
         if (mmdx_status rst = recording_thread_check(m)) return rst;
@@ -579,12 +584,12 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
             return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory");
         if (m->profile) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_profile_enable and graph recording exclude each other");
     }
-    const bool shared = (a->flags & MMDX_WEIGHTS_SHARED) != 0 || ni == 1;
-    const bool fast = (p.flags & MMDX_CREATE_FAST_MATH) != 0;      // contracted multiply-adds: this model opted out of bit-exactness
-    const uint64_t nvi = uint64_t(ni) * p.nv;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = m->stream;
-    hipEvent_t *pev = nullptr;  // {skin0, skin1, morph0, morph1} of this call when profiling
+    return MMDX_OK;
+}
+
+// `pev`: {skin0, skin1, morph0, morph1} of this call when it is one of the profiled ones, else nullptr
+static mmdx_status profile_events(mmdx_model_t m, hipEvent_t *&pev) {
+    pev = nullptr;
     // a full recording (kMaxProfiledCalls without mmdx_profile_collect) stops recording; it never fails the call
     if (m->profile && m->prof_calls < kMaxProfiledCalls && m->prof_seen++ % m->profile_stride == 0) {
         while (m->prof_events.size() < 4 * (m->prof_calls + 1)) {
@@ -594,63 +599,84 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
         }
         pev = m->prof_events.data() + 4 * m->prof_calls;
     }
+    return MMDX_OK;
+}
 
+// The kernel arguments that depend on the model alone; every per-call field zero
+static DeformParams static_params(const mmdx_model_s &m) {
+    const Plan &p = m.plan;
     DeformParams dp;
     std::memset(&dp, 0, sizeof(dp));
-    dp.tiles = static_cast<const TileHdr *>(m->tiles.ptr);
-    dp.spos = m->spos.ptr;
-    dp.snrm = static_cast<const float *>(m->snrm.ptr);
-    dp.suv = static_cast<const float *>(m->suv.ptr);
-    dp.perm = static_cast<const uint16_t *>(m->perm.ptr);
-    dp.skin1 = static_cast<const uint16_t *>(m->skin1.ptr);
-    dp.skin2_ids = static_cast<const uint32_t *>(m->skin2_ids.ptr);
-    dp.skin2_w = static_cast<const float *>(m->skin2_w.ptr);
-    dp.skin4_ids = static_cast<const uint2 *>(m->skin4_ids.ptr);
-    dp.skin4_w = static_cast<const float4 *>(m->skin4_w.ptr);
-    dp.bone_list = static_cast<const uint32_t *>(m->bone_list.ptr);
-    dp.ell = static_cast<const uint2 *>(m->ell.ptr);
-    dp.entries = m->entries.ptr;
-    dp.nv = p.nv; dp.nb = p.nb; dp.ns = p.ns; dp.ni = ni;
-    dp.pos_scale = a->pos_scale;
+    dp.tiles = static_cast<const TileHdr *>(m.tiles.ptr);
+    dp.spos = m.spos.ptr;
+    dp.snrm = static_cast<const float *>(m.snrm.ptr);
+    dp.suv = static_cast<const float *>(m.suv.ptr);
+    dp.perm = static_cast<const uint16_t *>(m.perm.ptr);
+    dp.skin1 = static_cast<const uint16_t *>(m.skin1.ptr);
+    dp.skin2_ids = static_cast<const uint32_t *>(m.skin2_ids.ptr);
+    dp.skin2_w = static_cast<const float *>(m.skin2_w.ptr);
+    dp.skin4_ids = static_cast<const uint2 *>(m.skin4_ids.ptr);
+    dp.skin4_w = static_cast<const float4 *>(m.skin4_w.ptr);
+    dp.bone_list = static_cast<const uint32_t *>(m.bone_list.ptr);
+    dp.ell = static_cast<const uint2 *>(m.ell.ptr);
+    dp.entries = m.entries.ptr;
+    dp.nv = p.nv; dp.nb = p.nb; dp.ns = p.ns;
     dp.pal_stride = p.max_tile_bones * 3;
     dp.finite_offsets = p.finite_offsets ? 1u : 0u;
-    const LaunchOverrides &ov = launch_overrides();
-    dp.interleave = uint32_t(ov.interleave);
+    dp.interleave = uint32_t(launch_overrides().interleave);
     dp.tile_order = (p.flags & MMDX_CREATE_TILE_ORDER) ? 1u : 0u;
+    return dp;
+}
 
-    // ---- instance list (select calls): device lists are used in place -- a recorded graph reads them afresh at every replay; host
-    // lists go to a scratch of the handle in stream order, count word first -------------------------------------------------
-    const uint32_t nwork = sel ? sel->n_ids : ni;       // instances the launch is sized for
-    if (sel) {
-        dp.sel_n = sel->n_ids;
-        dp.sel_interleave = ov.select_interleave != 0 ? 1u : 0u;
-        if (sel->flags & MMDX_SELECT_ON_DEVICE) {
-            dp.sel_ids = sel->ids; dp.sel_count = sel->count;
-        } else if (sel->n_ids) {
-            HIP_TRY(m->sel.ensure((size_t(sel->n_ids) + 1) * 4));
-            m->sel_host.resize(size_t(sel->n_ids) + 1);
-            m->sel_host[0] = sel_live_host;
-            std::memcpy(m->sel_host.data() + 1, sel->ids, size_t(sel->n_ids) * 4);
-            // (pageable source: the copy has left the host vector when the call returns)
-            HIP_TRY(hipMemcpyAsync(m->sel.ptr, m->sel_host.data(), m->sel_host.size() * 4, hipMemcpyHostToDevice, st));
-            dp.sel_count = static_cast<const uint32_t *>(m->sel.ptr);
-            dp.sel_ids = dp.sel_count + 1;
-        }
+// The instance list of a select call: device lists are used in place -- a recorded graph reads them afresh at every replay; host
+// lists go to a scratch of the handle in stream order, count word first
+static mmdx_status stage_select(mmdx_model_t m, const mmdx_instance_select *sel, uint32_t live_host, DeformParams &dp) {
+    dp.sel_n = sel->n_ids;
+    dp.sel_interleave = launch_overrides().select_interleave != 0 ? 1u : 0u;
+    if (sel->flags & MMDX_SELECT_ON_DEVICE) {
+        dp.sel_ids = sel->ids; dp.sel_count = sel->count;
+    } else if (sel->n_ids) {
+        HIP_TRY(m->sel.ensure((size_t(sel->n_ids) + 1) * 4));
+        m->sel_host.resize(size_t(sel->n_ids) + 1);
+        m->sel_host[0] = live_host;
+        std::memcpy(m->sel_host.data() + 1, sel->ids, size_t(sel->n_ids) * 4);
+        // (pageable source: the copy has left the host vector when the call returns)
+        HIP_TRY(hipMemcpyAsync(m->sel.ptr, m->sel_host.data(), m->sel_host.size() * 4, hipMemcpyHostToDevice, m->stream));
+        dp.sel_count = static_cast<const uint32_t *>(m->sel.ptr);
+        dp.sel_ids = dp.sel_count + 1;
     }
+    return MMDX_OK;
+}
 
-    // ---- palettes -------------------------------------------------------------------------------
-    const size_t pal_bytes = size_t(ni) * p.nb * 64;
+static mmdx_status stage_palettes(mmdx_model_t m, const mmdx_deform_args *a, PtrKind kind_pal, DeformParams &dp) {
+    const size_t pal_bytes = size_t(a->n_instances) * m->plan.nb * 64;
     if (a->flags & MMDX_PALETTE_ON_DEVICE) {
         if (reinterpret_cast<uintptr_t>(a->palettes) & 15)
             return fail(MMDX_ERR_INVALID_ARGUMENT, "device palettes must be 16-byte aligned");
         dp.palettes = a->palettes;
     } else {
         HIP_TRY(m->pal.ensure(pal_bytes));
-        HIP_TRY(copy_in(m, m->pal.ptr, a->palettes, kind_pal, pal_bytes, 0, st));
+        HIP_TRY(copy_in(m, m->pal.ptr, a->palettes, kind_pal, pal_bytes, 0, m->stream));
         dp.palettes = static_cast<const float *>(m->pal.ptr);
     }
+    return MMDX_OK;
+}
 
-    // ---- morph mode + slot weights ----------------------------------------------------------------
+// The morph mode of a call (kMorph*), and whether its shared morph pass can be left out
+struct MorphMode {
+    int morph = kMorphNone;
+    bool shared = false;             // one set of rates for the call
+    bool autoskip = false;           // MMDX_MORPH_AUTOSKIP
+    bool unchanged = false;          // the shared rates are those `morphed` was computed from: by the caller's word, or found equal here
+    bool host_skip = false;          // ... found equal here: the host-side comparison
+    bool host_rates_call = false;    // a crowd's shared rates, in host memory, that take the morph pass
+};
+
+// A decision only: reads the handle's record of what `morphed` holds, changes nothing
+static mmdx_status choose_morph_mode(const mmdx_model_s *m, const mmdx_deform_args *a, const mmdx_instance_select *sel, MorphMode &mm) {
+    const Plan &p = m->plan;
+    const uint32_t ni = a->n_instances;
+    const bool shared = mm.shared = (a->flags & MMDX_WEIGHTS_SHARED) != 0 || ni == 1;
     // Morph mode.  Shared rates: a single frame and SMALL crowds with one facial state gather the morphs inside the deform
     // kernel (every workgroup repeats its tile's walk; no separate launch: 8.8 vs 10.1 us for 2 instances of the 50k
     // model, break-even at 8, tools/archive/probes/shared_ab.py); larger crowds run the morph pass once, in front (257 vs 269 us for
@@ -658,103 +684,122 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
     bool unchanged = shared && ni > 1 && (a->flags & MMDX_MORPH_UNCHANGED);
     if (unchanged && !m->morphed_valid)
         return fail(MMDX_ERR_INVALID_ARGUMENT, "MMDX_MORPH_UNCHANGED without an earlier MMDX_WEIGHTS_SHARED crowd call on this model");
-    int morph = kMorphNone;
     const int sf = launch_overrides().shared_fused;          // 0: never for crowds, 1: small crowds (default), 2: always
     // The same without the caller's promise: vertex_images_ depends on morph_rates_ only (poser_impl.inl:362-386), so a crowd call
     // whose shared rates are, bit for bit, those of the morph pass whose result this handle still holds needs no morph pass.
     // Rates in HOST memory are compared here (memcmp with the copy kept of the last pass's), the launch and the upload are skipped;
     // rates in DEVICE memory are compared by morph_apply_kernel itself, which then skips its walk (RatesSeen, kernels.hpp).
-    const bool autoskip = launch_overrides().morph_autoskip != 0;
-    if (m->pin.replayed.exchange(false, std::memory_order_acq_rel)) m->host_rates_valid = false;   // a graph replay ran a morph pass
+    const bool autoskip = mm.autoskip = launch_overrides().morph_autoskip != 0;
     const bool crowd_pass = p.ns && shared && ni > 1 && !(p.ns <= kMaxFusedSlots && (sf == 2 || (sf == 1 && ni <= 8)));
     const bool host_rates_call = crowd_pass && !unchanged && !(a->flags & MMDX_WEIGHTS_ON_DEVICE);
     if (host_rates_call && autoskip && m->morphed_valid && m->host_rates_valid && m->host_rates.size() == p.nm &&
         std::memcmp(m->host_rates.data(), a->morph_weights, size_t(p.nm) * 4) == 0) {
-        unchanged = true;
-        ++m->host_skips;
+        unchanged = mm.host_skip = true;
     }
     // (a select call with an empty list launches no deform kernel: its shared rates take the morph pass, so that the positions
     // later MMDX_MORPH_UNCHANGED calls rely on are there)
     const bool gather_in_kernel = ni == 1 || (p.ns <= kMaxFusedSlots && !unchanged && (sf == 2 || (sf == 1 && ni <= 8)) &&
                                               !(sel && sel->n_ids == 0));
-    if (p.ns) morph = shared ? (gather_in_kernel ? kMorphFused1 : kMorphShared) : kMorphFused4;
-    if (morph != kMorphNone) {
-        const uint32_t niw = shared ? 1u : nwork;           // (select, per-instance rates: one row per list position)
-        const float *rates_dev;
-        if ((a->flags & MMDX_WEIGHTS_ON_DEVICE) || unchanged) {
-            rates_dev = a->morph_weights;                     // (unchanged: never read)
-        } else {
-            HIP_TRY(m->rates.ensure(size_t(niw) * p.nm * 4));
-            HIP_TRY(copy_in(m, m->rates.ptr, a->morph_weights, kind_w, size_t(niw) * p.nm * 4, kBounceInBytes / 2, st));
-            rates_dev = static_cast<const float *>(m->rates.ptr);
-        }
-        FlattenParams f{};
-        f.rates = rates_dev;
-        f.slot_top = static_cast<const uint32_t *>(m->slot_top.ptr);
-        f.chain_off = static_cast<const uint32_t *>(m->chain_off.ptr);
-        f.chain_rate = static_cast<const float *>(m->chain_rate.ptr);
-        f.nm = p.nm; f.ns = p.ns; f.niw = niw;
-        f.quad = morph == kMorphFused4 ? 1u : 0u;
-        f.seen = nullptr;
-        if (sel && !shared) { f.sel_ids = dp.sel_ids; f.sel_count = dp.sel_count; f.sel_ni = ni; }
-        const size_t rows = f.quad ? size_t((niw + 3) / 4) * 4 : niw;
-        HIP_TRY(m->wslot.ensure(rows * (size_t(p.ns) + 1) * 4));
-        f.out = static_cast<float *>(m->wslot.ptr);
-        if (pev) HIP_TRY(hipEventRecord(pev[2], st));
-        dp.wslot = f.out;
-        dp.morphed = static_cast<float *>(m->morphed.ptr);
-        if (morph == kMorphShared && unchanged) {
-            // nothing to launch: `morphed` holds the positions
-        } else if (morph == kMorphShared && p.ns <= kMaxFusedSlots) {
-            if (autoskip) f.seen = static_cast<uint32_t *>(m->seen.ptr);
-            HIP_TRY((fast ? launch_morph_apply_fast : launch_morph_apply)(p.f16, dp, &f, st));      // flatten fused in: one launch
-        } else if (morph == kMorphFused1) {
-            if (ni > 1) dp.morph_seen = static_cast<uint32_t *>(m->seen.ptr);   // it overwrites `morphed`: the record is void after it
-            // A single frame (ni == 1) leaves the model's kept positions alone: they belong to the last SHARED CROWD call
-            // (MMDX_MORPH_UNCHANGED is documented against that one), whichever kernel the frame takes.
-            if (ni == 1) dp.morphed = nullptr;
-            dp.fused_rates = rates_dev;                           // flatten inside the deform kernel
-            dp.slot_top = f.slot_top; dp.chain_off = f.chain_off; dp.chain_rate = f.chain_rate;
-            dp.nm = p.nm;
-        } else {
-            HIP_TRY(launch_flatten(f, st));
-            if (morph == kMorphShared) {
-                HIP_TRY((fast ? launch_morph_apply_fast : launch_morph_apply)(p.f16, dp, nullptr, st));
-                HIP_TRY(hipMemsetAsync(m->seen.ptr, 0, 4, st));       // this (rare: > 8192 slots) pass keeps no record of its rates
-            }
-        }
-        // the host's own record: the rates of the pass `morphed` now holds, when they were host memory
-        if (morph == kMorphShared && !unchanged) {
-            m->host_rates_valid = host_rates_call;
-            if (host_rates_call) m->host_rates.assign(a->morph_weights, a->morph_weights + p.nm);
-        } else if (morph == kMorphFused1 && ni > 1) {
-            m->host_rates_valid = false;
-        }
-        if (pev) HIP_TRY(hipEventRecord(pev[3], st));
-        if (morph == kMorphShared || (morph == kMorphFused1 && ni > 1)) m->morphed_valid = true;   // kept by either path
-    }
+    if (p.ns) mm.morph = shared ? (gather_in_kernel ? kMorphFused1 : kMorphShared) : kMorphFused4;
+    mm.unchanged = unchanged; mm.host_rates_call = host_rates_call;
+    return MMDX_OK;
+}
 
-    // ---- outputs ---------------------------------------------------------------------------------
-    const size_t bytes_a = out_bytes_a(layout, nvi), bytes_b = out_bytes_b(layout, nvi);
-    const bool out_dev = (a->flags & MMDX_OUT_ON_DEVICE) != 0;
-    // Host outputs in page-locked, device-mapped memory (mmdx_host_malloc / hipHostMalloc / hipHostRegister): the
-    // kernel stores straight into them over PCIe -- 16-byte coalesced stores, overlapped with the skinning -- and
-    // the staging buffer plus the device-to-host copy command (~10 us of fixed cost per frame) drop out.
-    // Anything else goes through the staging buffer as before.
-    // Small outputs bound for pageable memory (a frame of one model) take the same route into a page-locked
-    // bounce buffer of the model's and are copied out by the CPU after the wait: the copy command into pageable
-    // memory is the one piece of the per-frame call whose cost varies by 100 us between hosts.
-    // Pitched outputs: the kernel writes them pitched where it writes the caller's arrays (device, page-locked host); the
-    // staging and bounce buffers stay dense and the copy out of them spreads the instances (the gap is never written).
-    bool out_direct = false, out_bounce = false;
+// Morph mode + slot weights: decides the call's morph mode (`morph`, kMorph*), uploads the rates, runs the flatten / shared morph
+// pass where the mode has one, and fills the morph fields of `dp`.  The handle's record of what `morphed` holds (morphed_valid,
+// host_rates, the device-side RatesSeen) is written here and nowhere else.
+static mmdx_status run_morph_pass(mmdx_model_t m, const mmdx_deform_args *a, const mmdx_instance_select *sel, PtrKind kind_w,
+                                  hipEvent_t *pev, DeformParams &dp, int &morph) {
+    const Plan &p = m->plan;
+    const KernelSet &ks = kernel_set((p.flags & MMDX_CREATE_FAST_MATH) != 0);
+    const uint32_t ni = a->n_instances;
+    hipStream_t st = m->stream;
+    if (m->pin.replayed.exchange(false, std::memory_order_acq_rel)) m->host_rates_valid = false;   // a graph replay ran a morph pass
+    MorphMode mm;
+    if (mmdx_status s = choose_morph_mode(m, a, sel, mm)) return s;
+    if (mm.host_skip) ++m->host_skips;
+    morph = mm.morph;
+    const bool shared = mm.shared, autoskip = mm.autoskip, unchanged = mm.unchanged, host_rates_call = mm.host_rates_call;
+    if (morph == kMorphNone) return MMDX_OK;
+    const uint32_t niw = shared ? 1u : (sel ? sel->n_ids : ni);     // (select, per-instance rates: one row per list position)
+    const float *rates_dev;
+    if ((a->flags & MMDX_WEIGHTS_ON_DEVICE) || unchanged) {
+        rates_dev = a->morph_weights;                     // (unchanged: never read)
+    } else {
+        HIP_TRY(m->rates.ensure(size_t(niw) * p.nm * 4));
+        HIP_TRY(copy_in(m, m->rates.ptr, a->morph_weights, kind_w, size_t(niw) * p.nm * 4, kBounceInBytes / 2, st));
+        rates_dev = static_cast<const float *>(m->rates.ptr);
+    }
+    FlattenParams f{};
+    f.rates = rates_dev;
+    f.slot_top = static_cast<const uint32_t *>(m->slot_top.ptr);
+    f.chain_off = static_cast<const uint32_t *>(m->chain_off.ptr);
+    f.chain_rate = static_cast<const float *>(m->chain_rate.ptr);
+    f.nm = p.nm; f.ns = p.ns; f.niw = niw;
+    f.quad = morph == kMorphFused4 ? 1u : 0u;
+    f.seen = nullptr;
+    if (sel && !shared) { f.sel_ids = dp.sel_ids; f.sel_count = dp.sel_count; f.sel_ni = ni; }
+    const size_t rows = f.quad ? size_t((niw + 3) / 4) * 4 : niw;
+    HIP_TRY(m->wslot.ensure(rows * (size_t(p.ns) + 1) * 4));
+    f.out = static_cast<float *>(m->wslot.ptr);
+    if (pev) HIP_TRY(hipEventRecord(pev[2], st));
+    dp.wslot = f.out;
+    dp.morphed = static_cast<float *>(m->morphed.ptr);
+    if (morph == kMorphShared && unchanged) {
+        // nothing to launch: `morphed` holds the positions
+    } else if (morph == kMorphShared && p.ns <= kMaxFusedSlots) {
+        if (autoskip) f.seen = static_cast<uint32_t *>(m->seen.ptr);
+        HIP_TRY(ks.launch_morph_apply(p.f16, dp, &f, st));      // flatten fused in: one launch
+    } else if (morph == kMorphFused1) {
+        if (ni > 1) dp.morph_seen = static_cast<uint32_t *>(m->seen.ptr);   // it overwrites `morphed`: the record is void after it
+        // A single frame (ni == 1) leaves the model's kept positions alone: they belong to the last SHARED CROWD call
+        // (MMDX_MORPH_UNCHANGED is documented against that one), whichever kernel the frame takes.
+        if (ni == 1) dp.morphed = nullptr;
+        dp.fused_rates = rates_dev;                           // flatten inside the deform kernel
+        dp.slot_top = f.slot_top; dp.chain_off = f.chain_off; dp.chain_rate = f.chain_rate;
+        dp.nm = p.nm;
+    } else {
+        HIP_TRY(launch_flatten(f, st));
+        if (morph == kMorphShared) {
+            HIP_TRY(ks.launch_morph_apply(p.f16, dp, nullptr, st));
+            HIP_TRY(hipMemsetAsync(m->seen.ptr, 0, 4, st));       // this (rare: > 8192 slots) pass keeps no record of its rates
+        }
+    }
+    // the host's own record: the rates of the pass `morphed` now holds, when they were host memory
+    if (morph == kMorphShared && !unchanged) {
+        m->host_rates_valid = host_rates_call;
+        if (host_rates_call) m->host_rates.assign(a->morph_weights, a->morph_weights + p.nm);
+    } else if (morph == kMorphFused1 && ni > 1) {
+        m->host_rates_valid = false;
+    }
+    if (pev) HIP_TRY(hipEventRecord(pev[3], st));
+    if (morph == kMorphShared || (morph == kMorphFused1 && ni > 1)) m->morphed_valid = true;   // kept by either path
+    return MMDX_OK;
+}
+
+// Where the kernel writes (dp.out_a / out_b / out_aligned / pitch) and how the results reach the caller (`r`).
+// Host outputs in page-locked, device-mapped memory (mmdx_host_malloc / hipHostMalloc / hipHostRegister): the
+// kernel stores straight into them over PCIe -- 16-byte coalesced stores, overlapped with the skinning -- and
+// the staging buffer plus the device-to-host copy command (~10 us of fixed cost per frame) drop out.
+// Anything else goes through the staging buffer as before.
+// Small outputs bound for pageable memory (a frame of one model) take the same route into a page-locked
+// bounce buffer of the model's and are copied out by the CPU after the wait: the copy command into pageable
+// memory is the one piece of the per-frame call whose cost varies by 100 us between hosts.
+// Pitched outputs: the kernel writes them pitched where it writes the caller's arrays (device, page-locked host); the
+// staging and bounce buffers stay dense and the copy out of them spreads the instances (the gap is never written).
+static mmdx_status route_outputs(mmdx_model_t m, const mmdx_deform_args *a, const CallPointers &cp, DeformParams &dp, OutputRoute &r) {
+    const Plan &p = m->plan;
+    const uint64_t nvi = uint64_t(a->n_instances) * p.nv;
+    const size_t bytes_a = r.bytes_a = out_bytes_a(a->out_layout, nvi), bytes_b = r.bytes_b = out_bytes_b(a->out_layout, nvi);
+    r.out_dev = (a->flags & MMDX_OUT_ON_DEVICE) != 0;
     constexpr size_t kBounceMax = size_t(4) << 20;
-    const size_t off_b = (bytes_a + 63) & ~size_t(63);
-    if (out_dev) {
+    const size_t off_b = r.off_b = (bytes_a + 63) & ~size_t(63);
+    if (r.out_dev) {
         dp.out_a = a->out_a; dp.out_b = a->out_b;
     } else {
-        void *da = map_a, *db = bytes_b ? map_b : nullptr;
-        out_direct = da && (!bytes_b || db);
-        if (!out_direct && off_b + bytes_b <= kBounceMax && host_direct_enabled()) {
+        void *da = cp.map_a, *db = bytes_b ? cp.map_b : nullptr;
+        r.direct = da && (!bytes_b || db);
+        if (!r.direct && off_b + bytes_b <= kBounceMax && host_direct_enabled()) {
             if (m->bounce_bytes < off_b + bytes_b) {
                 if (m->bounce) (void)hipHostFree(m->bounce);
                 m->bounce = nullptr; m->bounce_bytes = 0; m->bounce_dev = nullptr;
@@ -764,11 +809,11 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
             if (m->bounce) {
                 if (!m->bounce_dev) m->bounce_dev = mapped_host_pointer(m->bounce);
                 da = m->bounce_dev;
-                out_bounce = da != nullptr;
-                if (out_bounce) db = static_cast<unsigned char *>(da) + off_b;
+                r.bounce = da != nullptr;
+                if (r.bounce) db = static_cast<unsigned char *>(da) + off_b;
             }
         }
-        if (out_direct || out_bounce) {
+        if (r.direct || r.bounce) {
             dp.out_a = da; dp.out_b = bytes_b ? db : nullptr;
         } else {
             HIP_TRY(m->out_a.ensure(bytes_a));
@@ -777,135 +822,49 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
         }
     }
     dp.out_aligned = ((reinterpret_cast<uintptr_t>(dp.out_a) | reinterpret_cast<uintptr_t>(dp.out_b)) & 15) == 0;
-    dp.pitch = out_dev || out_direct ? pitch : p.nv;
+    dp.pitch = r.out_dev || r.direct ? cp.pitch : p.nv;
+    return MMDX_OK;
+}
 
-    // ---- workgroup shape ------------------------------------------------------------------------------
-    // 256 threads / two vertex slots per lane everywhere except the per-instance-morph path: there one slot
-    // per lane (512 threads) leaves the registers to serve 8 instances per walk over a morph row.
-    // A single frame (one instance) is latency-bound: one slot per lane and twice the waves per tile finish sooner
-    // (config 2: 8.4 -> 6.9 us, config 5: 16.9 -> 14.9 us).
-    const bool one_frame = ni == 1 && nwork <= 1 && (morph == kMorphNone || morph == kMorphFused1);
-    // (tile-order outputs: no LDS image, 80 VGPRs with one slot per lane -- 512 threads measured 215.5 vs 219.1 us on the crowd)
-    int threads = (ov.threads ? ov.threads : (morph == kMorphFused4 || one_frame || dp.tile_order ? 512 : 256)) == 512 ? 512 : 256;
-    if (morph == kMorphFused4 && threads == 512) {   // tiles with hundreds of bones: 8 palettes do not fit, 4 may
-        uint32_t so, wo;
-        if (deform_lds_bytes(512, layout, morph, 8, p.max_tile_bones, p.ns, &so, &wo) > 160 * 1024) threads = 256;
-    }
-    // ---- store flavour: only where the launch shape has the write-through flavour, and only for outputs in device memory (stores
-    // into mapped host memory cross PCIe whatever their cache bits say) ------------------------------------------------------------
-    // (the bounds flavour has no write-through variant: its calls store cached whatever the hint says)
-    // (nor has the select flavour)
-    dp.write_through = !bounds && !sel && out_dev && deform_has_write_through(threads, int(layout), morph, p.f16, dp.tile_order != 0) &&
-                       write_through_for(bytes_a + bytes_b, a->flags) ? 1u : 0u;
-    m->last_write_through = dp.write_through != 0;
-    // ---- group size (instances per workgroup) from the LDS budget ---------------------------------
-    const uint32_t gmin = morph == kMorphFused4 ? (threads == 512 ? 8u : 4u) : 1u;
-    uint32_t group = gmin;
-    if (morph != kMorphFused1 || ni > 1) {
-        const uint32_t target = uint32_t(ov.lds_target ? ov.lds_target : (morph == kMorphFused4 ? 64 : 42) * 1024);
-        uint32_t so, wo;
-        const size_t fixed = deform_lds_bytes(threads, layout, morph, 0, p.max_tile_bones, p.ns, &so, &wo, dp.tile_order != 0);
-        const size_t per = size_t(p.max_tile_bones) * 48;
-        uint32_t g = target > fixed ? uint32_t((target - fixed) / per) : 0u;
-        g = std::min(g, (morph == kMorphFused4 || dp.tile_order) ? 16u : 32u);   // tile order: 16 219 us, 32 229 us, 8 244 us
-        if (g >= 8) g &= ~3u;   // measured: 16 beats 17 (even split of 1024 instances, aligned strides)
-        // write-through stores go to arrays that are not in the fast store mode; there 8 instances per workgroup (four workgroups
-        // per CU, half the open output streams each) beat 16 by 3-8 % -- 218-224 vs 225-241 us on four such pairs, while on a fast
-        // pair 16 wins (204 vs 211): profiles/r03/shape_sweep_write_through*.txt
-        if (dp.write_through) g = std::min(g, 8u);
-        g = std::max(g / gmin * gmin, gmin);
-        const uint32_t ni_up = (std::max(nwork, 1u) + gmin - 1) / gmin * gmin;
-        g = std::min(g, ni_up);
-        // keep the grid large enough to fill 256 CUs several times over
-        while (g > gmin && uint64_t(p.ntiles) * ((nwork + g - 1) / g) < 2048) {
-            const uint32_t half = std::max((g / 2) / gmin * gmin, gmin);
-            if (half == g) break;
-            g = half;
-        }
-        group = std::max(g, gmin);
-        const int forced = ov.group;
-        if (forced > 0) group = std::max(uint32_t(forced) / gmin * gmin, gmin);
-    }
-    dp.group = group;
-    // Per-instance morph weights, second shape (kernels.hip pack_kernel), OPT-IN (MMDX_FUSED_PACK=1): packs of 4 instances, 80 registers,
-    // three 8-wave workgroups per CU while a workgroup's LDS stays under a third of the CU's.  It runs at 5.7 waves per SIMD where
-    // deform_kernel<512, ., kMorphFused4> runs at 3.8 -- and loses (config 3' 372-382 us against 335-348; profiles/r04/fused_pack_*):
-    // the walk and the skinning of one CU do not overlap in either kernel (walk alone 132 us + skinning alone 254 us), and packs of 4
-    // walk the table twice as often as packs of 8.  Kept for the A/B, not the default.  Two-array layouts in original vertex order.
-    // The group: as many instances (multiple of 4, up to 16) as keep three workgroups on a CU, else as fit two.
-    // (bounds calls keep deform_kernel's bounds flavour: the pack kernel, an archived A/B, has none)
-    bool pack = !bounds && !sel && morph == kMorphFused4 && ov.fused_pack != 0 && kTileVerts == 512 && !dp.tile_order && layout != MMDX_OUT_VERTEX32 &&
-                !ov.threads;
-    size_t lds = 0;
-    if (pack) {
-        uint32_t so, wo, mo;
-        const size_t third = (160 * 1024) / 3 - 64, half = 80 * 1024 - 64;
-        uint32_t g = 0;
-        for (uint32_t c = 16; c >= 4 && !g; c -= 4)
-            if (pack_lds_bytes(c, p.max_tile_bones, p.ns, &so, &wo, &mo) <= third) g = c;
-        for (uint32_t c = 16; c >= 4 && !g; c -= 4)
-            if (pack_lds_bytes(c, p.max_tile_bones, p.ns, &so, &wo, &mo) <= half) g = c;
-        if (!g && pack_lds_bytes(4, p.max_tile_bones, p.ns, &so, &wo, &mo) <= 160 * 1024) g = 4;
-        if (ov.group > 0) g = std::max(uint32_t(ov.group) / 4 * 4, 4u);
-        if (g) {
-            g = std::min(g, (ni + 3) / 4 * 4);
-            while (g > 4 && uint64_t(p.ntiles) * ((ni + g - 1) / g) < 1536) g -= 4;     // keep 256 CUs x 3 workgroups busy twice over
-            dp.group = g;
-            lds = pack_lds_bytes(g, p.max_tile_bones, p.ns, &dp.stage_off, &dp.w_off, &dp.mp_off);
-            if (lds > 160 * 1024) pack = false;
-        } else {
-            pack = false;
-        }
-    }
-    if (!pack) {
-        dp.group = group;
-        lds = deform_lds_bytes(threads, layout, morph, group, p.max_tile_bones, p.ns, &dp.stage_off, &dp.w_off, dp.tile_order != 0);
-        if (bounds && !dp.tile_order) {
-            dp.bounds_off = uint32_t(lds);
-            lds += kBoundsLdsBytes;
-        }
-    }
-    // bounds: the kernel's partials, then the reduce into the caller's device array -- or into the tail of the same scratch, copied
-    // out to the host array next to the outputs
-    const uint32_t bounds_units = bounds ? deform_bounds_units(threads, p.ntiles, dp.tile_order != 0) : 0u;
-    float *bounds_dev = nullptr;
-    if (bounds) {
-        const size_t part = size_t(nwork) * bounds_units * 24;         // (select: partials by list position)
-        HIP_TRY(m->bnd.ensure(part + (out_dev ? 0 : size_t(ni) * 24)));
+// The planned launch: the shape's fields into `dp`, the bounds scratch, the deform kernel of the shape's kind, the bounds reduce.
+// bounds: the kernel's partials, then the reduce into the caller's device array -- or into the tail of the same scratch
+// (`bounds_dev`), copied out to the host array next to the outputs
+static mmdx_status launch_planned(mmdx_model_t m, const DeformCall &c, const LaunchShape &s, float *out_bounds, hipEvent_t *pev,
+                                  DeformParams &dp, float *&bounds_dev) {
+    const Plan &p = m->plan;
+    const KernelSet &ks = kernel_set((p.flags & MMDX_CREATE_FAST_MATH) != 0);      // contracted multiply-adds: this model opted out of bit-exactness
+    const uint32_t ni = c.ni;
+    const int layout = int(c.layout), morph = c.morph;
+    hipStream_t st = m->stream;
+    dp.write_through = s.write_through ? 1u : 0u;
+    dp.group = s.group;
+    dp.stage_off = s.stage_off; dp.w_off = s.w_off; dp.mp_off = s.mp_off; dp.bounds_off = s.bounds_off;
+    dp.stagger = s.stagger; dp.slots_per_cu = s.slots_per_cu;
+    if (c.bounds) {
+        const size_t part = size_t(c.nwork) * s.bounds_units * 24;         // (select: partials by list position)
+        HIP_TRY(m->bnd.ensure(part + (c.out_dev ? 0 : size_t(ni) * 24)));
         dp.bounds = static_cast<float *>(m->bnd.ptr);
-        bounds_dev = out_dev ? out_bounds : reinterpret_cast<float *>(static_cast<unsigned char *>(m->bnd.ptr) + part);
-    }
-    if (lds > 160 * 1024)
-        return fail(MMDX_ERR_UNSUPPORTED, "tile needs " + std::to_string(lds) + " bytes of LDS (> 160 KiB): "
-                                          "too many distinct bones in one vertex tile / too many morph slots");
-
-    if (morph == kMorphFused4) {
-        dp.stagger = uint32_t(std::max(ov.stagger, 0));
-        dp.slots_per_cu = std::max<uint32_t>(1u, std::min<uint32_t>(uint32_t(160 * 1024 / std::max<size_t>(lds, 1)), pack ? 3u : 2u));
+        bounds_dev = c.out_dev ? out_bounds : reinterpret_cast<float *>(static_cast<unsigned char *>(m->bnd.ptr) + part);
     }
     if (pev) HIP_TRY(hipEventRecord(pev[0], st));
-    // One frame of one model into device memory: the latency-ordered kernel (parts of tiles on every CU, direct stores).
-    // Outputs in mapped host memory keep the tile kernel: its 16-byte coalesced stores are what crosses PCIe well.
-    // Models with fewer tiles than the chip has CUs only (config 2: 6.3 us against the tile kernel's 6.9); a large model fills the
-    // chip with whole tiles and is better off with their coalesced stores (config 5: 14.9 us against 15.2).
-    // (bounds calls take the tile kernel's bounds flavour: the frame kernel has none)
-    const bool frame = !bounds && !sel && one_frame && !out_direct && !out_bounce && (ov.frame_kernel == 2 || (ov.frame_kernel == 1 && p.ntiles < 256));
-    if (frame) {
-        DeformParams fp = dp;
-        fp.morphed = nullptr;                                  // nothing reads a single frame's morphed positions later
-        const size_t flds = frame_lds_bytes(morph, p.max_tile_bones, p.ns, &fp.w_off);
-        if (flds > 160 * 1024)
-            return fail(MMDX_ERR_UNSUPPORTED, "tile needs " + std::to_string(flds) + " bytes of LDS (> 160 KiB)");
-        HIP_TRY((fast ? launch_frame_fast : launch_frame)(ov.frame_threads, int(layout), morph, p.f16, fp, p.ntiles, flds, st));
-    } else if (pack) {
-        HIP_TRY((fast ? launch_pack_fast : launch_pack)(int(layout), p.f16, dp, p.ntiles, lds, st));
-    } else if (sel && sel->n_ids == 0) {
-        // an empty list: no instance to write (the shared morph pass above has run as in the plain call)
-    } else {
-        HIP_TRY((fast ? launch_deform_fast : launch_deform)(threads, int(layout), morph, p.f16, dp, p.ntiles, lds, st));
-        if (bounds && sel)
-            HIP_TRY(launch_bounds_reduce_select(dp.bounds, bounds_units, ni, bounds_dev, dp.sel_ids, dp.sel_count, dp.sel_n, st));
-        else if (bounds) HIP_TRY(launch_bounds_reduce(dp.bounds, bounds_units, ni, bounds_dev, st));
+    switch (s.kernel) {
+    case LaunchShape::kFrame:
+        dp.morphed = nullptr;                                  // nothing reads a single frame's morphed positions later
+        HIP_TRY(ks.launch_frame(launch_overrides().frame_threads, layout, morph, p.f16, dp, p.ntiles, s.lds, st));
+        break;
+    case LaunchShape::kPack:
+        HIP_TRY(ks.launch_pack(layout, p.f16, dp, p.ntiles, s.lds, st));
+        break;
+    case LaunchShape::kNone:
+        // an empty list: no instance to write (the shared morph pass has run as in the plain call)
+        break;
+    case LaunchShape::kDeform:
+        HIP_TRY(ks.launch_deform({s.threads, layout, morph, p.f16, dp.tile_order != 0, s.write_through, c.bounds, c.select},
+                                 dp, p.ntiles, s.lds, st));
+        if (c.bounds && c.select)
+            HIP_TRY(launch_bounds_reduce_select(dp.bounds, s.bounds_units, ni, bounds_dev, dp.sel_ids, dp.sel_count, dp.sel_n, st));
+        else if (c.bounds) HIP_TRY(launch_bounds_reduce(dp.bounds, s.bounds_units, ni, bounds_dev, st));
+        break;
     }
     if (pev) {
         HIP_TRY(hipEventRecord(pev[1], st));
@@ -913,40 +872,75 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
         m->prof_has_morph[m->prof_calls] = morph != kMorphNone;
         ++m->prof_calls;
     }
+    return MMDX_OK;
+}
 
-    if (!out_dev) {
-        // one instance's bytes in the dense staging / bounce buffer and in the caller's pitched arrays
-        const size_t row_a = out_bytes_a(layout, p.nv), row_b = out_bytes_b(layout, p.nv);
-        const size_t pitch_a = out_bytes_a(layout, pitch), pitch_b = out_bytes_b(layout, pitch);
-        const bool spread = pitch != p.nv && ni > 1;
-        if (!out_direct && !out_bounce) {
-            if (spread) {
-                HIP_TRY(hipMemcpy2DAsync(a->out_a, pitch_a, dp.out_a, row_a, row_a, ni, hipMemcpyDeviceToHost, st));
-                if (bytes_b) HIP_TRY(hipMemcpy2DAsync(a->out_b, pitch_b, dp.out_b, row_b, row_b, ni, hipMemcpyDeviceToHost, st));
-            } else {
-                HIP_TRY(hipMemcpyAsync(a->out_a, dp.out_a, bytes_a, hipMemcpyDeviceToHost, st));
-                if (bytes_b) HIP_TRY(hipMemcpyAsync(a->out_b, dp.out_b, bytes_b, hipMemcpyDeviceToHost, st));
-            }
+// Results that the kernel did not write into the caller's arrays go there now; then the wait that a call with host operands ends in.
+static mmdx_status copy_out(mmdx_model_t m, const mmdx_deform_args *a, const OutputRoute &r, uint32_t pitch, const DeformParams &dp,
+                            float *out_bounds, const float *bounds_dev, bool host_inputs) {
+    const Plan &p = m->plan;
+    const uint32_t ni = a->n_instances, layout = a->out_layout;
+    hipStream_t st = m->stream;
+    if (r.out_dev) {
+        if (host_inputs) HIP_TRY(wait_stream(st));      // borrowed host inputs must be consumed before we return
+        return MMDX_OK;
+    }
+    // one instance's bytes in the dense staging / bounce buffer and in the caller's pitched arrays
+    const size_t row_a = out_bytes_a(layout, p.nv), row_b = out_bytes_b(layout, p.nv);
+    const size_t pitch_a = out_bytes_a(layout, pitch), pitch_b = out_bytes_b(layout, pitch);
+    const bool spread = pitch != p.nv && ni > 1;
+    if (!r.direct && !r.bounce) {
+        if (spread) {
+            HIP_TRY(hipMemcpy2DAsync(a->out_a, pitch_a, dp.out_a, row_a, row_a, ni, hipMemcpyDeviceToHost, st));
+            if (r.bytes_b) HIP_TRY(hipMemcpy2DAsync(a->out_b, pitch_b, dp.out_b, row_b, row_b, ni, hipMemcpyDeviceToHost, st));
+        } else {
+            HIP_TRY(hipMemcpyAsync(a->out_a, dp.out_a, r.bytes_a, hipMemcpyDeviceToHost, st));
+            if (r.bytes_b) HIP_TRY(hipMemcpyAsync(a->out_b, dp.out_b, r.bytes_b, hipMemcpyDeviceToHost, st));
         }
-        if (bounds) HIP_TRY(hipMemcpyAsync(out_bounds, bounds_dev, size_t(ni) * 24, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-        if (out_bounce && spread) {
-            const unsigned char *sa = static_cast<const unsigned char *>(m->bounce), *sb = sa + off_b;
-            for (uint32_t i = 0; i < ni; ++i) {
-                std::memcpy(static_cast<unsigned char *>(a->out_a) + i * pitch_a, sa + i * row_a, row_a);
-                if (bytes_b) std::memcpy(static_cast<unsigned char *>(a->out_b) + i * pitch_b, sb + i * row_b, row_b);
-            }
-        } else if (out_bounce) {
-            std::memcpy(a->out_a, m->bounce, bytes_a);
-            if (bytes_b) std::memcpy(a->out_b, static_cast<unsigned char *>(m->bounce) + off_b, bytes_b);
+    }
+    if (out_bounds) HIP_TRY(hipMemcpyAsync(out_bounds, bounds_dev, size_t(ni) * 24, hipMemcpyDeviceToHost, st));
+    HIP_TRY(wait_stream(st));
+    if (r.bounce && spread) {
+        const unsigned char *sa = static_cast<const unsigned char *>(m->bounce), *sb = sa + r.off_b;
+        for (uint32_t i = 0; i < ni; ++i) {
+            std::memcpy(static_cast<unsigned char *>(a->out_a) + i * pitch_a, sa + i * row_a, row_a);
+            if (r.bytes_b) std::memcpy(static_cast<unsigned char *>(a->out_b) + i * pitch_b, sb + i * row_b, row_b);
         }
-    } else if (!(a->flags & MMDX_PALETTE_ON_DEVICE) ||
-               (morph != kMorphNone && !(a->flags & MMDX_WEIGHTS_ON_DEVICE)) ||
-               (sel && !(sel->flags & MMDX_SELECT_ON_DEVICE) && sel->n_ids)) {
-        // borrowed host inputs must be consumed before we return
-        HIP_TRY(wait_stream(st));
+    } else if (r.bounce) {
+        std::memcpy(a->out_a, m->bounce, r.bytes_a);
+        if (r.bytes_b) std::memcpy(a->out_b, static_cast<unsigned char *>(m->bounce) + r.off_b, r.bytes_b);
     }
     return MMDX_OK;
+}
+
+static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, float *out_bounds,
+                                  const mmdx_instance_select *sel = nullptr) {
+    CallPointers cp;
+    if (mmdx_status s = validate_call(m, a, out_bounds, sel, cp)) return s;
+    HIP_TRY(hipSetDevice(m->device));
+    hipEvent_t *pev;
+    if (mmdx_status s = profile_events(m, pev)) return s;
+    DeformParams dp = static_params(*m);
+    dp.ni = a->n_instances;
+    dp.pos_scale = a->pos_scale;
+    if (sel)
+        if (mmdx_status s = stage_select(m, sel, cp.sel_live_host, dp)) return s;
+    if (mmdx_status s = stage_palettes(m, a, cp.kind_pal, dp)) return s;
+    int morph;
+    if (mmdx_status s = run_morph_pass(m, a, sel, cp.kind_w, pev, dp, morph)) return s;
+    OutputRoute route;
+    if (mmdx_status s = route_outputs(m, a, cp, dp, route)) return s;
+    const DeformCall call{a->out_layout, a->n_instances, sel ? sel->n_ids : a->n_instances, a->flags, morph, out_bounds != nullptr,
+                          sel != nullptr, route.out_dev, route.direct || route.bounce, route.bytes_a + route.bytes_b};
+    LaunchShape shape;
+    std::string err;
+    if (mmdx_status s = plan_deform_launch(m->plan, call, launch_overrides(), shape, err)) return fail(s, err);
+    m->last_write_through = shape.write_through;
+    float *bounds_dev = nullptr;
+    if (mmdx_status s = launch_planned(m, call, shape, out_bounds, pev, dp, bounds_dev)) return s;
+    const bool host_inputs = !(a->flags & MMDX_PALETTE_ON_DEVICE) || (morph != kMorphNone && !(a->flags & MMDX_WEIGHTS_ON_DEVICE)) ||
+                             (sel && !(sel->flags & MMDX_SELECT_ON_DEVICE) && sel->n_ids);
+    return copy_out(m, a, route, cp.pitch, dp, out_bounds, bounds_dev, host_inputs);
 }
 
 mmdx_status mmdx_deform_batched(mmdx_model_t m, const mmdx_deform_args *a) { return deform_batched(m, a, nullptr); }

@@ -15,6 +15,7 @@
 #include "error.hpp"
 #include "graph_pin.hpp"
 #include "kernels.hpp"
+#include "launch_shape.hpp"
 #include "plan.hpp"
 #include "rig_kernels.hpp"
 
@@ -49,23 +50,7 @@ struct DevBuf {
     }
 };
 
-// Launch-shape overrides for A/B runs (tools/): read ONCE, at the first deform call of the process -- the
-// per-frame call has a budget of a few microseconds and getenv walks the whole environment.
-struct LaunchOverrides {
-    int interleave, threads, lds_target, group, placement_log, placement_park;
-    int frame_kernel;   // MMDX_FRAME_KERNEL: 0 = a single frame always runs the tile kernel, 1 = models of fewer than 256 tiles run the
-                        // frame kernel (default), 2 = always (A/B); MMDX_FRAME_THREADS: 128 / 256 lanes per workgroup
-    int frame_threads;
-    int shared_fused;   // MMDX_SHARED_FUSED: crowds with a shared facial state gather the morphs inside the deform kernel: 0 never,
-                        // 1 up to 8 instances (default), 2 always (A/B, tests)
-    int store_wt;       // MMDX_STORE_WT: 0 / 1 force cached / write-through stores where the caller gave no hint (A/B); -1 default
-    int morph_autoskip; // MMDX_MORPH_AUTOSKIP: 0 turns the automatic "shared rates unchanged" detection off (A/B); 1 default
-    int fused_pack;     // MMDX_FUSED_PACK: 0 = per-instance morph weights run deform_kernel<512, ., kMorphFused4> (default),
-                        // 1 = pack_kernel (round 4's higher-occupancy shape: measured slower, kept for the A/B)
-    int stagger;        // MMDX_STAGGER: start offset between the workgroups of a CU, in units of 64 cycles per residency slot (A/B)
-    int select_interleave;   // MMDX_SELECT_INTERLEAVE: 1 = select launches deal list positions interleaved over the workgroups like the
-                             // plain crowd call (default, measured faster); 0 = blocked (A/B)
-};
+// The launch-shape overrides (launch_shape.hpp), as the environment sets them
 LaunchOverrides read_launch_overrides();
 LaunchOverrides &launch_overrides();
 int env_int(const char *name, int dflt);

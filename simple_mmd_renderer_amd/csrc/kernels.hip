@@ -57,18 +57,6 @@ constexpr float kLerpLo = 1e-7f;                  // float(mmd_math_const_eps)
 constexpr float kLerpHi = 0.99999988f;            // float(1.0 - mmd_math_const_eps)
 constexpr float kMorphEps = 1e-7f;                // rate < 1e-7 (double) <=> rate < 1e-7f
 
-// LDS staging images of one tile's output range (bytes; all multiples of 16)
-constexpr uint32_t kSoaImgBytes = (kTileVerts * 3 + 4) * 4;        // f32 xyz + alignment slack
-constexpr uint32_t kV32ImgBytes = kTileVerts * 32;
-constexpr uint32_t kP16ImgBytes = (kTileVerts * 3 + 8) * 2;        // f16 xyz + alignment slack
-static_assert(kSoaImgBytes % 16 == 0 && kP16ImgBytes % 16 == 0, "image alignment");
-
-__host__ __device__ constexpr uint32_t stage_bytes(int layout) {
-    return layout == MMDX_OUT_SOA ? 2 * kSoaImgBytes
-                                  : (layout == MMDX_OUT_VERTEX32 ? kV32ImgBytes
-                                                                 : kP16ImgBytes + kSoaImgBytes);
-}
-
 __device__ __forceinline__ float h2f(uint32_t bits16) {
     return float(__builtin_bit_cast(_Float16, (unsigned short)bits16));
 }
@@ -1210,9 +1198,6 @@ __global__ __launch_bounds__(THREADS) void deform_kernel(const DeformParams p) {
 //     done with them), the normal image is double buffered -- 48.6 KB of LDS for 8 instances of the 50k model.
 // Same operations in the same order as the reference (and as deform_kernel): bit-identical results.
 constexpr int kPkThreads = 512;
-constexpr uint32_t kPkPack = 4;
-constexpr uint32_t kPkRegion = kSoaImgBytes;          // one `mp` region: 512 x 3 f32 coordinates, or a position image (f32: 6160 B, f16: 3088 B)
-static_assert(kPkRegion >= kTileVerts * 12 && kPkRegion >= kP16ImgBytes && kPkRegion % 16 == 0, "mp region");
 
 // The vertex's static data as the pack kernel keeps it across its loops: 14 registers (load_slot's Slot: 21).
 struct PackSlot {
@@ -1800,66 +1785,65 @@ __global__ __launch_bounds__(64) void bounds_reduce_select_kernel(const float *p
 
 using KernelFn = void (*)(const DeformParams);
 
-template <int THREADS, int LAYOUT, bool F16, bool TILE, bool BOUNDS, bool SELECT = false>
+template <int THREADS, int LAYOUT, bool F16, bool TILE, bool BOUNDS, bool SELECT>
 KernelFn pick_morph(int morph) {
-    if constexpr (SELECT) {
-        switch (morph) {
-        case kMorphNone: return deform_kernel<THREADS, LAYOUT, kMorphNone | kMorphSelect, F16, TILE, false, BOUNDS>;
-        case kMorphShared: return deform_kernel<THREADS, LAYOUT, kMorphShared | kMorphSelect, F16, TILE, false, BOUNDS>;
-        case kMorphFused1: return deform_kernel<THREADS, LAYOUT, kMorphFused1 | kMorphSelect, F16, TILE, false, BOUNDS>;
-        default: return deform_kernel<THREADS, LAYOUT, kMorphFused4 | kMorphSelect, F16, TILE, false, BOUNDS>;
-        }
-    } else if constexpr (BOUNDS) {
-        switch (morph) {
-        case kMorphNone: return deform_kernel<THREADS, LAYOUT, kMorphNone, F16, TILE, false, true>;
-        case kMorphShared: return deform_kernel<THREADS, LAYOUT, kMorphShared, F16, TILE, false, true>;
-        case kMorphFused1: return deform_kernel<THREADS, LAYOUT, kMorphFused1, F16, TILE, false, true>;
-        default: return deform_kernel<THREADS, LAYOUT, kMorphFused4, F16, TILE, false, true>;
-        }
-    } else {
-        switch (morph) {
-        case kMorphNone: return deform_kernel<THREADS, LAYOUT, kMorphNone, F16, TILE>;
-        case kMorphShared: return deform_kernel<THREADS, LAYOUT, kMorphShared, F16, TILE>;
-        case kMorphFused1: return deform_kernel<THREADS, LAYOUT, kMorphFused1, F16, TILE>;
-        default: return deform_kernel<THREADS, LAYOUT, kMorphFused4, F16, TILE>;
-        }
+    constexpr int kSel = SELECT ? int(kMorphSelect) : 0;
+    switch (morph) {
+    case kMorphNone: return deform_kernel<THREADS, LAYOUT, kMorphNone | kSel, F16, TILE, false, BOUNDS>;
+    case kMorphShared: return deform_kernel<THREADS, LAYOUT, kMorphShared | kSel, F16, TILE, false, BOUNDS>;
+    case kMorphFused1: return deform_kernel<THREADS, LAYOUT, kMorphFused1 | kSel, F16, TILE, false, BOUNDS>;
+    default: return deform_kernel<THREADS, LAYOUT, kMorphFused4 | kSel, F16, TILE, false, BOUNDS>;
     }
 }
 
-template <int THREADS, bool TILE, bool BOUNDS, bool SELECT = false>
-KernelFn pick_t(int layout, int morph, bool f16) {
-    if (f16) return layout == MMDX_OUT_SOA_POS16 ? pick_morph<THREADS, MMDX_OUT_SOA_POS16, true, TILE, BOUNDS, SELECT>(morph) : nullptr;
-    if (layout == MMDX_OUT_SOA) return pick_morph<THREADS, MMDX_OUT_SOA, false, TILE, BOUNDS, SELECT>(morph);
-    if (layout == MMDX_OUT_VERTEX32) return pick_morph<THREADS, MMDX_OUT_VERTEX32, false, TILE, BOUNDS, SELECT>(morph);
+template <int THREADS, bool TILE, bool BOUNDS, bool SELECT>
+KernelFn pick_t(const DeformVariant &v) {
+    if (v.f16) return v.layout == MMDX_OUT_SOA_POS16 ? pick_morph<THREADS, MMDX_OUT_SOA_POS16, true, TILE, BOUNDS, SELECT>(v.morph) : nullptr;
+    if (v.layout == MMDX_OUT_SOA) return pick_morph<THREADS, MMDX_OUT_SOA, false, TILE, BOUNDS, SELECT>(v.morph);
+    if (v.layout == MMDX_OUT_VERTEX32) return pick_morph<THREADS, MMDX_OUT_VERTEX32, false, TILE, BOUNDS, SELECT>(v.morph);
     return nullptr;
 }
 
-template <bool BOUNDS, bool SELECT = false>
-KernelFn pick_b(int threads, int layout, int morph, bool f16, bool tile) {
+template <bool BOUNDS, bool SELECT>
+KernelFn pick_b(const DeformVariant &v) {
 #if MMDX_TILE >= 512
-    if (threads != 256)
-        return tile ? pick_t<512, true, BOUNDS, SELECT>(layout, morph, f16) : pick_t<512, false, BOUNDS, SELECT>(layout, morph, f16);
+    if (v.threads != 256) return v.tile ? pick_t<512, true, BOUNDS, SELECT>(v) : pick_t<512, false, BOUNDS, SELECT>(v);
 #endif
-    return tile ? pick_t<256, true, BOUNDS, SELECT>(layout, morph, f16) : pick_t<256, false, BOUNDS, SELECT>(layout, morph, f16);
+    return v.tile ? pick_t<256, true, BOUNDS, SELECT>(v) : pick_t<256, false, BOUNDS, SELECT>(v);
 }
 
-// tile = outputs in the engine's vertex order (MMDX_CREATE_TILE_ORDER): the direct-store variants.
-// wt = write-through stores (CopyFast): instantiated where it was measured to pay -- the SoA f32 crowd kernels (256 threads, no
-// morphs or shared morphs, original vertex order); every other shape keeps its nt stores whatever the hint says.
-// bounds = the BOUNDS flavour (mmdx_deform_batched_bounds): every shape, nt stores only.
-// select = the SELECT flavour (mmdx_deform_batched_select): every shape, with and without bounds, nt stores only.
-KernelFn pick(int threads, int layout, int morph, bool f16, bool tile, bool wt = false, bool bounds = false, bool select = false) {
-    if (select) return bounds ? pick_b<true, true>(threads, layout, morph, f16, tile) : pick_b<false, true>(threads, layout, morph, f16, tile);
-    if (bounds) return pick_b<true>(threads, layout, morph, f16, tile);
-    if (wt && deform_has_write_through(threads, layout, morph, f16, tile))
-        return morph == kMorphNone ? deform_kernel<256, MMDX_OUT_SOA, kMorphNone, false, false, true>
-                                   : deform_kernel<256, MMDX_OUT_SOA, kMorphShared, false, false, true>;
-    return pick_b<false>(threads, layout, morph, f16, tile);
+// The instantiation of deform_kernel for a variant (DeformVariant, kernels.hpp); nullptr: no such layout.  The write-through
+// flavour is instantiated where it was measured to pay -- the SoA f32 crowd kernels (deform_has_write_through()); the bounds and
+// select flavours have nt stores only.
+KernelFn pick(const DeformVariant &v) {
+    if (v.select) return v.bounds ? pick_b<true, true>(v) : pick_b<false, true>(v);
+    if (v.bounds) return pick_b<true, false>(v);
+    if (v.wt && deform_has_write_through(v.threads, v.layout, v.morph, v.f16, v.tile))
+        return v.morph == kMorphNone ? deform_kernel<256, MMDX_OUT_SOA, kMorphNone, false, false, true>
+                                     : deform_kernel<256, MMDX_OUT_SOA, kMorphShared, false, false, true>;
+    return pick_b<false, false>(v);
 }
 
-}  // namespace
+// fn(variant) for exactly the variants pick() has a kernel for, the two write-through ones included; stops at the first error
+template <typename Fn>
+hipError_t for_each_deform_variant(Fn fn) {
+    const int layouts[][2] = {{MMDX_OUT_SOA, 0}, {MMDX_OUT_VERTEX32, 0}, {MMDX_OUT_SOA_POS16, 1}};      // {layout, f16}
+    for (int threads : {256, 512})
+        for (const auto &l : layouts)
+            for (int morph = kMorphNone; morph <= kMorphFused4; ++morph) {
+                const bool f16 = l[1] != 0;
+                for (int tile = 0; tile < 2; ++tile)
+                    for (int bounds = 0; bounds < 2; ++bounds)
+                        for (int select = 0; select < 2; ++select)
+                            if (hipError_t e = fn(DeformVariant{threads, l[0], morph, f16, tile != 0, false, bounds != 0, select != 0});
+                                e != hipSuccess)
+                                return e;
+                if (deform_has_write_through(threads, l[0], morph, f16, false))
+                    if (hipError_t e = fn(DeformVariant{threads, l[0], morph, f16, false, true, false, false}); e != hipSuccess) return e;
+            }
+    return hipSuccess;
+}
 
-namespace {
 template <int THREADS, int LAYOUT, bool F16>
 KernelFn pick_frame_morph(int morph) {
     return morph == kMorphNone ? frame_kernel<THREADS, LAYOUT, kMorphNone, F16> : frame_kernel<THREADS, LAYOUT, kMorphFused1, F16>;
@@ -1876,37 +1860,7 @@ KernelFn pick_frame(int threads, int layout, int morph, bool f16) {
         return threads == 128 ? pick_frame_morph<128, MMDX_OUT_VERTEX32, false>(morph) : pick_frame_morph<256, MMDX_OUT_VERTEX32, false>(morph);
     return nullptr;
 }
-}  // namespace
 
-#ifndef MMDX_FAST_MATH
-size_t deform_lds_bytes(int threads, int layout, int morph, uint32_t group, uint32_t max_tile_bones, uint32_t ns,
-                        uint32_t *stage_off, uint32_t *w_off, bool tile_order) {
-    size_t off = size_t(group) * max_tile_bones * 48;
-    *stage_off = uint32_t(off);
-    if (!tile_order) off += 2 * size_t(stage_bytes(layout));     // tile-order outputs need no LDS image
-    *w_off = uint32_t(off);
-    if (morph == kMorphFused1) off += (size_t(ns + 1) * 4 + 15) / 16 * 16;
-    else if (morph == kMorphFused4) off += (threads == 512 ? 2 : 1) * size_t(ns + 1) * 16;   // one or two instance quads
-    return off;
-}
-
-#endif  // !MMDX_FAST_MATH
-
-#ifndef MMDX_FAST_MATH
-// pack_kernel: [palettes of the group][slot weights of one pack][kPkPack coordinate / position-image regions][2 normal images]
-size_t pack_lds_bytes(uint32_t group, uint32_t max_tile_bones, uint32_t ns, uint32_t *stage_off, uint32_t *w_off, uint32_t *mp_off) {
-    size_t off = size_t(group) * max_tile_bones * 48;
-    *w_off = uint32_t(off);
-    off += size_t(ns + 1) * 16;
-    *mp_off = uint32_t(off);
-    off += size_t(kPkPack) * kPkRegion;
-    *stage_off = uint32_t(off);
-    off += 2 * size_t(kSoaImgBytes);
-    return off;
-}
-#endif  // !MMDX_FAST_MATH
-
-namespace {
 KernelFn pick_pack(int layout, bool f16, bool finite) {
     if (f16) {
         if (layout != MMDX_OUT_SOA_POS16) return nullptr;
@@ -1915,9 +1869,8 @@ KernelFn pick_pack(int layout, bool f16, bool finite) {
     if (layout != MMDX_OUT_SOA) return nullptr;
     return finite ? pack_kernel<MMDX_OUT_SOA, false, true> : pack_kernel<MMDX_OUT_SOA, false, false>;
 }
-}  // namespace
 
-hipError_t MMDX_K(launch_pack)(int layout, bool f16, const DeformParams &p, uint32_t ntiles, size_t lds_bytes, hipStream_t stream) {
+hipError_t launch_pack(int layout, bool f16, const DeformParams &p, uint32_t ntiles, size_t lds_bytes, hipStream_t stream) {
     KernelFn fn = pick_pack(layout, f16, p.finite_offsets != 0);
     if (!fn || kTileVerts != 512) return hipErrorInvalidValue;
     DeformParams q = p;
@@ -1963,68 +1916,40 @@ hipError_t MMDX_K(launch_pack)(int layout, bool f16, const DeformParams &p, uint
     return hipGetLastError();
 }
 
-hipError_t MMDX_K(prepare_kernels)() {
+hipError_t raise_lds_limit(KernelFn fn) {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
+hipError_t prepare_kernels() {
     for (int f16 = 0; f16 < 2; ++f16)
-        for (int fin = 0; fin < 2; ++fin) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(pick_pack(f16 ? MMDX_OUT_SOA_POS16 : MMDX_OUT_SOA, f16 != 0, fin != 0)),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-    for (int threads = 256; threads <= 512; threads += 256)
-      for (int f16 = 0; f16 < 2; ++f16)
-        for (int layout = 0; layout < 3; ++layout)
-            for (int morph = 0; morph < 32; ++morph) {
-                KernelFn fn = pick(threads, layout, morph & 3, f16 != 0, (morph & 4) != 0, false, (morph & 8) != 0, morph >= 16);
-                if (!fn) continue;
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   160 * 1024);
-                if (e != hipSuccess) return e;
-            }
-    for (int morph : {int(kMorphNone), int(kMorphShared)}) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(pick(256, MMDX_OUT_SOA, morph, false, false, true)),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-    }
+        for (int fin = 0; fin < 2; ++fin)
+            if (hipError_t e = raise_lds_limit(pick_pack(f16 ? MMDX_OUT_SOA_POS16 : MMDX_OUT_SOA, f16 != 0, fin != 0)); e != hipSuccess) return e;
+    if (hipError_t e = for_each_deform_variant([](const DeformVariant &v) { return raise_lds_limit(pick(v)); }); e != hipSuccess) return e;
     for (int threads = 128; threads <= 256; threads += 128)
       for (int f16 = 0; f16 < 2; ++f16)
         for (int layout = 0; layout < 3; ++layout)
             for (int morph = 0; morph <= kMorphFused1; morph += kMorphFused1) {
                 KernelFn fn = pick_frame(threads, layout, morph, f16 != 0);
                 if (!fn) continue;
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) return e;
+                if (hipError_t e = raise_lds_limit(fn); e != hipSuccess) return e;
             }
     return hipSuccess;
 }
 
-hipError_t MMDX_K(launch_deform)(int threads, int layout, int morph, bool f16, const DeformParams &p,
-                         uint32_t ntiles, size_t lds_bytes, hipStream_t stream) {
-    const bool select = p.sel_ids != nullptr;
-    if (select && p.sel_n == 0) return hipSuccess;       // an empty list: nothing to launch
-    KernelFn fn = pick(threads, layout, morph, f16, p.tile_order != 0, p.write_through != 0, p.bounds != nullptr, select);
+hipError_t launch_deform(const DeformVariant &v, const DeformParams &p, uint32_t ntiles, size_t lds_bytes, hipStream_t stream) {
+    if (v.select && p.sel_n == 0) return hipSuccess;       // an empty list: nothing to launch
+    KernelFn fn = pick(v);
     if (!fn) return hipErrorInvalidValue;
     DeformParams q = p;
     q.ntiles = ntiles;
-    q.ngroups = ((select ? p.sel_n : p.ni) + p.group - 1) / p.group;     // select: the grid covers the list's capacity
+    q.ngroups = ((v.select ? p.sel_n : p.ni) + p.group - 1) / p.group;     // select: the grid covers the list's capacity
     q.rem_per_xcd = ((ntiles & 7u) * q.ngroups + 7u) / 8u;
     const dim3 grid(8u * ((ntiles >> 3) * q.ngroups + q.rem_per_xcd));
-    hipLaunchKernelGGL(fn, grid, dim3((threads == 256 || kTileVerts < 512) ? 256 : 512), lds_bytes, stream, q);
+    hipLaunchKernelGGL(fn, grid, dim3((v.threads == 256 || kTileVerts < 512) ? 256 : 512), lds_bytes, stream, q);
     return hipGetLastError();
 }
 
-#ifndef MMDX_FAST_MATH
-size_t frame_lds_bytes(int morph, uint32_t max_tile_bones, uint32_t ns, uint32_t *w_off) {
-    size_t off = (size_t(max_tile_bones) * 48 + 15) / 16 * 16;
-    *w_off = uint32_t(off);
-    if (morph == kMorphFused1) off += (size_t(ns + 1) * 4 + 15) / 16 * 16;
-    return off;
-}
-
-#endif  // !MMDX_FAST_MATH
-
-hipError_t MMDX_K(launch_frame)(int threads, int layout, int morph, bool f16, const DeformParams &p, uint32_t ntiles, size_t lds_bytes,
+hipError_t launch_frame(int threads, int layout, int morph, bool f16, const DeformParams &p, uint32_t ntiles, size_t lds_bytes,
                         hipStream_t stream) {
     threads = threads == 128 ? 128 : 256;
     KernelFn fn = pick_frame(threads, layout, morph, f16);
@@ -2033,8 +1958,7 @@ hipError_t MMDX_K(launch_frame)(int threads, int layout, int morph, bool f16, co
     return hipGetLastError();
 }
 
-hipError_t MMDX_K(launch_morph_apply)(bool f16, const DeformParams &p, const FlattenParams *fused,
-                              hipStream_t stream) {
+hipError_t launch_morph_apply(bool f16, const DeformParams &p, const FlattenParams *fused, hipStream_t stream) {
     const dim3 grid((p.nv + kThreads - 1) / kThreads);
     if (fused) {
         const size_t lds = size_t(fused->ns + 1) * 4;
@@ -2046,6 +1970,13 @@ hipError_t MMDX_K(launch_morph_apply)(bool f16, const DeformParams &p, const Fla
         else hipLaunchKernelGGL((morph_apply_kernel<false, false>), grid, dim3(kThreads), 0, stream, p, none);
     }
     return hipGetLastError();
+}
+
+}  // namespace
+
+const KernelSet &MMDX_K(kernels)() {
+    static const KernelSet set = {launch_deform, launch_frame, launch_pack, launch_morph_apply, prepare_kernels};
+    return set;
 }
 
 #ifndef MMDX_FAST_MATH

@@ -5,22 +5,11 @@
 
 #include <cstdint>
 
+#include "lds_layout.hpp"
 #include "plan.hpp"
 #include "vmd.hpp"
 
 namespace mmdx {
-
-// Morph handling of one deform launch
-enum : int {
-    kMorphNone = 0,     // model has no vertex-morph slot
-    kMorphShared = 1,   // positions come from the `morphed` buffer written by morph_apply (crowd
-                        // with one shared facial state: the morph pass runs once per call)
-    kMorphFused1 = 2,   // ONE set of morph rates for the launch, gathered inside the deform kernel: a single-model frame,
-                        // or a crowd with a shared facial state (every workgroup repeats its tile's walk)
-    kMorphFused4 = 3,   // per-instance weights, 4 instances share one pass over a CSR row
-    kMorphSelect = 16   // kernels.hip only: ORed into deform_kernel's morph-mode template argument for the flavour of
-                        // mmdx_deform_batched_select (modes 16..19 in kernel listings)
-};
 
 struct DeformParams {
     // static streams (HBM, uploaded once by mmdx_model_create)
@@ -68,7 +57,7 @@ struct DeformParams {
     uint32_t interleave;         // crowd modes: instance = g*ngroups + grp instead of grp*group + g
     uint32_t tile_order;         // MMDX_CREATE_TILE_ORDER: outputs in the engine's vertex order (tile-local class sort), stored straight
                                  // from registers -- no LDS image, no per-instance barrier
-    uint32_t write_through;      // launch the write-through flavour of the copy-out (api.cpp sets it only where deform_has_write_through())
+    uint32_t write_through;      // launch the write-through flavour of the copy-out (launch_shape.cpp sets it only where deform_has_write_through())
     uint32_t stagger;            // per-instance-morph kernels: first-round workgroups of residency slot k start k * stagger * 64 cycles late,
                                  // so that the workgroups sharing a CU are not all in their walk (or all in their stores) at once
     uint32_t slots_per_cu;       // ... with this many workgroups resident per CU
@@ -88,12 +77,6 @@ struct DeformParams {
     uint32_t sel_interleave;     // list position = g*ngroups + grp (default) instead of grp*group + g; never with kMorphFused4
 };
 
-// Partial bounds (6 floats) per instance of a bounds launch: one per tile, or one per wave of a tile for tile-order outputs (no
-// per-instance barrier there to combine the waves' partials).  `threads` as passed to launch_deform.
-inline uint32_t deform_bounds_units(int threads, uint32_t ntiles, bool tile_order) {
-    return tile_order ? ntiles * ((threads == 256 || kTileVerts < 512) ? 256u : 512u) / 64u : ntiles;
-}
-constexpr uint32_t kBoundsLdsBytes = 2 * 8 * 6 * 4;     // combine words: 2 instance parities x up to 8 waves x 6 floats
 // out[i][6] = bounds of instance i from the partials ([ni][units][6]), on `stream` behind the bounds launch
 hipError_t launch_bounds_reduce(const float *partials, uint32_t units, uint32_t ni, float *out, hipStream_t stream);
 // select launches: partials are [sel_n][units][6] by list position; block j writes out[ids[j]] when j is live and ids[j] < ni
@@ -119,31 +102,34 @@ struct FlattenParams {
     uint32_t sel_ni;
 };
 
-// Bytes of dynamic LDS the deform kernel needs for (layout, morph mode, group).
-size_t deform_lds_bytes(int threads, int layout, int morph, uint32_t group, uint32_t max_tile_bones, uint32_t ns,
-                        uint32_t *stage_off, uint32_t *w_off, bool tile_order = false);
+// One variant of deform_kernel: what pick() (kernels.hip) chooses an instantiation by.
+struct DeformVariant {
+    int threads, layout, morph;  // threads 256 / 512; morph: kMorphNone .. kMorphFused4
+    bool f16;
+    bool tile;                   // outputs in the engine's vertex order (MMDX_CREATE_TILE_ORDER): the direct-store variants
+    bool wt;                     // write-through stores; exists where deform_has_write_through(), every other shape keeps its nt stores
+    bool bounds, select;         // the BOUNDS / SELECT flavours (mmdx_deform_batched_bounds / _select): every shape, nt stores only
+};
 
-// Does this launch shape exist in the write-through store flavour?  (Measured to pay on the SoA f32 crowd kernels only: 256 threads,
-// no morphs or shared morphs, original vertex order.)  api.cpp asks before it sets DeformParams::write_through, pick() asserts it.
-constexpr bool deform_has_write_through(int threads, int layout, int morph, bool f16, bool tile_order) {
-    return threads == 256 && layout == 0 /* MMDX_OUT_SOA */ && !f16 && !tile_order && (morph == kMorphNone || morph == kMorphShared);
-}
-
-hipError_t launch_deform(int threads, int layout, int morph, bool f16, const DeformParams &p,
-                         uint32_t ntiles, size_t lds_bytes, hipStream_t stream);
-// Per-instance morph weights, packs of 4 instances, 512 threads (kernels.hip pack_kernel): SoA f32 and f16-position layouts, original
-// vertex order.  p.group a multiple of 4; LDS offsets from pack_lds_bytes.
-size_t pack_lds_bytes(uint32_t group, uint32_t max_tile_bones, uint32_t ns, uint32_t *stage_off, uint32_t *w_off, uint32_t *mp_off);
-hipError_t launch_pack(int layout, bool f16, const DeformParams &p, uint32_t ntiles, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_pack_fast(int layout, bool f16, const DeformParams &p, uint32_t ntiles, size_t lds_bytes, hipStream_t stream);
-// One frame of one model (ni == 1, kMorphNone / kMorphFused1): latency-ordered kernel, a workgroup = `threads` (128 / 256) sorted
-// slots of a tile, direct stores.  LDS: the tile's palette, then the slot weights at *w_off.
-size_t frame_lds_bytes(int morph, uint32_t max_tile_bones, uint32_t ns, uint32_t *w_off);
-hipError_t launch_frame(int threads, int layout, int morph, bool f16, const DeformParams &p, uint32_t ntiles, size_t lds_bytes,
-                        hipStream_t stream);
-// `fused` != nullptr: evaluate the slot weights inside the kernel (ns <= kMaxFusedSlots), no flatten launch
-hipError_t launch_morph_apply(bool f16, const DeformParams &p, const FlattenParams *fused,
-                              hipStream_t stream);
+// The launch functions of one build of the kernels: kernels.hip as it stands (bit-exact), or compiled a second time with multiply-add
+// contraction allowed (kernels_fast.hip, MMDX_CREATE_FAST_MATH models).
+struct KernelSet {
+    // LDS offsets of p and lds_bytes: from the launch's LaunchShape (launch_shape.hpp)
+    hipError_t (*launch_deform)(const DeformVariant &v, const DeformParams &p, uint32_t ntiles, size_t lds_bytes, hipStream_t stream);
+    // One frame of one model (ni == 1, kMorphNone / kMorphFused1): latency-ordered kernel, a workgroup = `threads` (128 / 256) sorted
+    // slots of a tile, direct stores.
+    hipError_t (*launch_frame)(int threads, int layout, int morph, bool f16, const DeformParams &p, uint32_t ntiles, size_t lds_bytes,
+                               hipStream_t stream);
+    // Per-instance morph weights, packs of 4 instances, 512 threads (kernels.hip pack_kernel): SoA f32 and f16-position layouts, original
+    // vertex order.  p.group a multiple of 4.
+    hipError_t (*launch_pack)(int layout, bool f16, const DeformParams &p, uint32_t ntiles, size_t lds_bytes, hipStream_t stream);
+    // `fused` != nullptr: evaluate the slot weights inside the kernel (ns <= kMaxFusedSlots), no flatten launch
+    hipError_t (*launch_morph_apply)(bool f16, const DeformParams &p, const FlattenParams *fused, hipStream_t stream);
+    hipError_t (*prepare)();     // raise the dynamic-LDS limit of every deform variant (once per device)
+};
+const KernelSet &kernels();         // kernels.hip
+const KernelSet &kernels_fast();    // kernels_fast.hip
+inline const KernelSet &kernel_set(bool fast) { return fast ? kernels_fast() : kernels(); }
 constexpr uint32_t kMaxFusedSlots = 8192;
 // pitch: vertices from one instance's piece to the next (0 = nv)
 hipError_t launch_pattern_fill(void *a, void *b, uint32_t nv, uint32_t ni, uint32_t bpva, uint32_t bpvb,
@@ -152,13 +138,5 @@ hipError_t launch_flatten(const FlattenParams &p, hipStream_t stream);
 hipError_t launch_morph_track_eval(const MorphTrackParams &t, hipStream_t stream);
 hipError_t launch_copy(void *dst, const void *src, size_t bytes, hipStream_t stream);
 hipError_t launch_fill(void *dst, size_t bytes, hipStream_t stream);
-hipError_t prepare_kernels();  // raise the dynamic-LDS limit of every deform variant (once)
-// kernels_fast.hip: the same kernels with multiply-add contraction allowed (MMDX_CREATE_FAST_MATH models)
-hipError_t launch_deform_fast(int threads, int layout, int morph, bool f16, const DeformParams &p,
-                              uint32_t ntiles, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_frame_fast(int threads, int layout, int morph, bool f16, const DeformParams &p, uint32_t ntiles, size_t lds_bytes,
-                             hipStream_t stream);
-hipError_t launch_morph_apply_fast(bool f16, const DeformParams &p, const FlattenParams *fused, hipStream_t stream);
-hipError_t prepare_kernels_fast();
 
 }  // namespace mmdx

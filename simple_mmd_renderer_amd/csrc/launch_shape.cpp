@@ -1,0 +1,152 @@
+// launch_shape.cpp -- see launch_shape.hpp.  This is where the project's measured knowledge about launch shapes lives: every constant
+// below carries a number from LAB_NOTES.md or profiles/.
+#include "launch_shape.hpp"
+
+#include <algorithm>
+
+namespace mmdx {
+
+namespace {
+constexpr size_t kLdsPerCu = 160 * 1024;
+
+// Store flavour of a crowd launch (kernels.hip CopyFast), decided from the CALL alone -- no table of addresses, no state behind the
+// boundary: the caller's hint first (mmdx_placement_info.store_flags hands it the probe's verdict for arrays from
+// mmdx_crowd_output_alloc), then MMDX_STORE_WT=0 / 1 (A/B runs), then the default for arrays nothing is known about: outputs large
+// enough to stream through the caches (>= 512 MB per call) are written through, because six plain allocations in seven are not in
+// the fast store mode (expected cost of the wrong guess: 2 % on a fast pair against 4.6-5 % on the others).
+bool write_through_for(size_t out_bytes, uint32_t flags, int store_wt) {
+    if (flags & MMDX_OUT_STORES_WRITE_THROUGH) return true;
+    if (flags & MMDX_OUT_STORES_CACHED) return false;
+    if (store_wt == 0 || store_wt == 1) return store_wt == 1;
+    return out_bytes >= (size_t(512) << 20);
+}
+}  // namespace
+
+mmdx_status plan_deform_launch(const Plan &p, const DeformCall &c, const LaunchOverrides &ov, LaunchShape &s, std::string &err) {
+    const uint32_t layout = c.layout, ni = c.ni, nwork = c.nwork;
+    const int morph = c.morph;
+    const bool tile_order = (p.flags & MMDX_CREATE_TILE_ORDER) != 0;
+    s = LaunchShape{};
+    // The bounds and the select flavours exist of deform_kernel only, and with nt stores only: such calls never take the write-through
+    // store flavour (they store cached whatever the hint says), the pack kernel (an archived A/B) or the frame kernel.
+    const bool plain = !c.bounds && !c.select;
+
+    // ---- workgroup shape ------------------------------------------------------------------------------
+    // 256 threads / two vertex slots per lane everywhere except the per-instance-morph path: there one slot
+    // per lane (512 threads) leaves the registers to serve 8 instances per walk over a morph row.
+    // A single frame (one instance) is latency-bound: one slot per lane and twice the waves per tile finish sooner
+    // (config 2: 8.4 -> 6.9 us, config 5: 16.9 -> 14.9 us).
+    const bool one_frame = ni == 1 && nwork <= 1 && (morph == kMorphNone || morph == kMorphFused1);
+    // (tile-order outputs: no LDS image, 80 VGPRs with one slot per lane -- 512 threads measured 215.5 vs 219.1 us on the crowd)
+    int threads = (ov.threads ? ov.threads : (morph == kMorphFused4 || one_frame || tile_order ? 512 : 256)) == 512 ? 512 : 256;
+    if (morph == kMorphFused4 && threads == 512) {   // tiles with hundreds of bones: 8 palettes do not fit, 4 may
+        uint32_t so, wo;
+        if (deform_lds_bytes(512, layout, morph, 8, p.max_tile_bones, p.ns, &so, &wo) > kLdsPerCu) threads = 256;
+    }
+    s.threads = threads;
+    // ---- store flavour: only where the launch shape has the write-through flavour, and only for outputs in device memory (stores
+    // into mapped host memory cross PCIe whatever their cache bits say) ------------------------------------------------------------
+    s.write_through = plain && c.out_dev && deform_has_write_through(threads, int(layout), morph, p.f16, tile_order) &&
+                      write_through_for(c.out_bytes, c.flags, ov.store_wt);
+    // ---- group size (instances per workgroup) from the LDS budget ---------------------------------
+    const uint32_t gmin = morph == kMorphFused4 ? (threads == 512 ? 8u : 4u) : 1u;
+    uint32_t group = gmin;
+    if (morph != kMorphFused1 || ni > 1) {
+        const uint32_t target = uint32_t(ov.lds_target ? ov.lds_target : (morph == kMorphFused4 ? 64 : 42) * 1024);
+        uint32_t so, wo;
+        const size_t fixed = deform_lds_bytes(threads, layout, morph, 0, p.max_tile_bones, p.ns, &so, &wo, tile_order);
+        const size_t per = size_t(p.max_tile_bones) * 48;
+        uint32_t g = target > fixed ? uint32_t((target - fixed) / per) : 0u;
+        g = std::min(g, (morph == kMorphFused4 || tile_order) ? 16u : 32u);   // tile order: 16 219 us, 32 229 us, 8 244 us
+        if (g >= 8) g &= ~3u;   // measured: 16 beats 17 (even split of 1024 instances, aligned strides)
+        // write-through stores go to arrays that are not in the fast store mode; there 8 instances per workgroup (four workgroups
+        // per CU, half the open output streams each) beat 16 by 3-8 % -- 218-224 vs 225-241 us on four such pairs, while on a fast
+        // pair 16 wins (204 vs 211): profiles/r03/shape_sweep_write_through*.txt
+        if (s.write_through) g = std::min(g, 8u);
+        g = std::max(g / gmin * gmin, gmin);
+        const uint32_t ni_up = (std::max(nwork, 1u) + gmin - 1) / gmin * gmin;
+        g = std::min(g, ni_up);
+        // keep the grid large enough to fill 256 CUs several times over
+        while (g > gmin && uint64_t(p.ntiles) * ((nwork + g - 1) / g) < 2048) {
+            const uint32_t half = std::max((g / 2) / gmin * gmin, gmin);
+            if (half == g) break;
+            g = half;
+        }
+        group = std::max(g, gmin);
+        const int forced = ov.group;
+        if (forced > 0) group = std::max(uint32_t(forced) / gmin * gmin, gmin);
+    }
+    s.group = group;
+    // Per-instance morph weights, second shape (kernels.hip pack_kernel), OPT-IN (MMDX_FUSED_PACK=1): packs of 4 instances, 80 registers,
+    // three 8-wave workgroups per CU while a workgroup's LDS stays under a third of the CU's.  It runs at 5.7 waves per SIMD where
+    // deform_kernel<512, ., kMorphFused4> runs at 3.8 -- and loses (config 3' 372-382 us against 335-348; profiles/r04/fused_pack_*):
+    // the walk and the skinning of one CU do not overlap in either kernel (walk alone 132 us + skinning alone 254 us), and packs of 4
+    // walk the table twice as often as packs of 8.  Kept for the A/B, not the default.  Two-array layouts in original vertex order.
+    // The group: as many instances (multiple of 4, up to 16) as keep three workgroups on a CU, else as fit two.
+    bool pack = plain && morph == kMorphFused4 && ov.fused_pack != 0 && kTileVerts == 512 && !tile_order && layout != MMDX_OUT_VERTEX32 &&
+                !ov.threads;
+    size_t lds = 0;
+    if (pack) {
+        uint32_t so, wo, mo;
+        const size_t third = kLdsPerCu / 3 - 64, half = 80 * 1024 - 64;
+        uint32_t g = 0;
+        for (uint32_t k = 16; k >= 4 && !g; k -= 4)
+            if (pack_lds_bytes(k, p.max_tile_bones, p.ns, &so, &wo, &mo) <= third) g = k;
+        for (uint32_t k = 16; k >= 4 && !g; k -= 4)
+            if (pack_lds_bytes(k, p.max_tile_bones, p.ns, &so, &wo, &mo) <= half) g = k;
+        if (!g && pack_lds_bytes(4, p.max_tile_bones, p.ns, &so, &wo, &mo) <= kLdsPerCu) g = 4;
+        if (ov.group > 0) g = std::max(uint32_t(ov.group) / 4 * 4, 4u);
+        if (g) {
+            g = std::min(g, (ni + 3) / 4 * 4);
+            while (g > 4 && uint64_t(p.ntiles) * ((ni + g - 1) / g) < 1536) g -= 4;     // keep 256 CUs x 3 workgroups busy twice over
+            s.group = g;
+            lds = pack_lds_bytes(g, p.max_tile_bones, p.ns, &s.stage_off, &s.w_off, &s.mp_off);
+            if (lds > kLdsPerCu) pack = false;
+        } else {
+            pack = false;
+        }
+    }
+    if (!pack) {
+        s.group = group;
+        lds = deform_lds_bytes(threads, layout, morph, group, p.max_tile_bones, p.ns, &s.stage_off, &s.w_off, tile_order);
+        if (c.bounds && !tile_order) {
+            s.bounds_off = uint32_t(lds);
+            lds += kBoundsLdsBytes;
+        }
+    }
+    s.bounds_units = c.bounds ? deform_bounds_units(threads, p.ntiles, tile_order) : 0u;
+    s.lds = lds;
+    if (lds > kLdsPerCu) {
+        err = "tile needs " + std::to_string(lds) + " bytes of LDS (> 160 KiB): "
+              "too many distinct bones in one vertex tile / too many morph slots";
+        return MMDX_ERR_UNSUPPORTED;
+    }
+
+    if (morph == kMorphFused4) {
+        s.stagger = uint32_t(std::max(ov.stagger, 0));
+        s.slots_per_cu = std::max<uint32_t>(1u, std::min<uint32_t>(uint32_t(kLdsPerCu / std::max<size_t>(lds, 1)), pack ? 3u : 2u));
+    }
+    // One frame of one model into device memory: the latency-ordered kernel (parts of tiles on every CU, direct stores).
+    // Outputs in mapped host memory keep the tile kernel: its 16-byte coalesced stores are what crosses PCIe well.
+    // Models with fewer tiles than the chip has CUs only (config 2: 6.3 us against the tile kernel's 6.9); a large model fills the
+    // chip with whole tiles and is better off with their coalesced stores (config 5: 14.9 us against 15.2).
+    const bool frame = plain && one_frame && !c.out_host_mapped && (ov.frame_kernel == 2 || (ov.frame_kernel == 1 && p.ntiles < 256));
+    if (frame) {
+        s.kernel = LaunchShape::kFrame;
+        s.lds = frame_lds_bytes(morph, p.max_tile_bones, p.ns, &s.w_off);
+        if (s.lds > kLdsPerCu) {
+            err = "tile needs " + std::to_string(s.lds) + " bytes of LDS (> 160 KiB)";
+            return MMDX_ERR_UNSUPPORTED;
+        }
+    } else if (pack) {
+        s.kernel = LaunchShape::kPack;
+    } else if (c.select && nwork == 0) {
+        // an empty list: no instance to write (the shared morph pass has run as in the plain call)
+        s.kernel = LaunchShape::kNone;
+    } else {
+        s.kernel = LaunchShape::kDeform;
+    }
+    return MMDX_OK;
+}
+
+}  // namespace mmdx
