@@ -659,6 +659,68 @@ MMDX_API mmdx_status mmdx_skeleton_solve_motion(mmdx_skeleton_t skeleton, mmdx_b
 MMDX_API mmdx_status mmdx_skeleton_solve_motion_time(mmdx_skeleton_t skeleton, mmdx_bone_motion_t motion, mmdx_model_t model,
                                                      uint32_t n_instances, const double *times, uint32_t flags,
                                                      float *out_palettes);
+
+/* ---- Motion sets: every instance of a crowd plays its own clip ------------------------------------------------------------------
+ * In the reference every Poser has its own MotionPlayer over whichever Motion it likes (L/motion/poser_impl.inl:522-555), so instance
+ * i playing clip c[i] at t[i] is plain reference behaviour.  A motion set is an immutable bank of clips bound to ONE model's bones
+ * and / or morphs; the entry points below take a clip index per instance next to the per-instance frame or time, and the result for
+ * instance i is, bit for bit, what the single-motion entry point (mmdx_bone_motion_eval*, mmdx_morph_motion_eval*,
+ * mmdx_skeleton_solve_motion*) returns for clip clips[i] at frames[i] / times[i] -- Motion::GetBonePose / GetMorphPose
+ * (L/motion/motion_impl.inl:255-380, :382-465) of that instance's Motion.  One launch whatever the mix of clips, nothing for the
+ * host to partition or gather.
+ *
+ * mmdx_motion_set_create COPIES the host tables of the given motions: the motions and their mmdx_vmd_t may be destroyed afterwards.
+ * At least one of the two arrays must be given; all bone motions must be bound to the same number of bones and all morph motions to
+ * the same number of morphs (MMDX_ERR_INVALID_ARGUMENT otherwise, as for n_clips == 0, a NULL element, or keys that in total do not
+ * fit 32-bit offsets).  An entry point of the side the set was created without returns MMDX_ERR_INVALID_ARGUMENT.
+ *
+ * clips[n_instances]: MMDX_CLIP_NONE = this instance plays nothing -- its row is still written: poses {0,0,0,0, 0,0,0,1} per bone
+ * (Poser::ResetPosing), rates 0, the palette the solve of the rest pose.  A HOST clip index >= n_clips that is not MMDX_CLIP_NONE
+ * returns MMDX_ERR_BAD_INDEX; a DEVICE clip index >= n_clips behaves as MMDX_CLIP_NONE.  No row of the output is left unwritten
+ * and nothing is read out of range.
+ *
+ * flags: MMDX_FRAMES_ON_DEVICE (= MMDX_TIMES_ON_DEVICE) | MMDX_OUT_ON_DEVICE; unknown bits are rejected.  MMDX_FRAMES_ON_DEVICE
+ * means BOTH clips and frames / times are device pointers; without it both are host pointers, copied through a scratch of the set
+ * in stream order.  The *_time forms follow points 1-6 at mmdx_morph_motion_eval_time (host NaN rejected, device NaN takes the
+ * first key).  Stream, device, first-use upload and graph recording as for mmdx_bone_motion_eval / mmdx_skeleton_solve_motion: run
+ * the call once before recording it; a set destroyed while a graph holds it invalidates the graph. */
+typedef struct mmdx_motion_set_s *mmdx_motion_set_t;
+enum { MMDX_CLIP_NONE = 0xFFFFFFFFu };        /* this instance plays nothing: rest pose, all rates 0  */
+
+typedef struct mmdx_motion_set_info {
+    uint32_t struct_size;
+    uint32_t n_clips, n_bones, n_morphs;      /* n_bones / n_morphs 0 when that side was not given    */
+    uint32_t n_bone_keys, n_morph_keys;       /* sums over the clips                                  */
+    uint32_t n_curves;                        /* presampled curve tables; byte-identical ones of
+                                                 different clips are stored once                      */
+} mmdx_motion_set_info;
+
+MMDX_API mmdx_status mmdx_motion_set_create(uint32_t n_clips, const mmdx_bone_motion_t *bone_motions /* [n_clips] or NULL */,
+                                            const mmdx_morph_motion_t *morph_motions /* [n_clips] or NULL */,
+                                            mmdx_motion_set_t *out_set);
+MMDX_API mmdx_status mmdx_motion_set_get_info(mmdx_motion_set_t set, mmdx_motion_set_info *info);
+MMDX_API void mmdx_motion_set_destroy(mmdx_motion_set_t set);
+/* out_poses[i][b][MMDX_POSE_FLOATS] = local pose of model bone b in clip clips[i] at frames[i] / times[i] seconds. */
+MMDX_API mmdx_status mmdx_motion_set_eval_bones(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
+                                                const uint32_t *clips, const uint32_t *frames, uint32_t flags, float *out_poses);
+MMDX_API mmdx_status mmdx_motion_set_eval_bones_time(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
+                                                     const uint32_t *clips, const double *times, uint32_t flags, float *out_poses);
+/* out_weights[i][m] = rate of model morph m in clip clips[i] at frames[i] / times[i] seconds. */
+MMDX_API mmdx_status mmdx_motion_set_eval_morphs(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
+                                                 const uint32_t *clips, const uint32_t *frames, uint32_t flags, float *out_weights);
+MMDX_API mmdx_status mmdx_motion_set_eval_morphs_time(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
+                                                      const uint32_t *clips, const double *times, uint32_t flags, float *out_weights);
+/* out_palettes[i][b][16]: bit for bit mmdx_motion_set_eval_bones* followed by mmdx_skeleton_solve.  One launch on parallel-FK
+ * skeletons of up to 2 048 bones (a workgroup per instance, its clip id and clock read once, the poses in LDS); skeletons with
+ * append bones / IK and larger ones take the two launches, the poses in the set's scratch buffer.  The set's bone motions must have
+ * been bound to this skeleton's bones (MMDX_ERR_INVALID_ARGUMENT on another bone count). */
+MMDX_API mmdx_status mmdx_skeleton_solve_motion_set(mmdx_skeleton_t skeleton, mmdx_motion_set_t set, mmdx_model_t model,
+                                                    uint32_t n_instances, const uint32_t *clips, const uint32_t *frames,
+                                                    uint32_t flags, float *out_palettes);
+MMDX_API mmdx_status mmdx_skeleton_solve_motion_set_time(mmdx_skeleton_t skeleton, mmdx_motion_set_t set, mmdx_model_t model,
+                                                         uint32_t n_instances, const uint32_t *clips, const double *times,
+                                                         uint32_t flags, float *out_palettes);
+
 /* The same with bone morphs applied first: morph_weights[i][n_morphs] (or one shared row with
  * MMDX_WEIGHTS_SHARED; device pointer with MMDX_WEIGHTS_ON_DEVICE) are the raw per-frame morph rates, the
  * ones mmdx_deform_batched takes.  Bone-morph rotations go through SLerp, i.e. through the device's double

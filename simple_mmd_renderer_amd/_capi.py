@@ -147,6 +147,20 @@ SIGNATURES = {
     "mmdx_skeleton_solve_motion": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "mmdx_skeleton_solve_motion_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                                     C.c_void_p]),
+    "mmdx_motion_set_create": (C.c_int32, [C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mmdx_motion_set_get_info": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mmdx_motion_set_destroy": (None, [C.c_void_p]),
+    # (set, model, n_instances, clips, frames | times, flags, out)
+    "mmdx_motion_set_eval_bones": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mmdx_motion_set_eval_bones_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                    C.c_void_p]),
+    "mmdx_motion_set_eval_morphs": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mmdx_motion_set_eval_morphs_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                     C.c_void_p]),
+    "mmdx_skeleton_solve_motion_set": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                   C.c_void_p]),
+    "mmdx_skeleton_solve_motion_set_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                        C.c_uint32, C.c_void_p]),
     "mmdx_skeleton_solve_morphed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),
     "mmdx_skeleton_solve_pre": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,

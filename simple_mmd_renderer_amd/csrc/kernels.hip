@@ -1672,10 +1672,7 @@ __global__ __launch_bounds__(kThreads) void flatten_select_kernel(const FlattenP
 // With a TimeClock: GetMorphPose(name, double time), :426-465 (motion_clock.hpp) -- no exact-hit shortcut,
 // so a key hit still goes through the blend (an infinite neighbour gives NaN there).
 template <class Clock>
-__global__ __launch_bounds__(kThreads) void morph_track_eval_kernel(const MorphTrackParams t) {
-    const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (idx >= size_t(t.ni) * t.nm) return;
-    const uint32_t i = uint32_t(idx / t.nm), m = uint32_t(idx - size_t(i) * t.nm);
+__device__ __forceinline__ float eval_morph_rate(const MorphTrackParams &t, uint32_t m, uint32_t i) {
     const uint32_t b = t.key_off[m], e = t.key_off[m + 1];
     const Clock clk = clock_of<Clock>(t.frames, t.times, i);
     float w = 0.f;
@@ -1699,6 +1696,31 @@ __global__ __launch_bounds__(kThreads) void morph_track_eval_kernel(const MorphT
                 w = t.key_weights[lo] * (1.0f - bary) + t.key_weights[hi] * bary;
             }
         }
+    }
+    return w;
+}
+
+template <class Clock>
+__global__ __launch_bounds__(kThreads) void morph_track_eval_kernel(const MorphTrackParams t) {
+    const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
+    if (idx >= size_t(t.ni) * t.nm) return;
+    const uint32_t i = uint32_t(idx / t.nm), m = uint32_t(idx - size_t(i) * t.nm);
+    t.out[idx] = eval_morph_rate<Clock>(t, m, i);
+}
+
+// Motion set (mmdx_motion_set_eval_morphs*): clip c of the bank is the single-motion table with key_off advanced by c * (nm+1), the
+// offsets there being absolute into the concatenated key arrays -- eval_morph_rate itself evaluates it.  The clip id is per lane (a
+// wave spans several instances); an id outside [0, n_clips) (MMDX_CLIP_NONE included) plays nothing: rate 0, no table read.
+template <class Clock>
+__global__ __launch_bounds__(kThreads) void morph_track_eval_set_kernel(MorphTrackParams t, const uint32_t *clips, const uint32_t n_clips) {
+    const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
+    if (idx >= size_t(t.ni) * t.nm) return;
+    const uint32_t i = uint32_t(idx / t.nm), m = uint32_t(idx - size_t(i) * t.nm);
+    const uint32_t clip = clips[i];
+    float w = 0.f;
+    if (clip < n_clips) {
+        t.key_off += size_t(clip) * (size_t(t.nm) + 1);
+        w = eval_morph_rate<Clock>(t, m, i);
     }
     t.out[idx] = w;
 }
@@ -2016,6 +2038,15 @@ hipError_t launch_morph_track_eval(const MorphTrackParams &t, hipStream_t stream
     const dim3 grid(uint32_t((n + kThreads - 1) / kThreads));
     if (t.times) hipLaunchKernelGGL(morph_track_eval_kernel<TimeClock>, grid, dim3(kThreads), 0, stream, t);
     else hipLaunchKernelGGL(morph_track_eval_kernel<FrameClock>, grid, dim3(kThreads), 0, stream, t);
+    return hipGetLastError();
+}
+
+hipError_t launch_morph_track_eval_set(const MorphTrackParams &t, const uint32_t *clips, uint32_t n_clips, hipStream_t stream) {
+    const size_t n = size_t(t.ni) * t.nm;
+    if (n == 0) return hipSuccess;
+    const dim3 grid(uint32_t((n + kThreads - 1) / kThreads));
+    if (t.times) hipLaunchKernelGGL(morph_track_eval_set_kernel<TimeClock>, grid, dim3(kThreads), 0, stream, t, clips, n_clips);
+    else hipLaunchKernelGGL(morph_track_eval_set_kernel<FrameClock>, grid, dim3(kThreads), 0, stream, t, clips, n_clips);
     return hipGetLastError();
 }
 

@@ -136,6 +136,8 @@ hipError_t launch_pattern_fill(void *a, void *b, uint32_t nv, uint32_t ni, uint3
                                hipStream_t stream, uint32_t pitch = 0);
 hipError_t launch_flatten(const FlattenParams &p, hipStream_t stream);
 hipError_t launch_morph_track_eval(const MorphTrackParams &t, hipStream_t stream);
+// a motion set's morph side: t holds the concatenated tables, clips[ni] (device) the clip of every instance; ids >= n_clips give rate 0
+hipError_t launch_morph_track_eval_set(const MorphTrackParams &t, const uint32_t *clips, uint32_t n_clips, hipStream_t stream);
 hipError_t launch_copy(void *dst, const void *src, size_t bytes, hipStream_t stream);
 hipError_t launch_fill(void *dst, size_t bytes, hipStream_t stream);
 

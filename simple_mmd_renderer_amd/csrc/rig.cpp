@@ -19,8 +19,10 @@
 // g++ and every curve degenerates to a constant; oracle/ref_harness.cpp therefore mirrors the viewer's
 // include order.
 #include "rig.hpp"
+#include "vmd.hpp"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -89,6 +91,76 @@ void build_bone_motion(const std::vector<std::string> &track_names, const std::v
         }
         out.key_off.push_back(uint32_t(out.key_frame.size()));
     }
+}
+
+// ---- motion set: the clips' tables laid end to end (rig.hpp MotionSetHost) -----------------------------------------------------
+mmdx_status build_motion_set_bones(const std::vector<const BoneMotionHost *> &clips, MotionSetHost &out, std::string &err) {
+    BoneMotionHost &o = out.bones;
+    o = BoneMotionHost();
+    o.nb = clips.empty() ? 0 : clips[0]->nb;
+    uint64_t keys = 0, tables = 0;
+    for (const BoneMotionHost *c : clips) {
+        if (c->nb != o.nb) {
+            err = "the bone motions are bound to different bone counts (" + std::to_string(o.nb) + " and " + std::to_string(c->nb) + ")";
+            return MMDX_ERR_INVALID_ARGUMENT;
+        }
+        keys += c->key_frame.size();
+        tables += c->lut.size() / kCurveSamples;
+    }
+    if (keys > 0xFFFFFFFFull || tables >= kLinearCurve || uint64_t(clips.size()) * (uint64_t(o.nb) + 1) > 0xFFFFFFFFull) {
+        err = "the clips' bone keys do not fit 32-bit offsets";
+        return MMDX_ERR_INVALID_ARGUMENT;
+    }
+    // a curve table is shared between clips only when its sampled values are byte-identical: compared as bit patterns
+    std::map<std::array<uint32_t, kCurveSamples>, uint32_t> table_of;
+    std::vector<uint32_t> remap;
+    for (const BoneMotionHost *c : clips) {
+        const uint32_t base = uint32_t(o.key_frame.size());
+        for (uint32_t b = 0; b <= o.nb; ++b) o.key_off.push_back(base + c->key_off[b]);
+        o.n_mapped = std::max(o.n_mapped, c->n_mapped);
+        o.key_frame.insert(o.key_frame.end(), c->key_frame.begin(), c->key_frame.end());
+        o.key_tr.insert(o.key_tr.end(), c->key_tr.begin(), c->key_tr.end());
+        o.key_rot.insert(o.key_rot.end(), c->key_rot.begin(), c->key_rot.end());
+        remap.assign(c->lut.size() / kCurveSamples, 0);
+        for (size_t t = 0; t < remap.size(); ++t) {
+            std::array<uint32_t, kCurveSamples> bits;
+            std::memcpy(bits.data(), c->lut.data() + t * kCurveSamples, sizeof(bits));
+            auto it = table_of.find(bits);
+            if (it == table_of.end()) {
+                it = table_of.emplace(bits, uint32_t(o.lut.size() / kCurveSamples)).first;
+                o.lut.insert(o.lut.end(), c->lut.begin() + t * kCurveSamples, c->lut.begin() + (t + 1) * kCurveSamples);
+            }
+            remap[t] = it->second;
+        }
+        for (uint32_t id : c->key_curve) o.key_curve.push_back(id == kLinearCurve ? kLinearCurve : remap[id]);
+    }
+    out.has_bones = true;
+    return MMDX_OK;
+}
+
+mmdx_status build_motion_set_morphs(const std::vector<MorphMotionHost> &clips, MotionSetHost &out, std::string &err) {
+    out.nm = clips.empty() ? 0 : clips[0].nm;
+    out.morph_key_off.clear(); out.morph_frames.clear(); out.morph_weights.clear();
+    uint64_t keys = 0;
+    for (const MorphMotionHost &c : clips) {
+        if (c.nm != out.nm) {
+            err = "the morph motions are bound to different morph counts (" + std::to_string(out.nm) + " and " + std::to_string(c.nm) + ")";
+            return MMDX_ERR_INVALID_ARGUMENT;
+        }
+        keys += c.nkeys;
+    }
+    if (keys > 0xFFFFFFFFull || uint64_t(clips.size()) * (uint64_t(out.nm) + 1) > 0xFFFFFFFFull) {
+        err = "the clips' morph keys do not fit 32-bit offsets";
+        return MMDX_ERR_INVALID_ARGUMENT;
+    }
+    for (const MorphMotionHost &c : clips) {
+        const uint32_t base = uint32_t(out.morph_frames.size());
+        for (uint32_t m = 0; m <= out.nm; ++m) out.morph_key_off.push_back(base + c.key_off[m]);
+        out.morph_frames.insert(out.morph_frames.end(), c.frames, c.frames + c.nkeys);
+        out.morph_weights.insert(out.morph_weights.end(), c.weights, c.weights + c.nkeys);
+    }
+    out.has_morphs = true;
+    return MMDX_OK;
 }
 
 void solve_event_sets(const SkeletonPlan &plan, uint32_t bone, std::vector<uint32_t> &reads, std::vector<uint32_t> &writes) {

@@ -45,6 +45,25 @@ struct BoneTrackParams {
     const double *times;                        // [ni] seconds instead of frames (MotionPlayer::SeekTime), or nullptr
 };
 
+// ---- motion set: a bank of clips bound to one model (mmdx_motion_set_*) ---------------------------
+// The clips' tables laid end to end.  Clip c is the single-motion table with key_off advanced by c * (nb+1) (morphs: c * (nm+1)):
+// the offsets are ABSOLUTE into the concatenated key arrays, the curve ids rebased into the set's one table (curve tables whose 32
+// samples are byte-identical are stored once).
+struct MotionSetHost {
+    uint32_t n_clips = 0;
+    bool has_bones = false, has_morphs = false;
+    BoneMotionHost bones;                       // nb of every clip; key_off [n_clips][nb+1]
+    uint32_t nm = 0;
+    std::vector<uint32_t> morph_key_off;        // [n_clips][nm+1]
+    std::vector<uint32_t> morph_frames;         // [K] ascending inside a (clip, morph)
+    std::vector<float> morph_weights;           // [K]
+};
+struct MorphMotionHost;                         // vmd.hpp
+// MMDX_ERR_INVALID_ARGUMENT (text in `err`) when the clips disagree about the bone / morph count or the keys of all clips do not
+// fit 32-bit offsets.  The clips are only read.
+mmdx_status build_motion_set_bones(const std::vector<const BoneMotionHost *> &clips, MotionSetHost &out, std::string &err);
+mmdx_status build_motion_set_morphs(const std::vector<MorphMotionHost> &clips, MotionSetHost &out, std::string &err);
+
 // ---- skeleton: local poses -> skinning palette --------------------------------------------------
 enum : uint32_t { kBoneAppendRot = 1u, kBoneAppendTr = 2u, kBoneIsIkLink = 4u, kBoneHasIk = 8u };
 enum : uint32_t { kFixNone = 0, kFixX = 1, kFixY = 2, kFixZ = 3, kFixAll = 4 };

@@ -12,6 +12,7 @@
 #include "../../include/mmdx.h"
 #include "error.hpp"
 #include "graph_pin.hpp"
+#include "kernels.hpp"
 #include "rig.hpp"
 #include "rig_kernels.hpp"
 #include "vmd.hpp"
@@ -85,6 +86,24 @@ struct mmdx_skeleton_s {
                        &state,
                        &apps, &app_chain, &rates_in, &morph_state, &over_bone, &over_strict, &over_skin})
             b->release();
+    }
+};
+
+// A bank of clips bound to one model (rig.hpp MotionSetHost): the concatenated tables of both sides, uploaded on first use.
+struct mmdx_motion_set_s {
+    MotionSetHost host;
+    int device = -1;
+    Buf key_off, key_frame, key_tr, key_rot, key_curve, lut;        // bone side
+    Buf m_key_off, m_frames, m_weights;                             // morph side
+    Buf clips_in, clock_in;                                         // host operands: 4 + 8 bytes per instance
+    Buf poses, out;                                                 // the two-launch palette path's poses; results bound for the host
+    GraphPin pin;                                                   // recorded graphs that hold these buffers' addresses
+    std::vector<Buf *> all() {
+        return {&key_off, &key_frame, &key_tr, &key_rot, &key_curve, &lut, &m_key_off, &m_frames, &m_weights, &clips_in, &clock_in,
+                &poses, &out};
+    }
+    mmdx_motion_set_s() {
+        for (Buf *b : all()) b->pin = &pin;
     }
 };
 
@@ -162,6 +181,13 @@ static mmdx_status bone_motion_eval(mmdx_bone_motion_t m, mmdx_model_t model, ui
                                     uint32_t flags, float *out_poses);
 static mmdx_status skeleton_solve_motion(mmdx_skeleton_t s, mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
                                          const void *clock, bool time, uint32_t flags, float *out_palettes);
+
+static mmdx_status set_eval_bones(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
+                                  const void *clock, bool time, uint32_t flags, float *out_poses);
+static mmdx_status set_eval_morphs(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
+                                   const void *clock, bool time, uint32_t flags, float *out_weights);
+static mmdx_status skeleton_solve_motion_set(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
+                                             const uint32_t *clips, const void *clock, bool time, uint32_t flags, float *out_palettes);
 
 extern "C" {
 
@@ -295,6 +321,87 @@ mmdx_status mmdx_skeleton_solve_post(mmdx_skeleton_t s, mmdx_model_t model, uint
                 return fail(MMDX_ERR_BAD_INDEX, "overrides: bone " + std::to_string(ov->bone[k]) + " out of range");
     }
     return skeleton_solve(s, model, n_instances, nullptr, nullptr, flags, out_palettes, 2u, ov);
+}
+
+mmdx_status mmdx_motion_set_create(uint32_t n_clips, const mmdx_bone_motion_t *bone_motions, const mmdx_morph_motion_t *morph_motions,
+                                   mmdx_motion_set_t *out) {
+    if (!out) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (!n_clips || (!bone_motions && !morph_motions))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "a motion set needs at least one clip and at least one of bone_motions / morph_motions");
+    for (uint32_t c = 0; c < n_clips; ++c)
+        if ((bone_motions && !bone_motions[c]) || (morph_motions && !morph_motions[c]))
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "clip " + std::to_string(c) + " is NULL");
+    try {
+        std::unique_ptr<mmdx_motion_set_s> set(new mmdx_motion_set_s);
+        set->host.n_clips = n_clips;
+        std::string err;
+        if (bone_motions) {
+            std::vector<const BoneMotionHost *> clips;
+            for (uint32_t c = 0; c < n_clips; ++c) clips.push_back(&bone_motions[c]->host);
+            if (mmdx_status st = build_motion_set_bones(clips, set->host, err)) return fail(st, "motion set: " + err);
+        }
+        if (morph_motions) {
+            std::vector<MorphMotionHost> clips;
+            for (uint32_t c = 0; c < n_clips; ++c) clips.push_back(morph_motion_host(morph_motions[c]));
+            if (mmdx_status st = build_motion_set_morphs(clips, set->host, err)) return fail(st, "motion set: " + err);
+        }
+        *out = set.release();
+    } catch (const std::bad_alloc &) {
+        return fail(MMDX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    }
+    return MMDX_OK;
+}
+
+mmdx_status mmdx_motion_set_get_info(mmdx_motion_set_t set, mmdx_motion_set_info *info) {
+    if (!set || !info || info->struct_size != sizeof(mmdx_motion_set_info))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or mmdx_motion_set_info.struct_size mismatch");
+    const MotionSetHost &h = set->host;
+    info->n_clips = h.n_clips;
+    info->n_bones = h.has_bones ? h.bones.nb : 0;
+    info->n_morphs = h.has_morphs ? h.nm : 0;
+    info->n_bone_keys = uint32_t(h.bones.key_frame.size());
+    info->n_morph_keys = uint32_t(h.morph_frames.size());
+    info->n_curves = uint32_t(h.bones.lut.size() / kCurveSamples);
+    return MMDX_OK;
+}
+
+void mmdx_motion_set_destroy(mmdx_motion_set_t set) {
+    if (!set) return;
+    graph_drop_handle(&set->pin);
+    if (set->device >= 0) (void)hipSetDevice(set->device);
+    for (Buf *b : set->all()) b->release();
+    delete set;
+}
+
+mmdx_status mmdx_motion_set_eval_bones(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
+                                       const uint32_t *frames, uint32_t flags, float *out_poses) {
+    return set_eval_bones(set, model, n_instances, clips, frames, false, flags, out_poses);
+}
+
+mmdx_status mmdx_motion_set_eval_bones_time(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
+                                            const double *times, uint32_t flags, float *out_poses) {
+    return set_eval_bones(set, model, n_instances, clips, times, true, flags, out_poses);
+}
+
+mmdx_status mmdx_motion_set_eval_morphs(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
+                                        const uint32_t *frames, uint32_t flags, float *out_weights) {
+    return set_eval_morphs(set, model, n_instances, clips, frames, false, flags, out_weights);
+}
+
+mmdx_status mmdx_motion_set_eval_morphs_time(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
+                                             const double *times, uint32_t flags, float *out_weights) {
+    return set_eval_morphs(set, model, n_instances, clips, times, true, flags, out_weights);
+}
+
+mmdx_status mmdx_skeleton_solve_motion_set(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
+                                           const uint32_t *clips, const uint32_t *frames, uint32_t flags, float *out_palettes) {
+    return skeleton_solve_motion_set(s, set, model, n_instances, clips, frames, false, flags, out_palettes);
+}
+
+mmdx_status mmdx_skeleton_solve_motion_set_time(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
+                                                const uint32_t *clips, const double *times, uint32_t flags, float *out_palettes) {
+    return skeleton_solve_motion_set(s, set, model, n_instances, clips, times, true, flags, out_palettes);
 }
 
 }  // extern "C"
@@ -528,6 +635,220 @@ static mmdx_status skeleton_solve_motion(mmdx_skeleton_t s, mmdx_bone_motion_t m
         HIP_TRY(wait_stream(st));
     } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
         HIP_TRY(wait_stream(st));                    // the borrowed host frame numbers / times must be consumed before returning
+    }
+    return MMDX_OK;
+}
+
+// ---- motion sets -----------------------------------------------------------------------------------------------------------------
+// Everything about a set call that can be decided without the device, in one place and before the first HIP call: NULLs, the
+// instance count, flag bits, NaN in host times (check_time_args), the side the set was created without, host clip ids.
+static mmdx_status set_check_args(mmdx_motion_set_t set, bool bone_side, uint32_t n_instances, const uint32_t *clips, const void *clock,
+                                  bool time, uint32_t flags, const float *out) {
+    if (!set || !clips || !clock || !out || !n_instances) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    const uint32_t allowed = MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
+    if (time) {
+        if (mmdx_status r = check_time_args(static_cast<const double *>(clock), n_instances, flags, allowed)) return r;
+    } else if (flags & ~allowed) {
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    }
+    if (bone_side ? !set->host.has_bones : !set->host.has_morphs)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("this motion set was created without ") + (bone_side ? "bone" : "morph") + " motions");
+    if (!(flags & MMDX_FRAMES_ON_DEVICE))
+        for (uint32_t i = 0; i < n_instances; ++i)
+            if (clips[i] >= set->host.n_clips && clips[i] != MMDX_CLIP_NONE)
+                return fail(MMDX_ERR_BAD_INDEX, "clips[" + std::to_string(i) + "] = " + std::to_string(clips[i]) + ": the set has " +
+                                                std::to_string(set->host.n_clips) + " clips");
+    return MMDX_OK;
+}
+
+static mmdx_status set_to_device(mmdx_motion_set_t set, int device) {
+    if (set->device == device) return MMDX_OK;
+    if (graph_pinned(&set->pin)) return hip_status(hipErrorIllegalState, "moving a motion set to another device");
+    const MotionSetHost &h = set->host;
+    for (Buf *b : set->all()) b->release();
+    if (h.has_bones) {
+        HIP_TRY(set->key_off.upload(h.bones.key_off));
+        HIP_TRY(set->key_frame.upload(h.bones.key_frame));
+        HIP_TRY(set->key_tr.upload(h.bones.key_tr));
+        HIP_TRY(set->key_rot.upload(h.bones.key_rot));
+        HIP_TRY(set->key_curve.upload(h.bones.key_curve));
+        HIP_TRY(set->lut.upload(h.bones.lut));
+    }
+    if (h.has_morphs) {
+        HIP_TRY(set->m_key_off.upload(h.morph_key_off));
+        HIP_TRY(set->m_frames.upload(h.morph_frames));
+        HIP_TRY(set->m_weights.upload(h.morph_weights));
+    }
+    set->device = device;
+    return MMDX_OK;
+}
+
+static BoneTrackParams set_bone_params(mmdx_motion_set_t set, uint32_t n_instances) {
+    BoneTrackParams p;
+    p.key_off = static_cast<const uint32_t *>(set->key_off.ptr);
+    p.key_frame = static_cast<const uint32_t *>(set->key_frame.ptr);
+    p.key_tr = static_cast<const float *>(set->key_tr.ptr);
+    p.key_rot = static_cast<const float *>(set->key_rot.ptr);
+    p.key_curve = static_cast<const uint32_t *>(set->key_curve.ptr);
+    p.lut = static_cast<const float *>(set->lut.ptr);
+    p.frames = nullptr; p.out = nullptr; p.times = nullptr;
+    p.nb = set->host.bones.nb; p.ni = n_instances;
+    return p;
+}
+
+// clip ids and the instant of every instance -> device addresses.  MMDX_FRAMES_ON_DEVICE covers both; host operands go through the
+// set's scratch (4 + 8 bytes per instance, room for frames or times) in stream order.
+static mmdx_status set_operands_in(mmdx_motion_set_t set, const uint32_t *clips, const void *clock, bool time, uint32_t n_instances,
+                                   uint32_t flags, hipStream_t st, const uint32_t **dev_clips, const void **dev_clock) {
+    *dev_clips = clips;
+    *dev_clock = clock;
+    if (flags & MMDX_FRAMES_ON_DEVICE) return MMDX_OK;
+    HIP_TRY(set->clips_in.ensure(size_t(n_instances) * 4));
+    HIP_TRY(set->clock_in.ensure(size_t(n_instances) * 8));
+    HIP_TRY(hipMemcpyAsync(set->clips_in.ptr, clips, size_t(n_instances) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(set->clock_in.ptr, clock, size_t(n_instances) * (time ? 8 : 4), hipMemcpyHostToDevice, st));
+    *dev_clips = static_cast<const uint32_t *>(set->clips_in.ptr);
+    *dev_clock = set->clock_in.ptr;
+    return MMDX_OK;
+}
+
+static const char *const kSetRecording = "while a graph is being recorded every operand must be in device memory and the motion set "
+                                         "must have run on this device before";
+
+// mmdx_motion_set_eval_bones / _time: frames (uint32_t) or, with `time`, seconds (double)
+static mmdx_status set_eval_bones(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
+                                  const void *clock, bool time, uint32_t flags, float *out_poses) {
+    if (mmdx_status r = set_check_args(set, true, n_instances, clips, clock, time, flags, out_poses)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const uint32_t on_device = MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
+    if (graph_recording() && ((flags & on_device) != on_device || set->device != device)) return fail(MMDX_ERR_INVALID_ARGUMENT, kSetRecording);
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    BoneTrackParams p = set_bone_params(set, n_instances);
+    const uint32_t *dev_clips;
+    const void *dev_clock;
+    if (mmdx_status r = set_operands_in(set, clips, clock, time, n_instances, flags, st, &dev_clips, &dev_clock)) return r;
+    if (time) p.times = static_cast<const double *>(dev_clock);
+    else p.frames = static_cast<const uint32_t *>(dev_clock);
+    const size_t out_bytes = size_t(n_instances) * p.nb * MMDX_POSE_FLOATS * sizeof(float);
+    if (flags & MMDX_OUT_ON_DEVICE) {
+        p.out = out_poses;
+    } else {
+        HIP_TRY(set->out.ensure(out_bytes));
+        p.out = static_cast<float *>(set->out.ptr);
+    }
+    HIP_TRY(launch_bone_track_eval_set(p, dev_clips, set->host.n_clips, st));
+    if (!(flags & MMDX_OUT_ON_DEVICE)) {
+        if (out_bytes) HIP_TRY(hipMemcpyAsync(out_poses, p.out, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(wait_stream(st));
+    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
+        HIP_TRY(wait_stream(st));   // borrowed host clip ids and frames / times must be consumed before returning
+    }
+    return MMDX_OK;
+}
+
+// mmdx_motion_set_eval_morphs / _time
+static mmdx_status set_eval_morphs(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
+                                   const void *clock, bool time, uint32_t flags, float *out_weights) {
+    if (mmdx_status r = set_check_args(set, false, n_instances, clips, clock, time, flags, out_weights)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const uint32_t on_device = MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
+    if (graph_recording() && ((flags & on_device) != on_device || set->device != device)) return fail(MMDX_ERR_INVALID_ARGUMENT, kSetRecording);
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    MorphTrackParams t;
+    t.key_off = static_cast<const uint32_t *>(set->m_key_off.ptr);
+    t.key_frames = static_cast<const uint32_t *>(set->m_frames.ptr);
+    t.key_weights = static_cast<const float *>(set->m_weights.ptr);
+    t.nm = set->host.nm; t.ni = n_instances;
+    t.frames = nullptr; t.times = nullptr;
+    const uint32_t *dev_clips;
+    const void *dev_clock;
+    if (mmdx_status r = set_operands_in(set, clips, clock, time, n_instances, flags, st, &dev_clips, &dev_clock)) return r;
+    if (time) t.times = static_cast<const double *>(dev_clock);
+    else t.frames = static_cast<const uint32_t *>(dev_clock);
+    const size_t out_bytes = size_t(n_instances) * t.nm * sizeof(float);
+    if (flags & MMDX_OUT_ON_DEVICE) {
+        t.out = out_weights;
+    } else {
+        HIP_TRY(set->out.ensure(out_bytes));
+        t.out = static_cast<float *>(set->out.ptr);
+    }
+    HIP_TRY(launch_morph_track_eval_set(t, dev_clips, set->host.n_clips, st));
+    if (!(flags & MMDX_OUT_ON_DEVICE)) {
+        if (out_bytes) HIP_TRY(hipMemcpyAsync(out_weights, t.out, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(wait_stream(st));
+    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
+        HIP_TRY(wait_stream(st));   // borrowed host clip ids and frames / times must be consumed before returning
+    }
+    return MMDX_OK;
+}
+
+// mmdx_skeleton_solve_motion_set / _time
+static mmdx_status skeleton_solve_motion_set(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
+                                             const uint32_t *clips, const void *clock, bool time, uint32_t flags, float *out_palettes) {
+    if (!s) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    if (mmdx_status r = set_check_args(set, true, n_instances, clips, clock, time, flags, out_palettes)) return r;
+    if (set->host.bones.nb != s->plan.nb)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "the motion set was bound to " + std::to_string(set->host.bones.nb) +
+                                               " bones, the skeleton has " + std::to_string(s->plan.nb));
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const SkeletonPlan &pl = s->plan;
+    const size_t pose_bytes = size_t(n_instances) * pl.nb * MMDX_POSE_FLOATS * sizeof(float);
+    if (pl.serial || size_t(pl.nb) * 32 > kMotionFkMaxLds) {
+        // append bones / IK (the ordered solver) or a skeleton too large for the LDS pose table: the two launches, the poses in the
+        // set's scratch buffer
+        if (graph_recording() && (set->poses.bytes < pose_bytes || set->device != device))
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "run the call once before recording: it sizes the motion set's pose buffer");
+        if (mmdx_status r = set_to_device(set, device)) return r;
+        HIP_TRY(set->poses.ensure(pose_bytes));
+        if (mmdx_status r = set_eval_bones(set, model, n_instances, clips, clock, time, (flags & MMDX_FRAMES_ON_DEVICE) | MMDX_OUT_ON_DEVICE,
+                                           static_cast<float *>(set->poses.ptr)))
+            return r;
+        return mmdx_skeleton_solve(s, model, n_instances, static_cast<const float *>(set->poses.ptr),
+                                   MMDX_POSES_ON_DEVICE | (flags & MMDX_OUT_ON_DEVICE), out_palettes);
+    }
+    const uint32_t on_device = MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
+    if (graph_recording() && ((flags & on_device) != on_device || set->device != device || s->device != device))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory and the motion "
+                                               "set and the skeleton must have run on this device before");
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    if (mmdx_status r = skeleton_to_device(s, device)) return r;
+    graph_note_handle(model, &set->pin);
+    graph_note_handle(model, &s->pin);
+    BoneTrackParams tp = set_bone_params(set, n_instances);
+    const uint32_t *dev_clips;
+    const void *dev_clock;
+    if (mmdx_status r = set_operands_in(set, clips, clock, time, n_instances, flags, st, &dev_clips, &dev_clock)) return r;
+    if (time) tp.times = static_cast<const double *>(dev_clock);
+    else tp.frames = static_cast<const uint32_t *>(dev_clock);
+    const size_t out_bytes = size_t(n_instances) * pl.nb * 16 * sizeof(float);
+    SkeletonParams fp;
+    fp.morph = nullptr;
+    fp.poses = nullptr;
+    if (flags & MMDX_OUT_ON_DEVICE) {
+        fp.out = out_palettes;
+    } else {
+        HIP_TRY(s->out.ensure(out_bytes));
+        fp.out = static_cast<float *>(s->out.ptr);
+    }
+    fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
+    fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
+    fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
+    fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
+    fp.nb = pl.nb; fp.ni = n_instances;
+    HIP_TRY(launch_motion_fk_set(tp, fp, dev_clips, set->host.n_clips, st));
+    if (!(flags & MMDX_OUT_ON_DEVICE)) {
+        HIP_TRY(hipMemcpyAsync(out_palettes, fp.out, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(wait_stream(st));
+    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
+        HIP_TRY(wait_stream(st));                    // the borrowed host clip ids and clocks must be consumed before returning
     }
     return MMDX_OK;
 }

@@ -105,6 +105,29 @@ __global__ __launch_bounds__(kRigThreads) void bone_track_eval_kernel(const Bone
     out[1] = q;
 }
 
+// Motion set (mmdx_motion_set_*): clip c of the bank is the single-motion table with key_off advanced by c * (nb+1) -- the offsets
+// stored there are absolute into the concatenated key arrays -- so the clip of an instance goes through eval_bone_pose itself.  A
+// clip id outside [0, n_clips) (MMDX_CLIP_NONE included) plays nothing: the rest pose of Poser::ResetPosing, and no table is read.
+__device__ __forceinline__ BoneTrackParams clip_of(BoneTrackParams p, uint32_t clip) {
+    p.key_off += size_t(clip) * (size_t(p.nb) + 1);
+    return p;
+}
+
+// One thread per (instance, bone), as above.  A wave spans two instances when nb is not a multiple of 64: the clip id is per lane.
+template <class Clock>
+__global__ __launch_bounds__(kRigThreads) void bone_track_eval_set_kernel(const BoneTrackParams p, const uint32_t *clips,
+                                                                          const uint32_t n_clips) {
+    const size_t idx = size_t(blockIdx.x) * kRigThreads + threadIdx.x;
+    if (idx >= size_t(p.ni) * p.nb) return;
+    const uint32_t i = uint32_t(idx / p.nb), bone = uint32_t(idx - size_t(i) * p.nb);
+    const uint32_t clip = clips[i];
+    float4 t = make_float4(0.f, 0.f, 0.f, 0.f), q = make_float4(0.f, 0.f, 0.f, 1.f);   // Poser::ResetPosing
+    if (clip < n_clips) eval_bone_pose(clip_of(p, clip), bone, clock_of<Clock>(p.frames, p.times, i), t, q);
+    float4 *out = reinterpret_cast<float4 *>(p.out) + idx * 2;
+    out[0] = t;
+    out[1] = q;
+}
+
 struct Mat4 {
     float m[4][4];
 };
@@ -207,6 +230,32 @@ __global__ __launch_bounds__(1024) void motion_fk_kernel(const BoneTrackParams t
     for (uint32_t b = threadIdx.x; b < p.nb; b += blockDim.x) {   // one bone per thread up to 1 024 bones: one latency chain, not several
         float4 tr, q;
         eval_bone_pose(t, b, clk, tr, q);
+        pose_lds[2 * b] = tr;
+        pose_lds[2 * b + 1] = q;
+        if (t.out) {
+            float4 *o = reinterpret_cast<float4 *>(t.out) + (size_t(i) * p.nb + b) * 2;
+            o[0] = tr; o[1] = q;
+        }
+    }
+    __syncthreads();
+    for (uint32_t bone = threadIdx.x; bone < p.nb; bone += blockDim.x)
+        fk_bone(p, [&](uint32_t k) { return pose_lds[k]; }, i, bone, reinterpret_cast<float4 *>(p.out) + (size_t(i) * p.nb + bone) * 4);
+}
+
+// The same for a motion set: the instance's clip id is read once per workgroup next to its clock (workgroup-uniform: a scalar load),
+// an id outside the bank puts the rest pose into LDS.  eval_bone_pose, the barrier and fk_bone are the ones above.
+template <class Clock>
+__global__ __launch_bounds__(1024) void motion_fk_set_kernel(const BoneTrackParams t0, const SkeletonParams p, const uint32_t *clips,
+                                                             const uint32_t n_clips) {
+    extern __shared__ float4 pose_lds[];                 // [nb][2]
+    const uint32_t i = blockIdx.x;
+    const uint32_t clip = clips[i];
+    const bool plays = clip < n_clips;
+    const BoneTrackParams t = clip_of(t0, plays ? clip : 0u);
+    const Clock clk = clock_of<Clock>(t.frames, t.times, i);
+    for (uint32_t b = threadIdx.x; b < p.nb; b += blockDim.x) {
+        float4 tr = make_float4(0.f, 0.f, 0.f, 0.f), q = make_float4(0.f, 0.f, 0.f, 1.f);   // Poser::ResetPosing
+        if (plays) eval_bone_pose(t, b, clk, tr, q);
         pose_lds[2 * b] = tr;
         pose_lds[2 * b + 1] = q;
         if (t.out) {
@@ -1196,6 +1245,15 @@ hipError_t launch_bone_track_eval(const BoneTrackParams &p, hipStream_t stream) 
     return hipGetLastError();
 }
 
+hipError_t launch_bone_track_eval_set(const BoneTrackParams &p, const uint32_t *clips, uint32_t n_clips, hipStream_t stream) {
+    const size_t n = size_t(p.ni) * p.nb;
+    if (n == 0) return hipSuccess;
+    const dim3 grid(uint32_t((n + kRigThreads - 1) / kRigThreads));
+    if (p.times) hipLaunchKernelGGL(bone_track_eval_set_kernel<TimeClock>, grid, dim3(kRigThreads), 0, stream, p, clips, n_clips);
+    else hipLaunchKernelGGL(bone_track_eval_set_kernel<FrameClock>, grid, dim3(kRigThreads), 0, stream, p, clips, n_clips);
+    return hipGetLastError();
+}
+
 hipError_t launch_skeleton_fk(const SkeletonParams &p, hipStream_t stream) {
     const size_t n = size_t(p.ni) * p.nb;
     if (n == 0) return hipSuccess;
@@ -1211,6 +1269,17 @@ hipError_t launch_motion_fk(const BoneTrackParams &t, const SkeletonParams &p, h
     const uint32_t threads = std::min<uint32_t>(1024u, (p.nb + 63u) / 64u * 64u);
     if (t.times) hipLaunchKernelGGL(motion_fk_kernel<TimeClock>, dim3(p.ni), dim3(threads), lds, stream, t, p);
     else hipLaunchKernelGGL(motion_fk_kernel<FrameClock>, dim3(p.ni), dim3(threads), lds, stream, t, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_motion_fk_set(const BoneTrackParams &t, const SkeletonParams &p, const uint32_t *clips, uint32_t n_clips,
+                                hipStream_t stream) {
+    if (p.ni == 0 || p.nb == 0) return hipSuccess;
+    const size_t lds = size_t(p.nb) * 32;
+    if (lds > kMotionFkMaxLds) return hipErrorInvalidValue;                  // callers check: the two-launch path takes over
+    const uint32_t threads = std::min<uint32_t>(1024u, (p.nb + 63u) / 64u * 64u);
+    if (t.times) hipLaunchKernelGGL(motion_fk_set_kernel<TimeClock>, dim3(p.ni), dim3(threads), lds, stream, t, p, clips, n_clips);
+    else hipLaunchKernelGGL(motion_fk_set_kernel<FrameClock>, dim3(p.ni), dim3(threads), lds, stream, t, p, clips, n_clips);
     return hipGetLastError();
 }
 

@@ -13,6 +13,11 @@ hipError_t launch_skeleton_fk(const SkeletonParams &p, hipStream_t stream);
 // bone tracks -> palette in one launch (parallel-FK skeletons): poses of an instance live in LDS (nb * 32 bytes <= kMotionFkMaxLds)
 constexpr size_t kMotionFkMaxLds = 64 * 1024;
 hipError_t launch_motion_fk(const BoneTrackParams &t, const SkeletonParams &p, hipStream_t stream);
+// the same two for a motion set (rig.hpp MotionSetHost): p / t hold the set's concatenated tables, clips[ni] the clip of every
+// instance (device memory); ids >= n_clips play nothing (rest pose)
+hipError_t launch_bone_track_eval_set(const BoneTrackParams &p, const uint32_t *clips, uint32_t n_clips, hipStream_t stream);
+hipError_t launch_motion_fk_set(const BoneTrackParams &t, const SkeletonParams &p, const uint32_t *clips, uint32_t n_clips,
+                                hipStream_t stream);
 hipError_t launch_skeleton_ordered(const SerialParams &p, const uint8_t *round_coop /* host, [n_rounds] or nullptr */, hipStream_t stream);
 hipError_t launch_bone_morph(const BoneMorphParams &p, hipStream_t stream);
 hipError_t launch_physics_override(const PhysicsParams &p, hipStream_t stream);

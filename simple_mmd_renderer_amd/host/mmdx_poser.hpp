@@ -215,6 +215,7 @@ public:
     }
 
     mmdx_model_t handle() const { return model_; }
+    mmdx_skeleton_t skeleton() const { return skeleton_; }
     uint32_t vertex_count() const { return nv_; }
     uint32_t bone_count() const { return nb_; }
     uint32_t morph_count() const { return nm_; }
@@ -327,6 +328,63 @@ private:
     mmdx_bone_motion_t bones_ = nullptr;
     mmdx_morph_motion_t morphs_ = nullptr;
     uint32_t mapped_bones_ = 0;
+};
+
+// A crowd of posers that share one model, each with its own MotionPlayer over whichever Motion it likes
+// (L/motion/poser_impl.inl:522-555): the motions become the clips of one bank (mmdx_motion_set_t), bound to the poser's bones
+// and morphs by name like MotionPlayer does, and instance i plays clip clips[i] at times[i] seconds (SeekTime) or frames[i]
+// (SeekFrame).  One call evaluates the whole crowd; clips[i] == MMDX_CLIP_NONE is a poser after ResetPosing().  The arrays are
+// host memory by default; with on_device = true clips, times / frames and the output are device memory and the call is
+// asynchronous on the poser's stream (and recordable into a graph).  The motions may be destroyed after construction.
+class MotionSet {
+public:
+    MotionSet(const std::vector<const Motion *> &motions, Poser &poser) : poser_(poser) {
+        std::vector<const char *> bn, mn;
+        for (const std::string &s : poser.bone_names()) bn.push_back(s.c_str());
+        for (const std::string &s : poser.morph_names()) mn.push_back(s.c_str());
+        std::vector<mmdx_bone_motion_t> bones(motions.size(), nullptr);
+        std::vector<mmdx_morph_motion_t> morphs(motions.size(), nullptr);
+        mmdx_status st = MMDX_OK;
+        for (size_t c = 0; c < motions.size() && st == MMDX_OK; ++c) {
+            st = mmdx_vmd_bind_bones(motions[c]->handle(), uint32_t(bn.size()), bn.data(), &bones[c]);
+            if (st == MMDX_OK) st = mmdx_vmd_bind_morphs(motions[c]->handle(), uint32_t(mn.size()), mn.data(), &morphs[c]);
+        }
+        if (st == MMDX_OK) st = mmdx_motion_set_create(uint32_t(motions.size()), bones.data(), morphs.data(), &set_);
+        const std::string why = st == MMDX_OK ? "" : mmdx_last_error_string();
+        for (mmdx_bone_motion_t b : bones) mmdx_bone_motion_destroy(b);          // the set holds copies of the tables
+        for (mmdx_morph_motion_t m : morphs) mmdx_morph_motion_destroy(m);
+        if (st != MMDX_OK) throw Error(st, why);
+    }
+    ~MotionSet() { mmdx_motion_set_destroy(set_); }
+    MotionSet(const MotionSet &) = delete;
+    MotionSet &operator=(const MotionSet &) = delete;
+
+    uint32_t clip_count() const {
+        mmdx_motion_set_info info;
+        info.struct_size = sizeof(info);
+        check(mmdx_motion_set_get_info(set_, &info));
+        return info.n_clips;
+    }
+    // out_palettes[i][bone][16] = the skinning matrices of instance i: SeekTime / SeekFrame + Pre/PostPhysicsPosing of its poser
+    void SeekTimePalettes(uint32_t n, const uint32_t *clips, const double *times, float *out_palettes, bool on_device = false) {
+        check(mmdx_skeleton_solve_motion_set_time(poser_.skeleton(), set_, poser_.handle(), n, clips, times, flags(on_device), out_palettes));
+    }
+    void SeekFramePalettes(uint32_t n, const uint32_t *clips, const uint32_t *frames, float *out_palettes, bool on_device = false) {
+        check(mmdx_skeleton_solve_motion_set(poser_.skeleton(), set_, poser_.handle(), n, clips, frames, flags(on_device), out_palettes));
+    }
+    // out_rates[i][morph] = the morph rates of instance i (what mmdx_deform_batched takes as per-instance weights)
+    void SeekTimeMorphRates(uint32_t n, const uint32_t *clips, const double *times, float *out_rates, bool on_device = false) {
+        check(mmdx_motion_set_eval_morphs_time(set_, poser_.handle(), n, clips, times, flags(on_device), out_rates));
+    }
+    void SeekFrameMorphRates(uint32_t n, const uint32_t *clips, const uint32_t *frames, float *out_rates, bool on_device = false) {
+        check(mmdx_motion_set_eval_morphs(set_, poser_.handle(), n, clips, frames, flags(on_device), out_rates));
+    }
+    mmdx_motion_set_t handle() const { return set_; }
+
+private:
+    static uint32_t flags(bool on_device) { return on_device ? uint32_t(MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE) : 0u; }
+    Poser &poser_;
+    mmdx_motion_set_t set_ = nullptr;
 };
 
 }  // namespace mmdx

@@ -3,9 +3,13 @@
 //   g++ -std=c++17 -O2 motion_example.cpp -I../../include -L.. -lmmdx -Wl,-rpath,'$ORIGIN/..' -o motion_example
 //   ./motion_example model.pmx motion.vmd [frames [hz]]
 // With `hz` the loop runs at that display rate: step n seeks to n / hz seconds (MotionPlayer::SeekTime) instead of frame n.
+//   ./motion_example --crowd instances hz model.pmx clip0.vmd [clip1.vmd ...]
+// Crowd mode (mmdx::MotionSet): the motions are the clips of one bank, instance i plays clip i % clips at i / hz seconds; one
+// call each gives every instance's palette and morph rates.
 // Prints per-run checksums so tests can compare with the Python path over the same C ABI.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "mmdx_poser.hpp"
 
@@ -16,7 +20,41 @@ static uint64_t checksum(const void *p, size_t n) {
     return h;
 }
 
+static int crowd(int argc, char **argv) {
+    if (argc < 6) { std::printf("usage: %s --crowd instances hz model.pmx|.pmd clip0.vmd [clip1.vmd ...]\n", argv[0]); return 64; }
+    const uint32_t ni = uint32_t(std::atoi(argv[2]));
+    const double hz = std::atof(argv[3]);
+    std::unique_ptr<mmdx::Poser> poser(mmdx::Poser::FromFile(argv[4]));
+    std::vector<std::unique_ptr<mmdx::Motion>> motions;
+    std::vector<const mmdx::Motion *> clips_of;
+    for (int a = 5; a < argc; ++a) {
+        motions.emplace_back(new mmdx::Motion(argv[a]));
+        clips_of.push_back(motions.back().get());
+    }
+    mmdx::MotionSet set(clips_of, *poser);
+    motions.clear();                          // the set copied what it needs
+    const uint32_t nc = set.clip_count();
+    std::vector<uint32_t> clips(ni);
+    std::vector<double> times(ni);
+    for (uint32_t i = 0; i < ni; ++i) { clips[i] = i % nc; times[i] = double(i) / hz; }
+    std::vector<float> palettes(size_t(ni) * poser->bone_count() * 16), rates(size_t(ni) * poser->morph_count());
+    set.SeekTimePalettes(ni, clips.data(), times.data(), palettes.data());
+    set.SeekTimeMorphRates(ni, clips.data(), times.data(), rates.data());
+    const uint64_t h = checksum(palettes.data(), palettes.size() * 4) * 31 + checksum(rates.data(), rates.size() * 4);
+    std::printf("crowd=%u clips=%u nb=%u nm=%u checksum=%016llx\n", ni, nc, poser->bone_count(), poser->morph_count(),
+                (unsigned long long)h);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && !std::strcmp(argv[1], "--crowd")) {
+        try {
+            return crowd(argc, argv);
+        } catch (const mmdx::Error &e) {
+            std::printf("mmdx error %d: %s\n", int(e.status), e.what());
+            return 1;
+        }
+    }
     if (argc < 3) { std::printf("usage: %s model.pmx|.pmd motion.vmd [frames [hz]]\n", argv[0]); return 64; }
     try {
         std::unique_ptr<mmdx::Poser> poser(mmdx::Poser::FromFile(argv[1]));

@@ -227,6 +227,92 @@ class BoneMotion:
             pass
 
 
+CLIP_NONE = 0xFFFFFFFF                   # MMDX_CLIP_NONE: the instance plays nothing (rest pose, all rates 0)
+
+
+class MotionSetInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_clips", C.c_uint32), ("n_bones", C.c_uint32), ("n_morphs", C.c_uint32),
+                ("n_bone_keys", C.c_uint32), ("n_morph_keys", C.c_uint32), ("n_curves", C.c_uint32)]
+
+
+class MotionSet:
+    """A bank of clips bound to one model (mmdx_motion_set_t): every instance of a crowd plays its own clip, clips[i], at its own
+    frame or time.  bone_motions / morph_motions: sequences of BoneMotion / MorphMotion, one per clip, at least one of the two;
+    their tables are copied, so the motions (and their Vmd) may be closed afterwards."""
+
+    def __init__(self, bone_motions: Optional[Sequence["BoneMotion"]] = None,
+                 morph_motions: Optional[Sequence["MorphMotion"]] = None):
+        n = len(bone_motions) if bone_motions is not None else len(morph_motions) if morph_motions is not None else 0
+        if bone_motions is not None and morph_motions is not None and len(bone_motions) != len(morph_motions):
+            raise ValueError("bone_motions and morph_motions must hold one motion per clip each")
+
+        def handles(ms):
+            return (C.c_void_p * max(n, 1))(*[m.h for m in ms]) if ms is not None else None
+        self.h = C.c_void_p()
+        api.check(api.lib().mmdx_motion_set_create(n, handles(bone_motions), handles(morph_motions), C.byref(self.h)))
+        info = MotionSetInfo()
+        info.struct_size = C.sizeof(MotionSetInfo)
+        api.check(api.lib().mmdx_motion_set_get_info(self.h, C.byref(info)))
+        self.info = {k: getattr(info, k) for k, _ in MotionSetInfo._fields_}
+        self.n_clips, self.nb, self.nm = info.n_clips, info.n_bones, info.n_morphs
+
+    def _host(self, fn, clips, clock, dtype, row_shape, model):
+        c = np.ascontiguousarray(clips, np.uint32).reshape(-1)
+        t = np.ascontiguousarray(clock, dtype).reshape(-1)
+        if c.size != t.size:
+            raise ValueError("one clip index per instance")
+        out = np.empty((c.size,) + row_shape, np.float32)
+        api.check(fn(self.h, model.h if model is not None else None, c.size, c.ctypes.data, t.ctypes.data, 0, out.ctypes.data))
+        return out
+
+    def eval_bones(self, clips, frames, model=None) -> np.ndarray:
+        """Host convenience: clip ids [NI], frames [NI] -> poses f32 [NI, NB, 8] (device evaluation + D2H)."""
+        return self._host(api.lib().mmdx_motion_set_eval_bones, clips, frames, np.uint32, (self.nb, POSE_FLOATS), model)
+
+    def eval_bones_time(self, clips, times, model=None) -> np.ndarray:
+        """Host convenience: clip ids [NI], times in seconds f64 [NI] -> poses f32 [NI, NB, 8]."""
+        return self._host(api.lib().mmdx_motion_set_eval_bones_time, clips, times, np.float64, (self.nb, POSE_FLOATS), model)
+
+    def eval_morphs(self, clips, frames, model=None) -> np.ndarray:
+        """Host convenience: clip ids [NI], frames [NI] -> rates f32 [NI, NM]."""
+        return self._host(api.lib().mmdx_motion_set_eval_morphs, clips, frames, np.uint32, (self.nm,), model)
+
+    def eval_morphs_time(self, clips, times, model=None) -> np.ndarray:
+        """Host convenience: clip ids [NI], times in seconds f64 [NI] -> rates f32 [NI, NM]."""
+        return self._host(api.lib().mmdx_motion_set_eval_morphs_time, clips, times, np.float64, (self.nm,), model)
+
+    def _device(self, fn, n_instances, clips_ptr, clock_ptr, out_ptr, model):
+        api.check(fn(self.h, model.h if model is not None else None, n_instances, clips_ptr, clock_ptr,
+                     FRAMES_ON_DEVICE | api.OUT_ON_DEVICE, out_ptr))
+
+    def eval_bones_device(self, n_instances: int, clips_ptr, frames_ptr, out_ptr, model=None) -> None:
+        """clips u32[NI], frames u32[NI] and out f32[NI][NB][8] resident in HBM; asynchronous on the model's stream."""
+        self._device(api.lib().mmdx_motion_set_eval_bones, n_instances, clips_ptr, frames_ptr, out_ptr, model)
+
+    def eval_bones_time_device(self, n_instances: int, clips_ptr, times_ptr, out_ptr, model=None) -> None:
+        """clips u32[NI], times f64[NI] (seconds) and out f32[NI][NB][8] resident in HBM."""
+        self._device(api.lib().mmdx_motion_set_eval_bones_time, n_instances, clips_ptr, times_ptr, out_ptr, model)
+
+    def eval_morphs_device(self, n_instances: int, clips_ptr, frames_ptr, out_ptr, model=None) -> None:
+        """clips u32[NI], frames u32[NI] and out f32[NI][NM] resident in HBM."""
+        self._device(api.lib().mmdx_motion_set_eval_morphs, n_instances, clips_ptr, frames_ptr, out_ptr, model)
+
+    def eval_morphs_time_device(self, n_instances: int, clips_ptr, times_ptr, out_ptr, model=None) -> None:
+        """clips u32[NI], times f64[NI] (seconds) and out f32[NI][NM] resident in HBM."""
+        self._device(api.lib().mmdx_motion_set_eval_morphs_time, n_instances, clips_ptr, times_ptr, out_ptr, model)
+
+    def close(self):
+        if getattr(self, "h", None):
+            api.lib().mmdx_motion_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SkeletonDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_bones", C.c_uint32), ("rest_position", C.c_void_p),
                 ("parent", C.c_void_p), ("transform_level", C.c_void_p), ("flags", C.c_void_p),
@@ -377,6 +463,37 @@ class Skeleton:
         """Times (f64 seconds) and palettes resident in HBM; asynchronous on the model's stream."""
         api.check(api.lib().mmdx_skeleton_solve_motion_time(self.h, motion.h, model.h if model is not None else None, n_instances,
                                                             times_ptr, TIMES_ON_DEVICE | api.OUT_ON_DEVICE, out_ptr))
+
+    # -- the same from a motion set: every instance its own clip -----------------------------------------------------
+    def _solve_set(self, fn, motion_set, clips, clock, dtype, model):
+        c = np.ascontiguousarray(clips, np.uint32).reshape(-1)
+        t = np.ascontiguousarray(clock, dtype).reshape(-1)
+        if c.size != t.size:
+            raise ValueError("one clip index per instance")
+        out = np.empty((c.size, self.nb, 16), np.float32)
+        api.check(fn(self.h, motion_set.h, model.h if model is not None else None, c.size, c.ctypes.data, t.ctypes.data, 0,
+                     out.ctypes.data))
+        return out
+
+    def solve_motion_set(self, motion_set: "MotionSet", clips, frames, model=None) -> np.ndarray:
+        """Host convenience: clip ids [NI], frame numbers [NI] -> palettes f32 [NI, NB, 16]."""
+        return self._solve_set(api.lib().mmdx_skeleton_solve_motion_set, motion_set, clips, frames, np.uint32, model)
+
+    def solve_motion_set_time(self, motion_set: "MotionSet", clips, times, model=None) -> np.ndarray:
+        """Host convenience: clip ids [NI], times in seconds f64 [NI] -> palettes f32 [NI, NB, 16]."""
+        return self._solve_set(api.lib().mmdx_skeleton_solve_motion_set_time, motion_set, clips, times, np.float64, model)
+
+    def solve_motion_set_device(self, motion_set: "MotionSet", n_instances: int, clips_ptr, frames_ptr, out_ptr, model=None) -> None:
+        """Clip ids, frame numbers and palettes resident in HBM; asynchronous on the model's stream."""
+        api.check(api.lib().mmdx_skeleton_solve_motion_set(self.h, motion_set.h, model.h if model is not None else None, n_instances,
+                                                           clips_ptr, frames_ptr, FRAMES_ON_DEVICE | api.OUT_ON_DEVICE, out_ptr))
+
+    def solve_motion_set_time_device(self, motion_set: "MotionSet", n_instances: int, clips_ptr, times_ptr, out_ptr,
+                                     model=None) -> None:
+        """Clip ids, times (f64 seconds) and palettes resident in HBM; asynchronous on the model's stream."""
+        api.check(api.lib().mmdx_skeleton_solve_motion_set_time(self.h, motion_set.h, model.h if model is not None else None,
+                                                                n_instances, clips_ptr, times_ptr,
+                                                                TIMES_ON_DEVICE | api.OUT_ON_DEVICE, out_ptr))
 
     def solve_device(self, n_instances: int, poses_ptr, out_ptr, model=None, weights_ptr=None, shared=False) -> None:
         """poses, palettes (and morph rates) resident in HBM; asynchronous on the model's stream."""

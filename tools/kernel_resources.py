@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """VGPRs / SGPRs / spills / static LDS of every kernel in a built libmmdx.so (no GPU needed):
     python tools/kernel_resources.py [path.so] [substring ...]
-Unbundles the gfx950 code object and reads the AMDGPU metadata note."""
+Unbundles the gfx950 code object of every translation unit and reads the AMDGPU metadata notes."""
 import os
 import re
 import subprocess
@@ -18,10 +18,18 @@ def main():
     with tempfile.TemporaryDirectory() as d:
         fat = os.path.join(d, "fat.bin")
         subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", so, fat], check=True)
-        co = os.path.join(d, "gfx950.co")
-        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
+        # one bundle per translation unit that holds kernels (kernels.hip, kernels_fast.hip, rig_kernels.hip), laid end to end
+        magic = b"__CLANG_OFFLOAD_BUNDLE__"
+        data = open(fat, "rb").read()
+        starts = [i for i in range(len(data)) if data.startswith(magic, i)]
+        notes = ""
+        for k, (b, e) in enumerate(zip(starts, starts[1:] + [len(data)])):
+            one, co = os.path.join(d, "fat%d.bin" % k), os.path.join(d, "gfx950_%d.co" % k)
+            open(one, "wb").write(data[b:e])
+            subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + one,
+                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
+            notes += subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True,
+                                    check=True).stdout
     for blk in notes.split("- .agpr_count:")[1:]:
         g = lambda k: (re.search(r"\." + k + r":\s+(\S+)", blk) or [None, "?"])[1]
         name = g("name")
