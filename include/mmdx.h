@@ -721,6 +721,50 @@ MMDX_API mmdx_status mmdx_skeleton_solve_motion_set_time(mmdx_skeleton_t skeleto
                                                          uint32_t n_instances, const uint32_t *clips, const double *times,
                                                          uint32_t flags, float *out_palettes);
 
+/* ---- Cross-fade between two clips of a motion set, per instance ----------------------------------------------------------------
+ * Rewriting clips[i] makes instance i jump from one clip to the other.  The reference has no cross-fade, but it has the operations
+ * one is made of, and uses them between two keys of one track: l*(1-lambda) + r*lambda per channel for translations and morph
+ * weights (L/motion/motion_impl.inl:364-372, :462) and NLerp(l, r)[lambda] for rotations (L/util/math_impl.inl:1260-1282).  The
+ * blend is exactly those operations applied between two clips, so it is held to the same bar: bit for bit against code that runs
+ * the real libmmd.
+ *
+ * For instance i, a = clips_a[i], b = clips_b[i], w = weights[i]: A is the row the mmdx_motion_set_eval_*_time call writes for
+ * (a, times_a[i]) -- the rest pose / rate 0 for MMDX_CLIP_NONE or a device id >= n_clips -- and B the same for (b, times_b[i]).
+ *   !(w >= 1e-7f)      the row is A, every bit (w < 1e-7f, negative, a device NaN); clip b is not evaluated, no table of it read
+ *   w > 1.0f - 1e-7f   the row is B, every bit; clip a is not evaluated
+ *   otherwise          translation  A.t.c * (1.0f - w) + B.t.c * w  for c = x, y, z (float, unfused, this order), fourth float 0
+ *                      rotation     the middle branch of NLerpProxy::operator[]: dot = A.q . B.q (4 terms, left to right);
+ *                                   (1-w)*A.q - w*B.q when dot < 0, else (1-w)*A.q + w*B.q; Normalize = * 1.0f / float(sqrt(double(
+ *                                   sum of squares)))
+ *                      morph rate   A.r * (1.0f - w) + B.r * w
+ * The short circuits are NLerp's, applied to the whole row: a crowd in which few instances are mid-transition pays one evaluation
+ * for the rest.  The palette call is bit for bit the blended poses followed by mmdx_skeleton_solve.
+ *
+ * Host operands are checked before the first HIP call: a clip id >= n_clips other than MMDX_CLIP_NONE in either array returns
+ * MMDX_ERR_BAD_INDEX, a NaN time or weight MMDX_ERR_INVALID_ARGUMENT.  Device operands follow the rules above (a NaN time takes
+ * the first key).  flags: MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE, unknown bits rejected; MMDX_TIMES_ON_DEVICE makes ALL FIVE
+ * operand arrays device pointers.  Only the time clock is offered; more than two clips and wrapping a clip's time stay with the
+ * caller.  Stream, device, first-use upload, graph recording and pinning as for mmdx_skeleton_solve_motion_set_time: run the call
+ * once before recording it. */
+typedef struct mmdx_motion_blend_args {
+    uint32_t struct_size, n_instances;    /* = sizeof(mmdx_motion_blend_args); NI >= 1            */
+    const uint32_t *clips_a, *clips_b;    /* [n_instances]                                        */
+    const double *times_a, *times_b;      /* [n_instances] seconds                                */
+    const float *weights;                 /* [n_instances] 0 = a, 1 = b                           */
+    uint32_t flags;                       /* MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE            */
+} mmdx_motion_blend_args;
+
+MMDX_API mmdx_status mmdx_motion_set_blend_bones_time(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args,
+                                                      float *out_poses /* [NI][NB][MMDX_POSE_FLOATS] */);
+MMDX_API mmdx_status mmdx_motion_set_blend_morphs_time(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args,
+                                                       float *out_weights /* [NI][NM] */);
+/* One launch on parallel-FK skeletons of up to 2 048 bones (both clip ids, both clocks and the weight read once per workgroup, the
+ * blend in registers, the poses in LDS); skeletons with append bones / IK and larger ones take the blend into the set's pose
+ * scratch, then mmdx_skeleton_solve. */
+MMDX_API mmdx_status mmdx_skeleton_solve_motion_set_blend_time(mmdx_skeleton_t skeleton, mmdx_motion_set_t set, mmdx_model_t model,
+                                                               const mmdx_motion_blend_args *args,
+                                                               float *out_palettes /* [NI][NB][16] */);
+
 /* The same with bone morphs applied first: morph_weights[i][n_morphs] (or one shared row with
  * MMDX_WEIGHTS_SHARED; device pointer with MMDX_WEIGHTS_ON_DEVICE) are the raw per-frame morph rates, the
  * ones mmdx_deform_batched takes.  Bone-morph rotations go through SLerp, i.e. through the device's double

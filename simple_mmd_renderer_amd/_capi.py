@@ -161,6 +161,10 @@ SIGNATURES = {
                                                    C.c_void_p]),
     "mmdx_skeleton_solve_motion_set_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                         C.c_uint32, C.c_void_p]),
+    # (set, model, mmdx_motion_blend_args*, out) and (skeleton, set, model, mmdx_motion_blend_args*, out)
+    "mmdx_motion_set_blend_bones_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmdx_motion_set_blend_morphs_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmdx_skeleton_solve_motion_set_blend_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmdx_skeleton_solve_morphed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),
     "mmdx_skeleton_solve_pre": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,

@@ -21,7 +21,7 @@ LIB = os.environ.get("MMDX_BUILD_OUT") or os.path.join(HERE, "libmmdx.so")   # M
 SOURCES = ["api.cpp", "bench_api.cpp", "kernels.hip", "kernels_fast.hip", "launch_shape.cpp", "plan.cpp", "pmx.cpp", "pmd.cpp", "vmd.cpp", "error.cpp",
            "rig.cpp", "rig_api.cpp", "rig_kernels.hip"]
 HEADERS = ["kernels.hpp", "plan.hpp", "error.hpp", "vmd.hpp", "rig.hpp", "rig_kernels.hpp", "pmx.hpp", "graph_pin.hpp", "api_internal.hpp",
-           "motion_clock.hpp", "launch_shape.hpp", "lds_layout.hpp",
+           "motion_clock.hpp", "motion_blend.hpp", "launch_shape.hpp", "lds_layout.hpp",
            os.path.join("..", "..", "include", "mmdx.h"), os.path.join("..", "..", "include", "mmdx_bench.h")]
 ARCH = "gfx950"
 

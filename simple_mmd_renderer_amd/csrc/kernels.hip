@@ -21,6 +21,7 @@
 //   HBM-bound: ~24-32 B written per vertex-instance against ~100 VALU ops; no MFMA (gather of small
 //   mat x vec, <= 3 flop/B).
 #include "kernels.hpp"
+#include "motion_blend.hpp"
 #include "motion_clock.hpp"
 
 #include <type_traits>
@@ -1725,6 +1726,32 @@ __global__ __launch_bounds__(kThreads) void morph_track_eval_set_kernel(MorphTra
     t.out[idx] = w;
 }
 
+// Cross-fade between two clips of a set (mmdx_motion_set_blend_morphs_time; motion_blend.hpp).  The rate of one (clip, time) of a
+// blend call: what morph_track_eval_set_kernel stores for it -- eval_morph_rate itself on the clip's table and that side's times.
+template <class Clock>
+__device__ __forceinline__ float eval_clip_rate(MorphTrackParams t, uint32_t clip, uint32_t n_clips, const double *times, uint32_t m,
+                                                uint32_t i) {
+    if (clip >= n_clips) return 0.f;
+    t.key_off += size_t(clip) * (size_t(t.nm) + 1);
+    t.times = times;
+    return eval_morph_rate<Clock>(t, m, i);
+}
+
+// One thread per (instance, morph); weight, clip ids and times per lane.  A lane evaluates one clip -- a, or b when the row is B --
+// and only a lane that blends evaluates b as well, so an end-point row reads nothing of the other clip.
+template <class Clock>
+__global__ __launch_bounds__(kThreads) void morph_track_blend_set_kernel(const MorphTrackParams t, const BlendOperands o) {
+    const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
+    if (idx >= size_t(t.ni) * t.nm) return;
+    const uint32_t i = uint32_t(idx / t.nm), m = uint32_t(idx - size_t(i) * t.nm);
+    const float w = o.weights[i];
+    const uint32_t side = blend_side(w);
+    const bool first_b = side == kBlendB;
+    float r = eval_clip_rate<Clock>(t, (first_b ? o.clips_b : o.clips_a)[i], o.n_clips, first_b ? o.times_b : o.times_a, m, i);
+    if (side == kBlendMix) r = blend_rate(r, eval_clip_rate<Clock>(t, o.clips_b[i], o.n_clips, o.times_b, m, i), w);
+    t.out[idx] = r;
+}
+
 // ---- streaming copy / fill: the practical HBM ceiling printed next to the roofline ---------------
 // Every workgroup owns one contiguous 4 KiB chunk, workgroups in address order: the shape that
 // reached the highest store rate on MI355X in tools/archive/probes/bw_probe (a few-thousand-block grid-stride loop
@@ -2047,6 +2074,14 @@ hipError_t launch_morph_track_eval_set(const MorphTrackParams &t, const uint32_t
     const dim3 grid(uint32_t((n + kThreads - 1) / kThreads));
     if (t.times) hipLaunchKernelGGL(morph_track_eval_set_kernel<TimeClock>, grid, dim3(kThreads), 0, stream, t, clips, n_clips);
     else hipLaunchKernelGGL(morph_track_eval_set_kernel<FrameClock>, grid, dim3(kThreads), 0, stream, t, clips, n_clips);
+    return hipGetLastError();
+}
+
+hipError_t launch_morph_track_blend_set(const MorphTrackParams &t, const BlendOperands &o, hipStream_t stream) {
+    const size_t n = size_t(t.ni) * t.nm;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(morph_track_blend_set_kernel<TimeClock>, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
+                       t, o);
     return hipGetLastError();
 }
 

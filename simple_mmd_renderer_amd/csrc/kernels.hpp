@@ -138,6 +138,9 @@ hipError_t launch_flatten(const FlattenParams &p, hipStream_t stream);
 hipError_t launch_morph_track_eval(const MorphTrackParams &t, hipStream_t stream);
 // a motion set's morph side: t holds the concatenated tables, clips[ni] (device) the clip of every instance; ids >= n_clips give rate 0
 hipError_t launch_morph_track_eval_set(const MorphTrackParams &t, const uint32_t *clips, uint32_t n_clips, hipStream_t stream);
+struct BlendOperands;
+// the cross-fade between two clips of a set (motion_blend.hpp), morph side: rates of clip a at time a and clip b at time b, blended
+hipError_t launch_morph_track_blend_set(const MorphTrackParams &t, const BlendOperands &o, hipStream_t stream);
 hipError_t launch_copy(void *dst, const void *src, size_t bytes, hipStream_t stream);
 hipError_t launch_fill(void *dst, size_t bytes, hipStream_t stream);
 

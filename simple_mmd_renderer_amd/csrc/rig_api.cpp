@@ -13,6 +13,7 @@
 #include "error.hpp"
 #include "graph_pin.hpp"
 #include "kernels.hpp"
+#include "motion_blend.hpp"
 #include "rig.hpp"
 #include "rig_kernels.hpp"
 #include "vmd.hpp"
@@ -96,11 +97,12 @@ struct mmdx_motion_set_s {
     Buf key_off, key_frame, key_tr, key_rot, key_curve, lut;        // bone side
     Buf m_key_off, m_frames, m_weights;                             // morph side
     Buf clips_in, clock_in;                                         // host operands: 4 + 8 bytes per instance
+    Buf blend_in;                                                   // host operands of a blend call: 28 bytes per instance
     Buf poses, out;                                                 // the two-launch palette path's poses; results bound for the host
     GraphPin pin;                                                   // recorded graphs that hold these buffers' addresses
     std::vector<Buf *> all() {
         return {&key_off, &key_frame, &key_tr, &key_rot, &key_curve, &lut, &m_key_off, &m_frames, &m_weights, &clips_in, &clock_in,
-                &poses, &out};
+                &blend_in, &poses, &out};
     }
     mmdx_motion_set_s() {
         for (Buf *b : all()) b->pin = &pin;
@@ -188,6 +190,11 @@ static mmdx_status set_eval_morphs(mmdx_motion_set_t set, mmdx_model_t model, ui
                                    const void *clock, bool time, uint32_t flags, float *out_weights);
 static mmdx_status skeleton_solve_motion_set(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
                                              const uint32_t *clips, const void *clock, bool time, uint32_t flags, float *out_palettes);
+
+static mmdx_status set_blend_bones(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args, float *out_poses);
+static mmdx_status set_blend_morphs(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args, float *out_weights);
+static mmdx_status skeleton_solve_motion_set_blend(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model,
+                                                   const mmdx_motion_blend_args *args, float *out_palettes);
 
 extern "C" {
 
@@ -402,6 +409,21 @@ mmdx_status mmdx_skeleton_solve_motion_set(mmdx_skeleton_t s, mmdx_motion_set_t 
 mmdx_status mmdx_skeleton_solve_motion_set_time(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
                                                 const uint32_t *clips, const double *times, uint32_t flags, float *out_palettes) {
     return skeleton_solve_motion_set(s, set, model, n_instances, clips, times, true, flags, out_palettes);
+}
+
+mmdx_status mmdx_motion_set_blend_bones_time(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args,
+                                             float *out_poses) {
+    return set_blend_bones(set, model, args, out_poses);
+}
+
+mmdx_status mmdx_motion_set_blend_morphs_time(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args,
+                                              float *out_weights) {
+    return set_blend_morphs(set, model, args, out_weights);
+}
+
+mmdx_status mmdx_skeleton_solve_motion_set_blend_time(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model,
+                                                      const mmdx_motion_blend_args *args, float *out_palettes) {
+    return skeleton_solve_motion_set_blend(s, set, model, args, out_palettes);
 }
 
 }  // extern "C"
@@ -851,4 +873,177 @@ static mmdx_status skeleton_solve_motion_set(mmdx_skeleton_t s, mmdx_motion_set_
         HIP_TRY(wait_stream(st));                    // the borrowed host clip ids and clocks must be consumed before returning
     }
     return MMDX_OK;
+}
+
+// ---- cross-fade between two clips of a set (mmdx_motion_set_blend_*_time, mmdx_skeleton_solve_motion_set_blend_time) ---------------
+// Everything about a blend call that can be decided without the device, before the first HIP call: NULLs, struct_size, the
+// instance count, flag bits, the side the set was created without, and -- for host operands -- clip ids of both arrays, NaN
+// times and NaN weights.
+static mmdx_status blend_check_args(mmdx_motion_set_t set, bool bone_side, const mmdx_motion_blend_args *a, const float *out) {
+    if (!set || !a || !out) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (a->struct_size != sizeof(mmdx_motion_blend_args)) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_motion_blend_args.struct_size mismatch");
+    if (!a->clips_a || !a->clips_b || !a->times_a || !a->times_b || !a->weights || !a->n_instances)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    if (a->flags & ~uint32_t(MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    if (bone_side ? !set->host.has_bones : !set->host.has_morphs)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("this motion set was created without ") + (bone_side ? "bone" : "morph") + " motions");
+    if (a->flags & MMDX_TIMES_ON_DEVICE) return MMDX_OK;
+    const struct { const char *name; const uint32_t *clips; const double *times; } sides[2] = {{"a", a->clips_a, a->times_a},
+                                                                                                 {"b", a->clips_b, a->times_b}};
+    for (const auto &s : sides)
+        for (uint32_t i = 0; i < a->n_instances; ++i)
+            if (s.clips[i] >= set->host.n_clips && s.clips[i] != MMDX_CLIP_NONE)
+                return fail(MMDX_ERR_BAD_INDEX, std::string("clips_") + s.name + "[" + std::to_string(i) + "] = " + std::to_string(s.clips[i]) +
+                                                ": the set has " + std::to_string(set->host.n_clips) + " clips");
+    for (const auto &s : sides)
+        for (uint32_t i = 0; i < a->n_instances; ++i)
+            if (s.times[i] != s.times[i])
+                return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("times_") + s.name + "[" + std::to_string(i) + "] is NaN");
+    for (uint32_t i = 0; i < a->n_instances; ++i)
+        if (a->weights[i] != a->weights[i]) return fail(MMDX_ERR_INVALID_ARGUMENT, "weights[" + std::to_string(i) + "] is NaN");
+    return MMDX_OK;
+}
+
+// the five operand arrays -> device addresses.  MMDX_TIMES_ON_DEVICE covers all five; host operands go through the set's scratch
+// (times_a, times_b, clips_a, clips_b, weights laid end to end: 28 bytes per instance) in stream order.
+static mmdx_status blend_operands_in(mmdx_motion_set_t set, const mmdx_motion_blend_args *a, hipStream_t st, BlendOperands *o) {
+    o->clips_a = a->clips_a; o->clips_b = a->clips_b;
+    o->times_a = a->times_a; o->times_b = a->times_b;
+    o->weights = a->weights;
+    o->n_clips = set->host.n_clips;
+    if (a->flags & MMDX_TIMES_ON_DEVICE) return MMDX_OK;
+    const size_t n = a->n_instances;
+    HIP_TRY(set->blend_in.ensure(n * 28));
+    char *base = static_cast<char *>(set->blend_in.ptr);
+    const struct { const void *src; size_t off, bytes; } parts[5] = {{a->times_a, 0, n * 8},       {a->times_b, n * 8, n * 8},
+                                                                     {a->clips_a, n * 16, n * 4}, {a->clips_b, n * 20, n * 4},
+                                                                     {a->weights, n * 24, n * 4}};
+    for (const auto &p : parts) HIP_TRY(hipMemcpyAsync(base + p.off, p.src, p.bytes, hipMemcpyHostToDevice, st));
+    o->times_a = reinterpret_cast<const double *>(base);
+    o->times_b = reinterpret_cast<const double *>(base + n * 8);
+    o->clips_a = reinterpret_cast<const uint32_t *>(base + n * 16);
+    o->clips_b = reinterpret_cast<const uint32_t *>(base + n * 20);
+    o->weights = reinterpret_cast<const float *>(base + n * 24);
+    return MMDX_OK;
+}
+
+// results bound for the host are copied out and waited for; borrowed host operands must be consumed before returning
+static mmdx_status blend_finish(uint32_t flags, hipStream_t st, float *host_out, const float *dev_out, size_t out_bytes) {
+    if (!(flags & MMDX_OUT_ON_DEVICE)) {
+        if (out_bytes) HIP_TRY(hipMemcpyAsync(host_out, dev_out, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(wait_stream(st));
+    } else if (!(flags & MMDX_TIMES_ON_DEVICE)) {
+        HIP_TRY(wait_stream(st));
+    }
+    return MMDX_OK;
+}
+
+// mmdx_motion_set_blend_bones_time
+static mmdx_status set_blend_bones(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *a, float *out_poses) {
+    if (mmdx_status r = blend_check_args(set, true, a, out_poses)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const uint32_t on_device = MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
+    if (graph_recording() && ((a->flags & on_device) != on_device || set->device != device)) return fail(MMDX_ERR_INVALID_ARGUMENT, kSetRecording);
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    BoneTrackParams p = set_bone_params(set, a->n_instances);
+    BlendOperands o;
+    if (mmdx_status r = blend_operands_in(set, a, st, &o)) return r;
+    const size_t out_bytes = size_t(a->n_instances) * p.nb * MMDX_POSE_FLOATS * sizeof(float);
+    if (a->flags & MMDX_OUT_ON_DEVICE) {
+        p.out = out_poses;
+    } else {
+        HIP_TRY(set->out.ensure(out_bytes));
+        p.out = static_cast<float *>(set->out.ptr);
+    }
+    HIP_TRY(launch_bone_track_blend_set(p, o, st));
+    return blend_finish(a->flags, st, out_poses, p.out, out_bytes);
+}
+
+// mmdx_motion_set_blend_morphs_time
+static mmdx_status set_blend_morphs(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *a, float *out_weights) {
+    if (mmdx_status r = blend_check_args(set, false, a, out_weights)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const uint32_t on_device = MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
+    if (graph_recording() && ((a->flags & on_device) != on_device || set->device != device)) return fail(MMDX_ERR_INVALID_ARGUMENT, kSetRecording);
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    MorphTrackParams t;
+    t.key_off = static_cast<const uint32_t *>(set->m_key_off.ptr);
+    t.key_frames = static_cast<const uint32_t *>(set->m_frames.ptr);
+    t.key_weights = static_cast<const float *>(set->m_weights.ptr);
+    t.nm = set->host.nm; t.ni = a->n_instances;
+    t.frames = nullptr; t.times = nullptr;
+    BlendOperands o;
+    if (mmdx_status r = blend_operands_in(set, a, st, &o)) return r;
+    const size_t out_bytes = size_t(a->n_instances) * t.nm * sizeof(float);
+    if (a->flags & MMDX_OUT_ON_DEVICE) {
+        t.out = out_weights;
+    } else {
+        HIP_TRY(set->out.ensure(out_bytes));
+        t.out = static_cast<float *>(set->out.ptr);
+    }
+    HIP_TRY(launch_morph_track_blend_set(t, o, st));
+    return blend_finish(a->flags, st, out_weights, t.out, out_bytes);
+}
+
+// mmdx_skeleton_solve_motion_set_blend_time
+static mmdx_status skeleton_solve_motion_set_blend(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model,
+                                                   const mmdx_motion_blend_args *a, float *out_palettes) {
+    if (!s) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (mmdx_status r = blend_check_args(set, true, a, out_palettes)) return r;
+    if (set->host.bones.nb != s->plan.nb)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "the motion set was bound to " + std::to_string(set->host.bones.nb) +
+                                               " bones, the skeleton has " + std::to_string(s->plan.nb));
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const SkeletonPlan &pl = s->plan;
+    const uint32_t ni = a->n_instances;
+    const size_t pose_bytes = size_t(ni) * pl.nb * MMDX_POSE_FLOATS * sizeof(float);
+    if (pl.serial || size_t(pl.nb) * 32 > kMotionFkMaxLds) {
+        // append bones / IK (the ordered solver) or a skeleton too large for the LDS pose table: the blend track kernel into the
+        // set's scratch buffer, then the solve
+        if (graph_recording() && (set->poses.bytes < pose_bytes || set->device != device))
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "run the call once before recording: it sizes the motion set's pose buffer");
+        if (mmdx_status r = set_to_device(set, device)) return r;
+        HIP_TRY(set->poses.ensure(pose_bytes));
+        mmdx_motion_blend_args to_scratch = *a;
+        to_scratch.flags = (a->flags & MMDX_TIMES_ON_DEVICE) | MMDX_OUT_ON_DEVICE;
+        if (mmdx_status r = set_blend_bones(set, model, &to_scratch, static_cast<float *>(set->poses.ptr))) return r;
+        return mmdx_skeleton_solve(s, model, ni, static_cast<const float *>(set->poses.ptr),
+                                   MMDX_POSES_ON_DEVICE | (a->flags & MMDX_OUT_ON_DEVICE), out_palettes);
+    }
+    const uint32_t on_device = MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
+    if (graph_recording() && ((a->flags & on_device) != on_device || set->device != device || s->device != device))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory and the motion "
+                                               "set and the skeleton must have run on this device before");
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    if (mmdx_status r = skeleton_to_device(s, device)) return r;
+    graph_note_handle(model, &set->pin);
+    graph_note_handle(model, &s->pin);
+    const BoneTrackParams tp = set_bone_params(set, ni);
+    BlendOperands o;
+    if (mmdx_status r = blend_operands_in(set, a, st, &o)) return r;
+    const size_t out_bytes = size_t(ni) * pl.nb * 16 * sizeof(float);
+    SkeletonParams fp;
+    fp.morph = nullptr;
+    fp.poses = nullptr;
+    if (a->flags & MMDX_OUT_ON_DEVICE) {
+        fp.out = out_palettes;
+    } else {
+        HIP_TRY(s->out.ensure(out_bytes));
+        fp.out = static_cast<float *>(s->out.ptr);
+    }
+    fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
+    fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
+    fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
+    fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
+    fp.nb = pl.nb; fp.ni = ni;
+    HIP_TRY(launch_motion_fk_blend_set(tp, fp, o, st));
+    return blend_finish(a->flags, st, out_palettes, fp.out, out_bytes);
 }

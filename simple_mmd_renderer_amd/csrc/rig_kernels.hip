@@ -5,6 +5,7 @@
 // palettes are bit-identical to libmmd's and the deform kernel downstream stays bit-exact end to end.
 #include <hip/hip_runtime.h>
 
+#include "motion_blend.hpp"
 #include "motion_clock.hpp"
 #include "rig.hpp"
 #include "rig_kernels.hpp"
@@ -123,6 +124,38 @@ __global__ __launch_bounds__(kRigThreads) void bone_track_eval_set_kernel(const 
     const uint32_t clip = clips[i];
     float4 t = make_float4(0.f, 0.f, 0.f, 0.f), q = make_float4(0.f, 0.f, 0.f, 1.f);   // Poser::ResetPosing
     if (clip < n_clips) eval_bone_pose(clip_of(p, clip), bone, clock_of<Clock>(p.frames, p.times, i), t, q);
+    float4 *out = reinterpret_cast<float4 *>(p.out) + idx * 2;
+    out[0] = t;
+    out[1] = q;
+}
+
+// Cross-fade between two clips of a set (mmdx_motion_set_blend_bones_time; motion_blend.hpp).  The pose of one (clip, time) of a
+// blend call: what bone_track_eval_set_kernel stores for it -- eval_bone_pose itself, or the rest pose for an id outside the bank.
+template <class Clock>
+__device__ __forceinline__ void eval_clip_pose(const BoneTrackParams &p, uint32_t clip, uint32_t n_clips, const Clock clk, uint32_t bone,
+                                               float4 &t, float4 &q) {
+    t = make_float4(0.f, 0.f, 0.f, 0.f); q = make_float4(0.f, 0.f, 0.f, 1.f);   // Poser::ResetPosing
+    if (clip < n_clips) eval_bone_pose(clip_of(p, clip), bone, clk, t, q);
+}
+
+// One thread per (instance, bone), as above; weight, clip ids and clocks are per lane (a wave spans instances).  A lane evaluates
+// ONE clip -- a, or b when the weight says the row is B -- and only a lane that blends evaluates b as well: an end-point row is the
+// set call's row bit for bit and reads nothing of the other clip, neither its id and time nor its tables.
+template <class Clock>
+__global__ __launch_bounds__(kRigThreads) void bone_track_blend_set_kernel(const BoneTrackParams p, const BlendOperands o) {
+    const size_t idx = size_t(blockIdx.x) * kRigThreads + threadIdx.x;
+    if (idx >= size_t(p.ni) * p.nb) return;
+    const uint32_t i = uint32_t(idx / p.nb), bone = uint32_t(idx - size_t(i) * p.nb);
+    const float w = o.weights[i];
+    const uint32_t side = blend_side(w);
+    const bool first_b = side == kBlendB;
+    float4 t, q;
+    eval_clip_pose(p, (first_b ? o.clips_b : o.clips_a)[i], o.n_clips, clock_of<Clock>(nullptr, first_b ? o.times_b : o.times_a, i), bone, t, q);
+    if (side == kBlendMix) {
+        float4 tb, qb;
+        eval_clip_pose(p, o.clips_b[i], o.n_clips, clock_of<Clock>(nullptr, o.times_b, i), bone, tb, qb);
+        blend_pose(t, q, tb, qb, w);
+    }
     float4 *out = reinterpret_cast<float4 *>(p.out) + idx * 2;
     out[0] = t;
     out[1] = q;
@@ -261,6 +294,45 @@ __global__ __launch_bounds__(1024) void motion_fk_set_kernel(const BoneTrackPara
         if (t.out) {
             float4 *o = reinterpret_cast<float4 *>(t.out) + (size_t(i) * p.nb + b) * 2;
             o[0] = tr; o[1] = q;
+        }
+    }
+    __syncthreads();
+    for (uint32_t bone = threadIdx.x; bone < p.nb; bone += blockDim.x)
+        fk_bone(p, [&](uint32_t k) { return pose_lds[k]; }, i, bone, reinterpret_cast<float4 *>(p.out) + (size_t(i) * p.nb + bone) * 4);
+}
+
+// The cross-fade in one launch (mmdx_skeleton_solve_motion_set_blend_time): both clip ids, both clocks and the weight are read once
+// per workgroup (workgroup-uniform: scalar loads, a uniform branch).  The thread that owns a bone evaluates A -- or B when the row
+// is B -- evaluates B as well when the workgroup blends, and blends in registers (blend_pose); LDS holds the one blended pose per
+// bone, [nb][2] float4 as above.  eval_bone_pose, the barrier and fk_bone are the ones above.
+template <class Clock>
+__global__ __launch_bounds__(1024) void motion_fk_blend_set_kernel(const BoneTrackParams t0, const SkeletonParams p, const BlendOperands o) {
+    extern __shared__ float4 pose_lds[];                 // [nb][2]
+    const uint32_t i = blockIdx.x;
+    const float w = o.weights[i];
+    const uint32_t side = blend_side(w);
+    const bool first_b = side == kBlendB, mix = side == kBlendMix;
+    const uint32_t clip0 = (first_b ? o.clips_b : o.clips_a)[i];
+    const Clock clk0 = clock_of<Clock>(nullptr, first_b ? o.times_b : o.times_a, i);
+    uint32_t clip1 = 0xFFFFFFFFu;
+    Clock clk1 = clk0;
+    if (mix) {
+        clip1 = o.clips_b[i];
+        clk1 = clock_of<Clock>(nullptr, o.times_b, i);
+    }
+    for (uint32_t b = threadIdx.x; b < p.nb; b += blockDim.x) {
+        float4 tr, q;
+        eval_clip_pose(t0, clip0, o.n_clips, clk0, b, tr, q);
+        if (mix) {
+            float4 tb, qb;
+            eval_clip_pose(t0, clip1, o.n_clips, clk1, b, tb, qb);
+            blend_pose(tr, q, tb, qb, w);
+        }
+        pose_lds[2 * b] = tr;
+        pose_lds[2 * b + 1] = q;
+        if (t0.out) {
+            float4 *out = reinterpret_cast<float4 *>(t0.out) + (size_t(i) * p.nb + b) * 2;
+            out[0] = tr; out[1] = q;
         }
     }
     __syncthreads();
@@ -1280,6 +1352,23 @@ hipError_t launch_motion_fk_set(const BoneTrackParams &t, const SkeletonParams &
     const uint32_t threads = std::min<uint32_t>(1024u, (p.nb + 63u) / 64u * 64u);
     if (t.times) hipLaunchKernelGGL(motion_fk_set_kernel<TimeClock>, dim3(p.ni), dim3(threads), lds, stream, t, p, clips, n_clips);
     else hipLaunchKernelGGL(motion_fk_set_kernel<FrameClock>, dim3(p.ni), dim3(threads), lds, stream, t, p, clips, n_clips);
+    return hipGetLastError();
+}
+
+hipError_t launch_bone_track_blend_set(const BoneTrackParams &p, const BlendOperands &o, hipStream_t stream) {
+    const size_t n = size_t(p.ni) * p.nb;
+    if (n == 0) return hipSuccess;
+    const dim3 grid(uint32_t((n + kRigThreads - 1) / kRigThreads));
+    hipLaunchKernelGGL(bone_track_blend_set_kernel<TimeClock>, grid, dim3(kRigThreads), 0, stream, p, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_motion_fk_blend_set(const BoneTrackParams &t, const SkeletonParams &p, const BlendOperands &o, hipStream_t stream) {
+    if (p.ni == 0 || p.nb == 0) return hipSuccess;
+    const size_t lds = size_t(p.nb) * 32;
+    if (lds > kMotionFkMaxLds) return hipErrorInvalidValue;                  // callers check: the two-launch path takes over
+    const uint32_t threads = std::min<uint32_t>(1024u, (p.nb + 63u) / 64u * 64u);
+    hipLaunchKernelGGL(motion_fk_blend_set_kernel<TimeClock>, dim3(p.ni), dim3(threads), lds, stream, t, p, o);
     return hipGetLastError();
 }
 

@@ -18,6 +18,11 @@ hipError_t launch_motion_fk(const BoneTrackParams &t, const SkeletonParams &p, h
 hipError_t launch_bone_track_eval_set(const BoneTrackParams &p, const uint32_t *clips, uint32_t n_clips, hipStream_t stream);
 hipError_t launch_motion_fk_set(const BoneTrackParams &t, const SkeletonParams &p, const uint32_t *clips, uint32_t n_clips,
                                 hipStream_t stream);
+struct BlendOperands;
+// the cross-fade between two clips of a set (motion_blend.hpp): the same two with the five per-instance operand arrays of
+// mmdx_motion_blend_args in device memory; time clock only
+hipError_t launch_bone_track_blend_set(const BoneTrackParams &p, const BlendOperands &o, hipStream_t stream);
+hipError_t launch_motion_fk_blend_set(const BoneTrackParams &t, const SkeletonParams &p, const BlendOperands &o, hipStream_t stream);
 hipError_t launch_skeleton_ordered(const SerialParams &p, const uint8_t *round_coop /* host, [n_rounds] or nullptr */, hipStream_t stream);
 hipError_t launch_bone_morph(const BoneMorphParams &p, hipStream_t stream);
 hipError_t launch_physics_override(const PhysicsParams &p, hipStream_t stream);

@@ -372,6 +372,20 @@ public:
     void SeekFramePalettes(uint32_t n, const uint32_t *clips, const uint32_t *frames, float *out_palettes, bool on_device = false) {
         check(mmdx_skeleton_solve_motion_set(poser_.skeleton(), set_, poser_.handle(), n, clips, frames, flags(on_device), out_palettes));
     }
+    // A poser on its way from one motion to another: instance i is weights[i] of the way from clip clips_a[i] at times_a[i] to
+    // clip clips_b[i] at times_b[i] (lerp of the translations, NLerp of the rotations -- what libmmd does between two keys);
+    // below 1e-7 the row is clip a's and above 1 - 1e-7 clip b's, bit for bit, and only that clip is evaluated.
+    void BlendTimePalettes(uint32_t n, const uint32_t *clips_a, const double *times_a, const uint32_t *clips_b, const double *times_b,
+                           const float *weights, float *out_palettes, bool on_device = false) {
+        mmdx_motion_blend_args a;
+        a.struct_size = sizeof(a);
+        a.n_instances = n;
+        a.clips_a = clips_a; a.clips_b = clips_b;
+        a.times_a = times_a; a.times_b = times_b;
+        a.weights = weights;
+        a.flags = flags(on_device);
+        check(mmdx_skeleton_solve_motion_set_blend_time(poser_.skeleton(), set_, poser_.handle(), &a, out_palettes));
+    }
     // out_rates[i][morph] = the morph rates of instance i (what mmdx_deform_batched takes as per-instance weights)
     void SeekTimeMorphRates(uint32_t n, const uint32_t *clips, const double *times, float *out_rates, bool on_device = false) {
         check(mmdx_motion_set_eval_morphs_time(set_, poser_.handle(), n, clips, times, flags(on_device), out_rates));

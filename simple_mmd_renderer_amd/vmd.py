@@ -235,6 +235,27 @@ class MotionSetInfo(C.Structure):
                 ("n_bone_keys", C.c_uint32), ("n_morph_keys", C.c_uint32), ("n_curves", C.c_uint32)]
 
 
+class MotionBlendArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_instances", C.c_uint32), ("clips_a", C.c_void_p), ("clips_b", C.c_void_p),
+                ("times_a", C.c_void_p), ("times_b", C.c_void_p), ("weights", C.c_void_p), ("flags", C.c_uint32)]
+
+
+def blend_args_host(clips_a, times_a, clips_b, times_b, weights):
+    """mmdx_motion_blend_args over host arrays -> (args, the arrays it points into: keep them alive over the call)."""
+    keep = [np.ascontiguousarray(clips_a, np.uint32).reshape(-1), np.ascontiguousarray(clips_b, np.uint32).reshape(-1),
+            np.ascontiguousarray(times_a, np.float64).reshape(-1), np.ascontiguousarray(times_b, np.float64).reshape(-1),
+            np.ascontiguousarray(weights, np.float32).reshape(-1)]
+    if len({a.size for a in keep}) != 1:
+        raise ValueError("one clip a, time a, clip b, time b and weight per instance")
+    return MotionBlendArgs(C.sizeof(MotionBlendArgs), keep[0].size, *[a.ctypes.data for a in keep], 0), keep
+
+
+def blend_args_device(n_instances, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr):
+    """mmdx_motion_blend_args over five device arrays, the output on the device as well."""
+    return MotionBlendArgs(C.sizeof(MotionBlendArgs), n_instances, clips_a_ptr, clips_b_ptr, times_a_ptr, times_b_ptr, weights_ptr,
+                           TIMES_ON_DEVICE | api.OUT_ON_DEVICE)
+
+
 class MotionSet:
     """A bank of clips bound to one model (mmdx_motion_set_t): every instance of a crowd plays its own clip, clips[i], at its own
     frame or time.  bone_motions / morph_motions: sequences of BoneMotion / MorphMotion, one per clip, at least one of the two;
@@ -300,6 +321,36 @@ class MotionSet:
     def eval_morphs_time_device(self, n_instances: int, clips_ptr, times_ptr, out_ptr, model=None) -> None:
         """clips u32[NI], times f64[NI] (seconds) and out f32[NI][NM] resident in HBM."""
         self._device(api.lib().mmdx_motion_set_eval_morphs_time, n_instances, clips_ptr, times_ptr, out_ptr, model)
+
+    # -- cross-fade between two clips, per instance (mmdx_motion_set_blend_*_time) --------------------------------------
+    def _blend_host(self, fn, clips_a, times_a, clips_b, times_b, weights, row_shape, model):
+        args, keep = blend_args_host(clips_a, times_a, clips_b, times_b, weights)
+        out = np.empty((args.n_instances,) + row_shape, np.float32)
+        api.check(fn(self.h, model.h if model is not None else None, C.byref(args), out.ctypes.data))
+        return out
+
+    def blend_bones_time(self, clips_a, times_a, clips_b, times_b, weights, model=None) -> np.ndarray:
+        """Host convenience: per instance clip a at time a, clip b at time b (seconds) and the weight of b -> poses f32
+        [NI, NB, 8]: A below 1e-7, B above 1 - 1e-7, else lerp of the translations and NLerp of the rotations."""
+        return self._blend_host(api.lib().mmdx_motion_set_blend_bones_time, clips_a, times_a, clips_b, times_b, weights,
+                                (self.nb, POSE_FLOATS), model)
+
+    def blend_morphs_time(self, clips_a, times_a, clips_b, times_b, weights, model=None) -> np.ndarray:
+        """Host convenience: the same for morph rates -> f32 [NI, NM]."""
+        return self._blend_host(api.lib().mmdx_motion_set_blend_morphs_time, clips_a, times_a, clips_b, times_b, weights,
+                                (self.nm,), model)
+
+    def blend_bones_time_device(self, n_instances: int, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr, out_ptr,
+                                model=None) -> None:
+        """clips u32[NI] x 2, times f64[NI] x 2, weights f32[NI] and out f32[NI][NB][8] resident in HBM; asynchronous."""
+        args = blend_args_device(n_instances, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr)
+        api.check(api.lib().mmdx_motion_set_blend_bones_time(self.h, model.h if model is not None else None, C.byref(args), out_ptr))
+
+    def blend_morphs_time_device(self, n_instances: int, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr, out_ptr,
+                                 model=None) -> None:
+        """The same for morph rates: out f32[NI][NM] resident in HBM."""
+        args = blend_args_device(n_instances, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr)
+        api.check(api.lib().mmdx_motion_set_blend_morphs_time(self.h, model.h if model is not None else None, C.byref(args), out_ptr))
 
     def close(self):
         if getattr(self, "h", None):
@@ -494,6 +545,21 @@ class Skeleton:
         api.check(api.lib().mmdx_skeleton_solve_motion_set_time(self.h, motion_set.h, model.h if model is not None else None,
                                                                 n_instances, clips_ptr, times_ptr,
                                                                 TIMES_ON_DEVICE | api.OUT_ON_DEVICE, out_ptr))
+
+    def solve_motion_set_blend_time(self, motion_set: "MotionSet", clips_a, times_a, clips_b, times_b, weights, model=None) -> np.ndarray:
+        """Host convenience: the cross-fade of MotionSet.blend_bones_time solved -> palettes f32 [NI, NB, 16]."""
+        args, keep = blend_args_host(clips_a, times_a, clips_b, times_b, weights)
+        out = np.empty((args.n_instances, self.nb, 16), np.float32)
+        api.check(api.lib().mmdx_skeleton_solve_motion_set_blend_time(self.h, motion_set.h, model.h if model is not None else None,
+                                                                      C.byref(args), out.ctypes.data))
+        return out
+
+    def solve_motion_set_blend_time_device(self, motion_set: "MotionSet", n_instances: int, clips_a_ptr, times_a_ptr, clips_b_ptr,
+                                           times_b_ptr, weights_ptr, out_ptr, model=None) -> None:
+        """All five operand arrays and the palettes resident in HBM; asynchronous on the model's stream."""
+        args = blend_args_device(n_instances, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr)
+        api.check(api.lib().mmdx_skeleton_solve_motion_set_blend_time(self.h, motion_set.h, model.h if model is not None else None,
+                                                                      C.byref(args), out_ptr))
 
     def solve_device(self, n_instances: int, poses_ptr, out_ptr, model=None, weights_ptr=None, shared=False) -> None:
         """poses, palettes (and morph rates) resident in HBM; asynchronous on the model's stream."""
