@@ -3,7 +3,8 @@
  * NOT part of the drop-in boundary (include/mmdx.h): nothing in the reference corresponds to these.  They exist
  * for bench.py, tools/ and the GPU tests: HIP-event timers on a model's stream, per-kernel profiling of
  * mmdx_deform_batched, the streaming copy / fill / store-pattern ceilings printed next to the roofline
- * (SURVEY.md section 8d), and the re-read of the launch-shape override environment.  Same library, same status codes.
+ * (SURVEY.md section 8d), the re-read of the launch-shape override environment and the record of the last launch shape.  Same
+ * library, same status codes.
  */
 #ifndef MMDX_BENCH_H_INCLUDED
 #define MMDX_BENCH_H_INCLUDED
@@ -35,6 +36,35 @@ MMDX_API void mmdx_debug_reload_env(void);
 /* Which store flavour the kernel of the model's last mmdx_deform_batched call ran with: 0 = cached non-temporal stores, 1 =
  * write-through (mmdx.h, MMDX_OUT_STORES_*; 1 only where the launched kernel has that flavour). */
 MMDX_API mmdx_status mmdx_debug_last_store_policy(mmdx_model_t model, int32_t *write_through);
+/* The launch shape of the model's last successfully planned mmdx_deform_batched* call, as handed to the kernel: tests read it to
+ * prove that they ran the instantiation and the instances-per-workgroup they claim (small crowds plan group == 1 on their own;
+ * MMDX_GROUP forces more).  Read-only host state: nothing here reaches a kernel. */
+typedef enum mmdx_debug_kernel {
+    MMDX_DEBUG_KERNEL_NONE = 0,      /* no call yet, or a select call with an empty list */
+    MMDX_DEBUG_KERNEL_DEFORM = 1,    /* the tile kernel (deform_kernel) */
+    MMDX_DEBUG_KERNEL_PACK = 2,      /* MMDX_FUSED_PACK=1 */
+    MMDX_DEBUG_KERNEL_FRAME = 3      /* one frame of one model, latency-ordered */
+} mmdx_debug_kernel;
+typedef struct mmdx_debug_launch_shape {
+    uint32_t struct_size;            /* sizeof(mmdx_debug_launch_shape), set by the caller */
+    uint32_t kernel;                 /* mmdx_debug_kernel */
+    uint32_t threads;                /* lanes per workgroup */
+    uint32_t group;                  /* instances per workgroup */
+    uint32_t ngroups;                /* workgroups per tile: ceil(n_instances / group), of a select call ceil(n_ids / group);
+                                        0 for the frame kernel and when nothing was launched */
+    uint32_t lds;                    /* bytes of dynamic LDS */
+    uint32_t morph;                  /* 0 no morphs, 1 shared (separate morph pass), 2 shared (gathered in the kernel),
+                                        3 per-instance weights */
+    uint32_t layout;                 /* MMDX_OUT_* */
+    uint32_t f16, tile_order;        /* the model's MMDX_CREATE_F16_POSITIONS / MMDX_CREATE_TILE_ORDER */
+    uint32_t bounds, select;         /* the flavour of mmdx_deform_batched_bounds / _select */
+    uint32_t write_through;          /* as mmdx_debug_last_store_policy */
+    uint32_t interleave;             /* MMDX_INTERLEAVE as the kernel received it: instances dealt g * ngroups + grp (1) or
+                                        grp * group + g (0); read by the shared-rate and no-morph modes only */
+    uint32_t sel_interleave;         /* MMDX_SELECT_INTERLEAVE likewise, of a select call (0 otherwise) */
+    uint32_t reserved0;
+} mmdx_debug_launch_shape;
+MMDX_API mmdx_status mmdx_debug_last_launch_shape(mmdx_model_t model, mmdx_debug_launch_shape *out);
 /* What became of the model's shared morph passes so far (mmdx.h, MMDX_MORPH_UNCHANGED): launches that walked the morph table,
  * launches whose device-side comparison found the rates unchanged and skipped the walk, and calls whose host-side comparison
  * skipped the launch altogether.  Waits for the model's stream. */

@@ -65,6 +65,18 @@ class ModelInfo(C.Structure):
                 ("device_ordinal", C.c_uint32), ("flags", C.c_uint32), ("reserved0", C.c_uint32)]
 
 
+class DebugLaunchShape(C.Structure):
+    """mmdx_debug_launch_shape (include/mmdx_bench.h): the shape of a model's last deform launch."""
+    _fields_ = [("struct_size", C.c_uint32), ("kernel", C.c_uint32), ("threads", C.c_uint32), ("group", C.c_uint32),
+                ("ngroups", C.c_uint32), ("lds", C.c_uint32), ("morph", C.c_uint32), ("layout", C.c_uint32),
+                ("f16", C.c_uint32), ("tile_order", C.c_uint32), ("bounds", C.c_uint32), ("select", C.c_uint32),
+                ("write_through", C.c_uint32), ("interleave", C.c_uint32), ("sel_interleave", C.c_uint32),
+                ("reserved0", C.c_uint32)]
+
+
+DEBUG_KERNELS = ("none", "deform", "pack", "frame")      # mmdx_debug_kernel
+
+
 class MmdxError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"mmdx error {status} ({ERR_NAMES.get(status, '?')}): {message}")
@@ -105,6 +117,7 @@ SIGNATURES = {
     "mmdx_device_synchronize": (C.c_int32, []),
     "mmdx_debug_reload_env": (None, []),
     "mmdx_debug_last_store_policy": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mmdx_debug_last_launch_shape": (C.c_int32, [C.c_void_p, C.POINTER(DebugLaunchShape)]),
     "mmdx_debug_morph_pass_stats": (C.c_int32, [C.c_void_p, _u32p, _u32p, _u32p]),
     "mmdx_build_source_sha": (C.c_char_p, []),
     "mmdx_bench_copy": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, _f32p]),

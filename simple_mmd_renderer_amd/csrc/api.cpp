@@ -913,6 +913,29 @@ static mmdx_status copy_out(mmdx_model_t m, const mmdx_deform_args *a, const Out
     return MMDX_OK;
 }
 
+// What mmdx_debug_last_launch_shape reports: the planned shape and what launch_planned handed to the kernel of its kind
+static void record_launch_shape(mmdx_model_t m, const DeformCall &c, const LaunchShape &s, const DeformParams &dp) {
+    mmdx_debug_launch_shape &r = m->last_shape;
+    r = mmdx_debug_launch_shape{};
+    r.kernel = uint32_t(s.kernel);
+    const bool tiles = s.kernel == LaunchShape::kDeform || s.kernel == LaunchShape::kPack;
+    r.threads = s.kernel == LaunchShape::kFrame ? (launch_overrides().frame_threads == 128 ? 128u : 256u)
+                                                : (s.kernel == LaunchShape::kPack ? 512u /* kernels.hip kPkThreads */ : uint32_t(s.threads));
+    r.group = s.group;
+    // launch_deform's and launch_pack's grid: a select call covers the list's capacity (c.nwork)
+    r.ngroups = tiles ? ((s.kernel == LaunchShape::kPack ? c.ni : c.nwork) + s.group - 1) / s.group : 0u;
+    r.lds = uint32_t(s.lds);
+    r.morph = uint32_t(c.morph);
+    r.layout = c.layout;
+    r.f16 = m->plan.f16 ? 1u : 0u;
+    r.tile_order = dp.tile_order;
+    r.bounds = c.bounds ? 1u : 0u;
+    r.select = c.select ? 1u : 0u;
+    r.write_through = s.write_through ? 1u : 0u;
+    r.interleave = dp.interleave;
+    r.sel_interleave = dp.sel_interleave;
+}
+
 static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, float *out_bounds,
                                   const mmdx_instance_select *sel = nullptr) {
     CallPointers cp;
@@ -938,6 +961,7 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
     m->last_write_through = shape.write_through;
     float *bounds_dev = nullptr;
     if (mmdx_status s = launch_planned(m, call, shape, out_bounds, pev, dp, bounds_dev)) return s;
+    record_launch_shape(m, call, shape, dp);
     const bool host_inputs = !(a->flags & MMDX_PALETTE_ON_DEVICE) || (morph != kMorphNone && !(a->flags & MMDX_WEIGHTS_ON_DEVICE)) ||
                              (sel && !(sel->flags & MMDX_SELECT_ON_DEVICE) && sel->n_ids);
     return copy_out(m, a, route, cp.pitch, dp, out_bounds, bounds_dev, host_inputs);

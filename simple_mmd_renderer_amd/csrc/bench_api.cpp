@@ -1,6 +1,6 @@
 // bench_api.cpp -- the entry points of include/mmdx_bench.h: HIP-event timers on a model's stream, per-kernel profiling of
 // mmdx_deform_batched (the events themselves are recorded by api.cpp's deform call), the streaming copy / fill / store-pattern
-// ceilings printed next to the roofline, and the re-read of the launch-shape override environment.  NOT part of the drop-in
+// ceilings printed next to the roofline, the re-read of the launch-shape override environment and the record of the last launch shape.  NOT part of the drop-in
 // boundary: nothing in the reference corresponds to these (SURVEY.md 8b lists four calls); they serve bench.py, tools/ and tests.
 #include "api_internal.hpp"
 
@@ -80,6 +80,15 @@ void mmdx_debug_reload_env(void) { launch_overrides() = read_launch_overrides();
 mmdx_status mmdx_debug_last_store_policy(mmdx_model_t model, int32_t *write_through) {
     if (!model || !write_through) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
     *write_through = model->last_write_through ? 1 : 0;
+    return MMDX_OK;
+}
+
+mmdx_status mmdx_debug_last_launch_shape(mmdx_model_t model, mmdx_debug_launch_shape *out) {
+    if (!model || !out) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (out->struct_size != sizeof(mmdx_debug_launch_shape))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_debug_launch_shape.struct_size mismatch");
+    *out = model->last_shape;
+    out->struct_size = sizeof(mmdx_debug_launch_shape);
     return MMDX_OK;
 }
 

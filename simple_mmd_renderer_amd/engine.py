@@ -381,6 +381,17 @@ class DeformModel:
         api.check(api.lib().mmdx_debug_last_store_policy(self.h, C.byref(wt)))
         return "sc1 nt" if wt.value else "nt"
 
+    def last_launch_shape(self) -> dict:
+        """mmdx_debug_last_launch_shape: what the last deform call of this model launched -- kernel ('none' | 'deform' | 'pack' |
+        'frame'), threads, group (instances per workgroup), ngroups, lds, morph (kMorph*), layout, and the 0 / 1 fields f16,
+        tile_order, bounds, select, write_through, interleave, sel_interleave."""
+        s = api.DebugLaunchShape()
+        s.struct_size = C.sizeof(api.DebugLaunchShape)
+        api.check(api.lib().mmdx_debug_last_launch_shape(self.h, C.byref(s)))
+        d = {name: int(getattr(s, name)) for name, _ in api.DebugLaunchShape._fields_ if name not in ("struct_size", "reserved0")}
+        d["kernel"] = api.DEBUG_KERNELS[d["kernel"]]
+        return d
+
     def timer_start(self) -> None:
         api.check(api.lib().mmdx_timer_start(self.h))
 

@@ -184,12 +184,18 @@ def _verify(exp, a, b, layout, ni, rates, pals, shared, pitch, scale, what):
 
 @pytest.fixture
 def set_env(monkeypatch, hip_lib):
+    """The teardown removes EVERY variable the test set and only then re-reads the environment (monkeypatch restores it after
+    this fixture has finished: a reload before that would keep the overrides for the next test)."""
+    was_set = set()
+
     def _set(**env):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
+            was_set.add(k)
         hip_lib.mmdx_debug_reload_env()
     yield _set
-    monkeypatch.delenv("MMDX_FUSED_PACK", raising=False)
+    for k in was_set:
+        monkeypatch.delenv(k, raising=False)
     hip_lib.mmdx_debug_reload_env()
 
 
