@@ -60,7 +60,9 @@ extern "C" {
  *    mmdx_deform_args.out_instance_pitch (was reserved0), mmdx_model_output_pitch, mmdx_crowd_output_alloc_pitched.  A library
  *    without them rejects the flag bit as unknown, so a caller that needs pitched outputs fails loudly there.
  *    mmdx_deform_batched_bounds (a new entry point; mmdx_deform_args unchanged).
- *    mmdx_deform_batched_select with mmdx_instance_select (a new entry point and structure; mmdx_deform_args unchanged). */
+ *    mmdx_deform_batched_select with mmdx_instance_select (a new entry point and structure; mmdx_deform_args unchanged).
+ *    mmdx_cull_bounds with mmdx_cull_view / mmdx_cull_args and mmdx_cull_planes_from_matrix (new entry points and structures;
+ *    nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -343,6 +345,79 @@ typedef struct mmdx_instance_select {
 MMDX_API mmdx_status mmdx_deform_batched_select(mmdx_model_t model, const mmdx_deform_args *args,
                                                 const mmdx_instance_select *select, float *out_bounds /* [NI][6] or NULL */);
 MMDX_API mmdx_status mmdx_sync(mmdx_model_t model);
+
+/* ---- culling and LOD on the device: the boxes of mmdx_deform_batched_bounds -> the lists of mmdx_deform_batched_select ----------
+ * The middle of the GPU-resident crowd loop: bounds (one box per instance, device memory) are tested against up to 16 planes and
+ * sorted by distance into up to 4 level-of-detail lists, without a read-back.  List l is out_ids + l * list_stride with its length
+ * at out_counts + l: EXACTLY what mmdx_instance_select.ids / .count take (MMDX_SELECT_ON_DEVICE, n_ids = n_instances), so a frame is
+ * mmdx_deform_batched_bounds -> mmdx_cull_bounds -> mmdx_deform_batched_select, recorded once and replayed.
+ *
+ * The arithmetic is part of the contract (the library is built with -ffp-contract=off).  Every operation is binary32,
+ * unfused, in this order, with m(a, b) = a > b ? a : b; a row of bounds is {min x, min y, min z, max x, max y, max z}:
+ *   box      lo = min - margin, hi = max + margin, per component.
+ *   plane p  px = a >= 0 ? hi.x : lo.x, likewise py (b) and pz (c); s = ((a*px + b*py) + c*pz) + d.  The instance is culled iff
+ *            s < 0 for some p < n_planes.  A NaN s never culls: a row that was never written (NaN) stays visible, and so does every
+ *            instance against a NaN plane.
+ *   level    from the box WITHOUT the margin: dx = m(m(min.x - eye.x, eye.x - max.x), 0.0f), likewise dy, dz;
+ *            d2 = (dx*dx + dy*dy) + dz*dz; level = the number of k < n_lods - 1 with d2 >= lod_distance[k] * lod_distance[k]
+ *            (a NaN d2 gives level 0).
+ *   lists    list l holds the visible instances of level l IN ASCENDING INSTANCE ORDER (no atomics decide an order: two runs, and
+ *            a CPU restatement of the lines above, agree byte for byte); out_counts[l] is its length, out_counts[l] = 0 for
+ *            n_lods <= l < MMDX_CULL_MAX_LODS; entries of out_ids behind a count keep what they held; out_levels[i] (when given)
+ *            = the level of instance i, or MMDX_CULLED, for every i < n_instances.
+ * n_instances == 0 is valid and writes only the zero counts.
+ * The planes are used as given (not normalised): the box is grown by `margin` in world units, which moves a plane's verdict by
+ * margin * (|a| + |b| + |c|), i.e. in PLANE UNITS; planes from mmdx_cull_planes_from_matrix are not unit length, so a caller who
+ * wants `margin` to act as a distance to the plane normalises them first.  margin is how stale bounds are used safely: bounds of the previous frame,
+ * grown by how far an instance can move in one frame. */
+#define MMDX_CULL_MAX_PLANES 16
+#define MMDX_CULL_MAX_LODS    4
+#define MMDX_CULLED 0xFFFFFFFFu
+
+typedef struct mmdx_cull_view {       /* POD, 4-byte aligned, host OR device memory                                     */
+    float    planes[MMDX_CULL_MAX_PLANES][4]; /* (a,b,c,d); a point is inside when a*x+b*y+c*z+d >= 0                  */
+    uint32_t n_planes;                /* 0..16; 0 = nothing is culled                                                   */
+    uint32_t n_lods;                  /* 1..4 lists                                                                     */
+    float    eye[3];                  /* LOD distances are measured from here to the box                                */
+    float    margin;                  /* >= 0: the box is grown by this on every side before the plane test             */
+    float    lod_distance[MMDX_CULL_MAX_LODS - 1]; /* ascending; level = how many of the first n_lods-1 the box has reached */
+    uint32_t reserved0;               /* 0                                                                              */
+} mmdx_cull_view;
+
+enum { MMDX_CULL_VIEW_ON_DEVICE = 1u << 0 }; /* view is a device pointer, read when the kernel RUNS */
+
+typedef struct mmdx_cull_args {
+    uint32_t struct_size, flags;      /* = sizeof(mmdx_cull_args); MMDX_CULL_*, unknown bits: MMDX_ERR_INVALID_ARGUMENT */
+    uint32_t n_instances;             /* rows of bounds                                                                 */
+    uint32_t list_stride;             /* list l starts at out_ids + l * list_stride; >= n_instances                     */
+    const float *bounds;              /* device [NI][6], as mmdx_deform_batched_bounds writes it                        */
+    const mmdx_cull_view *view;
+    uint32_t *out_ids;                /* device [n_lods][list_stride]                                                   */
+    uint32_t *out_counts;             /* device [MMDX_CULL_MAX_LODS]; entries >= n_lods are written 0                   */
+    uint32_t *out_levels;             /* device [NI] or NULL: level of instance i, or MMDX_CULLED                       */
+} mmdx_cull_args;
+
+/* `model` supplies the device, the stream (the call is asynchronous on it, in order with the model's deform calls), the graph
+ * recording and, for crowds large enough to take two launches, a per-chunk count scratch that a recorded graph pins like the
+ * model's other scratch buffers (run the call once un-recorded first, see the graph section).
+ *  - A view in host memory (no flag) is validated in full before anything touches the device -- n_planes > 16, n_lods outside 1..4,
+ *    a negative or NaN margin, descending or NaN lod_distance[0 .. n_lods-2], reserved0 != 0: MMDX_ERR_INVALID_ARGUMENT -- and
+ *    then passed to the kernel BY VALUE: it may be changed or freed as soon as the call returns, and the call records into a graph
+ *    (every replay then uses the recorded view).  It is read by the CPU: pass device memory with the flag only.
+ *  - A view in device memory (MMDX_CULL_VIEW_ON_DEVICE) is read when the kernel runs: a recorded call reads it afresh at every
+ *    replay, so a frame is "write the new planes and eye into the view, launch".  It cannot be checked: on the device n_planes and
+ *    n_lods are clamped to their maxima (n_lods == 0 acts as 1) and a NaN or negative margin acts as the arithmetic says.  out_ids
+ *    must have room for the n_lods the view holds when the kernel runs (MMDX_CULL_MAX_LODS lists always suffice).
+ *  - list_stride < n_instances, a NULL bounds / view / out_ids / out_counts, device pointers that are not 4-byte aligned and a
+ *    struct_size mismatch are MMDX_ERR_INVALID_ARGUMENT; a MMDX_CREATE_HOST_ONLY model is MMDX_ERR_NO_DEVICE (after validation).
+ *    bounds and out_ids may be NULL when n_instances == 0. */
+MMDX_API mmdx_status mmdx_cull_bounds(mmdx_model_t model, const mmdx_cull_args *args);
+/* The six frustum planes of a clip-space transform, pure host code.  m is column-major as HandmadeMath's HMM_Mat4 stores it (and
+ * OpenGL): element (r, c) is m[c*4+r], clip = m * (x, y, z, 1).  With row_r = (m[r], m[4+r], m[8+r], m[12+r]) the planes are, in
+ * this order: left row3 + row0, right row3 - row0, bottom row3 + row1, top row3 - row1, near row3 + row2 (depth in [-w, w]) or
+ * row2 alone when depth_zero_to_one (depth in [0, w]), far row3 - row2.  Each component is one binary32 add or subtract; the planes
+ * are NOT normalised (see `margin` above). */
+MMDX_API mmdx_status mmdx_cull_planes_from_matrix(const float m[16], uint32_t depth_zero_to_one, float out_planes[6][4]);
 
 /* ---- plain device-memory helpers (thin hipMalloc / hipMemcpy wrappers) ----------------------- */
 /* So that C, C++ and ctypes callers can keep palettes and outputs resident in HBM without linking

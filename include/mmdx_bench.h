@@ -43,7 +43,10 @@ typedef enum mmdx_debug_kernel {
     MMDX_DEBUG_KERNEL_NONE = 0,      /* no call yet, or a select call with an empty list */
     MMDX_DEBUG_KERNEL_DEFORM = 1,    /* the tile kernel (deform_kernel) */
     MMDX_DEBUG_KERNEL_PACK = 2,      /* MMDX_FUSED_PACK=1 */
-    MMDX_DEBUG_KERNEL_FRAME = 3      /* one frame of one model, latency-ordered */
+    MMDX_DEBUG_KERNEL_FRAME = 3,     /* one frame of one model, latency-ordered */
+    MMDX_DEBUG_KERNEL_CULL = 4       /* mmdx_cull_bounds was the model's last planned call: threads = lanes per workgroup, group =
+                                        instances per chunk, ngroups = chunks, select = the form (1: one workgroup walks the chunks,
+                                        2: a count launch and a scatter launch, one workgroup per chunk); every other field 0 */
 } mmdx_debug_kernel;
 typedef struct mmdx_debug_launch_shape {
     uint32_t struct_size;            /* sizeof(mmdx_debug_launch_shape), set by the caller */

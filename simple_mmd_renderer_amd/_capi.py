@@ -22,6 +22,8 @@ PALETTE_ON_DEVICE, WEIGHTS_ON_DEVICE, OUT_ON_DEVICE, WEIGHTS_SHARED, MORPH_UNCHA
 OUT_STORES_WRITE_THROUGH, OUT_STORES_CACHED = 32, 64
 OUT_PITCHED = 128        # mmdx_deform_args.out_instance_pitch is read: instance i of the outputs starts at vertex i * pitch
 SELECT_ON_DEVICE = 1     # mmdx_instance_select.flags: ids and count are device pointers
+CULL_MAX_PLANES, CULL_MAX_LODS, CULLED = 16, 4, 0xFFFFFFFF      # mmdx_cull_view / mmdx_cull_bounds
+CULL_VIEW_ON_DEVICE = 1  # mmdx_cull_args.flags: view is a device pointer, read when the kernel runs
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
@@ -54,6 +56,20 @@ class InstanceSelect(C.Structure):
                 ("n_ids", C.c_uint32), ("reserved0", C.c_uint32)]
 
 
+class CullView(C.Structure):
+    """mmdx_cull_view: planes, eye and LOD distances of one mmdx_cull_bounds call (host or device memory)."""
+    _fields_ = [("planes", (C.c_float * 4) * CULL_MAX_PLANES), ("n_planes", C.c_uint32), ("n_lods", C.c_uint32),
+                ("eye", C.c_float * 3), ("margin", C.c_float), ("lod_distance", C.c_float * (CULL_MAX_LODS - 1)),
+                ("reserved0", C.c_uint32)]
+
+
+class CullArgs(C.Structure):
+    """mmdx_cull_args: bounds in, instance lists / counts / levels out (all device memory)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("list_stride", C.c_uint32),
+                ("bounds", C.c_void_p), ("view", C.c_void_p), ("out_ids", C.c_void_p), ("out_counts", C.c_void_p),
+                ("out_levels", C.c_void_p)]
+
+
 class ModelInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32),
                 ("n_vertices", C.c_uint32), ("n_bones", C.c_uint32), ("n_morphs", C.c_uint32),
@@ -74,7 +90,7 @@ class DebugLaunchShape(C.Structure):
                 ("reserved0", C.c_uint32)]
 
 
-DEBUG_KERNELS = ("none", "deform", "pack", "frame")      # mmdx_debug_kernel
+DEBUG_KERNELS = ("none", "deform", "pack", "frame", "cull")      # mmdx_debug_kernel
 
 
 class MmdxError(RuntimeError):
@@ -102,6 +118,8 @@ SIGNATURES = {
     "mmdx_deform_batched": (C.c_int32, [C.c_void_p, C.POINTER(DeformArgs)]),
     "mmdx_deform_batched_bounds": (C.c_int32, [C.c_void_p, C.POINTER(DeformArgs), C.c_void_p]),
     "mmdx_deform_batched_select": (C.c_int32, [C.c_void_p, C.POINTER(DeformArgs), C.POINTER(InstanceSelect), C.c_void_p]),
+    "mmdx_cull_bounds": (C.c_int32, [C.c_void_p, C.POINTER(CullArgs)]),
+    "mmdx_cull_planes_from_matrix": (C.c_int32, [_f32p, C.c_uint32, _f32p]),
     "mmdx_sync": (C.c_int32, [C.c_void_p]),
     "mmdx_timer_start": (C.c_int32, [C.c_void_p]),
     "mmdx_timer_stop": (C.c_int32, [C.c_void_p, _f32p]),

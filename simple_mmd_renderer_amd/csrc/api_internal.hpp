@@ -53,6 +53,7 @@ struct DevBuf {
 // The launch-shape overrides (launch_shape.hpp), as the environment sets them
 LaunchOverrides read_launch_overrides();
 LaunchOverrides &launch_overrides();
+void reload_cull_overrides();       // MMDX_CULL_FORM / MMDX_CULL_CHUNK (cull_api.cpp), re-read with the launch-shape overrides
 int env_int(const char *name, int dflt);
 // average ms of `iters` store-pattern launches on the default stream (after one warm-up launch); bench_api.cpp
 hipError_t time_store_pattern(void *a, void *b, uint32_t nv, uint32_t ni, uint32_t bpva, uint32_t bpvb, int iters, float *avg_ms,
@@ -82,6 +83,7 @@ struct mmdx_model_s {
     mmdx::DevBuf bnd;               // mmdx_deform_batched_bounds: partial bounds, then (host bounds) the [NI][6] result
     mmdx::DevBuf sel;               // mmdx_deform_batched_select with a host list: {live count, ids[n_ids]}
     std::vector<uint32_t> sel_host; // ... and its image on the host, the source of the upload
+    mmdx::DevBuf cull;              // mmdx_cull_bounds in two launches: per-chunk, per-level counts
     bool morphed_valid = false;     // `morphed` holds the result of a shared morph pass (MMDX_MORPH_UNCHANGED)
     std::vector<float> host_rates;  // ... and the host's copy of those rates when they came from host memory
     bool host_rates_valid = false;
@@ -94,7 +96,7 @@ struct mmdx_model_s {
     bool last_write_through = false;          // store flavour of the last crowd launch (mmdx_debug_last_store_policy)
     mmdx_debug_launch_shape last_shape{};     // ... and the rest of its shape (mmdx_debug_last_launch_shape); struct_size unused
     mmdx_model_s() {
-        for (mmdx::DevBuf *b : {&pal, &rates, &wslot, &morphed, &out_a, &out_b, &bnd, &sel}) b->pin = &pin;
+        for (mmdx::DevBuf *b : {&pal, &rates, &wslot, &morphed, &out_a, &out_b, &bnd, &sel, &cull}) b->pin = &pin;
     }
     // page-locked bounce buffer for small outputs bound for pageable host memory (see mmdx_deform_batched)
     void *bounce = nullptr, *bounce_dev = nullptr;  // host address, device-side address

@@ -75,7 +75,10 @@ mmdx_status mmdx_profile_collect(mmdx_model_t m, uint32_t *n_calls, float *skin_
     return MMDX_OK;
 }
 
-void mmdx_debug_reload_env(void) { launch_overrides() = read_launch_overrides(); }
+void mmdx_debug_reload_env(void) {
+    launch_overrides() = read_launch_overrides();
+    reload_cull_overrides();
+}
 
 mmdx_status mmdx_debug_last_store_policy(mmdx_model_t model, int32_t *write_through) {
     if (!model || !write_through) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");

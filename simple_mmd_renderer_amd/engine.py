@@ -49,6 +49,34 @@ def device_synchronize() -> None:
     api.check(api.lib().mmdx_device_synchronize())
 
 
+def planes_from_matrix(m, depth_zero_to_one: bool = False) -> np.ndarray:
+    """mmdx_cull_planes_from_matrix: the six frustum planes (left, right, bottom, top, near, far; f32 [6,4], not normalised) of a
+    column-major clip-space transform m (16 floats, element (r, c) at m[c*4+r], as HandmadeMath and OpenGL store it)."""
+    m = _c(m, np.float32).reshape(16)
+    out = np.empty((6, 4), np.float32)
+    api.check(api.lib().mmdx_cull_planes_from_matrix(_ptr(m, _f32p), 1 if depth_zero_to_one else 0, _ptr(out, _f32p)))
+    return out
+
+
+def make_cull_view(planes=(), eye=(0.0, 0.0, 0.0), lod_distance=(), margin: float = 0.0, n_planes=None, n_lods=None) -> api.CullView:
+    """An mmdx_cull_view from arrays: planes [n,4] (a,b,c,d), the eye, up to 3 ascending LOD distances (n_lods = their number + 1).
+    n_planes / n_lods override the counts as written into the structure (device views are not validated)."""
+    v = api.CullView()
+    pl = _c(planes, np.float32).reshape(-1, 4)
+    assert pl.shape[0] <= api.CULL_MAX_PLANES and len(lod_distance) <= api.CULL_MAX_LODS - 1
+    for p in range(pl.shape[0]):
+        for k in range(4):
+            v.planes[p][k] = pl[p, k]
+    v.n_planes = pl.shape[0] if n_planes is None else n_planes
+    v.n_lods = len(lod_distance) + 1 if n_lods is None else n_lods
+    for k in range(3):
+        v.eye[k] = eye[k]
+    v.margin = margin
+    for k, d in enumerate(lod_distance):
+        v.lod_distance[k] = d
+    return v
+
+
 class DeviceBuffer:
     """A hipMalloc'ed range owned through the C ABI's memory helpers."""
 
@@ -365,6 +393,25 @@ class DeformModel:
                                 select_count_ptr=C.addressof(cnt) if cnt is not None else None, n_select=int(ids.size),
                                 select_on_device=False)
 
+    def cull_bounds(self, bounds_buf, view, ni: int, ids_buf, counts_buf, levels_buf=None, list_stride=None) -> None:
+        """mmdx_cull_bounds: the boxes in bounds_buf (device f32 [ni][6], as mmdx_deform_batched_bounds writes them) against the
+        planes and LOD distances of `view` -- an api.CullView (host memory, validated, passed by value) or a DeviceBuffer holding
+        one (read when the kernel runs: a recorded call reads it afresh at every replay).  List l (visible instances of level l in
+        ascending order) goes to ids_buf at u32 offset l * list_stride (default ni), its length to counts_buf[l] (u32 [4]); these
+        are what deform_batched_raw takes as select_ptr / select_count_ptr.  levels_buf (optional, u32 [ni]): every instance's
+        level or api.CULLED.  Buffers are DeviceBuffers (or raw device addresses).  Asynchronous on the model's stream."""
+        dev = lambda b: getattr(b, "ptr", b)
+        a = api.CullArgs()
+        a.struct_size = C.sizeof(api.CullArgs)
+        a.n_instances = ni
+        a.list_stride = ni if list_stride is None else list_stride
+        a.bounds, a.out_ids, a.out_counts, a.out_levels = dev(bounds_buf), dev(ids_buf), dev(counts_buf), dev(levels_buf)
+        if isinstance(view, api.CullView):
+            a.flags, a.view = 0, C.addressof(view)
+        else:
+            a.flags, a.view = api.CULL_VIEW_ON_DEVICE, dev(view)
+        api.check(api.lib().mmdx_cull_bounds(self.h, C.byref(a)))
+
     def sync(self) -> None:
         api.check(api.lib().mmdx_sync(self.h))
 
@@ -383,7 +430,7 @@ class DeformModel:
 
     def last_launch_shape(self) -> dict:
         """mmdx_debug_last_launch_shape: what the last deform call of this model launched -- kernel ('none' | 'deform' | 'pack' |
-        'frame'), threads, group (instances per workgroup), ngroups, lds, morph (kMorph*), layout, and the 0 / 1 fields f16,
+        'frame' | 'cull': then group = instances per chunk, ngroups = chunks, select = the form), threads, group (instances per workgroup), ngroups, lds, morph (kMorph*), layout, and the 0 / 1 fields f16,
         tile_order, bounds, select, write_through, interleave, sel_interleave."""
         s = api.DebugLaunchShape()
         s.struct_size = C.sizeof(api.DebugLaunchShape)

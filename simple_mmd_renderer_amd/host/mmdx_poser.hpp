@@ -214,6 +214,27 @@ public:
                                    vertices.data()));
     }
 
+    // Culling and LOD of a crowd of this model on the device (mmdx.h, mmdx_cull_bounds): the boxes a mmdx_deform_batched_bounds call
+    // on handle() left in device memory against the planes and LOD distances of `view`; list l (visible instances of level l, ascending)
+    // goes to ids_dev + l * list_stride, its length to counts_dev[l] -- what mmdx_instance_select.ids / .count take.  A view in host
+    // memory is validated and passed by value; with view_on_device it is read when the kernel runs (a recorded call: at every replay).
+    // Asynchronous on the model's stream.  list_stride 0 = n_instances.
+    void CullBounds(const float *bounds_dev, uint32_t n_instances, const mmdx_cull_view *view, bool view_on_device, uint32_t *ids_dev,
+                    uint32_t *counts_dev, uint32_t *levels_dev = nullptr, uint32_t list_stride = 0) {
+        mmdx_cull_args a{};
+        a.struct_size = sizeof(a);
+        a.flags = view_on_device ? uint32_t(MMDX_CULL_VIEW_ON_DEVICE) : 0u;
+        a.n_instances = n_instances;
+        a.list_stride = list_stride ? list_stride : n_instances;
+        a.bounds = bounds_dev; a.view = view;
+        a.out_ids = ids_dev; a.out_counts = counts_dev; a.out_levels = levels_dev;
+        check(mmdx_cull_bounds(model_, &a));
+    }
+    // The six planes (left, right, bottom, top, near, far) of a column-major view-projection matrix, e.g. &HMM_Mat4.Elements[0][0]
+    static void PlanesFromMatrix(const float m[16], bool depth_zero_to_one, float out_planes[6][4]) {
+        check(mmdx_cull_planes_from_matrix(m, depth_zero_to_one ? 1u : 0u, out_planes));
+    }
+
     mmdx_model_t handle() const { return model_; }
     mmdx_skeleton_t skeleton() const { return skeleton_; }
     uint32_t vertex_count() const { return nv_; }
