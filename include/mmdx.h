@@ -62,7 +62,9 @@ extern "C" {
  *    mmdx_deform_batched_bounds (a new entry point; mmdx_deform_args unchanged).
  *    mmdx_deform_batched_select with mmdx_instance_select (a new entry point and structure; mmdx_deform_args unchanged).
  *    mmdx_cull_bounds with mmdx_cull_view / mmdx_cull_args and mmdx_cull_planes_from_matrix (new entry points and structures;
- *    nothing existing changes). */
+ *    nothing existing changes).
+ *    mmdx_palette_place with mmdx_place_args, MMDX_PLACE_ON_DEVICE and MMDX_PLACE_MATRIX (a new entry point, structure and two
+ *    flag bits no other call accepts; nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -839,6 +841,53 @@ MMDX_API mmdx_status mmdx_motion_set_blend_morphs_time(mmdx_motion_set_t set, mm
 MMDX_API mmdx_status mmdx_skeleton_solve_motion_set_blend_time(mmdx_skeleton_t skeleton, mmdx_motion_set_t set, mmdx_model_t model,
                                                                const mmdx_motion_blend_args *args,
                                                                float *out_palettes /* [NI][NB][16] */);
+
+/* ---- where every instance stands: palette x world matrix ----------------------------------------------------------------------
+ * Every palette the solves above write is in model space.  mmdx_palette_place multiplies each skinning matrix of instance i on the
+ * right by that instance's world matrix W[i], so the deform that follows, its bounds and mmdx_cull_bounds are all in world space:
+ *     out[i][b] = S[i][b] * W[i]                                  for every bone b of the model
+ * This is Matrix4x4<float>::operator* (L/util/math_impl.inl:984-1003): each of the 16 elements is the left-to-right four-term sum
+ * a_r1*w_1c + a_r2*w_2c + a_r3*w_3c + a_r4*w_4c in binary32, unfused (the library is built with -ffp-contract=off; models created
+ * with MMDX_CREATE_FAST_MATH run the same, uncontracted kernel).  W[i] comes from placements[i] in one of two forms:
+ *   pose form (default)            placements[i] is MMDX_POSE_FLOATS = 8 floats {tx, ty, tz, 0, qx, qy, qz, qw}, the layout of a local
+ *                                  bone pose.  W = q.ToRotateMatrix() (L/util/math_impl.inl:540-563) with row 4 then set to
+ *                                  {tx, ty, tz, 1}: exactly how libmmd builds a bone's local_matrix_ from its rotation and
+ *                                  translation (L/motion/poser_impl.inl:161-162) with no local offset -- a placement is "a world
+ *                                  bone".  The quaternion is NOT normalised (libmmd does not either); the fourth float is ignored.
+ *   matrix form (MMDX_PLACE_MATRIX) placements[i] is 16 floats in libmmd's v[0..15] order: a11, a12, ..., translation in v[12..14].
+ *                                  Byte for byte the reference viewer's g_state.model_matrix array (main.cpp:171, :1912-1930).
+ *                                  Used as given: scale and shear are the caller's business, and normals come out as the deform
+ *                                  makes them from such a palette.
+ * There are no short circuits: an identity placement is still multiplied, so a -0 element can become +0 and an infinite element
+ * times a zero of W gives NaN, as operator* does.  Results are bit-identical to libmmd's; only the sign and payload of a NaN are
+ * not part of the contract (they differ between CPUs and the GPU).
+ * The definition is a post-multiplication of the FINISHED skinning matrix.  It is not "the root's parent is a world bone": that
+ * would associate as L_c * (L_p * (L_root * W)) and differs in the last bit. */
+enum {
+    MMDX_PLACE_ON_DEVICE = 1u << 8,   /* placements is a device pointer, read when the kernel RUNS (else host, copied per call)    */
+    MMDX_PLACE_MATRIX = 1u << 9       /* placements[i] is a 16-float matrix (else an 8-float pose)                                 */
+};
+typedef struct mmdx_place_args {
+    uint32_t struct_size;      /* = sizeof(mmdx_place_args)                                                                       */
+    uint32_t flags;            /* MMDX_PALETTE_ON_DEVICE | MMDX_PLACE_ON_DEVICE | MMDX_OUT_ON_DEVICE | MMDX_PLACE_MATRIX; any other
+                                  bit: MMDX_ERR_INVALID_ARGUMENT                                                                   */
+    uint32_t n_instances;
+    uint32_t reserved0;        /* must be 0                                                                                       */
+    const float *palettes;     /* [NI][NB][16], NB = the model's bone count                                                       */
+    const float *placements;   /* [NI][8] or, with MMDX_PLACE_MATRIX, [NI][16]                                                    */
+    float *out_palettes;       /* [NI][NB][16]; may be the same pointer as palettes                                               */
+} mmdx_place_args;
+/* `model` supplies the bone count, the device and the stream: the call is asynchronous on it, in order with the model's solve and
+ * deform calls, and records into mmdx_graph_begin / _end (every operand in device memory then; a recorded call reads palettes AND
+ * placements afresh at every replay, so moving the crowd is "rewrite the placement array, launch").
+ *  - out_palettes == palettes (in place) is allowed: every lane reads all it needs of a row before it writes that row.  Any other
+ *    overlap of the two ranges, and placements overlapping out_palettes, are MMDX_ERR_INVALID_ARGUMENT.
+ *  - An operand without its *_ON_DEVICE flag is host memory, copied per call through scratch of the model as mmdx_skeleton_solve
+ *    does, and the call returns when the work is done.  The designed path is all three in device memory.
+ *  - Device palettes / out_palettes must be 16-byte aligned (every device allocation is), device placements 4-byte aligned.
+ *  - n_instances == 0 is MMDX_OK and launches nothing.  NULL model / args / pointers, a struct_size mismatch, an unknown flag bit and
+ *    reserved0 != 0 are MMDX_ERR_INVALID_ARGUMENT; a MMDX_CREATE_HOST_ONLY model is MMDX_ERR_NO_DEVICE (after validation). */
+MMDX_API mmdx_status mmdx_palette_place(mmdx_model_t model, const mmdx_place_args *args);
 
 /* The same with bone morphs applied first: morph_weights[i][n_morphs] (or one shared row with
  * MMDX_WEIGHTS_SHARED; device pointer with MMDX_WEIGHTS_ON_DEVICE) are the raw per-frame morph rates, the

@@ -24,6 +24,9 @@ OUT_PITCHED = 128        # mmdx_deform_args.out_instance_pitch is read: instance
 SELECT_ON_DEVICE = 1     # mmdx_instance_select.flags: ids and count are device pointers
 CULL_MAX_PLANES, CULL_MAX_LODS, CULLED = 16, 4, 0xFFFFFFFF      # mmdx_cull_view / mmdx_cull_bounds
 CULL_VIEW_ON_DEVICE = 1  # mmdx_cull_args.flags: view is a device pointer, read when the kernel runs
+PLACE_ON_DEVICE, PLACE_MATRIX = 256, 512     # mmdx_place_args.flags (with PALETTE_ON_DEVICE / OUT_ON_DEVICE): placements is a device
+#                                              pointer; placements[i] is a 16-float matrix instead of an 8-float pose
+POSE_FLOATS = 8          # MMDX_POSE_FLOATS: translation xyz, 0, quaternion xyzw
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
@@ -68,6 +71,12 @@ class CullArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("list_stride", C.c_uint32),
                 ("bounds", C.c_void_p), ("view", C.c_void_p), ("out_ids", C.c_void_p), ("out_counts", C.c_void_p),
                 ("out_levels", C.c_void_p)]
+
+
+class PlaceArgs(C.Structure):
+    """mmdx_place_args: palettes x per-instance world matrices (mmdx_palette_place)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("reserved0", C.c_uint32),
+                ("palettes", C.c_void_p), ("placements", C.c_void_p), ("out_palettes", C.c_void_p)]
 
 
 class ModelInfo(C.Structure):
@@ -120,6 +129,7 @@ SIGNATURES = {
     "mmdx_deform_batched_select": (C.c_int32, [C.c_void_p, C.POINTER(DeformArgs), C.POINTER(InstanceSelect), C.c_void_p]),
     "mmdx_cull_bounds": (C.c_int32, [C.c_void_p, C.POINTER(CullArgs)]),
     "mmdx_cull_planes_from_matrix": (C.c_int32, [_f32p, C.c_uint32, _f32p]),
+    "mmdx_palette_place": (C.c_int32, [C.c_void_p, C.POINTER(PlaceArgs)]),
     "mmdx_sync": (C.c_int32, [C.c_void_p]),
     "mmdx_timer_start": (C.c_int32, [C.c_void_p]),
     "mmdx_timer_stop": (C.c_int32, [C.c_void_p, _f32p]),

@@ -84,6 +84,7 @@ struct mmdx_model_s {
     mmdx::DevBuf sel;               // mmdx_deform_batched_select with a host list: {live count, ids[n_ids]}
     std::vector<uint32_t> sel_host; // ... and its image on the host, the source of the upload
     mmdx::DevBuf cull;              // mmdx_cull_bounds in two launches: per-chunk, per-level counts
+    mmdx::DevBuf place_in, place_w, place_out;   // mmdx_palette_place with host operands: palettes, placements, result
     bool morphed_valid = false;     // `morphed` holds the result of a shared morph pass (MMDX_MORPH_UNCHANGED)
     std::vector<float> host_rates;  // ... and the host's copy of those rates when they came from host memory
     bool host_rates_valid = false;
@@ -96,7 +97,7 @@ struct mmdx_model_s {
     bool last_write_through = false;          // store flavour of the last crowd launch (mmdx_debug_last_store_policy)
     mmdx_debug_launch_shape last_shape{};     // ... and the rest of its shape (mmdx_debug_last_launch_shape); struct_size unused
     mmdx_model_s() {
-        for (mmdx::DevBuf *b : {&pal, &rates, &wslot, &morphed, &out_a, &out_b, &bnd, &sel, &cull}) b->pin = &pin;
+        for (mmdx::DevBuf *b : {&pal, &rates, &wslot, &morphed, &out_a, &out_b, &bnd, &sel, &cull, &place_in, &place_w, &place_out}) b->pin = &pin;
     }
     // page-locked bounce buffer for small outputs bound for pageable host memory (see mmdx_deform_batched)
     void *bounce = nullptr, *bounce_dev = nullptr;  // host address, device-side address

@@ -412,6 +412,30 @@ class DeformModel:
             a.flags, a.view = api.CULL_VIEW_ON_DEVICE, dev(view)
         api.check(api.lib().mmdx_cull_bounds(self.h, C.byref(a)))
 
+    def place_palettes(self, n_instances: int, palettes_ptr, placements_ptr, out_ptr, flags: int) -> None:
+        """mmdx_palette_place, the raw form: out[i][b] = palettes[i][b] * W[i] for the n_instances x NB skinning matrices at
+        palettes_ptr, W[i] from the 8-float pose {tx, ty, tz, 0, qx, qy, qz, qw} (or, with api.PLACE_MATRIX, the 16-float matrix)
+        at placements_ptr + i.  flags: api.PALETTE_ON_DEVICE | api.PLACE_ON_DEVICE | api.OUT_ON_DEVICE say which of the three
+        addresses are device memory (the others are host memory, copied inside the call) | api.PLACE_MATRIX.  out_ptr may equal
+        palettes_ptr.  With all three on the device the call is asynchronous on the model's stream and records into a graph."""
+        a = api.PlaceArgs()
+        a.struct_size = C.sizeof(api.PlaceArgs)
+        a.flags, a.n_instances = flags, n_instances
+        a.palettes, a.placements, a.out_palettes = palettes_ptr, placements_ptr, out_ptr
+        api.check(api.lib().mmdx_palette_place(self.h, C.byref(a)))
+
+    def place(self, palettes, placements) -> np.ndarray:
+        """Host arrays in, host array out (copies + sync inside the call): palettes [NI,NB,16] and placements [NI,8] (poses) or
+        [NI,16] / [NI,4,4] (matrices, translation in elements 12..14) -> the placed palettes [NI,NB,16]."""
+        pal = _c(palettes, np.float32).reshape(-1, self.nb, 16)
+        ni = pal.shape[0]
+        pl = _c(placements, np.float32).reshape(ni, -1)
+        if pl.shape[1] not in (api.POSE_FLOATS, 16):
+            raise ValueError("placements must be [NI,8] poses or [NI,16] matrices")
+        out = np.empty_like(pal)
+        self.place_palettes(ni, pal.ctypes.data, pl.ctypes.data, out.ctypes.data, api.PLACE_MATRIX if pl.shape[1] == 16 else 0)
+        return out
+
     def sync(self) -> None:
         api.check(api.lib().mmdx_sync(self.h))
 

@@ -407,6 +407,20 @@ public:
         a.flags = flags(on_device);
         check(mmdx_skeleton_solve_motion_set_blend_time(poser_.skeleton(), set_, poser_.handle(), &a, out_palettes));
     }
+    // Where every instance stands (mmdx.h, mmdx_palette_place): out_palettes[i][bone] = palettes[i][bone] * W[i], W[i] from the pose
+    // {tx, ty, tz, 0, qx, qy, qz, qw} at placements + 8 * i ("a world bone") or, with matrix = true, the 16 floats at placements +
+    // 16 * i -- the layout of the viewer's g_state.model_matrix.  out_palettes may be palettes (in place).  Host arrays by default;
+    // with on_device = true all three are device memory and the call is asynchronous on the poser's stream.
+    void PlacePalettes(uint32_t n, const float *palettes, const float *placements, float *out_palettes, bool matrix = false,
+                       bool on_device = false) {
+        mmdx_place_args a{};
+        a.struct_size = sizeof(a);
+        a.flags = (on_device ? uint32_t(MMDX_PALETTE_ON_DEVICE | MMDX_PLACE_ON_DEVICE | MMDX_OUT_ON_DEVICE) : 0u) |
+                  (matrix ? uint32_t(MMDX_PLACE_MATRIX) : 0u);
+        a.n_instances = n;
+        a.palettes = palettes; a.placements = placements; a.out_palettes = out_palettes;
+        check(mmdx_palette_place(poser_.handle(), &a));
+    }
     // out_rates[i][morph] = the morph rates of instance i (what mmdx_deform_batched takes as per-instance weights)
     void SeekTimeMorphRates(uint32_t n, const uint32_t *clips, const double *times, float *out_rates, bool on_device = false) {
         check(mmdx_motion_set_eval_morphs_time(set_, poser_.handle(), n, clips, times, flags(on_device), out_rates));

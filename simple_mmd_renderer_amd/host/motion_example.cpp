@@ -43,6 +43,11 @@ static int crowd(int argc, char **argv) {
     const uint64_t h = checksum(palettes.data(), palettes.size() * 4) * 31 + checksum(rates.data(), rates.size() * 4);
     std::printf("crowd=%u clips=%u nb=%u nm=%u checksum=%016llx\n", ni, nc, poser->bone_count(), poser->morph_count(),
                 (unsigned long long)h);
+    // where every instance stands: 12 units apart along x, unrotated -- one pose {tx, ty, tz, 0, qx, qy, qz, qw} per instance
+    std::vector<float> where(size_t(ni) * 8, 0.f), placed(palettes.size());
+    for (uint32_t i = 0; i < ni; ++i) { where[8 * i] = 12.f * float(i); where[8 * i + 7] = 1.f; }
+    set.PlacePalettes(ni, palettes.data(), where.data(), placed.data());
+    std::fprintf(stderr, "placed checksum=%016llx\n", (unsigned long long)checksum(placed.data(), placed.size() * 4));
     return 0;
 }
 
