@@ -64,7 +64,9 @@ extern "C" {
  *    mmdx_cull_bounds with mmdx_cull_view / mmdx_cull_args and mmdx_cull_planes_from_matrix (new entry points and structures;
  *    nothing existing changes).
  *    mmdx_palette_place with mmdx_place_args, MMDX_PLACE_ON_DEVICE and MMDX_PLACE_MATRIX (a new entry point, structure and two
- *    flag bits no other call accepts; nothing existing changes). */
+ *    flag bits no other call accepts; nothing existing changes).
+ *    mmdx_palette_bounds with mmdx_palette_bounds_args, and mmdx_model_get_bone_boxes with mmdx_bone_box_info (two new entry points
+ *    and structures; mmdx_model_info, mmdx_deform_args and every existing call are unchanged). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -888,6 +890,74 @@ typedef struct mmdx_place_args {
  *  - n_instances == 0 is MMDX_OK and launches nothing.  NULL model / args / pointers, a struct_size mismatch, an unknown flag bit and
  *    reserved0 != 0 are MMDX_ERR_INVALID_ARGUMENT; a MMDX_CREATE_HOST_ONLY model is MMDX_ERR_NO_DEVICE (after validation). */
 MMDX_API mmdx_status mmdx_palette_place(mmdx_model_t model, const mmdx_place_args *args);
+
+/* ---- a box per instance BEFORE the deform: bone boxes x palette ---------------------------------------------------------------
+ * mmdx_deform_batched_bounds gives the box of the vertices it wrote, so a cull that uses it tests last frame's box, and an instance
+ * that is not deformed keeps an old one.  mmdx_palette_bounds gives a conservative box of the CURRENT frame from the palette alone
+ * (NI x n_boxes matrices instead of NI x NV vertices), so the loop is solve -> place -> palette bounds -> cull -> select-deform.
+ *
+ * The table (built once by mmdx_model_create, on every model).  From the skin as mmdx_model_get_skin returns it and the base
+ * positions and morph offsets as the kernels read them (binary16 widened for MMDX_CREATE_F16_POSITIONS).  Bone b is USED by vertex
+ * v: BDEF1 id0; BDEF2 id0 iff w != 0 and id1 iff 1.0f - w != 0; BDEF4 id_k iff w_k != 0.  One row per used bone, ascending:
+ *   lo, hi   min / max of the base positions of its vertices;
+ *   reach    max over its vertices of R(v), R(v)[axis] = the sum of |offset[axis]| over the vertex-morph entries on v after group
+ *            expansion (one per slot application, no rate), summed in double, rounded to float, one nextafter towards +inf.
+ * max_vertex_entries = the most such entries on one vertex; weight_sum_dev = max_v |s_v - 1| with s_v the weight sum as applied, in
+ * double (BDEF1 1; BDEF2 double(w) + double(1.0f - w); BDEF4 the sum of the four), rounded to float, one nextafter up;
+ * eps = float((32 + max_vertex_entries) * 2^-24) + weight_sum_dev (a float addition; DESIGN.md 6.8 derives it); n_nonconvex = the
+ * vertices with a negative applied weight (BDEF4 w_k < 0; BDEF2 w < 0 or w > 1).
+ *
+ * The arithmetic is part of the contract.  Everything is binary32, unfused, in this order (models created with
+ * MMDX_CREATE_FAST_MATH run the same, uncontracted kernel), with min(a, b) = b < a ? b : a and max(a, b) = a < b ? b : a,
+ * ms = morph_scale, M = palettes[i][bone] (translation in M[3][0..2]).  For every table row and output axis j:
+ *   L = lo - reach*ms          H = hi + reach*ms                                  (per component)
+ *   pkL = L[k]*M[k][j]         pkH = H[k]*M[k][j]                                 k = 0, 1, 2
+ *   mn = ((min(p0L,p0H) + min(p1L,p1H)) + min(p2L,p2H)) + M[3][j]
+ *   mx = ((max(p0L,p0H) + max(p1L,p1H)) + max(p2L,p2H)) + M[3][j]
+ *   a  = ((max(|p0L|,|p0H|) + max(|p1L|,|p1H|)) + max(|p2L|,|p2H|)) + |M[3][j]|
+ *   pad = a*eps                blo = mn - pad             bhi = mx + pad
+ * Row i of out_bounds is the fold of blo (minimum) and bhi (maximum) over all table rows in the total order the deform bounds use
+ * (-0 < +0), so it does not depend on any reduction order; each of the six components is then multiplied by pos_scale.  Layout
+ * {min x, min y, min z, max x, max y, max z}, as mmdx_deform_batched_bounds writes and mmdx_cull_bounds reads.  If any blo or bhi of
+ * an instance is NaN the whole row is six quiet NaNs, and so is every row when the table is empty: a broken palette stays visible
+ * to the cull ("a NaN never culls").  Infinities go through the arithmetic as written (an infinite translation gives inf - inf).
+ *
+ * The guarantee.  If every applied weight of the model is >= 0 (n_nonconvex == 0; the call refuses other models), every slot weight
+ * of instance i is <= morph_scale (slot weights are the morph rates times the group chains, mmdx_model_slot_weights; 0 when no morph
+ * is in use) and the palette is finite, then row i contains every position mmdx_deform_batched* writes for instance i from the same
+ * palette and pos_scale in the float32 layouts (MMDX_OUT_SOA, MMDX_OUT_VERTEX32), in the bit-exact and the fast-math build alike.
+ * Limits: binary16 positions (MMDX_OUT_SOA_POS16) are rounded after the fact and can exceed the box by half a binary16 ulp -- give
+ * mmdx_cull_view.margin that much.  The box is conservative, not tight: it is the union of the bones' transformed boxes (a rotated
+ * box's box is larger than the rotated points' box, and a bone's box holds every vertex the bone touches at any weight), grown by
+ * reach * morph_scale on every side whichever morphs are actually in use. */
+typedef struct mmdx_bone_box_info {
+    uint32_t struct_size, n_boxes, n_nonconvex, max_vertex_entries;
+    float eps, weight_sum_dev;
+    uint32_t reserved0[2];
+} mmdx_bone_box_info;
+/* Works on MMDX_CREATE_HOST_ONLY models.  bones [n_boxes] and boxes [n_boxes][9] = lo xyz, hi xyz, reach xyz may be NULL (call once
+ * for n_boxes, then again with arrays). */
+MMDX_API mmdx_status mmdx_model_get_bone_boxes(mmdx_model_t model, mmdx_bone_box_info *info, uint32_t *bones, float *boxes);
+
+typedef struct mmdx_palette_bounds_args {
+    uint32_t struct_size, flags;      /* MMDX_PALETTE_ON_DEVICE | MMDX_OUT_ON_DEVICE; any other bit is refused                  */
+    uint32_t n_instances, reserved0;  /* reserved0 must be 0                                                                    */
+    const float *palettes;            /* [NI][NB][16], 16-byte aligned on the device                                            */
+    float *out_bounds;                /* [NI][6]                                                                                */
+    float pos_scale;                  /* finite, > 0: the args.pos_scale of the deform it stands in for                         */
+    float morph_scale;                /* finite, >= 0: upper bound of every slot weight; 0 = no morphs in use                   */
+} mmdx_palette_bounds_args;
+/* `model` supplies the table, the device and the stream: the call is asynchronous on it, in order with the model's solve, place,
+ * cull and deform calls, and records into mmdx_graph_begin / _end (both operands in device memory then; a recorded call reads the
+ * palettes afresh at every replay).
+ *  - An operand without its *_ON_DEVICE flag is host memory, copied per call through scratch of the model in stream order, and the
+ *    call returns when the work is done.
+ *  - n_instances == 0 is MMDX_OK and launches nothing.  NULL model / args / pointers, a struct_size mismatch, an unknown flag bit,
+ *    reserved0 != 0, a pos_scale that is not finite and > 0, a morph_scale that is not finite and >= 0, palettes overlapping
+ *    out_bounds, device palettes that are not 16-byte aligned and a device out_bounds that is not 4-byte aligned are
+ *    MMDX_ERR_INVALID_ARGUMENT.  Then a model with n_nonconvex > 0 is MMDX_ERR_UNSUPPORTED (the message names the count), and only
+ *    then a MMDX_CREATE_HOST_ONLY model is MMDX_ERR_NO_DEVICE. */
+MMDX_API mmdx_status mmdx_palette_bounds(mmdx_model_t model, const mmdx_palette_bounds_args *args);
 
 /* The same with bone morphs applied first: morph_weights[i][n_morphs] (or one shared row with
  * MMDX_WEIGHTS_SHARED; device pointer with MMDX_WEIGHTS_ON_DEVICE) are the raw per-frame morph rates, the

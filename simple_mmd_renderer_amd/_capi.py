@@ -79,6 +79,18 @@ class PlaceArgs(C.Structure):
                 ("palettes", C.c_void_p), ("placements", C.c_void_p), ("out_palettes", C.c_void_p)]
 
 
+class BoneBoxInfo(C.Structure):
+    """mmdx_bone_box_info: the scalars of a model's bone-box table (mmdx_model_get_bone_boxes)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_boxes", C.c_uint32), ("n_nonconvex", C.c_uint32), ("max_vertex_entries", C.c_uint32),
+                ("eps", C.c_float), ("weight_sum_dev", C.c_float), ("reserved0", C.c_uint32 * 2)]
+
+
+class PaletteBoundsArgs(C.Structure):
+    """mmdx_palette_bounds_args: palettes in, one conservative box per instance out (mmdx_palette_bounds)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("reserved0", C.c_uint32),
+                ("palettes", C.c_void_p), ("out_bounds", C.c_void_p), ("pos_scale", C.c_float), ("morph_scale", C.c_float)]
+
+
 class ModelInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32),
                 ("n_vertices", C.c_uint32), ("n_bones", C.c_uint32), ("n_morphs", C.c_uint32),
@@ -130,6 +142,8 @@ SIGNATURES = {
     "mmdx_cull_bounds": (C.c_int32, [C.c_void_p, C.POINTER(CullArgs)]),
     "mmdx_cull_planes_from_matrix": (C.c_int32, [_f32p, C.c_uint32, _f32p]),
     "mmdx_palette_place": (C.c_int32, [C.c_void_p, C.POINTER(PlaceArgs)]),
+    "mmdx_model_get_bone_boxes": (C.c_int32, [C.c_void_p, C.POINTER(BoneBoxInfo), _u32p, _f32p]),
+    "mmdx_palette_bounds": (C.c_int32, [C.c_void_p, C.POINTER(PaletteBoundsArgs)]),
     "mmdx_sync": (C.c_int32, [C.c_void_p]),
     "mmdx_timer_start": (C.c_int32, [C.c_void_p]),
     "mmdx_timer_stop": (C.c_int32, [C.c_void_p, _f32p]),

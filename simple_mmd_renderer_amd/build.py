@@ -21,9 +21,11 @@ LIB = os.environ.get("MMDX_BUILD_OUT") or os.path.join(HERE, "libmmdx.so")   # M
 SOURCES = ["api.cpp", "bench_api.cpp", "kernels.hip", "kernels_fast.hip", "launch_shape.cpp", "plan.cpp", "pmx.cpp", "pmd.cpp", "vmd.cpp", "error.cpp",
            "rig.cpp", "rig_api.cpp", "rig_kernels.hip",
            # (behind the others: tools/disassembly_diff.py keys kernels by the position of their translation unit)
-           "cull_api.cpp", "cull_kernels.hip", "cull_shape.cpp", "place_api.cpp", "place_kernels.hip"]
+           "cull_api.cpp", "cull_kernels.hip", "cull_shape.cpp", "place_api.cpp", "place_kernels.hip",
+           "pbounds_api.cpp", "pbounds_kernels.hip"]
 HEADERS = ["kernels.hpp", "plan.hpp", "error.hpp", "vmd.hpp", "rig.hpp", "rig_kernels.hpp", "pmx.hpp", "graph_pin.hpp", "api_internal.hpp",
            "motion_clock.hpp", "motion_blend.hpp", "launch_shape.hpp", "lds_layout.hpp", "cull_shape.hpp", "cull_kernels.hpp", "place_kernels.hpp", "place_math.hpp",
+           "pbounds_kernels.hpp", "pbounds_math.hpp",
            os.path.join("..", "..", "include", "mmdx.h"), os.path.join("..", "..", "include", "mmdx_bench.h")]
 ARCH = "gfx950"
 

@@ -167,6 +167,7 @@ mmdx_status upload_model(mmdx_model_s *m) {
     HIP_TRY(upload(m->slot_top, p.slot_top, t));
     HIP_TRY(upload(m->chain_off, p.chain_off, t));
     HIP_TRY(upload(m->chain_rate, p.chain_rate, t));
+    HIP_TRY(upload(m->bone_boxes, bone_box_device_table(p), t));
     if (p.ns) {
         HIP_TRY(m->morphed.ensure(size_t(p.nv) * 12));
         t += size_t(p.nv) * 12;
@@ -188,7 +189,7 @@ void free_model(mmdx_model_s *m) {
                           &m->skin2_w, &m->skin4_ids, &m->skin4_w, &m->bone_list, &m->ell,
                           &m->entries, &m->slot_top, &m->chain_off, &m->chain_rate, &m->pal, &m->rates,
                           &m->wslot, &m->morphed, &m->seen, &m->out_a, &m->out_b, &m->bnd, &m->sel, &m->cull,
-                          &m->place_in, &m->place_w, &m->place_out})
+                          &m->place_in, &m->place_w, &m->place_out, &m->bone_boxes, &m->pbounds_in, &m->pbounds_out})
             b->release();
         if (m->bounce) (void)hipHostFree(m->bounce);
         if (m->bounce_in) (void)hipHostFree(m->bounce_in);

@@ -55,6 +55,7 @@ LaunchOverrides read_launch_overrides();
 LaunchOverrides &launch_overrides();
 void reload_cull_overrides();       // MMDX_CULL_FORM / MMDX_CULL_CHUNK (cull_api.cpp), re-read with the launch-shape overrides
 int env_int(const char *name, int dflt);
+std::vector<float> bone_box_device_table(const Plan &p);   // pbounds_api.cpp: the plan's bone boxes in the kernel's row layout
 // average ms of `iters` store-pattern launches on the default stream (after one warm-up launch); bench_api.cpp
 hipError_t time_store_pattern(void *a, void *b, uint32_t nv, uint32_t ni, uint32_t bpva, uint32_t bpvb, int iters, float *avg_ms,
                               uint32_t pitch = 0);   // pitch: vertices from one instance to the next (0 = nv)
@@ -85,6 +86,8 @@ struct mmdx_model_s {
     std::vector<uint32_t> sel_host; // ... and its image on the host, the source of the upload
     mmdx::DevBuf cull;              // mmdx_cull_bounds in two launches: per-chunk, per-level counts
     mmdx::DevBuf place_in, place_w, place_out;   // mmdx_palette_place with host operands: palettes, placements, result
+    mmdx::DevBuf bone_boxes;                     // static: the bone-box table of mmdx_palette_bounds (pbounds_kernels.hpp row layout)
+    mmdx::DevBuf pbounds_in, pbounds_out;        // mmdx_palette_bounds with host operands: palettes, result
     bool morphed_valid = false;     // `morphed` holds the result of a shared morph pass (MMDX_MORPH_UNCHANGED)
     std::vector<float> host_rates;  // ... and the host's copy of those rates when they came from host memory
     bool host_rates_valid = false;
@@ -97,7 +100,8 @@ struct mmdx_model_s {
     bool last_write_through = false;          // store flavour of the last crowd launch (mmdx_debug_last_store_policy)
     mmdx_debug_launch_shape last_shape{};     // ... and the rest of its shape (mmdx_debug_last_launch_shape); struct_size unused
     mmdx_model_s() {
-        for (mmdx::DevBuf *b : {&pal, &rates, &wslot, &morphed, &out_a, &out_b, &bnd, &sel, &cull, &place_in, &place_w, &place_out}) b->pin = &pin;
+        for (mmdx::DevBuf *b : {&pal, &rates, &wslot, &morphed, &out_a, &out_b, &bnd, &sel, &cull, &place_in, &place_w, &place_out, &pbounds_in,
+                                 &pbounds_out}) b->pin = &pin;
     }
     // page-locked bounce buffer for small outputs bound for pageable host memory (see mmdx_deform_batched)
     void *bounce = nullptr, *bounce_dev = nullptr;  // host address, device-side address

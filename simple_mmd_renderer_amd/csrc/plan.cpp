@@ -2,7 +2,9 @@
 #include "plan.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <limits>
 
 namespace mmdx {
 
@@ -82,6 +84,94 @@ uint16_t f32_to_f16_rne(float f) {
     if (rem > mid || (rem == mid && (q & 1u))) ++q;
     return uint16_t(sign | (half + q));  // mantissa carry correctly bumps the exponent
 }
+
+float f16_to_f32(uint16_t h) {
+    const uint32_t sign = uint32_t(h & 0x8000u) << 16, exp = (h >> 10) & 31u, man = h & 0x3ffu;
+    uint32_t bits;
+    if (exp == 0) {                          // zero / subnormal: man * 2^-24, exact in binary32
+        const float f = float(man) * 5.9604644775390625e-8f;
+        std::memcpy(&bits, &f, 4);
+        bits |= sign;
+    } else if (exp == 31) {
+        bits = sign | 0x7f800000u | (man << 13);
+    } else {
+        bits = sign | ((exp + 112u) << 23) | (man << 13);
+    }
+    float f;
+    std::memcpy(&f, &bits, 4);
+    return f;
+}
+
+namespace {
+
+// The bone-box table of mmdx_palette_bounds (include/mmdx.h states it): for every bone some vertex uses, the box of those
+// vertices' base positions and the largest per-axis sum of |morph offset| among them -- positions and offsets as the kernels read
+// them (the sorted streams, binary16 widened), the skin as mmdx_model_get_skin returns it.  cnt[v] = vertex-morph entries on v.
+void build_bone_boxes(Plan &p, const std::vector<uint32_t> &cnt) {
+    const float inf = std::numeric_limits<float>::infinity();
+    std::vector<float> lo(size_t(p.nb) * 3, inf), hi(size_t(p.nb) * 3, -inf), reach(size_t(p.nb) * 3, 0.0f);
+    std::vector<uint8_t> used(p.nb, 0);
+    double wdev = 0.0;
+    for (const TileHdr &t : p.tiles)
+        for (uint32_t s = 0; s < t.nv; ++s) {
+            const uint32_t g = t.v0 + s, v = t.v0 + p.perm[g];
+            float pos[3], r[3];
+            double sum[3] = {0.0, 0.0, 0.0};
+            const size_t first = p.ell[2 * size_t(g >> 6)];
+            for (uint32_t j = 0; j < cnt[v]; ++j) {
+                const size_t at = first + size_t(j) * 64 + (g & 63);
+                for (int c = 0; c < 3; ++c)
+                    sum[c] += std::fabs(double(p.f16 ? f16_to_f32(p.entries16[4 * at + c]) : p.entries[4 * at + c]));
+            }
+            for (int c = 0; c < 3; ++c) {
+                pos[c] = p.f16 ? f16_to_f32(p.spos16[4 * size_t(g) + c]) : p.spos[3 * size_t(g) + c];
+                r[c] = std::nextafter(float(sum[c]), inf);
+            }
+            p.box_r_max = std::max(p.box_r_max, cnt[v]);
+            const int32_t *id = p.ids.data() + 4 * size_t(v);
+            const float *w = p.wts.data() + 4 * size_t(v);
+            bool use[4] = {false, false, false, false}, negative = false;
+            double s_v = 1.0;
+            if (p.cls[v] == 0) {
+                use[0] = true;
+            } else if (p.cls[v] == 1) {
+                const float w1 = 1.0f - w[0];
+                use[0] = w[0] != 0.0f; use[1] = w1 != 0.0f;
+                s_v = double(w[0]) + double(w1);
+                negative = w[0] < 0.0f || w[0] > 1.0f;
+            } else {
+                s_v = 0.0;
+                for (int k = 0; k < 4; ++k) {
+                    use[k] = w[k] != 0.0f;
+                    s_v += double(w[k]);
+                    negative |= w[k] < 0.0f;
+                }
+            }
+            wdev = std::max(wdev, std::fabs(s_v - 1.0));
+            p.n_nonconvex += negative ? 1u : 0u;
+            for (int k = 0; k < 4; ++k) {
+                if (!use[k]) continue;
+                const size_t b = size_t(id[k]);
+                used[b] = 1;
+                for (int c = 0; c < 3; ++c) {
+                    if (pos[c] < lo[3 * b + c]) lo[3 * b + c] = pos[c];
+                    if (pos[c] > hi[3 * b + c]) hi[3 * b + c] = pos[c];
+                    if (r[c] > reach[3 * b + c]) reach[3 * b + c] = r[c];
+                }
+            }
+        }
+    for (uint32_t b = 0; b < p.nb; ++b) {
+        if (!used[b]) continue;
+        p.box_bone.push_back(b);
+        p.box.insert(p.box.end(), lo.begin() + 3 * size_t(b), lo.begin() + 3 * size_t(b) + 3);
+        p.box.insert(p.box.end(), hi.begin() + 3 * size_t(b), hi.begin() + 3 * size_t(b) + 3);
+        p.box.insert(p.box.end(), reach.begin() + 3 * size_t(b), reach.begin() + 3 * size_t(b) + 3);
+    }
+    p.box_wdev = std::nextafter(float(wdev), inf);
+    p.box_eps = float(double(32 + uint64_t(p.box_r_max)) * 5.9604644775390625e-8) + p.box_wdev;
+}
+
+}  // namespace
 
 void flatten_slot_weights(const Plan &plan, const float *rates, float *out) {
     for (uint32_t s = 0; s < plan.ns; ++s) {
@@ -385,6 +475,7 @@ mmdx_status build_plan(const mmdx_model_desc &d, Plan &p, std::string &err) {
         for (size_t i = 0; i < p.spos16.size(); ++i)
             if (p.spos16[i] == 0x8000u) p.spos16[i] = 0;
     }
+    build_bone_boxes(p, cnt);
     return MMDX_OK;
 }
 

@@ -81,6 +81,13 @@ struct Plan {
     std::vector<uint32_t> slot_top;   // [NS] top-level morph whose rate starts the chain
     std::vector<uint32_t> chain_off;  // [NS+1]
     std::vector<float> chain_rate;    // sub-rates applied in order (outermost group first)
+
+    // bone boxes (mmdx_palette_bounds, include/mmdx.h): one row per bone that some vertex uses, ascending bone order
+    std::vector<uint32_t> box_bone;   // [n_boxes]
+    std::vector<float> box;           // [n_boxes][9] lo xyz, hi xyz of the base positions, reach xyz of the morph offsets
+    uint32_t box_r_max = 0;           // most vertex-morph entries on one vertex
+    uint32_t n_nonconvex = 0;         // vertices with a negative applied weight
+    float box_wdev = 0.0f, box_eps = 0.0f;
 };
 
 // Returns MMDX_OK or an error code with a message in `err`.
@@ -92,5 +99,6 @@ mmdx_status build_plan(const mmdx_model_desc &desc, Plan &plan, std::string &err
 void flatten_slot_weights(const Plan &plan, const float *rates, float *out);
 
 uint16_t f32_to_f16_rne(float f);
+float f16_to_f32(uint16_t h);
 
 }  // namespace mmdx

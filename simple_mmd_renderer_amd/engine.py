@@ -436,6 +436,39 @@ class DeformModel:
         self.place_palettes(ni, pal.ctypes.data, pl.ctypes.data, out.ctypes.data, api.PLACE_MATRIX if pl.shape[1] == 16 else 0)
         return out
 
+    def bone_boxes(self) -> dict:
+        """mmdx_model_get_bone_boxes: the table mmdx_palette_bounds transforms -- bones u32 [n], boxes f32 [n,9] (lo xyz, hi xyz of
+        the base positions of the vertices the bone moves, reach xyz of their morph offsets), and the scalars eps, weight_sum_dev,
+        max_vertex_entries, n_nonconvex.  Works on host-only models."""
+        info = api.BoneBoxInfo()
+        info.struct_size = C.sizeof(api.BoneBoxInfo)
+        api.check(api.lib().mmdx_model_get_bone_boxes(self.h, C.byref(info), None, None))
+        bones, boxes = np.empty(info.n_boxes, np.uint32), np.empty((info.n_boxes, 9), np.float32)
+        api.check(api.lib().mmdx_model_get_bone_boxes(self.h, C.byref(info), _ptr(bones, _u32p), _ptr(boxes, _f32p)))
+        return dict(bones=bones, boxes=boxes, n_boxes=int(info.n_boxes), n_nonconvex=int(info.n_nonconvex),
+                    max_vertex_entries=int(info.max_vertex_entries), eps=np.float32(info.eps),
+                    weight_sum_dev=np.float32(info.weight_sum_dev))
+
+    def palette_bounds_raw(self, n_instances: int, palettes_ptr, bounds_ptr, flags: int, pos_scale: float = 1.0,
+                           morph_scale: float = 1.0) -> None:
+        """mmdx_palette_bounds, the raw form: bounds_ptr[i] = {min xyz, max xyz} of a box that contains every position a deform of
+        instance i from the palettes at palettes_ptr with this pos_scale writes, as long as no slot weight exceeds morph_scale.
+        flags: api.PALETTE_ON_DEVICE | api.OUT_ON_DEVICE say which of the two addresses are device memory.  With both on the device
+        the call is asynchronous on the model's stream and records into a graph."""
+        a = api.PaletteBoundsArgs()
+        a.struct_size = C.sizeof(api.PaletteBoundsArgs)
+        a.flags, a.n_instances = flags, n_instances
+        a.palettes, a.out_bounds = palettes_ptr, bounds_ptr
+        a.pos_scale, a.morph_scale = pos_scale, morph_scale
+        api.check(api.lib().mmdx_palette_bounds(self.h, C.byref(a)))
+
+    def palette_bounds(self, palettes, pos_scale: float = 1.0, morph_scale: float = 1.0) -> np.ndarray:
+        """Host array in, host array out (copies + sync inside the call): palettes [NI,NB,16] -> boxes f32 [NI,6]."""
+        pal = _c(palettes, np.float32).reshape(-1, self.nb, 16)
+        out = np.empty((pal.shape[0], 6), np.float32)
+        self.palette_bounds_raw(pal.shape[0], pal.ctypes.data, out.ctypes.data, 0, pos_scale, morph_scale)
+        return out
+
     def sync(self) -> None:
         api.check(api.lib().mmdx_sync(self.h))
 

@@ -421,6 +421,19 @@ public:
         a.palettes = palettes; a.placements = placements; a.out_palettes = out_palettes;
         check(mmdx_palette_place(poser_.handle(), &a));
     }
+    // A conservative box per instance from the palette alone, before any deform (mmdx.h, mmdx_palette_bounds): out_bounds[i] =
+    // {min xyz, max xyz} contains every position a deform of instance i from `palettes` with this pos_scale writes while no slot
+    // weight exceeds morph_scale.  What mmdx_cull_bounds takes, one frame earlier than the deform's own bounds.
+    void PaletteBounds(uint32_t n, const float *palettes, float *out_bounds, float pos_scale = 1.0f, float morph_scale = 1.0f,
+                       bool on_device = false) {
+        mmdx_palette_bounds_args a{};
+        a.struct_size = sizeof(a);
+        a.flags = on_device ? uint32_t(MMDX_PALETTE_ON_DEVICE | MMDX_OUT_ON_DEVICE) : 0u;
+        a.n_instances = n;
+        a.palettes = palettes; a.out_bounds = out_bounds;
+        a.pos_scale = pos_scale; a.morph_scale = morph_scale;
+        check(mmdx_palette_bounds(poser_.handle(), &a));
+    }
     // out_rates[i][morph] = the morph rates of instance i (what mmdx_deform_batched takes as per-instance weights)
     void SeekTimeMorphRates(uint32_t n, const uint32_t *clips, const double *times, float *out_rates, bool on_device = false) {
         check(mmdx_motion_set_eval_morphs_time(set_, poser_.handle(), n, clips, times, flags(on_device), out_rates));
