@@ -249,7 +249,19 @@ MMDX_API mmdx_status mmdx_model_get_vertex_order(mmdx_model_t model, uint32_t *e
  * what the device consumes (a slot whose chain hits the reference's `rate < 1e-7` skip gets 0). */
 MMDX_API mmdx_status mmdx_model_slot_weights(mmdx_model_t model, const float *morph_weights,
                                              float *slot_weights);
-/* Borrow an external HIP stream (hipStream_t) instead of the handle's own; NULL restores it. */
+/* Borrow an external HIP stream (hipStream_t) instead of the handle's own; NULL restores it.  Every entry point that takes
+ * `model` -- deform, bounds, select, cull, place, palette bounds, the motion and rig calls, graph recording, mmdx_sync --
+ * then enqueues on that stream and on no other.
+ *  - Order across a switch: work enqueued after the switch starts after ALL work this model enqueued before it, on whichever
+ *    stream (the new stream waits for an event on the old one; the host never blocks, and a switch to the stream the model
+ *    already has does nothing).  The model's device state -- morphed positions, scratch buffers -- moves with it safely.
+ *  - A switch between mmdx_graph_begin and mmdx_graph_end is refused (MMDX_ERR_INVALID_ARGUMENT), the recording goes on.
+ *  - A graph replays on the stream it was recorded on, also after the model has left that stream.
+ *  - Lifetime: the borrowed stream must stay alive until the model has been switched away from it (or destroyed) AND the
+ *    graphs recorded on it are destroyed.  mmdx_model_destroy waits for the model's current stream, which is ordered behind
+ *    everything earlier.
+ *  - The stream must belong to the model's device: another device's stream is refused (MMDX_ERR_INVALID_ARGUMENT).
+ * A host-only model has no stream: MMDX_ERR_NO_DEVICE. */
 MMDX_API mmdx_status mmdx_model_set_stream(mmdx_model_t model, void *hip_stream);
 
 /* ---- HIP-graph replay of a frame's device work ------------------------------------------------------

@@ -193,7 +193,7 @@ void free_model(mmdx_model_s *m) {
             b->release();
         if (m->bounce) (void)hipHostFree(m->bounce);
         if (m->bounce_in) (void)hipHostFree(m->bounce_in);
-        for (hipEvent_t ev : {m->ev_t0, m->ev_t1})
+        for (hipEvent_t ev : {m->ev_t0, m->ev_t1, m->ev_switch})
             if (ev) (void)hipEventDestroy(ev);
         for (hipEvent_t ev : m->prof_events) (void)hipEventDestroy(ev);
         if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
@@ -391,6 +391,7 @@ mmdx_status mmdx_model_create(const mmdx_model_desc *desc, mmdx_model_t *out_mod
     m->stream = m->own_stream;
     for (hipEvent_t *ev : {&m->ev_t0, &m->ev_t1})
         if ((e = hipEventCreate(ev)) != hipSuccess) return bail(hip_fail(e, "hipEventCreate"));
+    if ((e = hipEventCreateWithFlags(&m->ev_switch, hipEventDisableTiming)) != hipSuccess) return bail(hip_fail(e, "hipEventCreate"));
     st = upload_model(m);
     if (st != MMDX_OK) return bail(st);
     *out_model = m;
@@ -467,7 +468,27 @@ mmdx_status mmdx_model_slot_weights(mmdx_model_t m, const float *rates, float *o
 mmdx_status mmdx_model_set_stream(mmdx_model_t m, void *hip_stream) {
     if (!m) return fail(MMDX_ERR_INVALID_ARGUMENT, "model is NULL");
     if (m->device < 0) return fail(MMDX_ERR_NO_DEVICE, "host-only model");
-    m->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : m->own_stream;
+    if (m->capturing)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "this model's stream is recording a graph: end the recording (mmdx_graph_end) before "
+                                               "switching streams");
+    hipStream_t next = hip_stream ? static_cast<hipStream_t>(hip_stream) : m->own_stream;
+    if (next == m->stream) return MMDX_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    if (hip_stream) {
+        hipDevice_t dev = -1;
+        if (hipStreamGetDevice(next, &dev) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "hip_stream is not a HIP stream the runtime knows");
+        }
+        if (int(dev) != m->device)
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "hip_stream belongs to device " + std::to_string(int(dev)) + ", the model lives on device " +
+                                                   std::to_string(m->device));
+    }
+    // The model's device state (morphed positions, the RatesSeen record, every scratch buffer) goes with it from one stream to the
+    // next: whatever is enqueued from now on starts after everything enqueued so far.  An event, not a wait: the host never blocks.
+    HIP_TRY(hipEventRecord(m->ev_switch, m->stream));
+    HIP_TRY(hipStreamWaitEvent(next, m->ev_switch, 0));
+    m->stream = next;
     return MMDX_OK;
 }
 

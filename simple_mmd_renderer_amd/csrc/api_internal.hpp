@@ -67,6 +67,7 @@ struct mmdx_model_s {
     int device = -1;  // -1: host-only
     hipStream_t own_stream = nullptr, stream = nullptr;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+    hipEvent_t ev_switch = nullptr;   // mmdx_model_set_stream: orders the new stream behind the old one (no timing)
     // per-call kernel timing (mmdx_profile_*): event quadruples {skin0, skin1, morph0, morph1},
     // recorded on the launch stream without any host sync; read back by mmdx_profile_collect
     std::vector<hipEvent_t> prof_events;

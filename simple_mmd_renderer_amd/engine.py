@@ -469,6 +469,13 @@ class DeformModel:
         self.palette_bounds_raw(pal.shape[0], pal.ctypes.data, out.ctypes.data, 0, pos_scale, morph_scale)
         return out
 
+    def set_stream(self, stream) -> None:
+        """mmdx_model_set_stream: every later call of this model (and of the motion / rig calls that take it) is enqueued on the
+        caller's hipStream_t `stream` (an address, or a ctypes.c_void_p), behind everything the model enqueued before; None goes
+        back to the handle's own stream.  Refused while a graph is being recorded and for a stream of another device.  The stream
+        must outlive its use: switch away from it (and destroy the graphs recorded on it) before destroying it."""
+        api.check(api.lib().mmdx_model_set_stream(self.h, getattr(stream, "value", stream)))
+
     def sync(self) -> None:
         api.check(api.lib().mmdx_sync(self.h))
 
