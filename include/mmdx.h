@@ -66,7 +66,8 @@ extern "C" {
  *    mmdx_palette_place with mmdx_place_args, MMDX_PLACE_ON_DEVICE and MMDX_PLACE_MATRIX (a new entry point, structure and two
  *    flag bits no other call accepts; nothing existing changes).
  *    mmdx_palette_bounds with mmdx_palette_bounds_args, and mmdx_model_get_bone_boxes with mmdx_bone_box_info (two new entry points
- *    and structures; mmdx_model_info, mmdx_deform_args and every existing call are unchanged). */
+ *    and structures; mmdx_model_info, mmdx_deform_args and every existing call are unchanged).
+ *    mmdx_skeleton_solve_select (a new entry point that takes the existing mmdx_instance_select; nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -1009,6 +1010,39 @@ MMDX_API mmdx_status mmdx_skeleton_solve_morphed(mmdx_skeleton_t skeleton, mmdx_
                                                  uint32_t n_instances, const float *poses,
                                                  const float *morph_weights, uint32_t flags,
                                                  float *out_palettes);
+/* ---- solving a subset of a crowd: mmdx_skeleton_solve_morphed (mmdx_skeleton_solve when morph_weights == NULL) for the instances of
+ * an mmdx_instance_select only -- the list type of mmdx_deform_batched_select, so mmdx_cull_bounds' out_ids / out_counts go in as they
+ * are.  On rigs with CCD-IK the solve is the frame's largest step; this makes it scale with the instances in view.
+ *  1. n_instances = NI is the extent of poses, morph_weights and out_palettes: instance i reads pose row i and rate row i (or the one
+ *     shared row with MMDX_WEIGHTS_SHARED) and writes palette row i.  The list only says which i take part.
+ *  2. For every listed i < NI the 64 * NB bytes of palette row i are identical to what mmdx_skeleton_solve_morphed writes for that
+ *     instance from the same operands: the parallel-FK solver; the ordered solver with append bones, CCD-IK on one lane and on sixteen
+ *     lanes per solve (MMDX_IK_COOP=0/1) and nested IK; its two-workgroups-per-CU variant; bone morphs, per instance and shared.
+ *  3. Nothing else is written: palette rows of instances that are not listed keep every byte.  Pose and rate rows of unlisted
+ *     instances may hold anything (NaN, uninitialised memory) and influence no written byte.
+ *  4. The first min(*count, n_ids) ids are used.  *count == 0 or n_ids == 0 is a valid call that writes nothing.
+ *  5. An id >= NI: in a host list the call fails with MMDX_ERR_INVALID_ARGUMENT before anything is launched; in a device list the
+ *     entry is skipped on the device (nothing read or written for it).  An id that occurs twice is allowed and costs twice: the
+ *     solver's per-bone state and the bone-morph state are kept per LIST POSITION, so both solves are independent and store the same
+ *     bytes.  The skeleton's scratch is therefore sized by n_ids, not by NI.
+ *  6. The device-resident form only: MMDX_POSES_ON_DEVICE | MMDX_OUT_ON_DEVICE are required, and MMDX_WEIGHTS_ON_DEVICE when
+ *     morph_weights is given; anything else is MMDX_ERR_INVALID_ARGUMENT (the staging copies of host operands move whole arrays and
+ *     cannot honour rule 3), as are unknown flag bits, select == NULL, a struct_size mismatch, unknown select->flags bits and
+ *     reserved0 != 0 -- all of them, and NULL skeleton / poses / out_palettes and n_instances == 0, before the device is touched.  A
+ *     host-resident list is supported: it is copied through a scratch buffer of the skeleton in stream order, and the call returns
+ *     after its work has completed.
+ *  7. With a device list the call is asynchronous on `model`'s stream (a borrowed stream applies; without a model, the selected
+ *     device's default stream) and records into mmdx_graph_begin / mmdx_graph_end after one un-recorded run; a host list is refused
+ *     while recording.  A replay reads ids and *count afresh.  The skeleton's scratch is pinned by the graph like that of the other
+ *     solves: a later call whose n_ids would make it grow fails with MMDX_ERR_INVALID_ARGUMENT.  ids and count are 4-byte aligned.
+ *  8. The launches are sized from n_ids: workgroups whose list positions all lie behind *count return at once.
+ *  9. Only the one-step solve has a select form, the physics seam (_pre / _post) has none.  On a MMDX_SKELETON_PHYSICS_SEAM skeleton
+ *     the call behaves toward a pending pre step exactly as mmdx_skeleton_solve does: the pre step is void.
+ * 10. Track evaluation (mmdx_motion_set_blend_bones_time and its siblings) is not selected: it runs for every instance and feeds
+ *     `poses`.  An instance that is not solved keeps its last model-space palette. */
+MMDX_API mmdx_status mmdx_skeleton_solve_select(mmdx_skeleton_t skeleton, mmdx_model_t model, uint32_t n_instances, const float *poses,
+                                                const float *morph_weights /* or NULL */, uint32_t flags,
+                                                const mmdx_instance_select *select, float *out_palettes /* [NI][NB][16] */);
 MMDX_API void mmdx_skeleton_destroy(mmdx_skeleton_t skeleton);
 /* Fills `desc` with pointers into `pmx` (valid until mmdx_pmx_destroy): rest positions, parents, transform
  * levels, flag words, append and IK tables exactly as the file states them (PmxReader,

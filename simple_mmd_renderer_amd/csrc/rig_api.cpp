@@ -73,19 +73,21 @@ struct mmdx_skeleton_s {
     Buf order, bones, iks, links, events, rounds, state;  // ordered solver
     Buf apps, app_chain, rates_in, morph_state;           // bone morphs
     Buf over_bone, over_strict, over_skin;                // physics seam: the reactor's writes of one frame
+    Buf sel_in;                                           // mmdx_skeleton_solve_select with a host list: {live count, ids[live]}
+    std::vector<uint32_t> sel_host;                       // ... its source, alive until the copy has left it
     uint32_t pre_instances = 0;                           // instances of the last mmdx_skeleton_solve_pre (0: none pending)
     const float *pre_poses = nullptr;                     // the poses that call solved (device address)
     const float *pre_morph = nullptr;
     GraphPin pin;                                         // recorded graphs that hold these buffers' addresses
     mmdx_skeleton_s() {
         for (Buf *b : {&local_offset, &neg_rest, &chain_off, &chain, &poses_in, &out, &order, &bones, &iks, &links, &events, &rounds,
-                       &state, &apps, &app_chain, &rates_in, &morph_state, &over_bone, &over_strict, &over_skin})
+                       &state, &apps, &app_chain, &rates_in, &morph_state, &over_bone, &over_strict, &over_skin, &sel_in})
             b->pin = &pin;
     }
     void release_all() {
         for (Buf *b : {&local_offset, &neg_rest, &chain_off, &chain, &poses_in, &out, &order, &bones, &iks, &links, &events, &rounds,
                        &state,
-                       &apps, &app_chain, &rates_in, &morph_state, &over_bone, &over_strict, &over_skin})
+                       &apps, &app_chain, &rates_in, &morph_state, &over_bone, &over_strict, &over_skin, &sel_in})
             b->release();
     }
 };
@@ -179,6 +181,9 @@ static mmdx_status skeleton_to_device(mmdx_skeleton_t s, int device) {
 static mmdx_status skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
                                   const float *morph_weights, uint32_t flags, float *out_palettes, uint32_t passes,
                                   const mmdx_physics_overrides *ov);
+static mmdx_status skeleton_solve_select(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
+                                         const float *morph_weights, uint32_t flags, const mmdx_instance_select *sel,
+                                         float *out_palettes);
 static mmdx_status bone_motion_eval(mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances, const void *clock, bool time,
                                     uint32_t flags, float *out_poses);
 static mmdx_status skeleton_solve_motion(mmdx_skeleton_t s, mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
@@ -304,6 +309,12 @@ mmdx_status mmdx_skeleton_solve_morphed(mmdx_skeleton_t s, mmdx_model_t model, u
                                         const float *poses, const float *morph_weights, uint32_t flags,
                                         float *out_palettes) {
     return skeleton_solve(s, model, n_instances, poses, morph_weights, flags, out_palettes, 3u, nullptr);
+}
+
+mmdx_status mmdx_skeleton_solve_select(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
+                                       const float *morph_weights, uint32_t flags, const mmdx_instance_select *select,
+                                       float *out_palettes) {
+    return skeleton_solve_select(s, model, n_instances, poses, morph_weights, flags, select, out_palettes);
 }
 
 mmdx_status mmdx_skeleton_solve_pre(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
@@ -555,6 +566,115 @@ static mmdx_status skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_
     } else if (!(flags & MMDX_POSES_ON_DEVICE) || borrowed_rates) {
         HIP_TRY(wait_stream(st));   // borrowed host poses / rates must be consumed before returning
     }
+    return MMDX_OK;
+}
+
+// mmdx_skeleton_solve_select: mmdx_skeleton_solve_morphed for the listed instances (include/mmdx.h, rules 1-10).  Everything that can
+// be decided without the device comes first, in the header's order; `live_host` = the ids of a host list that are in use.
+static mmdx_status check_select_args(mmdx_skeleton_t s, uint32_t n_instances, const float *poses, const float *morph_weights,
+                                     uint32_t flags, const mmdx_instance_select *sel, const float *out_palettes, uint32_t &live_host) {
+    if (!s || !poses || !out_palettes || !n_instances) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    const uint32_t need = MMDX_POSES_ON_DEVICE | MMDX_OUT_ON_DEVICE | (morph_weights ? uint32_t(MMDX_WEIGHTS_ON_DEVICE) : 0u);
+    if ((flags & need) != need)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_skeleton_solve_select takes device operands only: pass MMDX_POSES_ON_DEVICE | "
+                                               "MMDX_OUT_ON_DEVICE, and MMDX_WEIGHTS_ON_DEVICE with morph_weights");
+    if (flags & ~uint32_t(MMDX_POSES_ON_DEVICE | MMDX_OUT_ON_DEVICE | MMDX_WEIGHTS_ON_DEVICE | MMDX_WEIGHTS_SHARED))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    if (!sel) return fail(MMDX_ERR_INVALID_ARGUMENT, "select is NULL (mmdx_skeleton_solve / _morphed solve every instance)");
+    if (sel->struct_size != sizeof(mmdx_instance_select))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.struct_size mismatch");
+    if (sel->flags & ~uint32_t(MMDX_SELECT_ON_DEVICE))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown bits in mmdx_instance_select.flags");
+    if (sel->reserved0 != 0) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.reserved0 must be 0");
+    if (sel->n_ids && !sel->ids) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids is NULL");
+    if (sel->flags & MMDX_SELECT_ON_DEVICE) {
+        if ((reinterpret_cast<uintptr_t>(sel->ids) | reinterpret_cast<uintptr_t>(sel->count)) & 3)
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "device ids / count of mmdx_instance_select must be 4-byte aligned");
+        return MMDX_OK;
+    }
+    if (graph_recording())
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded the instance list must be in device memory "
+                                               "(MMDX_SELECT_ON_DEVICE)");
+    live_host = sel->count ? std::min(*sel->count, sel->n_ids) : sel->n_ids;
+    for (uint32_t j = 0; j < live_host; ++j)
+        if (sel->ids[j] >= n_instances)
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids[" + std::to_string(j) + "] = " +
+                                                   std::to_string(sel->ids[j]) + " is not below n_instances");
+    return MMDX_OK;
+}
+
+static mmdx_status skeleton_solve_select(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
+                                         const float *morph_weights, uint32_t flags, const mmdx_instance_select *sel,
+                                         float *out_palettes) {
+    uint32_t live_host = 0;
+    if (mmdx_status r = check_select_args(s, n_instances, poses, morph_weights, flags, sel, out_palettes, live_host)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const SkeletonPlan &pl = s->plan;
+    const bool host_list = !(sel->flags & MMDX_SELECT_ON_DEVICE);
+    if (graph_recording() && s->device != device)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded the skeleton must have run on this device before");
+    if (mmdx_status r = skeleton_to_device(s, device)) return r;
+    graph_note_handle(model, &s->pin);
+    // state and bone-morph cells are per LIST POSITION: the capacity of a device list, the ids in use of a host list
+    const uint32_t cells = host_list ? live_host : sel->n_ids;
+    if (cells == 0) return MMDX_OK;                                 // an empty list writes nothing
+    InstanceList list = {sel->ids, sel->count, n_instances};
+    if (host_list) {                                                // through the skeleton's scratch in stream order, count word first
+        HIP_TRY(s->sel_in.ensure((size_t(cells) + 1) * 4));
+        s->sel_host.resize(size_t(cells) + 1);
+        s->sel_host[0] = cells;
+        std::copy(sel->ids, sel->ids + cells, s->sel_host.begin() + 1);
+        HIP_TRY(hipMemcpyAsync(s->sel_in.ptr, s->sel_host.data(), s->sel_host.size() * 4, hipMemcpyHostToDevice, st));
+        list.count = static_cast<const uint32_t *>(s->sel_in.ptr);
+        list.ids = list.count + 1;
+    }
+    const float *morph_state = nullptr;
+    if (morph_weights && !pl.apps.empty()) {
+        HIP_TRY(s->morph_state.ensure(size_t(cells) * pl.nb * kMorphStateFloats * sizeof(float)));
+        BoneMorphParams mp;
+        mp.rates = morph_weights;
+        mp.apps = static_cast<const BoneMorphApp *>(s->apps.ptr);
+        mp.chain = static_cast<const float *>(s->app_chain.ptr);
+        mp.out = static_cast<float *>(s->morph_state.ptr);
+        mp.napps = uint32_t(pl.apps.size()); mp.nb = pl.nb; mp.ni = cells; mp.nm = pl.nm;
+        mp.shared = (flags & MMDX_WEIGHTS_SHARED) ? 1u : 0u;
+        HIP_TRY(launch_bone_morph_select(mp, list, st));
+        morph_state = mp.out;
+    }
+    if (pl.serial) {
+        HIP_TRY(s->state.ensure(size_t(cells) * pl.nb * kSerialStateFloats * sizeof(float)));
+        SerialParams sp;
+        sp.morph = morph_state;
+        sp.poses = poses; sp.out = out_palettes;
+        sp.state = static_cast<float *>(s->state.ptr);
+        sp.order = static_cast<const uint32_t *>(s->order.ptr);
+        sp.bones = static_cast<const BoneRec *>(s->bones.ptr);
+        sp.iks = static_cast<const IkRec *>(s->iks.ptr);
+        sp.links = static_cast<const LinkRec *>(s->links.ptr);
+        sp.events = static_cast<const uint32_t *>(s->events.ptr);
+        sp.rounds = static_cast<const RoundRec *>(s->rounds.ptr);
+        sp.nb = pl.nb; sp.ni = cells; sp.n_pre = pl.n_pre;
+        sp.n_rounds_pre = pl.n_rounds_pre; sp.n_rounds = uint32_t(pl.rounds.size());
+        sp.fast_slots = pl.fast_slots;
+        sp.windows = pl.windows;
+        sp.passes = 3u;
+        sp.nested = pl.nested_ik ? 1u : 0u;
+        HIP_TRY(launch_skeleton_ordered_select(sp, pl.round_coop.empty() ? nullptr : pl.round_coop.data(), list, st));
+        s->pre_instances = 0;                                       // (the scratch a pending pre step left is gone, as after mmdx_skeleton_solve)
+    } else {
+        SkeletonParams fp;
+        fp.morph = morph_state;
+        fp.poses = poses; fp.out = out_palettes;
+        fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
+        fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
+        fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
+        fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
+        fp.nb = pl.nb; fp.ni = cells;
+        HIP_TRY(launch_skeleton_fk_select(fp, list, st));
+    }
+    if (host_list) HIP_TRY(wait_stream(st));                        // the borrowed list is consumed and the results are there
     return MMDX_OK;
 }
 

@@ -250,6 +250,43 @@ __global__ __launch_bounds__(kRigThreads) void skeleton_fk_kernel(const Skeleton
     fk_bone(p, [&](uint32_t k) { return pose[k]; }, i, bone, reinterpret_cast<float4 *>(p.out) + idx * 4);
 }
 
+// ---- which instance a lane works on ------------------------------------------------------------------------------------------
+// `cell` indexes what a call keeps per instance in its own scratch (the ordered solver's state, the bone-morph state: p.ni cells,
+// instance fastest), `row` the caller's arrays (poses, rates, palettes).  The plain calls: cell k is instance k and so is its row.
+// mmdx_skeleton_solve_select: cell k is LIST POSITION k -- an id listed twice gets two cells, two solves and the same bytes twice --
+// and the row is ids[k]; positions behind min(*count, capacity) and ids that are no row of the arrays are dead.  p.ni is the number of
+// cells: the instance count of a plain call, the list's capacity of a select call.  The plain kernels derive cell = row = instance
+// themselves, as they always did; the select forms go through ListedInstances.
+struct Lane {
+    uint32_t cell, row;
+    bool live;
+};
+struct ListedInstances {
+    InstanceList l;
+    // (the same address in every lane: one scalar load per wave, once per kernel)
+    __device__ __forceinline__ uint32_t used(uint32_t cells) const { return l.count ? min(*l.count, cells) : cells; }
+    __device__ __forceinline__ Lane lane(uint32_t k, uint32_t used) const {
+        const bool in = k < used;
+        const uint32_t id = in ? l.ids[k] : 0u;
+        return {k, id, in && id < l.n_rows};
+    }
+};
+
+// skeleton_fk_kernel for the listed instances: one thread per (list position, bone); the bone morphs' state by position, the pose
+// and the palette row by id.  Workgroups wholly behind the count leave first.
+__global__ __launch_bounds__(kRigThreads) void skeleton_fk_select_kernel(const SkeletonParams p, const InstanceList list) {
+    const ListedInstances sel = {list};
+    const uint32_t used = sel.used(p.ni);
+    const size_t idx = size_t(blockIdx.x) * kRigThreads + threadIdx.x;
+    if (size_t(blockIdx.x) * kRigThreads >= size_t(used) * p.nb) return;
+    if (idx >= size_t(used) * p.nb) return;
+    const uint32_t k = uint32_t(idx / p.nb), bone = uint32_t(idx - size_t(k) * p.nb);
+    const Lane ln = sel.lane(k, used);
+    if (!ln.live) return;
+    const float4 *pose = reinterpret_cast<const float4 *>(p.poses) + size_t(ln.row) * p.nb * 2;
+    fk_bone(p, [&](uint32_t j) { return pose[j]; }, ln.cell, bone, reinterpret_cast<float4 *>(p.out) + (size_t(ln.row) * p.nb + bone) * 4);
+}
+
 // Bone tracks -> palette in ONE launch (mmdx_skeleton_solve_motion on a parallel-FK skeleton): a workgroup is one instance; its
 // threads evaluate the bones' local poses at the instance's frame into LDS (eval_bone_pose: what bone_track_eval_kernel writes to
 // HBM), one barrier, then every thread rebuilds its bones' matrices from those poses (fk_bone: what skeleton_fk_kernel does from
@@ -841,29 +878,18 @@ __device__ void solve_ik(const State &st, const SerialParams &p, const float4 *p
 __global__ __launch_bounds__(kBoneMorphThreads) void bone_morph_kernel(const BoneMorphParams p) {
     const uint32_t inst = blockIdx.x * kBoneMorphThreads + threadIdx.x;
     if (inst >= p.ni) return;
-    float *out = p.out + inst;
-    const size_t n = p.ni;
-    for (uint32_t b = 0; b < p.nb; ++b) {
-        float *o = out + size_t(b) * kMorphStateFloats * n;
-        o[0] = 0.f; o[n] = 0.f; o[2 * n] = 0.f;
-        o[3 * n] = 0.f; o[4 * n] = 0.f; o[5 * n] = 0.f; o[6 * n] = 1.f;
-    }
-    const float *rates = p.rates + (p.shared ? 0 : size_t(inst) * p.nm);
-    for (uint32_t a = 0; a < p.napps; ++a) {
-        const BoneMorphApp app = p.apps[a];
-        float r = rates[app.top];
-        bool skip = r < 1e-7f;
-        for (uint32_t c = 0; !skip && c < app.chain_len; ++c) {
-            r = p.chain[app.chain_off + c] * r;
-            skip = r < 1e-7f;
-        }
-        if (skip) continue;
-        float *o = out + size_t(app.bone) * kMorphStateFloats * n;
-        o[0] = o[0] + app.tr[0] * r; o[n] = o[n] + app.tr[1] * r; o[2 * n] = o[2 * n] + app.tr[2] * r;
-        const Quat cur = {o[3 * n], o[4 * n], o[5 * n], o[6 * n]};
-        const Quat q = q_mul(cur, q_slerp_from_identity({app.rot[0], app.rot[1], app.rot[2], app.rot[3]}, r));
-        o[3 * n] = q.i; o[4 * n] = q.j; o[5 * n] = q.k; o[6 * n] = q.e;
-    }
+    const uint32_t row = inst;
+#include "bone_morph_body.inl"
+}
+// ... for the listed instances: one thread per list position, the state cell by position, the rates row by id
+__global__ __launch_bounds__(kBoneMorphThreads) void bone_morph_select_kernel(const BoneMorphParams p, const InstanceList list) {
+    const ListedInstances sel = {list};
+    const uint32_t used = sel.used(p.ni);
+    if (blockIdx.x * kBoneMorphThreads >= used) return;
+    const Lane ln = sel.lane(blockIdx.x * kBoneMorphThreads + threadIdx.x, used);
+    if (!ln.live) return;
+    const uint32_t inst = ln.cell, row = ln.row;
+#include "bone_morph_body.inl"
 }
 
 // The ordered solver.  A workgroup holds kSolveInstances instances x kSolveSlots slots (instance fastest, so
@@ -877,67 +903,30 @@ __global__ __launch_bounds__(kBoneMorphThreads) void bone_morph_kernel(const Bon
 // 72 KB LDS budget of the windows (rig.hpp), TWO workgroups share a CU.  A lone wave per SIMD is all a crowd of up to
 // 16 x (number of CUs) instances can use, and there the plain variant is 5 % faster (37 spilled registers); beyond that the
 // second wave per SIMD is worth 1.5 x the palettes per second (16 384 instances: 7.6 instead of 11.2 ms).  Chosen per launch.
+// The kernels derive the lane's instance, skeleton_ordered_body.inl is the program: state and bone-morph cells by `inst`, the pose and
+// the palette row by `row`.  Plain: both are the instance.
 template <bool NESTED, bool DENSE>
 __global__ __launch_bounds__(kSolveInstances * kSolveSlots, DENSE ? 2 : 1) void skeleton_ordered_kernel(const SerialParams p) {
     const uint32_t slot = threadIdx.x / kSolveInstances;
     const uint32_t inst = blockIdx.x * kSolveInstances + threadIdx.x % kSolveInstances;
     const bool live = inst < p.ni;       // dead lanes skip the work but reach every barrier
-    const State st = {p.state + (live ? inst : 0), p.ni};
-    extern __shared__ float chain_lds[];   // (windows x instances) lanes x window_floats of state, then the
-                                           // windows' link constants
-    // Which event of a round this slot runs: the events are dealt over the WAVES first (slot 4w + k runs event 4k + w), so that
-    // a round's IK solves -- the first events of the round -- sit in different waves as far as possible: lanes of one wave that
-    // solve DIFFERENT chains take turns through every divergent piece of the CCD loop (two chains per wave instead of four on the
-    // bench rig: measured).  The LDS windows belong to the round's first p.windows events, whichever slot runs them.
-    constexpr uint32_t kSlotsPerWave = 64 / kSolveInstances, kSolveWaves = kSolveSlots / kSlotsPerWave;
-    const uint32_t ev = (slot % kSlotsPerWave) * kSolveWaves + slot / kSlotsPerWave;
-    const uint32_t wf = window_floats(p.fast_slots);
-    auto *lds_lane = (__attribute__((address_space(3))) float *)chain_lds + (ev * kSolveInstances + threadIdx.x % kSolveInstances) * wf;
-    auto *lds_consts = (__attribute__((address_space(3))) float *)chain_lds +
-                       size_t(p.windows) * kSolveInstances * wf + ev * (kMaxFastLinks * kLinkConstFloats);
-    const float4 *pose = reinterpret_cast<const float4 *>(p.poses) + size_t(live ? inst : 0) * p.nb * 2;
-    if (live && (p.passes & 1u) && (p.seg_flags & 1u)) {
-        for (uint32_t b = slot; b < p.nb; b += kSolveSlots) {   // PrePhysicsPosing's reset, poser_impl.inl:366-377
-            st.set_quat(b, kStTotalRot, q_identity());
-            st.set_quat(b, kStIkRot, q_identity());
-            st.set_quat(b, kStPreIkRot, q_identity());
-            st.at(b, kStTotalTr + 0) = 0.f; st.at(b, kStTotalTr + 1) = 0.f; st.at(b, kStTotalTr + 2) = 0.f;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) st.at(b, kStLocal + k) = (k % 5 == 0) ? 1.f : 0.f;
-        }
-    }
-    __syncthreads();
-    float4 *out = reinterpret_cast<float4 *>(p.out) + size_t(live ? inst : 0) * p.nb * 4;
-    for (uint32_t pass = 0; pass < 2; ++pass) {
-        if (!(p.passes >> pass & 1u)) continue;              // the physics seam runs the two lists as two launches
-        const uint32_t r0 = max(pass ? p.n_rounds_pre : 0u, p.seg_r0), r1 = min(pass ? p.n_rounds : p.n_rounds_pre, p.seg_r1);
-        for (uint32_t r = r0; r < r1; ++r) {
-            const RoundRec rr = p.rounds[r];
-            if (live && ev < rr.count) {
-                const uint32_t b = p.events[rr.first + ev];
-                transform_bone(st, p, pose, inst, b);
-                if (p.bones[b].bits & kBoneHasIk) solve_ik<NESTED>(st, p, pose, inst, b, lds_lane, lds_consts);
-            }
-            __syncthreads();
-        }
-        const uint32_t s0 = pass ? p.n_pre : 0, s1 = pass ? p.nb : p.n_pre;
-        if (live && (p.seg_flags >> (1 + pass) & 1u)) {
-            for (uint32_t s = s0 + slot; s < s1; s += kSolveSlots) {   // UpdateBoneSkinningMatrix of this list
-                const uint32_t b = p.order[s];
-                const BoneRec rec = p.bones[b];
-                Mat4 G;
-#pragma unroll
-                for (int y = 0; y < 4; ++y)
-#pragma unroll
-                    for (int x = 0; x < 4; ++x) G.m[y][x] = x == y ? 1.f : 0.f;
-                G.m[3][0] = rec.neg_rest[0]; G.m[3][1] = rec.neg_rest[1]; G.m[3][2] = rec.neg_rest[2];
-                const Mat4 S = mul(G, st.local(b));
-#pragma unroll
-                for (int y = 0; y < 4; ++y) out[4 * size_t(b) + y] = make_float4(S.m[y][0], S.m[y][1], S.m[y][2], S.m[y][3]);
-            }
-        }
-        __syncthreads();                                     // the second list's IK may rewrite these bones
-    }
+    const uint32_t row = inst;
+#include "skeleton_ordered_body.inl"
+}
+// mmdx_skeleton_solve_select: the list is a kernel argument of its own, SerialParams is the plain kernel's with ni = the list's capacity.
+// A workgroup whose cells all lie behind the count leaves before the first barrier (the condition is the same in every lane); in a
+// workgroup that stays, dead lanes reach every barrier like the plain kernel's.
+template <bool NESTED, bool DENSE>
+__global__ __launch_bounds__(kSolveInstances * kSolveSlots, DENSE ? 2 : 1) void skeleton_ordered_select_kernel(const SerialParams p,
+                                                                                                                const InstanceList list) {
+    const uint32_t slot = threadIdx.x / kSolveInstances;
+    const ListedInstances sel = {list};
+    const uint32_t used = sel.used(p.ni);
+    if (blockIdx.x * kSolveInstances >= used) return;
+    const Lane ln = sel.lane(blockIdx.x * kSolveInstances + threadIdx.x % kSolveInstances, used);
+    const uint32_t inst = ln.cell, row = ln.row;
+    const bool live = ln.live;
+#include "skeleton_ordered_body.inl"
 }
 
 // ---- CCD-IK with SIXTEEN lanes per solve (round 4) ---------------------------------------------------------------------------------
@@ -1032,160 +1021,23 @@ __global__ __launch_bounds__(kCoopLanes * kCoopSolves) void ik_coop_kernel(const
     const uint32_t solve = threadIdx.x / kCoopLanes, sub = threadIdx.x % kCoopLanes;
     const uint32_t inst = iblk * kCoopSolves + solve;
     if (inst >= p.ni) return;                                  // (whole 16-lane groups leave: nothing below synchronises across groups)
-    const State st = {p.state + inst, p.ni};
-    const float4 *pose = reinterpret_cast<const float4 *>(p.poses) + size_t(inst) * p.nb * 2;
-    auto *win = (__attribute__((address_space(3))) float *)coop_lds + solve * kCoopWindow;
-    const ChainState cs = {win, 0};
-    const uint32_t b = p.events[rr.first + ev];
-    const IkRec ik = p.iks[p.bones[b].ik];
-    const LinkRec *links = p.links + ik.link0;
-    const uint32_t n = ik.nlinks, tidx = n;
-    const int32_t outside = ik.outside_parent;
-    const WindowChain ch = {win + kCoopConsts, n, outside >= 0 ? int32_t(n + 1) : -1};
-    auto group_sync = [] { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); };
-
-    // the event's own bone first, as the ordered kernel does (UpdateBoneTransform up to the solve), then the chain into the window
-    if (sub == 0) {
-        transform_bone(st, p, pose, inst, b);
-        win[kCoopMisc + 0] = st.at(b, kStLocal + 12); win[kCoopMisc + 1] = st.at(b, kStLocal + 13); win[kCoopMisc + 2] = st.at(b, kStLocal + 14);
-    }
-    auto copy = [&](uint32_t slot, uint32_t bone, bool in) {
-        for (uint32_t f = sub; f < kSerialStateFloats; f += kCoopLanes) {
-            if (in) cs.at(slot, f) = st.at(bone, f); else st.at(bone, f) = cs.at(slot, f);
-        }
-    };
-    for (uint32_t j = 0; j < n; ++j) copy(j, links[j].bone, true);
-    copy(n, ik.target, true);
-    if (outside >= 0) copy(n + 1, uint32_t(outside), true);
-    if (sub < n) {                                             // link constants, as solve_ik lays them out
-        const LinkRec lk = links[sub];
-        const float *off = p.bones[lk.bone].local_offset;
-        auto *c = win + kCoopConsts + sub * kLinkConstFloats;
-        c[0] = off[0]; c[1] = off[1]; c[2] = off[2];
-        c[3] = __uint_as_float(lk.limited | lk.order << 8 | lk.fix << 16);
-        c[4] = lk.lo[0]; c[5] = lk.lo[1]; c[6] = lk.lo[2];
-        c[7] = lk.hi[0]; c[8] = lk.hi[1]; c[9] = lk.hi[2];
-    }
-    group_sync();
-    const V3 ik_pos = {win[kCoopMisc + 0], win[kCoopMisc + 1], win[kCoopMisc + 2]};
-    const BoneRec trec = p.bones[ik.target];
-
-    // ccd()'s preamble on the window, one lane: the links root-first, the target, the convergence test; then what the loop keeps
-    if (sub == 0) {
-        for (uint32_t i = 0; i < n; ++i) cs.set_quat(ch.idx(i), kStIkRot, q_identity());
-        for (uint32_t i = 0; i < n; ++i) {
-            const uint32_t j = n - i - 1, lb = links[j].bone;
-            const BoneRec rec = p.bones[lb];
-            transform_at(cs, rec, morph_of(p, lb, inst), pose[2 * size_t(lb)], pose[2 * size_t(lb) + 1], ch.idx(j), ch.par(j),
-                         uint32_t(rec.append_parent));
-        }
-        transform_at(cs, trec, morph_of(p, ik.target, inst), pose[2 * size_t(ik.target)], pose[2 * size_t(ik.target) + 1], tidx, 0,
-                     uint32_t(trec.append_parent));
-        const V3 t0 = {cs.at(tidx, kStLocal + 12), cs.at(tidx, kStLocal + 13), cs.at(tidx, kStLocal + 14)};
-        const V3 e0 = {ik_pos.x - t0.x, ik_pos.y - t0.y, ik_pos.z - t0.z};
-        win[kCoopMisc + 3] = v_dot(e0, e0) < 1e-7f ? 0.f : 1.f;
-        auto pre_parent = [&](uint32_t idx, const float *off, uint32_t at) {       // a bone's local matrix before its parent product
-            Mat4 L = q_to_matrix(cs.quat(idx, kStTotalRot));
-            L.m[3][0] = cs.at(idx, kStTotalTr + 0) + off[0];
-            L.m[3][1] = cs.at(idx, kStTotalTr + 1) + off[1];
-            L.m[3][2] = cs.at(idx, kStTotalTr + 2) + off[2];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) win[at + k] = L.m[k / 4][k % 4];
-        };
-        for (uint32_t j = 0; j < n; ++j) {
-            const V3 off = ch.offset(j);
-            const float o[3] = {off.x, off.y, off.z};
-            pre_parent(j, o, kCoopLpre + j * 16);
-        }
-        pre_parent(tidx, trec.local_offset, kCoopTpre);
-    }
-    group_sync();
-    const bool run = win[kCoopMisc + 3] != 0.f;
-    if (run) {
-        const float tpre = win[kCoopTpre + sub];
-        V3 tgt = {cs.at(tidx, kStLocal + 12), cs.at(tidx, kStLocal + 13), cs.at(tidx, kStLocal + 14)};
-        const uint32_t ikt = ik.loop / 2;
-        for (uint32_t i = 0; i < ik.loop; ++i) {
-            bool changed = false;
-            for (uint32_t j = 0; j < n; ++j) {
-                const LinkInfo lk = ch.link(j);
-                if (lk.fix == kFixAll) continue;
-                const uint32_t ls = j;
-                const int32_t lp = ch.par(j);
-                const V3 lpos = {cs.at(ls, kStLocal + 12), cs.at(ls, kStLocal + 13), cs.at(ls, kStLocal + 14)};
-                const V3 tdir = v_normalize({lpos.x - tgt.x, lpos.y - tgt.y, lpos.z - tgt.z});
-                const V3 idir = v_normalize({lpos.x - ik_pos.x, lpos.y - ik_pos.y, lpos.z - ik_pos.z});
-                V3 axis = {tdir.y * idir.z - tdir.z * idir.y, tdir.z * idir.x - tdir.x * idir.z,
-                           tdir.x * idir.y - tdir.y * idir.x};
-                if (fabsf(axis.x) < 1e-7f) axis.x = 1e-7f;
-                if (fabsf(axis.y) < 1e-7f) axis.y = 1e-7f;
-                if (fabsf(axis.z) < 1e-7f) axis.z = 1e-7f;
-                // the parent's matrix: this lane's element for the product below, the rotation part whole for the axis
-                const float loc = lp >= 0 ? cs.at(uint32_t(lp), kStLocal + sub) : (sub % 5u == 0u ? 1.f : 0.f);
-                auto L = [&](uint32_t y, uint32_t x) { return lp >= 0 ? cs.at(uint32_t(lp), kStLocal + 4 * y + x) : (x == y ? 1.f : 0.f); };
-                if (lk.limited && lk.fix != kFixNone && i < ikt) {
-                    const uint32_t row = lk.fix - kFixX;
-                    const float d = axis.x * L(row, 0) + axis.y * L(row, 1) + axis.z * L(row, 2);
-                    const float sgn = d >= 0.0f ? 1.0f : -1.0f;
-                    axis = {row == 0 ? sgn : 0.f, row == 1 ? sgn : 0.f, row == 2 ? sgn : 0.f};
-                } else {                                       // rotate(axis, loc.Transpose()).Normalize()
-                    const V3 r = {axis.x * L(0, 0) + axis.y * L(0, 1) + axis.z * L(0, 2),
-                                  axis.x * L(1, 0) + axis.y * L(1, 1) + axis.z * L(1, 2),
-                                  axis.x * L(2, 0) + axis.y * L(2, 1) + axis.z * L(2, 2)};
-                    axis = v_normalize(r);
-                }
-                float dot = v_dot(tdir, idir);
-                dot = dot < -1.0f ? -1.0f : dot;
-                dot = 1.0f < dot ? 1.0f : dot;
-                const float ac = d_acos(dot), cap = ik.angle_limit * float(j + 1);
-                const float angle = cap < ac ? cap : ac;
-                const Quat ikr_old = cs.quat(ls, kStIkRot);
-                Quat ikr = q_mul(axis_to_quat(axis, angle), ikr_old);
-                const Quat pre = cs.quat(ls, kStPreIkRot);
-                if (lk.limited) {
-                    Quat lr = q_mul(ikr, pre);
-                    float e[3];
-                    quat_to_euler_coop(lk.order, lr, e, sub);
-                    limit_euler(e, lk.lo, lk.hi, i < ikt);
-                    lr = euler_to_quat_coop(lk.order, e, sub);
-                    ikr = q_mul(lr, q_inverse(pre));
-                }
-                changed = changed || __float_as_uint(ikr.i) != __float_as_uint(ikr_old.i) || __float_as_uint(ikr.j) != __float_as_uint(ikr_old.j) ||
-                          __float_as_uint(ikr.k) != __float_as_uint(ikr_old.k) || __float_as_uint(ikr.e) != __float_as_uint(ikr_old.e);
-                // the link just turned: ik_rotation * pre-IK rotation, as the reference; its matrix before the parent product
-                const Quat total = q_mul(ikr, pre);
-                Mat4 M = q_to_matrix(total);
-                const V3 off = ch.offset(j);
-                M.m[3][0] = cs.at(ls, kStTotalTr + 0) + off.x;
-                M.m[3][1] = cs.at(ls, kStTotalTr + 1) + off.y;
-                M.m[3][2] = cs.at(ls, kStTotalTr + 2) + off.z;
-                const float mine = pick16(M, sub);
-                group_sync();                                  // every lane has read what the stores below replace
-                if (sub == 0) { cs.set_quat(ls, kStIkRot, ikr); cs.set_quat(ls, kStTotalRot, total); }
-                win[kCoopLpre + ls * 16 + sub] = mine;
-                float prev = lp >= 0 ? coop_mul(mine, loc) : mine;
-                cs.at(ls, kStLocal + sub) = prev;
-                for (uint32_t k = 1; k <= j; ++k) {            // below it nothing changed: the cached matrix IS the recomputed one
-                    const uint32_t jj = j - k;
-                    prev = coop_mul(win[kCoopLpre + jj * 16 + sub], prev);
-                    cs.at(jj, kStLocal + sub) = prev;
-                }
-                const float T = coop_mul(tpre, prev);          // the target hangs off link 0, the last one placed
-                cs.at(tidx, kStLocal + sub) = T;
-                tgt = {lane_of_group<12>(T), lane_of_group<13>(T), lane_of_group<14>(T)};
-                group_sync();                                  // the next link step reads the matrices just stored
-            }
-            const V3 err = {ik_pos.x - tgt.x, ik_pos.y - tgt.y, ik_pos.z - tgt.z};
-            if (v_dot(err, err) < 1e-7f) break;
-            if (!changed) {
-                if (i >= ikt) break;
-                i = ikt - 1;
-            }
-        }
-    }
-    group_sync();
-    for (uint32_t j = 0; j < n; ++j) copy(j, links[j].bone, false);
-    copy(n, ik.target, false);
+    const uint32_t row = inst;
+#include "ik_coop_body.inl"
+}
+// ... for the listed instances: a block is 16 consecutive list positions, p.ni the list's capacity
+__global__ __launch_bounds__(kCoopLanes * kCoopSolves) void ik_coop_select_kernel(const SerialParams p, const uint32_t round,
+                                                                                  const InstanceList list) {
+    extern __shared__ float coop_lds[];
+    const RoundRec rr = p.rounds[round];
+    const uint32_t nblk = (p.ni + kCoopSolves - 1) / kCoopSolves;
+    const uint32_t ev = blockIdx.x / nblk, iblk = blockIdx.x - ev * nblk;       // which IK bone of the round, which 16 list positions
+    if (ev >= rr.count) return;
+    const uint32_t solve = threadIdx.x / kCoopLanes, sub = threadIdx.x % kCoopLanes;
+    const ListedInstances sel = {list};
+    const Lane ln = sel.lane(iblk * kCoopSolves + solve, sel.used(p.ni));
+    if (!ln.live) return;                                      // (whole 16-lane groups leave, as above)
+    const uint32_t inst = ln.cell, row = ln.row;
+#include "ik_coop_body.inl"
 }
 
 // Matrix4x4<T>::Inverse(), L/util/math_impl.inl:822-897: Gauss-Jordan on [M | I] with scaled partial pivoting (a zero
@@ -1334,6 +1186,14 @@ hipError_t launch_skeleton_fk(const SkeletonParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+hipError_t launch_skeleton_fk_select(const SkeletonParams &p, const InstanceList &list, hipStream_t stream) {
+    const size_t n = size_t(p.ni) * p.nb;                      // p.ni: the list's capacity
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(skeleton_fk_select_kernel, dim3(uint32_t((n + kRigThreads - 1) / kRigThreads)),
+                       dim3(kRigThreads), 0, stream, p, list);
+    return hipGetLastError();
+}
+
 hipError_t launch_motion_fk(const BoneTrackParams &t, const SkeletonParams &p, hipStream_t stream) {
     if (p.ni == 0 || p.nb == 0) return hipSuccess;
     const size_t lds = size_t(p.nb) * 32;
@@ -1379,12 +1239,21 @@ hipError_t launch_bone_morph(const BoneMorphParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-static hipError_t launch_ordered_segment(const SerialParams &p, hipStream_t stream);
+hipError_t launch_bone_morph_select(const BoneMorphParams &p, const InstanceList &list, hipStream_t stream) {
+    if (p.ni == 0 || p.nb == 0) return hipSuccess;             // p.ni: the list's capacity
+    hipLaunchKernelGGL(bone_morph_select_kernel, dim3((p.ni + kBoneMorphThreads - 1) / kBoneMorphThreads), dim3(kBoneMorphThreads), 0,
+                       stream, p, list);
+    return hipGetLastError();
+}
+
+// `list` == nullptr: the plain kernels; else their select forms, the list as one more kernel argument.  Either way the launches
+// are sized from p.ni, the number of state cells: the instances of a plain call, the list's capacity of a select call.
+static hipError_t launch_ordered_segment(const SerialParams &p, const InstanceList *list, hipStream_t stream);
 
 // The whole schedule.  Rounds that consist of window-chain IK solves only (`round_coop`, host array of p.n_rounds entries: the
 // round's number of solves, 0 for every other round; nullptr: none) go to ik_coop_kernel, sixteen lanes per solve; the rounds between them to the ordered kernel, segment by segment:
 // a handful of dependent launches (~2 us each) around solves that take milliseconds on one lane.  MMDX_IK_COOP=0: one launch, as before.
-hipError_t launch_skeleton_ordered(const SerialParams &p0, const uint8_t *round_coop, hipStream_t stream) {
+static hipError_t launch_ordered(const SerialParams &p0, const uint8_t *round_coop, const InstanceList *list, hipStream_t stream) {
     if (p0.ni == 0 || p0.nb == 0) return hipSuccess;
     SerialParams p = p0;
     const int coop_env = env_int("MMDX_IK_COOP", 1);        // (read per call: an IK launch is milliseconds, tests flip it in one process)
@@ -1392,7 +1261,7 @@ hipError_t launch_skeleton_ordered(const SerialParams &p0, const uint8_t *round_
     for (uint32_t r = 0; round_coop && coop_env != 0 && !p.nested && r < p.n_rounds; ++r) any = any || round_coop[r];
     if (!any) {
         p.seg_r0 = 0; p.seg_r1 = p.n_rounds; p.seg_flags = 7u;
-        return launch_ordered_segment(p, stream);
+        return launch_ordered_segment(p, list, stream);
     }
     bool first = true;
     auto segment = [&](uint32_t a, uint32_t b, uint32_t flags) -> hipError_t {
@@ -1400,7 +1269,7 @@ hipError_t launch_skeleton_ordered(const SerialParams &p0, const uint8_t *round_
         if (a >= b && !flags) return hipSuccess;
         first = false;
         p.seg_r0 = a; p.seg_r1 = b; p.seg_flags = flags;
-        return launch_ordered_segment(p, stream);
+        return launch_ordered_segment(p, list, stream);
     };
     for (uint32_t pass = 0; pass < 2; ++pass) {
         if (!(p.passes >> pass & 1u)) continue;
@@ -1411,8 +1280,10 @@ hipError_t launch_skeleton_ordered(const SerialParams &p0, const uint8_t *round_
             hipError_t e = segment(a, r, 0u);
             if (e != hipSuccess) return e;
             const uint32_t nblk = (p.ni + kCoopSolves - 1) / kCoopSolves;
-            hipLaunchKernelGGL(ik_coop_kernel, dim3(nblk * round_coop[r]), dim3(kCoopLanes * kCoopSolves), kCoopWindow * kCoopSolves * sizeof(float),
-                               stream, p, r);
+            const dim3 grid(nblk * round_coop[r]), block(kCoopLanes * kCoopSolves);
+            const size_t lds = kCoopWindow * kCoopSolves * sizeof(float);
+            if (list) hipLaunchKernelGGL(ik_coop_select_kernel, grid, block, lds, stream, p, r, *list);
+            else hipLaunchKernelGGL(ik_coop_kernel, grid, block, lds, stream, p, r);
             if ((e = hipGetLastError()) != hipSuccess) return e;
             a = r + 1;
         }
@@ -1422,7 +1293,14 @@ hipError_t launch_skeleton_ordered(const SerialParams &p0, const uint8_t *round_
     return hipSuccess;
 }
 
-static hipError_t launch_ordered_segment(const SerialParams &p, hipStream_t stream) {
+hipError_t launch_skeleton_ordered(const SerialParams &p, const uint8_t *round_coop, hipStream_t stream) {
+    return launch_ordered(p, round_coop, nullptr, stream);
+}
+hipError_t launch_skeleton_ordered_select(const SerialParams &p, const uint8_t *round_coop, const InstanceList &list, hipStream_t stream) {
+    return launch_ordered(p, round_coop, &list, stream);
+}
+
+static hipError_t launch_ordered_segment(const SerialParams &p, const InstanceList *list, hipStream_t stream) {
     if (p.ni == 0 || p.nb == 0) return hipSuccess;
     const size_t lds = (size_t(window_floats(p.fast_slots)) * p.windows * kSolveInstances +
                         size_t(p.windows) * kMaxFastLinks * kLinkConstFloats) * sizeof(float);
@@ -1444,15 +1322,21 @@ static hipError_t launch_ordered_segment(const SerialParams &p, hipStream_t stre
         }
         dense = dense_env != 0 && wgs > uint32_t(cus);
     }
-    auto kernel = p.nested ? skeleton_ordered_kernel<true, false>
-                           : (dense ? skeleton_ordered_kernel<false, true> : skeleton_ordered_kernel<false, false>);
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(kSolveInstances * kSolveSlots), lds, stream, p);
-    return hipGetLastError();
+    auto launch = [&](auto kernel, auto... more) -> hipError_t {
+        if (lds > 64 * 1024) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(kernel, dim3(wgs), dim3(kSolveInstances * kSolveSlots), lds, stream, p, more...);
+        return hipGetLastError();
+    };
+    if (list)
+        return launch(p.nested ? skeleton_ordered_select_kernel<true, false>
+                               : (dense ? skeleton_ordered_select_kernel<false, true> : skeleton_ordered_select_kernel<false, false>),
+                      *list);
+    return launch(p.nested ? skeleton_ordered_kernel<true, false>
+                           : (dense ? skeleton_ordered_kernel<false, true> : skeleton_ordered_kernel<false, false>));
 }
 
 }  // namespace mmdx

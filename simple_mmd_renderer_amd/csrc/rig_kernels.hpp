@@ -26,6 +26,16 @@ hipError_t launch_motion_fk_blend_set(const BoneTrackParams &t, const SkeletonPa
 hipError_t launch_skeleton_ordered(const SerialParams &p, const uint8_t *round_coop /* host, [n_rounds] or nullptr */, hipStream_t stream);
 hipError_t launch_bone_morph(const BoneMorphParams &p, hipStream_t stream);
 hipError_t launch_physics_override(const PhysicsParams &p, hipStream_t stream);
+// mmdx_skeleton_solve_select: the select forms of the one-step solve's kernels.  Their parameter blocks are the plain ones with
+// ni = the list's CAPACITY (state and bone-morph cells are per list position); the list travels as a kernel argument of its own.
+struct InstanceList {
+    const uint32_t *ids;                        // [capacity], device memory
+    const uint32_t *count;                      // device memory; the first min(*count, capacity) ids are used; nullptr = all
+    uint32_t n_rows;                            // NI: rows of poses / rates / palettes; an id >= n_rows is skipped
+};
+hipError_t launch_skeleton_fk_select(const SkeletonParams &p, const InstanceList &list, hipStream_t stream);
+hipError_t launch_bone_morph_select(const BoneMorphParams &p, const InstanceList &list, hipStream_t stream);
+hipError_t launch_skeleton_ordered_select(const SerialParams &p, const uint8_t *round_coop, const InstanceList &list, hipStream_t stream);
 
 // api.cpp: the device and stream a motion / rig call runs on -- the model's own when a (device) model
 // is given, so that the deform call that follows is ordered after it; else the selected device's

@@ -407,6 +407,20 @@ public:
         a.flags = flags(on_device);
         check(mmdx_skeleton_solve_motion_set_blend_time(poser_.skeleton(), set_, poser_.handle(), &a, out_palettes));
     }
+    // The bone solve for a listed subset of the crowd (mmdx.h, mmdx_skeleton_solve_select): out_palettes[i] for the first *count
+    // (NULL = n_ids) instances i of ids, bit for bit what the plain solve writes; every other row keeps its bytes.  poses [n][bones][8],
+    // morph_rates [n][morphs] (or NULL) and out_palettes [n][bones][16] are device memory; ids / count are device memory too (what
+    // mmdx_cull_bounds wrote; asynchronous on the poser's stream) or, with list_on_device = false, host memory.
+    void SolveSelect(uint32_t n, const float *poses, const float *morph_rates, const uint32_t *ids, const uint32_t *count, uint32_t n_ids,
+                     float *out_palettes, bool list_on_device = true) {
+        mmdx_instance_select s{};
+        s.struct_size = sizeof(s);
+        s.flags = list_on_device ? uint32_t(MMDX_SELECT_ON_DEVICE) : 0u;
+        s.ids = ids; s.count = count; s.n_ids = n_ids;
+        check(mmdx_skeleton_solve_select(poser_.skeleton(), poser_.handle(), n, poses, morph_rates,
+                                         MMDX_POSES_ON_DEVICE | MMDX_OUT_ON_DEVICE | (morph_rates ? uint32_t(MMDX_WEIGHTS_ON_DEVICE) : 0u),
+                                         &s, out_palettes));
+    }
     // Where every instance stands (mmdx.h, mmdx_palette_place): out_palettes[i][bone] = palettes[i][bone] * W[i], W[i] from the pose
     // {tx, ty, tz, 0, qx, qy, qz, qw} at placements + 8 * i ("a world bone") or, with matrix = true, the 16 floats at placements +
     // 16 * i -- the layout of the viewer's g_state.model_matrix.  out_palettes may be palettes (in place).  Host arrays by default;

@@ -568,6 +568,56 @@ class Skeleton:
         api.check(api.lib().mmdx_skeleton_solve_morphed(self.h, model.h if model is not None else None, n_instances,
                                                         poses_ptr, weights_ptr, flags, out_ptr))
 
+    # -- the solve for a listed subset of the crowd (mmdx_skeleton_solve_select) --------------------------------------
+    def solve_select_device(self, n_instances: int, poses_ptr, out_ptr, ids_ptr, n_ids: int, count_ptr=None, model=None,
+                            weights_ptr=None, shared=False, select_on_device=True) -> None:
+        """poses, palettes (and morph rates) resident in HBM, [n_instances] rows each; only the instances in the u32 list at
+        ids_ptr (capacity n_ids, the first *count_ptr in use; count_ptr None = all n_ids) are solved, every other palette row
+        keeps its bytes.  List and count in device memory (asynchronous on the model's stream) or, with select_on_device=False,
+        in host memory (the call returns when its work is done)."""
+        flags = POSES_ON_DEVICE | api.OUT_ON_DEVICE | (api.WEIGHTS_ON_DEVICE if weights_ptr else 0) | \
+            (api.WEIGHTS_SHARED if shared else 0)
+        s = api.InstanceSelect()
+        s.struct_size = C.sizeof(api.InstanceSelect)
+        s.flags = api.SELECT_ON_DEVICE if select_on_device else 0
+        s.ids, s.count, s.n_ids = ids_ptr, count_ptr, n_ids
+        api.check(api.lib().mmdx_skeleton_solve_select(self.h, model.h if model is not None else None, n_instances, poses_ptr,
+                                                       weights_ptr, flags, C.byref(s), out_ptr))
+
+    def solve_select(self, poses, ids, count=None, model=None, morph_weights=None, out=None) -> np.ndarray:
+        """Host convenience: uploads poses [NI, NB, 8] (+ rates [NI, NM] or shared [NM]), the id list and `out` (the palettes
+        [NI, NB, 16] as they stand before the call; zeros when None), solves the first `count` (None = all) listed instances
+        and downloads the WHOLE palette array, so the rows the call must not touch can be looked at."""
+        from .engine import DeviceBuffer
+        p = np.ascontiguousarray(poses, np.float32).reshape(-1, self.nb, POSE_FLOATS)
+        ni = p.shape[0]
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        before = np.zeros((ni, self.nb, 16), np.float32) if out is None else np.ascontiguousarray(out, np.float32)
+        assert before.shape == (ni, self.nb, 16)
+        bufs = [DeviceBuffer.from_numpy(p), DeviceBuffer.from_numpy(before), DeviceBuffer(max(ids.nbytes, 4))]
+        d_pose, d_out, d_ids = bufs
+        if ids.size:
+            d_ids.upload(ids)
+        d_cnt = d_w = None
+        if count is not None:
+            d_cnt = DeviceBuffer.from_numpy(np.array([count], np.uint32))
+            bufs.append(d_cnt)
+        shared = False
+        if morph_weights is not None:
+            w = np.ascontiguousarray(morph_weights, np.float32)
+            shared = w.ndim == 1
+            assert w.shape[-1] == self.nm and (shared or w.shape[0] == ni)
+            d_w = DeviceBuffer.from_numpy(w)
+            bufs.append(d_w)
+        try:
+            self.solve_select_device(ni, d_pose.ptr, d_out.ptr, d_ids.ptr, ids.size, d_cnt.ptr if d_cnt else None, model,
+                                     d_w.ptr if d_w else None, shared)
+            api.check(api.lib().mmdx_sync(model.h) if model is not None else api.lib().mmdx_device_synchronize())
+            return d_out.download((ni, self.nb, 16), np.float32)
+        finally:
+            for b in bufs:
+                b.free()
+
     def close(self):
         if getattr(self, "h", None):
             api.lib().mmdx_skeleton_destroy(self.h)
