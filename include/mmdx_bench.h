@@ -3,7 +3,7 @@
  * NOT part of the drop-in boundary (include/mmdx.h): nothing in the reference corresponds to these.  They exist
  * for bench.py, tools/ and the GPU tests: HIP-event timers on a model's stream, per-kernel profiling of
  * mmdx_deform_batched, the streaming copy / fill / store-pattern ceilings printed next to the roofline
- * (SURVEY.md section 8d), the re-read of the launch-shape override environment and the record of the last launch shape.  Same
+ * (SURVEY.md section 8d), the re-read of the launch-shape override environment and the records of the last launch shape and the last solve shape.  Same
  * library, same status codes.
  */
 #ifndef MMDX_BENCH_H_INCLUDED
@@ -68,6 +68,30 @@ typedef struct mmdx_debug_launch_shape {
     uint32_t reserved0;
 } mmdx_debug_launch_shape;
 MMDX_API mmdx_status mmdx_debug_last_launch_shape(mmdx_model_t model, mmdx_debug_launch_shape *out);
+/* What the skeleton's last successful solve launched (mmdx_skeleton_solve and every call that ends in it, _solve_morphed, _solve_pre,
+ * _solve_post, _solve_select, _solve_motion*): tests read it to prove which compilation of the ordered bone solver they ran -- the
+ * two-workgroups-per-CU one (`dense`) is chosen by crowd size on its own (more workgroups than the device has CUs) and forced or
+ * forbidden by MMDX_SOLVE_DENSE=1 / 0, read per call.  Read-only host state: nothing here reaches a kernel.  A select call with an
+ * empty list launches nothing and leaves the record as it was. */
+typedef enum mmdx_debug_solver {
+    MMDX_DEBUG_SOLVER_NONE = 0,        /* no solve yet */
+    MMDX_DEBUG_SOLVER_ORDERED = 1,     /* the ordered solver (append bones, IK, physics seam): the fields below describe it */
+    MMDX_DEBUG_SOLVER_PARALLEL_FK = 2  /* parallel FK (also fused with the motion evaluation): every field below is 0 */
+} mmdx_debug_solver;
+typedef struct mmdx_debug_solve_shape {
+    uint32_t struct_size;            /* sizeof(mmdx_debug_solve_shape), set by the caller */
+    uint32_t solver;                 /* mmdx_debug_solver */
+    uint32_t nested;                 /* the nested-IK compilation (never dense) */
+    uint32_t dense;                  /* the two-workgroups-per-CU compilation */
+    uint32_t select;                 /* the select form (mmdx_skeleton_solve_select) */
+    uint32_t workgroups;             /* of each ordered-segment launch: ceil(state cells / 16); the cells are the instances, of a
+                                        select call the list's capacity (device list) or its ids in use (host list) */
+    uint32_t lds;                    /* bytes of dynamic LDS of those launches */
+    uint32_t segments;               /* ordered-segment launches of the call (1 unless ik_coop rounds cut the schedule) */
+    uint32_t coop_launches;          /* ik_coop launches of the call (0 under MMDX_IK_COOP=0, on nested rigs, without window chains) */
+    uint32_t reserved0;
+} mmdx_debug_solve_shape;
+MMDX_API mmdx_status mmdx_debug_last_solve_shape(mmdx_skeleton_t skeleton, mmdx_debug_solve_shape *out);
 /* What became of the model's shared morph passes so far (mmdx.h, MMDX_MORPH_UNCHANGED): launches that walked the morph table,
  * launches whose device-side comparison found the rates unchanged and skipped the walk, and calls whose host-side comparison
  * skipped the launch altogether.  Waits for the model's stream. */

@@ -114,6 +114,16 @@ class DebugLaunchShape(C.Structure):
 DEBUG_KERNELS = ("none", "deform", "pack", "frame", "cull")      # mmdx_debug_kernel
 
 
+class DebugSolveShape(C.Structure):
+    """mmdx_debug_solve_shape (include/mmdx_bench.h): what a skeleton's last solve launched."""
+    _fields_ = [("struct_size", C.c_uint32), ("solver", C.c_uint32), ("nested", C.c_uint32), ("dense", C.c_uint32),
+                ("select", C.c_uint32), ("workgroups", C.c_uint32), ("lds", C.c_uint32), ("segments", C.c_uint32),
+                ("coop_launches", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
+DEBUG_SOLVERS = ("none", "ordered", "parallel_fk")               # mmdx_debug_solver
+
+
 class MmdxError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"mmdx error {status} ({ERR_NAMES.get(status, '?')}): {message}")
@@ -160,6 +170,7 @@ SIGNATURES = {
     "mmdx_debug_reload_env": (None, []),
     "mmdx_debug_last_store_policy": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
     "mmdx_debug_last_launch_shape": (C.c_int32, [C.c_void_p, C.POINTER(DebugLaunchShape)]),
+    "mmdx_debug_last_solve_shape": (C.c_int32, [C.c_void_p, C.POINTER(DebugSolveShape)]),
     "mmdx_debug_morph_pass_stats": (C.c_int32, [C.c_void_p, _u32p, _u32p, _u32p]),
     "mmdx_build_source_sha": (C.c_char_p, []),
     "mmdx_bench_copy": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, _f32p]),

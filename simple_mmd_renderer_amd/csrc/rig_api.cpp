@@ -10,12 +10,14 @@
 #include <vector>
 
 #include "../../include/mmdx.h"
+#include "../../include/mmdx_bench.h"
 #include "error.hpp"
 #include "graph_pin.hpp"
 #include "kernels.hpp"
 #include "motion_blend.hpp"
 #include "rig.hpp"
 #include "rig_kernels.hpp"
+#include "solve_shape.hpp"
 #include "vmd.hpp"
 
 using namespace mmdx;
@@ -78,6 +80,7 @@ struct mmdx_skeleton_s {
     uint32_t pre_instances = 0;                           // instances of the last mmdx_skeleton_solve_pre (0: none pending)
     const float *pre_poses = nullptr;                     // the poses that call solved (device address)
     const float *pre_morph = nullptr;
+    SolveShape last_solve;                                // what the last successful solve launched (mmdx_debug_last_solve_shape)
     GraphPin pin;                                         // recorded graphs that hold these buffers' addresses
     mmdx_skeleton_s() {
         for (Buf *b : {&local_offset, &neg_rest, &chain_off, &chain, &poses_in, &out, &order, &bones, &iks, &links, &events, &rounds,
@@ -284,6 +287,16 @@ mmdx_status mmdx_skeleton_get_info(mmdx_skeleton_t s, mmdx_skeleton_info *info) 
     info->n_solve_rounds = uint32_t(s->plan.rounds.size());
     info->n_ik_rounds_16_lanes = 0;
     for (uint8_t c : s->plan.round_coop) info->n_ik_rounds_16_lanes += (c && !s->plan.nested_ik) ? 1u : 0u;
+    return MMDX_OK;
+}
+
+mmdx_status mmdx_debug_last_solve_shape(mmdx_skeleton_t s, mmdx_debug_solve_shape *out) {
+    if (!s || !out) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (out->struct_size != sizeof(mmdx_debug_solve_shape))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_debug_solve_shape.struct_size mismatch");
+    const SolveShape &l = s->last_solve;
+    *out = mmdx_debug_solve_shape{sizeof(mmdx_debug_solve_shape), l.solver, l.nested, l.dense, l.select, l.workgroups, l.lds,
+                                  l.segments, l.coop_launches, 0u};
     return MMDX_OK;
 }
 
@@ -546,7 +559,7 @@ static mmdx_status skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_
             HIP_TRY(launch_physics_override(pp, st));
         }
         (void)borrowed_over;
-        HIP_TRY(launch_skeleton_ordered(sp, pl.round_coop.empty() ? nullptr : pl.round_coop.data(), st));
+        HIP_TRY(launch_skeleton_ordered(sp, pl.round_coop.empty() ? nullptr : pl.round_coop.data(), st, &s->last_solve));
         if (passes == 1u) { s->pre_instances = n_instances; s->pre_poses = p.poses; s->pre_morph = morph_state; }
         else s->pre_instances = 0;
     } else {
@@ -559,6 +572,7 @@ static mmdx_status skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_
         fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
         fp.nb = pl.nb; fp.ni = n_instances;
         HIP_TRY(launch_skeleton_fk(fp, st));
+        s->last_solve = SolveShape{}; s->last_solve.solver = 2;
     }
     if (!(flags & MMDX_OUT_ON_DEVICE)) {
         if (out_bytes) HIP_TRY(hipMemcpyAsync(out_palettes, p.out, out_bytes, hipMemcpyDeviceToHost, st));
@@ -661,7 +675,7 @@ static mmdx_status skeleton_solve_select(mmdx_skeleton_t s, mmdx_model_t model, 
         sp.windows = pl.windows;
         sp.passes = 3u;
         sp.nested = pl.nested_ik ? 1u : 0u;
-        HIP_TRY(launch_skeleton_ordered_select(sp, pl.round_coop.empty() ? nullptr : pl.round_coop.data(), list, st));
+        HIP_TRY(launch_skeleton_ordered_select(sp, pl.round_coop.empty() ? nullptr : pl.round_coop.data(), list, st, &s->last_solve));
         s->pre_instances = 0;                                       // (the scratch a pending pre step left is gone, as after mmdx_skeleton_solve)
     } else {
         SkeletonParams fp;
@@ -673,6 +687,7 @@ static mmdx_status skeleton_solve_select(mmdx_skeleton_t s, mmdx_model_t model, 
         fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
         fp.nb = pl.nb; fp.ni = cells;
         HIP_TRY(launch_skeleton_fk_select(fp, list, st));
+        s->last_solve = SolveShape{}; s->last_solve.solver = 2;
     }
     if (host_list) HIP_TRY(wait_stream(st));                        // the borrowed list is consumed and the results are there
     return MMDX_OK;
@@ -772,6 +787,7 @@ static mmdx_status skeleton_solve_motion(mmdx_skeleton_t s, mmdx_bone_motion_t m
     fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
     fp.nb = pl.nb; fp.ni = n_instances;
     HIP_TRY(launch_motion_fk(tp, fp, st));
+    s->last_solve = SolveShape{}; s->last_solve.solver = 2;
     if (!(flags & MMDX_OUT_ON_DEVICE)) {
         HIP_TRY(hipMemcpyAsync(out_palettes, fp.out, out_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(wait_stream(st));
@@ -986,6 +1002,7 @@ static mmdx_status skeleton_solve_motion_set(mmdx_skeleton_t s, mmdx_motion_set_
     fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
     fp.nb = pl.nb; fp.ni = n_instances;
     HIP_TRY(launch_motion_fk_set(tp, fp, dev_clips, set->host.n_clips, st));
+    s->last_solve = SolveShape{}; s->last_solve.solver = 2;
     if (!(flags & MMDX_OUT_ON_DEVICE)) {
         HIP_TRY(hipMemcpyAsync(out_palettes, fp.out, out_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(wait_stream(st));
@@ -1165,5 +1182,6 @@ static mmdx_status skeleton_solve_motion_set_blend(mmdx_skeleton_t s, mmdx_motio
     fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
     fp.nb = pl.nb; fp.ni = ni;
     HIP_TRY(launch_motion_fk_blend_set(tp, fp, o, st));
+    s->last_solve = SolveShape{}; s->last_solve.solver = 2;
     return blend_finish(a->flags, st, out_palettes, fp.out, out_bytes);
 }

@@ -9,6 +9,7 @@
 #include "motion_clock.hpp"
 #include "rig.hpp"
 #include "rig_kernels.hpp"
+#include "solve_shape.hpp"
 
 #include <atomic>
 
@@ -1248,12 +1249,13 @@ hipError_t launch_bone_morph_select(const BoneMorphParams &p, const InstanceList
 
 // `list` == nullptr: the plain kernels; else their select forms, the list as one more kernel argument.  Either way the launches
 // are sized from p.ni, the number of state cells: the instances of a plain call, the list's capacity of a select call.
-static hipError_t launch_ordered_segment(const SerialParams &p, const InstanceList *list, hipStream_t stream);
+static hipError_t launch_ordered_segment(const SerialParams &p, const InstanceList *list, hipStream_t stream, SolveShape &shape);
 
 // The whole schedule.  Rounds that consist of window-chain IK solves only (`round_coop`, host array of p.n_rounds entries: the
 // round's number of solves, 0 for every other round; nullptr: none) go to ik_coop_kernel, sixteen lanes per solve; the rounds between them to the ordered kernel, segment by segment:
 // a handful of dependent launches (~2 us each) around solves that take milliseconds on one lane.  MMDX_IK_COOP=0: one launch, as before.
-static hipError_t launch_ordered(const SerialParams &p0, const uint8_t *round_coop, const InstanceList *list, hipStream_t stream) {
+static hipError_t launch_ordered_rounds(const SerialParams &p0, const uint8_t *round_coop, const InstanceList *list, hipStream_t stream,
+                                        SolveShape &shape) {
     if (p0.ni == 0 || p0.nb == 0) return hipSuccess;
     SerialParams p = p0;
     const int coop_env = env_int("MMDX_IK_COOP", 1);        // (read per call: an IK launch is milliseconds, tests flip it in one process)
@@ -1261,7 +1263,7 @@ static hipError_t launch_ordered(const SerialParams &p0, const uint8_t *round_co
     for (uint32_t r = 0; round_coop && coop_env != 0 && !p.nested && r < p.n_rounds; ++r) any = any || round_coop[r];
     if (!any) {
         p.seg_r0 = 0; p.seg_r1 = p.n_rounds; p.seg_flags = 7u;
-        return launch_ordered_segment(p, list, stream);
+        return launch_ordered_segment(p, list, stream, shape);
     }
     bool first = true;
     auto segment = [&](uint32_t a, uint32_t b, uint32_t flags) -> hipError_t {
@@ -1269,7 +1271,7 @@ static hipError_t launch_ordered(const SerialParams &p0, const uint8_t *round_co
         if (a >= b && !flags) return hipSuccess;
         first = false;
         p.seg_r0 = a; p.seg_r1 = b; p.seg_flags = flags;
-        return launch_ordered_segment(p, list, stream);
+        return launch_ordered_segment(p, list, stream, shape);
     };
     for (uint32_t pass = 0; pass < 2; ++pass) {
         if (!(p.passes >> pass & 1u)) continue;
@@ -1285,6 +1287,7 @@ static hipError_t launch_ordered(const SerialParams &p0, const uint8_t *round_co
             if (list) hipLaunchKernelGGL(ik_coop_select_kernel, grid, block, lds, stream, p, r, *list);
             else hipLaunchKernelGGL(ik_coop_kernel, grid, block, lds, stream, p, r);
             if ((e = hipGetLastError()) != hipSuccess) return e;
+            ++shape.coop_launches;
             a = r + 1;
         }
         const hipError_t e = segment(a, r1, 2u << pass);
@@ -1293,35 +1296,48 @@ static hipError_t launch_ordered(const SerialParams &p0, const uint8_t *round_co
     return hipSuccess;
 }
 
-hipError_t launch_skeleton_ordered(const SerialParams &p, const uint8_t *round_coop, hipStream_t stream) {
-    return launch_ordered(p, round_coop, nullptr, stream);
-}
-hipError_t launch_skeleton_ordered_select(const SerialParams &p, const uint8_t *round_coop, const InstanceList &list, hipStream_t stream) {
-    return launch_ordered(p, round_coop, &list, stream);
+// `shape_out` (may be nullptr) receives what was launched, once every launch of the call has succeeded.
+static hipError_t launch_ordered(const SerialParams &p0, const uint8_t *round_coop, const InstanceList *list, hipStream_t stream,
+                                 SolveShape *shape_out) {
+    SolveShape shape;
+    shape.solver = 1; shape.nested = p0.nested ? 1u : 0u; shape.select = list ? 1u : 0u;
+    const hipError_t e = launch_ordered_rounds(p0, round_coop, list, stream, shape);
+    if (e == hipSuccess && shape_out) *shape_out = shape;
+    return e;
 }
 
-static hipError_t launch_ordered_segment(const SerialParams &p, const InstanceList *list, hipStream_t stream) {
+hipError_t launch_skeleton_ordered(const SerialParams &p, const uint8_t *round_coop, hipStream_t stream, SolveShape *shape) {
+    return launch_ordered(p, round_coop, nullptr, stream, shape);
+}
+hipError_t launch_skeleton_ordered_select(const SerialParams &p, const uint8_t *round_coop, const InstanceList &list, hipStream_t stream,
+                                          SolveShape *shape) {
+    return launch_ordered(p, round_coop, &list, stream, shape);
+}
+
+// CU count of the current device, asked once per device and process (two runtime calls per IK launch otherwise)
+static uint32_t cached_cu_count() {
+    static std::atomic<int> cu_count[16] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+    int cus = dev >= 0 && dev < 16 ? cu_count[dev].load(std::memory_order_relaxed) : 0;
+    if (cus == 0) {
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
+            (void)hipGetLastError();
+            cus = 256;
+        }
+        if (dev >= 0 && dev < 16) cu_count[dev].store(cus, std::memory_order_relaxed);
+    }
+    return uint32_t(cus);
+}
+
+static hipError_t launch_ordered_segment(const SerialParams &p, const InstanceList *list, hipStream_t stream, SolveShape &shape) {
     if (p.ni == 0 || p.nb == 0) return hipSuccess;
     const size_t lds = (size_t(window_floats(p.fast_slots)) * p.windows * kSolveInstances +
                         size_t(p.windows) * kMaxFastLinks * kLinkConstFloats) * sizeof(float);
     const uint32_t wgs = (p.ni + kSolveInstances - 1) / kSolveInstances;
-    static const int dense_env = env_int("MMDX_SOLVE_DENSE", -1);             // A/B: 0 never, 1 whenever it fits
-    bool dense = !p.nested && 2 * (lds + 1024) <= 160 * 1024;
-    if (dense && dense_env != 1) {
-        // CU count of the current device, asked once per device and process (two runtime calls per IK launch otherwise)
-        static std::atomic<int> cu_count[16] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-        int cus = dev >= 0 && dev < 16 ? cu_count[dev].load(std::memory_order_relaxed) : 0;
-        if (cus == 0) {
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-                (void)hipGetLastError();
-                cus = 256;
-            }
-            if (dev >= 0 && dev < 16) cu_count[dev].store(cus, std::memory_order_relaxed);
-        }
-        dense = dense_env != 0 && wgs > uint32_t(cus);
-    }
+    const int dense_env = env_int("MMDX_SOLVE_DENSE", -1);   // A/B: 0 never, 1 whenever it fits (read per call, like MMDX_IK_COOP)
+    const uint32_t cus = p.nested ? 0u : cached_cu_count();      // (nested rigs have one compilation: nothing to decide)
+    const bool dense = plan_solve_dense(p.nested != 0, lds, wgs, cus, dense_env);
     auto launch = [&](auto kernel, auto... more) -> hipError_t {
         if (lds > 64 * 1024) {
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
@@ -1329,7 +1345,12 @@ static hipError_t launch_ordered_segment(const SerialParams &p, const InstanceLi
             if (e != hipSuccess) return e;
         }
         hipLaunchKernelGGL(kernel, dim3(wgs), dim3(kSolveInstances * kSolveSlots), lds, stream, p, more...);
-        return hipGetLastError();
+        const hipError_t e = hipGetLastError();
+        if (e == hipSuccess) {
+            shape.dense = dense ? 1u : 0u; shape.workgroups = wgs; shape.lds = uint32_t(lds);
+            ++shape.segments;
+        }
+        return e;
     };
     if (list)
         return launch(p.nested ? skeleton_ordered_select_kernel<true, false>

@@ -23,7 +23,10 @@ struct BlendOperands;
 // mmdx_motion_blend_args in device memory; time clock only
 hipError_t launch_bone_track_blend_set(const BoneTrackParams &p, const BlendOperands &o, hipStream_t stream);
 hipError_t launch_motion_fk_blend_set(const BoneTrackParams &t, const SkeletonParams &p, const BlendOperands &o, hipStream_t stream);
-hipError_t launch_skeleton_ordered(const SerialParams &p, const uint8_t *round_coop /* host, [n_rounds] or nullptr */, hipStream_t stream);
+// `shape` (solve_shape.hpp; may be nullptr) receives what the call launched, and only when every launch succeeded
+struct SolveShape;
+hipError_t launch_skeleton_ordered(const SerialParams &p, const uint8_t *round_coop /* host, [n_rounds] or nullptr */, hipStream_t stream,
+                                   SolveShape *shape);
 hipError_t launch_bone_morph(const BoneMorphParams &p, hipStream_t stream);
 hipError_t launch_physics_override(const PhysicsParams &p, hipStream_t stream);
 // mmdx_skeleton_solve_select: the select forms of the one-step solve's kernels.  Their parameter blocks are the plain ones with
@@ -35,7 +38,8 @@ struct InstanceList {
 };
 hipError_t launch_skeleton_fk_select(const SkeletonParams &p, const InstanceList &list, hipStream_t stream);
 hipError_t launch_bone_morph_select(const BoneMorphParams &p, const InstanceList &list, hipStream_t stream);
-hipError_t launch_skeleton_ordered_select(const SerialParams &p, const uint8_t *round_coop, const InstanceList &list, hipStream_t stream);
+hipError_t launch_skeleton_ordered_select(const SerialParams &p, const uint8_t *round_coop, const InstanceList &list, hipStream_t stream,
+                                          SolveShape *shape);
 
 // api.cpp: the device and stream a motion / rig call runs on -- the model's own when a (device) model
 // is given, so that the deform call that follows is ordered after it; else the selected device's

@@ -440,6 +440,17 @@ class Skeleton:
         self.info = {k: getattr(info, k) for k, _ in SkeletonInfo._fields_}
         self.nb = nb
 
+    def last_solve_shape(self) -> dict:
+        """mmdx_debug_last_solve_shape: what the last solve of this skeleton launched -- solver ('none' | 'ordered' |
+        'parallel_fk') and, of the ordered solver, nested / dense / select, workgroups, lds, segments (ordered-segment launches)
+        and coop_launches (ik_coop launches).  Tests prove with it which compilation of the ordered kernel they ran."""
+        s = api.DebugSolveShape()
+        s.struct_size = C.sizeof(api.DebugSolveShape)
+        api.check(api.lib().mmdx_debug_last_solve_shape(self.h, C.byref(s)))
+        d = {k: int(getattr(s, k)) for k, _ in api.DebugSolveShape._fields_ if k not in ("struct_size", "reserved0")}
+        d["solver"] = api.DEBUG_SOLVERS[d["solver"]]
+        return d
+
     def solve(self, poses, model=None, morph_weights=None) -> np.ndarray:
         """Host convenience: poses f32 [NI, NB, 8] (+ morph rates [NI, NM] or shared [NM]) -> palettes
         f32 [NI, NB, 16]."""

@@ -565,10 +565,14 @@ def test_gpu_ik_skeleton_crowd_beyond_one_workgroup_per_cu(oracle):
     poses[..., 0:3] += rng.uniform(-0.2, 0.2, (ni, nb, 3)).astype(np.float32)     # every instance its own pose
     sk = vmd.Skeleton(rest, parent, level, flags, ap, ar, ik)
     got = sk.solve(poses)
+    shape = sk.last_solve_shape()                        # by crowd size alone: MMDX_SOLVE_DENSE is not set here
+    assert shape["solver"] == "ordered" and shape["dense"] == 1 and shape["workgroups"] == (ni + 15) // 16, shape
     for i in sorted(set(range(0, ni, 7)) | {1, ni - 2, ni - 1}):
         want = oracle.bone_solve_full(rest, parent, poses[i], level, flags, ap, ar, ik)
         gu.assert_bits_equal_or_both_nan(got[i], want, f"palette of instance {i}")
     small = sk.solve(poses[:70])
+    shape = sk.last_solve_shape()
+    assert shape["solver"] == "ordered" and shape["dense"] == 0 and shape["workgroups"] == 5, shape
     assert np.array_equal(np.nan_to_num(small).view(np.uint32), np.nan_to_num(got[:70]).view(np.uint32))
 
 
@@ -638,12 +642,8 @@ def test_gpu_ik_sixteen_lanes_per_solve_equals_one_lane(monkeypatch, oracle, ni)
         gu.assert_bits_equal_or_both_nan(coop[ni - 1], want, f"rig {seed} vs oracle")
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("n_links", [1, 6, 7, 12])
-def test_gpu_long_ik_chains(oracle, n_links):
-    """A 200-bone line with one IK bone at its end: chains of up to 6 links run on the solver's LDS window,
-    longer ones on the HBM scratch state -- both sides of that boundary against the oracle."""
-    nb = 200
+def long_chain_rig(n_links, nb=200):
+    """A line of nb bones with one IK bone at its end that solves the last n_links of them: (rest, parent, flags, ik)."""
     rest = np.stack([np.zeros(nb), np.arange(nb) * 0.1, np.zeros(nb)], 1).astype(np.float32)
     parent = np.arange(-1, nb - 1).astype(np.int32)
     parent[nb - 1] = 0
@@ -658,6 +658,16 @@ def test_gpu_long_ik_chains(oracle, n_links):
               link_hi=np.zeros((n_links, 3), np.float32))
     ik["target"][nb - 1], ik["loop"][nb - 1], ik["angle"][nb - 1] = tgt, 12, 1.0
     ik["link_off"][nb:] = n_links
+    return rest, parent, flags, ik
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_links", [1, 6, 7, 12])
+def test_gpu_long_ik_chains(oracle, n_links):
+    """A 200-bone line with one IK bone at its end: chains of up to 6 links run on the solver's LDS window,
+    longer ones on the HBM scratch state -- both sides of that boundary against the oracle."""
+    nb = 200
+    rest, parent, flags, ik = long_chain_rig(n_links, nb)
     sk = vmd.Skeleton(rest, parent, None, flags, None, None, ik)
     rng = np.random.RandomState(n_links)
     poses = np.zeros((70, nb, 8), np.float32)
@@ -672,11 +682,8 @@ def test_gpu_long_ik_chains(oracle, n_links):
     assert moved > 60                                    # the chains really bend
 
 
-@pytest.mark.gpu
-def test_gpu_many_long_chains_share_a_round(oracle):
-    """Eight independent 6-link chains: all of them fit one round, each on its own LDS window -- 95 KB of dynamic
-    LDS, past the 64 KB a kernel gets without asking -- and the result is the oracle's."""
-    n_chains, seg, n_links = 8, 10, 6
+def many_long_chains_rig(n_chains=8, seg=10, n_links=6):
+    """n_chains independent lines of seg bones, each with an IK bone over its last n_links: (rest, parent, flags, ik)."""
     nb = n_chains * seg
     rest = np.zeros((nb, 3), np.float32)
     parent = np.full(nb, -1, np.int32)
@@ -701,6 +708,16 @@ def test_gpu_many_long_chains_share_a_round(oracle):
         ik["link_off"][ikb + 1:] = len(ik["link_bone"])
     ik = dict(ik, link_bone=np.asarray(ik["link_bone"], np.int32), link_limited=np.asarray(ik["link_limited"], np.uint8),
               link_lo=np.asarray(ik["link_lo"], np.float32), link_hi=np.asarray(ik["link_hi"], np.float32))
+    return rest, parent, flags, ik
+
+
+@pytest.mark.gpu
+def test_gpu_many_long_chains_share_a_round(oracle):
+    """Eight independent 6-link chains: all of them fit one round, each on its own LDS window -- 95 KB of dynamic
+    LDS, past the 64 KB a kernel gets without asking -- and the result is the oracle's."""
+    n_chains, seg = 8, 10
+    nb = n_chains * seg
+    rest, parent, flags, ik = many_long_chains_rig(n_chains, seg, 6)
     sk = vmd.Skeleton(rest, parent, None, flags, None, None, ik)
     assert sk.info["n_ik_bones"] == n_chains and sk.info["n_solve_rounds"] <= seg + 1   # the chains run side by side
     rng = np.random.RandomState(5)

@@ -332,6 +332,12 @@ def test_gpu_select_beyond_one_workgroup_per_cu():
     rows = listed_rows(ids, None, ni)
     assert rows.sum() == k
     check(run(sk, nan_unlisted(poses, rows), ids, k), want, rows, "4 200 of 4 300")
+    shape = sk.last_solve_shape()                                 # by crowd size alone: MMDX_SOLVE_DENSE is not set here
+    assert shape["solver"] == "ordered" and shape["select"] == 1 and shape["dense"] == 1 and shape["workgroups"] == (k + 15) // 16, shape
+    small = np.arange(NI, dtype=np.uint32)
+    check(run(sk, poses[:NI], small, NI), want[:NI], np.ones(NI, bool), "the first 70 alone")
+    shape = sk.last_solve_shape()
+    assert shape["solver"] == "ordered" and shape["select"] == 1 and shape["dense"] == 0 and shape["workgroups"] == 5, shape
 
 
 @pytest.mark.gpu
