@@ -67,7 +67,9 @@ extern "C" {
  *    flag bits no other call accepts; nothing existing changes).
  *    mmdx_palette_bounds with mmdx_palette_bounds_args, and mmdx_model_get_bone_boxes with mmdx_bone_box_info (two new entry points
  *    and structures; mmdx_model_info, mmdx_deform_args and every existing call are unchanged).
- *    mmdx_skeleton_solve_select (a new entry point that takes the existing mmdx_instance_select; nothing existing changes). */
+ *    mmdx_skeleton_solve_select (a new entry point that takes the existing mmdx_instance_select; nothing existing changes).
+ *    mmdx_motion_set_clip_frames and the mmdx_animator_* family with mmdx_animator_desc / _clip / _info / _arrays and
+ *    MMDX_ANIM_DT_ON_DEVICE (new entry points, structures and a flag bit no other call accepts; nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -835,9 +837,9 @@ MMDX_API mmdx_status mmdx_skeleton_solve_motion_set_time(mmdx_skeleton_t skeleto
  * Host operands are checked before the first HIP call: a clip id >= n_clips other than MMDX_CLIP_NONE in either array returns
  * MMDX_ERR_BAD_INDEX, a NaN time or weight MMDX_ERR_INVALID_ARGUMENT.  Device operands follow the rules above (a NaN time takes
  * the first key).  flags: MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE, unknown bits rejected; MMDX_TIMES_ON_DEVICE makes ALL FIVE
- * operand arrays device pointers.  Only the time clock is offered; more than two clips and wrapping a clip's time stay with the
- * caller.  Stream, device, first-use upload, graph recording and pinning as for mmdx_skeleton_solve_motion_set_time: run the call
- * once before recording it. */
+ * operand arrays device pointers.  Only the time clock is offered; more than two clips stay with the caller; advancing and wrapping
+ * the clocks, the fade weight and the hand-over at the end of a fade are mmdx_animator_advance's (below).  Stream, device,
+ * first-use upload, graph recording and pinning as for mmdx_skeleton_solve_motion_set_time: run the call once before recording it. */
 typedef struct mmdx_motion_blend_args {
     uint32_t struct_size, n_instances;    /* = sizeof(mmdx_motion_blend_args); NI >= 1            */
     const uint32_t *clips_a, *clips_b;    /* [n_instances]                                        */
@@ -856,6 +858,139 @@ MMDX_API mmdx_status mmdx_motion_set_blend_morphs_time(mmdx_motion_set_t set, mm
 MMDX_API mmdx_status mmdx_skeleton_solve_motion_set_blend_time(mmdx_skeleton_t skeleton, mmdx_motion_set_t set, mmdx_model_t model,
                                                                const mmdx_motion_blend_args *args,
                                                                float *out_palettes /* [NI][NB][16] */);
+
+/* ---- Crowd animator: clocks, loops and cross-fades advanced on the device -----------------------------------------------------
+ * The reference's whole clock is g_state.time += dt for one MotionPlayer (main.cpp:1757) plus Motion::GetLength(); a crowd has one
+ * such clock per Poser.  An animator keeps a playback state per instance in device memory and advances all of them with one
+ * launch from a single dt.  Its arrays ARE the five operand arrays of the blend calls above (mmdx_animator_operands), so a recorded
+ * frame is: rewrite 8 bytes (dt), launch.
+ *
+ * Clip lengths.  mmdx_motion_set_clip_frames returns, per clip, the largest key frame over the clip's bone and morph tracks,
+ * whichever sides the set has: Motion::GetLength() (L/motion/motion_impl.inl:223-244) of a motion holding those tracks, 0 for a clip
+ * without keys.  Host only, computed at mmdx_motion_set_create.  A clip's length in seconds is double(last_frame) / 30.0.
+ *
+ * The state, eleven arrays of [n_instances] in device memory (mmdx_animator_arrays):
+ *   clips_a, clips_b  u32  the clip playing and the clip being faded to            initially MMDX_CLIP_NONE both
+ *   times_a, times_b  f64  their clocks, seconds                                   0
+ *   weights           f32  blend weight, 0 = a, 1 = b                              0
+ *   speed             f32  playback rate, may be negative                          1
+ *   fade_rate         f32  weight per second, 0 = not fading                       0
+ *   req_clip          u32  pending request, MMDX_ANIM_NO_REQUEST = none; MMDX_CLIP_NONE is a valid request (fade out to rest)
+ *   req_fade          f32  the request's fade, seconds                             0
+ *   req_time          f64  start time of the requested clip                        0
+ *   loops             u32  steps in which clock a wrapped                          0
+ * and a per-clip table [n_clips] from mmdx_animator_desc.clips: length (seconds; <= 0 or NaN = the clip's own length, see above),
+ * mode MMDX_ANIM_LOOP / _HOLD / _THEN, and for _THEN the clip that follows (`next`, a clip id or MMDX_CLIP_NONE) and the fade into
+ * it (`fade`, seconds).  clips == NULL: every clip loops over its own length.
+ *
+ * mmdx_animator_advance.  The arithmetic is part of the contract: IEEE operations only, no libm, unfused (-ffp-contract=off), so
+ * a host restatement agrees bit for bit.  A NaN dt changes nothing.  Otherwise, for every instance, in this order
+ * (L(c), mode(c), next(c), fade(c) = the table row of clip c):
+ *   1. s = double(speed) * dt
+ *   2. times_a = wrap(clips_a, times_a + s); loops += 1 if that wrap folded the clock
+ *   3. only if fade_rate > 0:
+ *        times_b = wrap(clips_b, times_b + s)                       (never counted in loops)
+ *        weights = weights + float(dt) * fade_rate                  (float; the product and the sum are two roundings)
+ *        if !(weights >= 0): weights = 0
+ *        if weights > 1.0f - 1e-7f (the blend's "the row is B" threshold): PROMOTE -- clips_a = clips_b, times_a = times_b,
+ *            clips_b = MMDX_CLIP_NONE, times_b = 0, weights = 0, fade_rate = 0
+ *   4. only if fade_rate == 0 now, pick a transition (c, fade, t0):
+ *        req_clip != MMDX_ANIM_NO_REQUEST                           -> (req_clip, req_fade, req_time)
+ *        else clips_a < n_clips, mode(clips_a) == MMDX_ANIM_THEN and times_a >= L(clips_a) - double(fade(clips_a))
+ *                                                                   -> (next(clips_a), fade(clips_a), 0.0)
+ *        and if there is one: !(fade > 0): clips_a = c, times_a = t0 (a switch at once);
+ *                             otherwise clips_b = c, times_b = t0, weights = 0, fade_rate = 1.0f / fade;
+ *                             then req_clip = MMDX_ANIM_NO_REQUEST.
+ *      So a request that arrives during a fade waits until that fade is promoted and starts in the same step as the promotion.
+ *   clamp(t, L) = t > L ? L : (t >= 0 ? t : 0)                      (a NaN clock becomes 0)
+ *   wrap(c, t):  c >= n_clips (MMDX_CLIP_NONE, an id out of range): t, the rest pose has no length
+ *                mode(c) is not MMDX_ANIM_LOOP: clamp(t, L(c))
+ *                MMDX_ANIM_LOOP, !(L > 0): 0
+ *                MMDX_ANIM_LOOP, L > 0: if t < 0 or t >= L: t = clamp(t - floor(t / L) * L, L) -- a division, a floor, a multiply
+ *                and a subtraction -- and the clock has folded, once per step however many lengths the step spans; else t.
+ *   The evaluators clamp outside [first key, last key], so a clock that lands exactly on L shows the last key for one step.
+ * The call always advances ALL instances: a culled character's clock keeps running, only its solve and deform are skipped by the
+ * select calls.  One lane per instance, on `model`'s stream, in order with the solve that follows.
+ * dt: a host double, passed to the kernel BY VALUE -- a recorded graph freezes that value, every replay takes the same step.  With
+ * MMDX_ANIM_DT_ON_DEVICE dt is a device pointer (8-byte aligned) read when the kernel RUNS: a replay is "rewrite 8 bytes, launch".
+ * A host NaN dt is MMDX_ERR_INVALID_ARGUMENT; a device NaN dt leaves every array unchanged.
+ *
+ * Every call of the family takes a `model` for the device, the stream and the graph recording, like the motion-set calls (NULL: the
+ * selected device's default stream).  The state is allocated and initialised on the device of the first call that needs it
+ * (mmdx_animator_operands and _device_arrays: the calling thread's selected device) and stays there: a model of another device is
+ * MMDX_ERR_INVALID_ARGUMENT.  Creating, destroying and mmdx_animator_get_info need no device.  Graph rules are the motion set's: run
+ * a call once before recording it; host lists, mmdx_animator_set_state and _get_state are refused while recording; the handle is
+ * pinned while a graph holds its addresses and destroying it invalidates the graph. */
+#define MMDX_ANIM_NO_REQUEST 0xFFFFFFFEu
+enum { MMDX_ANIM_LOOP = 0, MMDX_ANIM_HOLD = 1, MMDX_ANIM_THEN = 2 };   /* mmdx_animator_clip.mode                                */
+enum { MMDX_ANIM_DT_ON_DEVICE = 1u << 10 };                             /* mmdx_animator_advance: dt is a device pointer          */
+
+typedef struct mmdx_animator_s *mmdx_animator_t;
+
+typedef struct mmdx_animator_clip {
+    double length;             /* seconds; <= 0 or NaN: the clip's own length, double(last_frame) / 30.0                          */
+    uint32_t mode;             /* MMDX_ANIM_LOOP / _HOLD / _THEN; anything else: MMDX_ERR_INVALID_ARGUMENT                        */
+    uint32_t next;             /* _THEN: the clip that follows, < n_clips or MMDX_CLIP_NONE (else MMDX_ERR_BAD_INDEX)             */
+    float fade;                /* _THEN: seconds of cross-fade into `next`; <= 0: switch at once; NaN: MMDX_ERR_INVALID_ARGUMENT  */
+    uint32_t reserved0;        /* 0                                                                                               */
+} mmdx_animator_clip;
+
+typedef struct mmdx_animator_desc {
+    uint32_t struct_size;      /* = sizeof(mmdx_animator_desc)                                                                    */
+    uint32_t n_instances;      /* NI >= 1, fixed for the life of the handle                                                       */
+    const mmdx_animator_clip *clips; /* [n_clips] host, or NULL: every clip loops over its own length                             */
+    uint32_t n_clips;          /* with clips: must equal the set's clip count; ignored when clips == NULL                         */
+    uint32_t reserved0;        /* 0                                                                                               */
+} mmdx_animator_desc;
+
+typedef struct mmdx_animator_info {
+    uint32_t struct_size;
+    uint32_t n_instances, n_clips;
+    int32_t device_ordinal;    /* where the state lives, -1 = not allocated yet                                                   */
+} mmdx_animator_info;
+
+/* The eleven arrays: device addresses from mmdx_animator_device_arrays, host arrays for mmdx_animator_set_state / _get_state.   */
+typedef struct mmdx_animator_arrays {
+    uint32_t struct_size, n_instances;
+    uint32_t *clips_a, *clips_b;
+    double *times_a, *times_b;
+    float *weights, *speed, *fade_rate;
+    uint32_t *req_clip;
+    float *req_fade;
+    double *req_time;
+    uint32_t *loops;
+} mmdx_animator_arrays;
+
+MMDX_API mmdx_status mmdx_motion_set_clip_frames(mmdx_motion_set_t set, uint32_t *last_frames /* [n_clips] */);
+/* The animator copies what it needs of the set (clip count and lengths): the set may be destroyed afterwards. */
+MMDX_API mmdx_status mmdx_animator_create(mmdx_motion_set_t set, const mmdx_animator_desc *desc, mmdx_animator_t *out_animator);
+MMDX_API void mmdx_animator_destroy(mmdx_animator_t animator);
+/* clips (may be NULL) receives the table as resolved: the lengths in seconds that advance uses. */
+MMDX_API mmdx_status mmdx_animator_get_info(mmdx_animator_t animator, mmdx_animator_info *info, mmdx_animator_clip *clips /* [n_clips] */);
+/* Fills *out with clips_a, clips_b, times_a, times_b, weights of the state, n_instances and MMDX_TIMES_ON_DEVICE |
+ * MMDX_OUT_ON_DEVICE: the three blend calls take the animator's state with no glue. */
+MMDX_API mmdx_status mmdx_animator_operands(mmdx_animator_t animator, mmdx_motion_blend_args *out);
+/* Every device address of the state (out->struct_size set by the caller): an adopter's own behaviour kernel can write requests or
+ * speeds and read `loops` (root motion, events), in stream order with the calls here. */
+MMDX_API mmdx_status mmdx_animator_device_arrays(mmdx_animator_t animator, mmdx_animator_arrays *out);
+/* Copy any subset of the arrays from / to host arrays (a NULL member = leave that array alone; n_instances must be the handle's),
+ * in `model`'s stream order; both return when the copies are done.  set_state checks the host values before the first HIP call:
+ * a clip id >= n_clips other than MMDX_CLIP_NONE in clips_a / clips_b / req_clip (where MMDX_ANIM_NO_REQUEST is valid too) is
+ * MMDX_ERR_BAD_INDEX, a NaN in any time, weight, speed, fade_rate or req_fade MMDX_ERR_INVALID_ARGUMENT. */
+MMDX_API mmdx_status mmdx_animator_set_state(mmdx_animator_t animator, mmdx_model_t model, const mmdx_animator_arrays *state);
+MMDX_API mmdx_status mmdx_animator_get_state(mmdx_animator_t animator, mmdx_model_t model, const mmdx_animator_arrays *state);
+/* Scatter n requests: instance ids[j] gets (req_clip, req_fade, req_time) = (clips[j], fades[j], start_times[j]); fades == NULL
+ * means 0 (switch at once), start_times == NULL means 0.  The ids of one call must be distinct (otherwise which request an
+ * instance keeps is unspecified; a host list longer than n_instances is MMDX_ERR_INVALID_ARGUMENT).  A later request replaces one that has not started yet.  flags: MMDX_TIMES_ON_DEVICE = all lists are
+ * device pointers, read when the kernel runs (recordable); an id >= n_instances is then skipped on the device and clip ids are
+ * used as they are (an id out of range plays the rest pose).  Host lists are checked before the first HIP call -- an id >=
+ * n_instances or a clip id >= n_clips other than MMDX_CLIP_NONE: MMDX_ERR_BAD_INDEX; a NaN fade or start time:
+ * MMDX_ERR_INVALID_ARGUMENT -- then copied through a scratch of the handle in stream order, and the call returns when they have
+ * been consumed.  n == 0 is MMDX_OK and does nothing. */
+MMDX_API mmdx_status mmdx_animator_request(mmdx_animator_t animator, mmdx_model_t model, uint32_t n, const uint32_t *ids,
+                                           const uint32_t *clips, const float *fades, const double *start_times, uint32_t flags);
+/* flags: MMDX_ANIM_DT_ON_DEVICE or 0; unknown bits are rejected. */
+MMDX_API mmdx_status mmdx_animator_advance(mmdx_animator_t animator, mmdx_model_t model, const double *dt, uint32_t flags);
 
 /* ---- where every instance stands: palette x world matrix ----------------------------------------------------------------------
  * Every palette the solves above write is in model space.  mmdx_palette_place multiplies each skinning matrix of instance i on the

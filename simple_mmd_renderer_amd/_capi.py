@@ -231,6 +231,19 @@ SIGNATURES = {
     "mmdx_motion_set_blend_bones_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmdx_motion_set_blend_morphs_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmdx_skeleton_solve_motion_set_blend_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the crowd animator: (set, last_frames); (set, mmdx_animator_desc*, out); (animator, info*, clips*); (animator, blend args*);
+    # (animator, arrays*); (animator, model, arrays*) x 2; (animator, model, n, ids, clips, fades, start_times, flags);
+    # (animator, model, dt*, flags)
+    "mmdx_motion_set_clip_frames": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mmdx_animator_create": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mmdx_animator_destroy": (None, [C.c_void_p]),
+    "mmdx_animator_get_info": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmdx_animator_operands": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mmdx_animator_device_arrays": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "mmdx_animator_set_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmdx_animator_get_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmdx_animator_request": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "mmdx_animator_advance": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "mmdx_skeleton_solve_morphed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),
     # (skeleton, model, n_instances, poses, morph_weights, flags, mmdx_instance_select*, out)

@@ -11,6 +11,7 @@
 
 #include "../../include/mmdx.h"
 #include "../../include/mmdx_bench.h"
+#include "anim_kernels.hpp"
 #include "error.hpp"
 #include "graph_pin.hpp"
 #include "kernels.hpp"
@@ -98,6 +99,7 @@ struct mmdx_skeleton_s {
 // A bank of clips bound to one model (rig.hpp MotionSetHost): the concatenated tables of both sides, uploaded on first use.
 struct mmdx_motion_set_s {
     MotionSetHost host;
+    std::vector<uint32_t> clip_frames;                              // [n_clips] largest key frame of each clip (mmdx_motion_set_clip_frames)
     int device = -1;
     Buf key_off, key_frame, key_tr, key_rot, key_curve, lut;        // bone side
     Buf m_key_off, m_frames, m_weights;                             // morph side
@@ -113,6 +115,8 @@ struct mmdx_motion_set_s {
         for (Buf *b : all()) b->pin = &pin;
     }
 };
+
+const std::vector<uint32_t> &mmdx::motion_set_clip_frames(const mmdx_motion_set_s *set) { return set->clip_frames; }
 
 // static tables of a motion / a skeleton -> the device they are about to run on (once per device)
 static mmdx_status motion_to_device(mmdx_bone_motion_t m, int device) {
@@ -377,6 +381,7 @@ mmdx_status mmdx_motion_set_create(uint32_t n_clips, const mmdx_bone_motion_t *b
             for (uint32_t c = 0; c < n_clips; ++c) clips.push_back(morph_motion_host(morph_motions[c]));
             if (mmdx_status st = build_motion_set_morphs(clips, set->host, err)) return fail(st, "motion set: " + err);
         }
+        set->clip_frames = motion_set_last_frames(set->host);
         *out = set.release();
     } catch (const std::bad_alloc &) {
         return fail(MMDX_ERR_OUT_OF_MEMORY, "host allocation failed");

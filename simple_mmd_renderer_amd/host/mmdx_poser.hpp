@@ -455,12 +455,81 @@ public:
     void SeekFrameMorphRates(uint32_t n, const uint32_t *clips, const uint32_t *frames, float *out_rates, bool on_device = false) {
         check(mmdx_motion_set_eval_morphs(set_, poser_.handle(), n, clips, frames, flags(on_device), out_rates));
     }
+    // = Motion::GetLength() of every clip over the tracks bound to the poser: its largest key frame; seconds = frames / 30.0
+    std::vector<uint32_t> ClipFrames() const {
+        std::vector<uint32_t> frames(clip_count());
+        check(mmdx_motion_set_clip_frames(set_, frames.data()));
+        return frames;
+    }
+    // The blend calls over ready-made operands -- mmdx::Animator::operands(): the animator's device arrays, outputs on the device
+    void BlendTimePalettes(const mmdx_motion_blend_args &operands, float *out_palettes) {
+        check(mmdx_skeleton_solve_motion_set_blend_time(poser_.skeleton(), set_, poser_.handle(), &operands, out_palettes));
+    }
+    void BlendTimeMorphRates(const mmdx_motion_blend_args &operands, float *out_rates) {
+        check(mmdx_motion_set_blend_morphs_time(set_, poser_.handle(), &operands, out_rates));
+    }
     mmdx_motion_set_t handle() const { return set_; }
+    Poser &poser() const { return poser_; }
 
 private:
     static uint32_t flags(bool on_device) { return on_device ? uint32_t(MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE) : 0u; }
     Poser &poser_;
     mmdx_motion_set_t set_ = nullptr;
+};
+
+// The clocks of a crowd: the reference's g_state.time += dt (main.cpp:1757) for one MotionPlayer becomes one launch for all posers.
+// Every instance has a clip playing, a clip it is fading to, their clocks and the fade weight, all in device memory; Advance(dt)
+// steps them -- loop wrap, hold, "then" chains, the fade and its hand-over, pending requests (mmdx.h states the arithmetic) -- and
+// operands() is what MotionSet::BlendTimePalettes / BlendTimeMorphRates take.  table: one mmdx_animator_clip per clip of the set
+// (empty = every clip loops over its own length).
+class Animator {
+public:
+    Animator(MotionSet &set, uint32_t n_instances, const std::vector<mmdx_animator_clip> &table = {}) : set_(set), n_(n_instances) {
+        mmdx_animator_desc d{};
+        d.struct_size = sizeof(d);
+        d.n_instances = n_instances;
+        d.clips = table.empty() ? nullptr : table.data();
+        d.n_clips = uint32_t(table.size());
+        check(mmdx_animator_create(set.handle(), &d, &anim_));
+    }
+    ~Animator() { mmdx_animator_destroy(anim_); }
+    Animator(const Animator &) = delete;
+    Animator &operator=(const Animator &) = delete;
+
+    // one step for every instance, on the poser's stream; a recorded graph freezes dt -- record AdvanceDeviceDt instead
+    void Advance(double dt) { check(mmdx_animator_advance(anim_, set_.poser().handle(), &dt, 0)); }
+    void AdvanceDeviceDt(const double *dt_device) { check(mmdx_animator_advance(anim_, set_.poser().handle(), dt_device, MMDX_ANIM_DT_ON_DEVICE)); }
+    // instance ids[j] fades over fades[j] seconds (NULL: at once) to clips[j], started at start_times[j] (NULL: 0); host lists
+    void Request(uint32_t n, const uint32_t *ids, const uint32_t *clips, const float *fades = nullptr, const double *start_times = nullptr,
+                 bool on_device = false) {
+        check(mmdx_animator_request(anim_, set_.poser().handle(), n, ids, clips, fades, start_times, on_device ? uint32_t(MMDX_TIMES_ON_DEVICE) : 0u));
+    }
+    // host arrays in / out; NULL members are left alone (state.struct_size and n_instances are filled in here)
+    void SetState(mmdx_animator_arrays state) {
+        state.struct_size = sizeof(state); state.n_instances = n_;
+        check(mmdx_animator_set_state(anim_, set_.poser().handle(), &state));
+    }
+    void GetState(mmdx_animator_arrays state) {
+        state.struct_size = sizeof(state); state.n_instances = n_;
+        check(mmdx_animator_get_state(anim_, set_.poser().handle(), &state));
+    }
+    mmdx_motion_blend_args operands() {
+        mmdx_motion_blend_args a;
+        check(mmdx_animator_operands(anim_, &a));
+        return a;
+    }
+    mmdx_animator_arrays device_arrays() {
+        mmdx_animator_arrays a{};
+        a.struct_size = sizeof(a);
+        check(mmdx_animator_device_arrays(anim_, &a));
+        return a;
+    }
+    mmdx_animator_t handle() const { return anim_; }
+
+private:
+    MotionSet &set_;
+    uint32_t n_;
+    mmdx_animator_t anim_ = nullptr;
 };
 
 }  // namespace mmdx

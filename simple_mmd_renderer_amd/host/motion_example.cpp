@@ -5,7 +5,7 @@
 // With `hz` the loop runs at that display rate: step n seeks to n / hz seconds (MotionPlayer::SeekTime) instead of frame n.
 //   ./motion_example --crowd instances hz model.pmx clip0.vmd [clip1.vmd ...]
 // Crowd mode (mmdx::MotionSet): the motions are the clips of one bank, instance i plays clip i % clips at i / hz seconds; one
-// call each gives every instance's palette and morph rates.
+// call each gives every instance's palette and morph rates; then mmdx::Animator runs the crowd's clocks on the device for 60 steps.
 // Prints per-run checksums so tests can compare with the Python path over the same C ABI.
 #include <cstdio>
 #include <cstdlib>
@@ -48,6 +48,32 @@ static int crowd(int argc, char **argv) {
     for (uint32_t i = 0; i < ni; ++i) { where[8 * i] = 12.f * float(i); where[8 * i + 7] = 1.f; }
     set.PlacePalettes(ni, palettes.data(), where.data(), placed.data());
     std::fprintf(stderr, "placed checksum=%016llx\n", (unsigned long long)checksum(placed.data(), placed.size() * 4));
+    // the same crowd on its own clocks (mmdx::Animator): every instance starts its clip at once, every other one asks for a
+    // half-second fade to the next clip after 30 steps; 60 steps of 1 / hz, one launch each, the palettes from the animator's arrays
+    mmdx::Animator animator(set, ni);
+    std::vector<uint32_t> ids(ni), next;
+    for (uint32_t i = 0; i < ni; ++i) ids[i] = i;
+    animator.Request(ni, ids.data(), clips.data());
+    void *d_palettes = nullptr;
+    mmdx::check(mmdx_device_malloc(&d_palettes, palettes.size() * 4));
+    ids.clear();
+    for (uint32_t i = 0; i < ni; i += 2) { ids.push_back(i); next.push_back((i + 1) % nc); }
+    const std::vector<float> fades(ids.size(), 0.5f);
+    for (int step = 0; step < 60; ++step) {
+        if (step == 30) animator.Request(uint32_t(ids.size()), ids.data(), next.data(), fades.data());
+        animator.Advance(1.0 / hz);
+        set.BlendTimePalettes(animator.operands(), static_cast<float *>(d_palettes));
+    }
+    mmdx::check(mmdx_sync(poser->handle()));          // the steps ran on the poser's stream; the copy below does not wait for it
+    mmdx::check(mmdx_memcpy_d2h(palettes.data(), d_palettes, palettes.size() * 4));
+    mmdx::check(mmdx_device_free(d_palettes));
+    std::vector<double> clock(ni);
+    std::vector<uint32_t> loops(ni);
+    mmdx_animator_arrays state{};
+    state.times_a = clock.data(); state.loops = loops.data();
+    animator.GetState(state);
+    std::fprintf(stderr, "animated checksum=%016llx clock[0]=%.6f loops[0]=%u\n", (unsigned long long)checksum(palettes.data(), palettes.size() * 4),
+                 clock[0], loops[0]);
     return 0;
 }
 

@@ -352,9 +352,142 @@ class MotionSet:
         args = blend_args_device(n_instances, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr)
         api.check(api.lib().mmdx_motion_set_blend_morphs_time(self.h, model.h if model is not None else None, C.byref(args), out_ptr))
 
+    def clip_frames(self) -> np.ndarray:
+        """u32 [n_clips]: the largest key frame of every clip over the sides the set has (Motion::GetLength of those tracks);
+        a clip's length in seconds is frames / 30.0."""
+        out = np.zeros(self.n_clips, np.uint32)
+        api.check(api.lib().mmdx_motion_set_clip_frames(self.h, out.ctypes.data))
+        return out
+
     def close(self):
         if getattr(self, "h", None):
             api.lib().mmdx_motion_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- the crowd animator (mmdx_animator_*): clocks, loops and cross-fades advanced on the device ---------------------------
+ANIM_NO_REQUEST = 0xFFFFFFFE             # MMDX_ANIM_NO_REQUEST: no pending request in req_clip
+ANIM_LOOP, ANIM_HOLD, ANIM_THEN = 0, 1, 2
+ANIM_DT_ON_DEVICE = 1 << 10              # mmdx_animator_advance: dt is a device pointer, read when the kernel runs
+
+
+class AnimatorClip(C.Structure):
+    _fields_ = [("length", C.c_double), ("mode", C.c_uint32), ("next", C.c_uint32), ("fade", C.c_float), ("reserved0", C.c_uint32)]
+
+
+class AnimatorDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_instances", C.c_uint32), ("clips", C.c_void_p), ("n_clips", C.c_uint32),
+                ("reserved0", C.c_uint32)]
+
+
+class AnimatorInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_instances", C.c_uint32), ("n_clips", C.c_uint32), ("device_ordinal", C.c_int32)]
+
+
+# the eleven state arrays in the order of mmdx_animator_arrays, with their element types
+ANIMATOR_ARRAYS = (("clips_a", np.uint32), ("clips_b", np.uint32), ("times_a", np.float64), ("times_b", np.float64),
+                   ("weights", np.float32), ("speed", np.float32), ("fade_rate", np.float32), ("req_clip", np.uint32),
+                   ("req_fade", np.float32), ("req_time", np.float64), ("loops", np.uint32))
+
+
+class AnimatorArrays(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_instances", C.c_uint32)] + [(k, C.c_void_p) for k, _ in ANIMATOR_ARRAYS]
+
+
+class Animator:
+    """The playback state of every instance of a crowd, in device memory (mmdx_animator_t): advance() steps all clocks, loops,
+    fades and pending requests with one launch, and operands() is what the three blend calls take.
+    clips: None (every clip loops over its own length) or one (length, mode, next, fade) per clip of the set; length <= 0 = the
+    clip's own."""
+
+    def __init__(self, motion_set: "MotionSet", n_instances: int, clips=None):
+        desc = AnimatorDesc(C.sizeof(AnimatorDesc), n_instances, None, 0, 0)
+        if clips is not None:
+            table = (AnimatorClip * max(len(clips), 1))(*[AnimatorClip(float(l), int(m), int(n), float(f), 0) for l, m, n, f in clips])
+            desc.clips, desc.n_clips = C.addressof(table), len(clips)
+        self.h = C.c_void_p()
+        api.check(api.lib().mmdx_animator_create(motion_set.h, C.byref(desc), C.byref(self.h)))
+        self.ni, self.n_clips = n_instances, motion_set.n_clips
+
+    def clip_table(self) -> List[tuple]:
+        """The table as resolved: (length in seconds, mode, next, fade) per clip."""
+        info = AnimatorInfo(C.sizeof(AnimatorInfo))
+        table = (AnimatorClip * max(self.n_clips, 1))()
+        api.check(api.lib().mmdx_animator_get_info(self.h, C.byref(info), table))
+        return [(table[c].length, table[c].mode, table[c].next, table[c].fade) for c in range(self.n_clips)]
+
+    def advance(self, dt: float, model=None) -> None:
+        """One step of `dt` seconds for every instance (a recorded graph freezes this dt)."""
+        api.check(api.lib().mmdx_animator_advance(self.h, model.h if model is not None else None, C.byref(C.c_double(dt)), 0))
+
+    def advance_device_dt(self, dt_ptr, model=None) -> None:
+        """The same with dt a device double, read when the kernel runs: a replayed graph rewrites 8 bytes."""
+        api.check(api.lib().mmdx_animator_advance(self.h, model.h if model is not None else None, dt_ptr, ANIM_DT_ON_DEVICE))
+
+    def request(self, ids, clips, fades=None, start_times=None, model=None) -> None:
+        """Host lists: instance ids[j] fades (fades[j] seconds, default 0 = at once) to clips[j] started at start_times[j]."""
+        i, c = np.ascontiguousarray(ids, np.uint32).reshape(-1), np.ascontiguousarray(clips, np.uint32).reshape(-1)
+        f = None if fades is None else np.ascontiguousarray(fades, np.float32).reshape(-1)
+        t = None if start_times is None else np.ascontiguousarray(start_times, np.float64).reshape(-1)
+        if any(x is not None and x.size != i.size for x in (c, f, t)):
+            raise ValueError("one clip (and fade, start time) per listed instance")
+        api.check(api.lib().mmdx_animator_request(self.h, model.h if model is not None else None, i.size, i.ctypes.data, c.ctypes.data,
+                                                  f.ctypes.data if f is not None else None, t.ctypes.data if t is not None else None, 0))
+
+    def request_device(self, n: int, ids_ptr, clips_ptr, fades_ptr=None, start_times_ptr=None, model=None) -> None:
+        """The same with the lists in device memory (recordable); an id >= n_instances is skipped on the device."""
+        api.check(api.lib().mmdx_animator_request(self.h, model.h if model is not None else None, n, ids_ptr, clips_ptr, fades_ptr,
+                                                  start_times_ptr, TIMES_ON_DEVICE))
+
+    def set_state(self, model=None, **arrays) -> None:
+        """Overwrite the named arrays (clips_a=..., speed=..., ...: ANIMATOR_ARRAYS), [n_instances] each; the others keep their bytes."""
+        s = AnimatorArrays(C.sizeof(AnimatorArrays), self.ni)
+        keep = []
+        types = dict(ANIMATOR_ARRAYS)
+        for k, v in arrays.items():
+            a = np.ascontiguousarray(v, types[k]).reshape(-1)
+            if a.size != self.ni:
+                raise ValueError(f"{k}: one value per instance")
+            keep.append(a)
+            setattr(s, k, a.ctypes.data)
+        api.check(api.lib().mmdx_animator_set_state(self.h, model.h if model is not None else None, C.byref(s)))
+
+    def get_state(self, model=None, names=None) -> Dict[str, np.ndarray]:
+        """The named arrays (default: all eleven) as numpy arrays."""
+        s = AnimatorArrays(C.sizeof(AnimatorArrays), self.ni)
+        out = {k: np.zeros(self.ni, t) for k, t in ANIMATOR_ARRAYS if names is None or k in names}
+        for k, a in out.items():
+            setattr(s, k, a.ctypes.data)
+        api.check(api.lib().mmdx_animator_get_state(self.h, model.h if model is not None else None, C.byref(s)))
+        return out
+
+    def operands(self) -> MotionBlendArgs:
+        """mmdx_motion_blend_args over the animator's own device arrays, ready for the three blend calls."""
+        a = MotionBlendArgs()
+        api.check(api.lib().mmdx_animator_operands(self.h, C.byref(a)))
+        return a
+
+    def operand_ptrs(self) -> tuple:
+        """The same five device addresses in the order the *_blend_time_device methods take them: clips a, times a, clips b,
+        times b, weights."""
+        a = self.operands()
+        return a.clips_a, a.times_a, a.clips_b, a.times_b, a.weights
+
+    def device_arrays(self) -> Dict[str, int]:
+        """Device address of every state array (for an adopter's own kernels)."""
+        s = AnimatorArrays(C.sizeof(AnimatorArrays), self.ni)
+        api.check(api.lib().mmdx_animator_device_arrays(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in ANIMATOR_ARRAYS}
+
+    def close(self):
+        if getattr(self, "h", None):
+            api.lib().mmdx_animator_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -1,0 +1,124 @@
+// tests/anim_math_driver.cpp -- TEST INFRASTRUCTURE ONLY: csrc/anim_math.hpp, the arithmetic of mmdx_animator_advance, compiled for
+// the host.  A stand-alone program: `anim_math_driver in.bin out.bin` reads a crowd's state, the clip table, a dt per step and the
+// requests that arrive before each step, runs the steps and writes every state array after every step.  tests/test_animator.py
+// builds it once plain and once with -fsanitize=address,undefined (both with -ffp-contract=off) and compares the output with
+// tests/animator_ref.py bit for bit.
+//
+// in.bin   u32 ni, nc, n_steps, n_req
+//          table   f64 length[nc]; u32 mode[nc]; u32 next[nc]; f32 fade[nc]
+//          state   u32 clips_a[ni], clips_b[ni]; f64 times_a[ni], times_b[ni]; f32 weights[ni], speed[ni], fade_rate[ni];
+//                  u32 req_clip[ni]; f32 req_fade[ni]; f64 req_time[ni]; u32 loops[ni]        (the order of mmdx_animator_arrays)
+//          f64 dt[n_steps]
+//          requests, sorted by step: u32 step[n_req], id[n_req], clip[n_req]; f32 fade[n_req]; f64 time[n_req]
+// out.bin  the eleven state arrays in the same order after step 0, after step 1, ...
+// A NaN dt leaves the state alone, as the kernel does; a request with id >= ni is skipped, as the scatter kernel does.
+//
+// With -DANIM_DRIVER_LIBMMD (and the reference's libmmd on the include path, which the GPU machines do not have) the file is
+// instead built as a shared library with one function, the real Motion::GetLength() of a .vmd file.
+#ifdef ANIM_DRIVER_LIBMMD
+
+#include <math.h>
+#include <stdlib.h>
+
+#include <mmd/mmd.hxx>
+
+#include <exception>
+#include <string>
+
+extern "C" long long amd_motion_length(const char *path) {
+    mmd::Motion m;
+    try {
+        std::string p(path);
+        mmd::FileReader file(std::wstring(p.begin(), p.end()));
+        mmd::VmdReader(file).ReadMotion(m);
+    } catch (const std::exception &) {
+        return -1;
+    }
+    return static_cast<long long>(m.GetLength());
+}
+
+#else
+
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "../simple_mmd_renderer_amd/csrc/anim_math.hpp"
+
+namespace {
+
+template <typename T>
+std::vector<T> take(std::FILE *f, size_t n) {
+    std::vector<T> v(n);
+    if (n && std::fread(v.data(), sizeof(T), n, f) != n) {
+        std::fprintf(stderr, "anim_math_driver: input too short\n");
+        std::exit(2);
+    }
+    return v;
+}
+
+template <typename T>
+void put(std::FILE *f, const std::vector<T> &v) {
+    if (!v.empty() && std::fwrite(v.data(), sizeof(T), v.size(), f) != v.size()) {
+        std::fprintf(stderr, "anim_math_driver: write failed\n");
+        std::exit(2);
+    }
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    if (argc != 3) {
+        std::fprintf(stderr, "usage: anim_math_driver in.bin out.bin\n");
+        return 2;
+    }
+    std::FILE *in = std::fopen(argv[1], "rb"), *out = std::fopen(argv[2], "wb");
+    if (!in || !out) {
+        std::fprintf(stderr, "anim_math_driver: cannot open the files\n");
+        return 2;
+    }
+    const std::vector<uint32_t> head = take<uint32_t>(in, 4);
+    const size_t ni = head[0], nc = head[1], n_steps = head[2], n_req = head[3];
+    const auto length = take<double>(in, nc);
+    const auto mode = take<uint32_t>(in, nc), next = take<uint32_t>(in, nc);
+    const auto fade = take<float>(in, nc);
+    auto clips_a = take<uint32_t>(in, ni), clips_b = take<uint32_t>(in, ni);
+    auto times_a = take<double>(in, ni), times_b = take<double>(in, ni);
+    auto weights = take<float>(in, ni), speed = take<float>(in, ni), fade_rate = take<float>(in, ni);
+    auto req_clip = take<uint32_t>(in, ni);
+    auto req_fade = take<float>(in, ni);
+    auto req_time = take<double>(in, ni);
+    auto loops = take<uint32_t>(in, ni);
+    const auto dt = take<double>(in, n_steps);
+    const auto r_step = take<uint32_t>(in, n_req), r_id = take<uint32_t>(in, n_req), r_clip = take<uint32_t>(in, n_req);
+    const auto r_fade = take<float>(in, n_req);
+    const auto r_time = take<double>(in, n_req);
+    const mmdx::AnimClips table{length.data(), mode.data(), next.data(), fade.data(), uint32_t(nc)};
+    size_t r = 0;
+    for (size_t step = 0; step < n_steps; ++step) {
+        for (; r < n_req && r_step[r] == step; ++r) {
+            if (r_id[r] >= ni) continue;
+            req_clip[r_id[r]] = r_clip[r];
+            req_fade[r_id[r]] = r_fade[r];
+            req_time[r_id[r]] = r_time[r];
+        }
+        for (size_t i = 0; i < ni && dt[step] == dt[step]; ++i) {
+            mmdx::AnimLane s{clips_a[i], clips_b[i], times_a[i], times_b[i], weights[i], speed[i], fade_rate[i],
+                             req_clip[i], req_fade[i], req_time[i], loops[i]};
+            mmdx::anim_advance(table, s, dt[step]);
+            clips_a[i] = s.clip_a; clips_b[i] = s.clip_b;
+            times_a[i] = s.time_a; times_b[i] = s.time_b;
+            weights[i] = s.weight; speed[i] = s.speed; fade_rate[i] = s.fade_rate;
+            req_clip[i] = s.req_clip; req_fade[i] = s.req_fade; req_time[i] = s.req_time;
+            loops[i] = s.loops;
+        }
+        put(out, clips_a); put(out, clips_b); put(out, times_a); put(out, times_b);
+        put(out, weights); put(out, speed); put(out, fade_rate);
+        put(out, req_clip); put(out, req_fade); put(out, req_time); put(out, loops);
+    }
+    std::fclose(in);
+    if (std::fclose(out) != 0) return 2;
+    return 0;
+}
+
+#endif
