@@ -69,7 +69,10 @@ extern "C" {
  *    and structures; mmdx_model_info, mmdx_deform_args and every existing call are unchanged).
  *    mmdx_skeleton_solve_select (a new entry point that takes the existing mmdx_instance_select; nothing existing changes).
  *    mmdx_motion_set_clip_frames and the mmdx_animator_* family with mmdx_animator_desc / _clip / _info / _arrays and
- *    MMDX_ANIM_DT_ON_DEVICE (new entry points, structures and a flag bit no other call accepts; nothing existing changes). */
+ *    MMDX_ANIM_DT_ON_DEVICE (new entry points, structures and a flag bit no other call accepts; nothing existing changes).
+ *    mmdx_motion_set_blend_bones_time_select, mmdx_motion_set_blend_morphs_time_select and
+ *    mmdx_skeleton_solve_motion_set_blend_time_select (new entry points over the existing mmdx_motion_blend_args and
+ *    mmdx_instance_select; nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -1173,11 +1176,54 @@ MMDX_API mmdx_status mmdx_skeleton_solve_morphed(mmdx_skeleton_t skeleton, mmdx_
  *  8. The launches are sized from n_ids: workgroups whose list positions all lie behind *count return at once.
  *  9. Only the one-step solve has a select form, the physics seam (_pre / _post) has none.  On a MMDX_SKELETON_PHYSICS_SEAM skeleton
  *     the call behaves toward a pending pre step exactly as mmdx_skeleton_solve does: the pre step is void.
- * 10. Track evaluation (mmdx_motion_set_blend_bones_time and its siblings) is not selected: it runs for every instance and feeds
- *     `poses`.  An instance that is not solved keeps its last model-space palette. */
+ * 10. Track evaluation has a select form of its own that takes the same list: mmdx_motion_set_blend_bones_time_select writes the
+ *     listed rows of `poses`, and mmdx_skeleton_solve_motion_set_blend_time_select (below) is tracks and solve in one call.  An
+ *     instance that is not solved keeps its last model-space palette. */
 MMDX_API mmdx_status mmdx_skeleton_solve_select(mmdx_skeleton_t skeleton, mmdx_model_t model, uint32_t n_instances, const float *poses,
                                                 const float *morph_weights /* or NULL */, uint32_t flags,
                                                 const mmdx_instance_select *select, float *out_palettes /* [NI][NB][16] */);
+/* ---- evaluating the motion tracks of a subset of a crowd: the three cross-fade calls (mmdx_motion_set_blend_bones_time,
+ * mmdx_motion_set_blend_morphs_time, mmdx_skeleton_solve_motion_set_blend_time) for the instances of an mmdx_instance_select only.  The
+ * tracks are a pure function of the clocks, and the clocks stay with mmdx_animator_advance, which runs for everyone: an instance that
+ * comes back into view is evaluated at its current time and nothing was skipped.  With this the frame costs what is in view from its
+ * first evaluation on.
+ *  1. args->n_instances = NI is the extent of the five operand arrays and of the output: instance i reads operand row i and writes
+ *     output row i.  The list only says which i take part.
+ *  2. For every listed i < NI the bytes of output row i are identical to what the plain call writes for that instance from the same
+ *     operands: every weight class (A, B, mix, NaN), MMDX_CLIP_NONE and device ids >= n_clips.  An end-point row still reads nothing
+ *     of the other clip.
+ *  3. Nothing else is written: output rows of instances that are not listed keep every byte.  Operand rows of unlisted instances may
+ *     hold anything (clip ids out of range, NaN times, NaN weights, uninitialised memory) and influence no written byte.
+ *  4. The first min(*count, n_ids) ids are used.  *count == 0 or n_ids == 0 is a valid call that writes nothing.
+ *  5. An id >= NI: in a host list the call fails with MMDX_ERR_INVALID_ARGUMENT before anything is launched; in a device list the
+ *     entry is skipped on the device (nothing read or written for it).  An id that occurs twice is allowed and costs twice; both
+ *     writers store the same bytes.  Output rows are addressed by id: these calls keep no state per list position.
+ *  6. The device-resident form only: MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE are required (the staging copies of host operands move
+ *     whole arrays and cannot honour rule 3).  Anything else is MMDX_ERR_INVALID_ARGUMENT, as are unknown flag bits, select == NULL, a
+ *     struct_size mismatch of either structure, unknown select->flags bits, reserved0 != 0, NULL handles or arrays, n_instances == 0,
+ *     a set created without the side asked for and a bone count of the set that is not the skeleton's -- all of them before the
+ *     device is touched.  A host-resident list is supported: it is copied through a scratch buffer of the set (on the ordered path of
+ *     the palette call, of the skeleton as well) in stream order, count word first, and the call returns after its work has completed.
+ *  7. With a device list the call is asynchronous on `model`'s stream (a borrowed stream applies; without a model, the selected
+ *     device's default stream) and records into mmdx_graph_begin / mmdx_graph_end after one un-recorded run; a host list is refused
+ *     while recording.  A replay reads ids, *count and the operands afresh.  Pinning as for the calls it is made of: the set's tables
+ *     and scratch, and the skeleton's for the palette call.  ids and count are 4-byte aligned.
+ *  8. The launches are sized from n_ids: workgroups whose list positions all lie behind *count return at once.
+ *  9. The palette call is one launch on a parallel-FK skeleton of up to 2 048 bones (a workgroup per list position).  Otherwise (append
+ *     bones / IK, or larger) the blend select goes into the set's pose scratch -- [NI] rows addressed by id, sized and pinned as for
+ *     the plain call -- and mmdx_skeleton_solve_select runs with the same list; the skeleton's scratch is then sized by n_ids, as
+ *     stated there.  On either path the skeleton's record of its last solve (mmdx_bench.h) is set as the plain call sets it.
+ * 10. mmdx_animator_advance has no select form on purpose: clocks run for everyone.  The frame and single-motion clocks, the
+ *     non-blend set calls and the physics seam get no select form either; a weight of 0 gives the set call's row, every bit. */
+MMDX_API mmdx_status mmdx_motion_set_blend_bones_time_select(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args,
+                                                             const mmdx_instance_select *select,
+                                                             float *out_poses /* [NI][NB][MMDX_POSE_FLOATS] */);
+MMDX_API mmdx_status mmdx_motion_set_blend_morphs_time_select(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args,
+                                                              const mmdx_instance_select *select, float *out_weights /* [NI][NM] */);
+MMDX_API mmdx_status mmdx_skeleton_solve_motion_set_blend_time_select(mmdx_skeleton_t skeleton, mmdx_motion_set_t set, mmdx_model_t model,
+                                                                      const mmdx_motion_blend_args *args,
+                                                                      const mmdx_instance_select *select,
+                                                                      float *out_palettes /* [NI][NB][16] */);
 MMDX_API void mmdx_skeleton_destroy(mmdx_skeleton_t skeleton);
 /* Fills `desc` with pointers into `pmx` (valid until mmdx_pmx_destroy): rest positions, parents, transform
  * levels, flag words, append and IK tables exactly as the file states them (PmxReader,

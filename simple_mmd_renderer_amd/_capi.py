@@ -231,6 +231,11 @@ SIGNATURES = {
     "mmdx_motion_set_blend_bones_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmdx_motion_set_blend_morphs_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmdx_skeleton_solve_motion_set_blend_time": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the same three for the listed instances: (set, model, args*, mmdx_instance_select*, out) and (skeleton, set, model, args*, select*, out)
+    "mmdx_motion_set_blend_bones_time_select": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(InstanceSelect), C.c_void_p]),
+    "mmdx_motion_set_blend_morphs_time_select": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(InstanceSelect), C.c_void_p]),
+    "mmdx_skeleton_solve_motion_set_blend_time_select": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                     C.POINTER(InstanceSelect), C.c_void_p]),
     # the crowd animator: (set, last_frames); (set, mmdx_animator_desc*, out); (animator, info*, clips*); (animator, blend args*);
     # (animator, arrays*); (animator, model, arrays*) x 2; (animator, model, n, ids, clips, fades, start_times, flags);
     # (animator, model, dt*, flags)

@@ -20,6 +20,7 @@
 //     class sort), then written out cooperatively as 16-byte coalesced stores.
 //   HBM-bound: ~24-32 B written per vertex-instance against ~100 VALU ops; no MFMA (gather of small
 //   mat x vec, <= 3 flop/B).
+#include "instance_list.hpp"
 #include "kernels.hpp"
 #include "motion_blend.hpp"
 #include "motion_clock.hpp"
@@ -1752,6 +1753,29 @@ __global__ __launch_bounds__(kThreads) void morph_track_blend_set_kernel(const M
     t.out[idx] = r;
 }
 
+// The same for the listed instances (mmdx_motion_set_blend_morphs_time_select; instance_list.hpp): one thread per (list position,
+// morph), t.ni = the list's capacity; the id is per lane, operand rows and the rate row are addressed by it.  Workgroups wholly behind
+// the count leave first.
+template <class Clock>
+__global__ __launch_bounds__(kThreads) void morph_track_blend_set_select_kernel(const MorphTrackParams t, const BlendOperands o,
+                                                                                const InstanceList list) {
+    const ListedInstances sel = {list};
+    const uint32_t used = sel.used(t.ni);
+    const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
+    if (size_t(blockIdx.x) * kThreads >= size_t(used) * t.nm) return;
+    if (idx >= size_t(used) * t.nm) return;
+    const uint32_t k = uint32_t(idx / t.nm), m = uint32_t(idx - size_t(k) * t.nm);
+    const Lane ln = sel.lane(k, used);
+    if (!ln.live) return;
+    const uint32_t i = ln.row;
+    const float w = o.weights[i];
+    const uint32_t side = blend_side(w);
+    const bool first_b = side == kBlendB;
+    float r = eval_clip_rate<Clock>(t, (first_b ? o.clips_b : o.clips_a)[i], o.n_clips, first_b ? o.times_b : o.times_a, m, i);
+    if (side == kBlendMix) r = blend_rate(r, eval_clip_rate<Clock>(t, o.clips_b[i], o.n_clips, o.times_b, m, i), w);
+    t.out[size_t(i) * t.nm + m] = r;
+}
+
 // ---- streaming copy / fill: the practical HBM ceiling printed next to the roofline ---------------
 // Every workgroup owns one contiguous 4 KiB chunk, workgroups in address order: the shape that
 // reached the highest store rate on MI355X in tools/archive/probes/bw_probe (a few-thousand-block grid-stride loop
@@ -2082,6 +2106,15 @@ hipError_t launch_morph_track_blend_set(const MorphTrackParams &t, const BlendOp
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(morph_track_blend_set_kernel<TimeClock>, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
                        t, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_morph_track_blend_set_select(const MorphTrackParams &t, const BlendOperands &o, const InstanceList &list,
+                                               hipStream_t stream) {
+    const size_t n = size_t(t.ni) * t.nm;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(morph_track_blend_set_select_kernel<TimeClock>, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       stream, t, o, list);
     return hipGetLastError();
 }
 

@@ -141,6 +141,11 @@ hipError_t launch_morph_track_eval_set(const MorphTrackParams &t, const uint32_t
 struct BlendOperands;
 // the cross-fade between two clips of a set (motion_blend.hpp), morph side: rates of clip a at time a and clip b at time b, blended
 hipError_t launch_morph_track_blend_set(const MorphTrackParams &t, const BlendOperands &o, hipStream_t stream);
+// mmdx_motion_set_blend_morphs_time_select: the same for the listed instances (instance_list.hpp); t.ni = the list's capacity,
+// operand rows and rate rows addressed by id
+struct InstanceList;
+hipError_t launch_morph_track_blend_set_select(const MorphTrackParams &t, const BlendOperands &o, const InstanceList &list,
+                                               hipStream_t stream);
 hipError_t launch_copy(void *dst, const void *src, size_t bytes, hipStream_t stream);
 hipError_t launch_fill(void *dst, size_t bytes, hipStream_t stream);
 

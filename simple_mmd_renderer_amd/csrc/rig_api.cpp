@@ -106,10 +106,12 @@ struct mmdx_motion_set_s {
     Buf clips_in, clock_in;                                         // host operands: 4 + 8 bytes per instance
     Buf blend_in;                                                   // host operands of a blend call: 28 bytes per instance
     Buf poses, out;                                                 // the two-launch palette path's poses; results bound for the host
+    Buf sel_in;                                                     // a *_blend_*_time_select call with a host list: {live count, ids[live]}
+    std::vector<uint32_t> sel_host;                                 // ... its source, alive until the copy has left it
     GraphPin pin;                                                   // recorded graphs that hold these buffers' addresses
     std::vector<Buf *> all() {
         return {&key_off, &key_frame, &key_tr, &key_rot, &key_curve, &lut, &m_key_off, &m_frames, &m_weights, &clips_in, &clock_in,
-                &blend_in, &poses, &out};
+                &blend_in, &poses, &out, &sel_in};
     }
     mmdx_motion_set_s() {
         for (Buf *b : all()) b->pin = &pin;
@@ -588,6 +590,8 @@ static mmdx_status skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_
     return MMDX_OK;
 }
 
+static mmdx_status check_instance_list(const mmdx_instance_select *sel, uint32_t n_instances, const char *plain, uint32_t &live_host);
+
 // mmdx_skeleton_solve_select: mmdx_skeleton_solve_morphed for the listed instances (include/mmdx.h, rules 1-10).  Everything that can
 // be decided without the device comes first, in the header's order; `live_host` = the ids of a host list that are in use.
 static mmdx_status check_select_args(mmdx_skeleton_t s, uint32_t n_instances, const float *poses, const float *morph_weights,
@@ -599,7 +603,13 @@ static mmdx_status check_select_args(mmdx_skeleton_t s, uint32_t n_instances, co
                                                "MMDX_OUT_ON_DEVICE, and MMDX_WEIGHTS_ON_DEVICE with morph_weights");
     if (flags & ~uint32_t(MMDX_POSES_ON_DEVICE | MMDX_OUT_ON_DEVICE | MMDX_WEIGHTS_ON_DEVICE | MMDX_WEIGHTS_SHARED))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
-    if (!sel) return fail(MMDX_ERR_INVALID_ARGUMENT, "select is NULL (mmdx_skeleton_solve / _morphed solve every instance)");
+    return check_instance_list(sel, n_instances, "mmdx_skeleton_solve / _morphed solve every instance", live_host);
+}
+
+// The list of a select call (mmdx_skeleton_solve_select, the *_blend_*_time_select calls), decided without the device: `plain` names
+// the calls that take every instance; `live_host` = the ids of a host list that are in use.
+static mmdx_status check_instance_list(const mmdx_instance_select *sel, uint32_t n_instances, const char *plain, uint32_t &live_host) {
+    if (!sel) return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("select is NULL (") + plain + ")");
     if (sel->struct_size != sizeof(mmdx_instance_select))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.struct_size mismatch");
     if (sel->flags & ~uint32_t(MMDX_SELECT_ON_DEVICE))
@@ -1190,3 +1200,173 @@ static mmdx_status skeleton_solve_motion_set_blend(mmdx_skeleton_t s, mmdx_motio
     s->last_solve = SolveShape{}; s->last_solve.solver = 2;
     return blend_finish(a->flags, st, out_palettes, fp.out, out_bytes);
 }
+
+// ---- the cross-fade for the listed instances (mmdx_motion_set_blend_*_time_select, mmdx_skeleton_solve_motion_set_blend_time_select;
+// include/mmdx.h, rules 1-10) -----------------------------------------------------------------------------------------------------------
+// Everything that can be decided without the device, before the first HIP call.  The device-resident form is checked ahead of
+// blend_check_args, which reads host operands when MMDX_TIMES_ON_DEVICE is absent; the rest of the operand checks are its own.
+static mmdx_status blend_select_check(mmdx_motion_set_t set, bool bone_side, const mmdx_motion_blend_args *a,
+                                      const mmdx_instance_select *sel, const float *out, uint32_t &live_host) {
+    if (!set || !a || !out) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (a->struct_size != sizeof(mmdx_motion_blend_args)) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_motion_blend_args.struct_size mismatch");
+    if (a->flags & ~uint32_t(MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    const uint32_t need = MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
+    if ((a->flags & need) != need)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "the select form of a blend call takes device operands only: pass MMDX_TIMES_ON_DEVICE | "
+                                               "MMDX_OUT_ON_DEVICE");
+    if (mmdx_status r = blend_check_args(set, bone_side, a, out)) return r;
+    return check_instance_list(sel, a->n_instances, "the calls without _select evaluate every instance", live_host);
+}
+
+// the list -> device addresses: a device list as it is; a host list through the set's scratch in stream order, count word first.
+// `cells` = list positions the launch is sized from: the capacity of a device list, the ids in use of a host list.
+static mmdx_status set_list_in(mmdx_motion_set_t set, const mmdx_instance_select *sel, uint32_t n_instances, uint32_t live_host,
+                               hipStream_t st, InstanceList *list, uint32_t *cells) {
+    *list = InstanceList{sel->ids, sel->count, n_instances};
+    if (sel->flags & MMDX_SELECT_ON_DEVICE) {
+        *cells = sel->n_ids;
+        return MMDX_OK;
+    }
+    *cells = live_host;
+    if (live_host == 0) return MMDX_OK;
+    HIP_TRY(set->sel_in.ensure((size_t(live_host) + 1) * 4));
+    set->sel_host.resize(size_t(live_host) + 1);
+    set->sel_host[0] = live_host;
+    std::copy(sel->ids, sel->ids + live_host, set->sel_host.begin() + 1);
+    HIP_TRY(hipMemcpyAsync(set->sel_in.ptr, set->sel_host.data(), set->sel_host.size() * 4, hipMemcpyHostToDevice, st));
+    list->count = static_cast<const uint32_t *>(set->sel_in.ptr);
+    list->ids = list->count + 1;
+    return MMDX_OK;
+}
+
+static BlendOperands blend_operands_device(mmdx_motion_set_t set, const mmdx_motion_blend_args *a) {
+    BlendOperands o;
+    o.clips_a = a->clips_a; o.clips_b = a->clips_b;
+    o.times_a = a->times_a; o.times_b = a->times_b;
+    o.weights = a->weights;
+    o.n_clips = set->host.n_clips;
+    return o;
+}
+
+// mmdx_motion_set_blend_bones_time_select
+static mmdx_status set_blend_bones_select(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *a,
+                                          const mmdx_instance_select *sel, float *out_poses) {
+    uint32_t live_host = 0;
+    if (mmdx_status r = blend_select_check(set, true, a, sel, out_poses, live_host)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    if (graph_recording() && set->device != device) return fail(MMDX_ERR_INVALID_ARGUMENT, kSetRecording);
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    InstanceList list;
+    uint32_t cells;
+    if (mmdx_status r = set_list_in(set, sel, a->n_instances, live_host, st, &list, &cells)) return r;
+    if (cells == 0) return MMDX_OK;                                 // an empty list writes nothing
+    BoneTrackParams p = set_bone_params(set, cells);
+    p.out = out_poses;
+    HIP_TRY(launch_bone_track_blend_set_select(p, blend_operands_device(set, a), list, st));
+    if (!(sel->flags & MMDX_SELECT_ON_DEVICE)) HIP_TRY(wait_stream(st));   // the borrowed list is consumed and the results are there
+    return MMDX_OK;
+}
+
+// mmdx_motion_set_blend_morphs_time_select
+static mmdx_status set_blend_morphs_select(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *a,
+                                           const mmdx_instance_select *sel, float *out_weights) {
+    uint32_t live_host = 0;
+    if (mmdx_status r = blend_select_check(set, false, a, sel, out_weights, live_host)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    if (graph_recording() && set->device != device) return fail(MMDX_ERR_INVALID_ARGUMENT, kSetRecording);
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    InstanceList list;
+    uint32_t cells;
+    if (mmdx_status r = set_list_in(set, sel, a->n_instances, live_host, st, &list, &cells)) return r;
+    if (cells == 0) return MMDX_OK;
+    MorphTrackParams t;
+    t.key_off = static_cast<const uint32_t *>(set->m_key_off.ptr);
+    t.key_frames = static_cast<const uint32_t *>(set->m_frames.ptr);
+    t.key_weights = static_cast<const float *>(set->m_weights.ptr);
+    t.nm = set->host.nm; t.ni = cells;
+    t.frames = nullptr; t.times = nullptr;
+    t.out = out_weights;
+    HIP_TRY(launch_morph_track_blend_set_select(t, blend_operands_device(set, a), list, st));
+    if (!(sel->flags & MMDX_SELECT_ON_DEVICE)) HIP_TRY(wait_stream(st));
+    return MMDX_OK;
+}
+
+// mmdx_skeleton_solve_motion_set_blend_time_select
+static mmdx_status skeleton_solve_motion_set_blend_select(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model,
+                                                          const mmdx_motion_blend_args *a, const mmdx_instance_select *sel,
+                                                          float *out_palettes) {
+    if (!s) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    uint32_t live_host = 0;
+    if (mmdx_status r = blend_select_check(set, true, a, sel, out_palettes, live_host)) return r;
+    if (set->host.bones.nb != s->plan.nb)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "the motion set was bound to " + std::to_string(set->host.bones.nb) +
+                                               " bones, the skeleton has " + std::to_string(s->plan.nb));
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const SkeletonPlan &pl = s->plan;
+    const uint32_t ni = a->n_instances;
+    if (pl.serial || size_t(pl.nb) * 32 > kMotionFkMaxLds) {
+        // append bones / IK (the ordered solver) or a skeleton too large for the LDS pose table: the blend select into the set's pose
+        // scratch -- [NI] rows, addressed by id -- then the select solve with the same list
+        const size_t pose_bytes = size_t(ni) * pl.nb * MMDX_POSE_FLOATS * sizeof(float);
+        if (graph_recording() && (set->poses.bytes < pose_bytes || set->device != device))
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "run the call once before recording: it sizes the motion set's pose buffer");
+        if (mmdx_status r = set_to_device(set, device)) return r;
+        HIP_TRY(set->poses.ensure(pose_bytes));
+        if (mmdx_status r = set_blend_bones_select(set, model, a, sel, static_cast<float *>(set->poses.ptr))) return r;
+        return mmdx_skeleton_solve_select(s, model, ni, static_cast<const float *>(set->poses.ptr), nullptr,
+                                          MMDX_POSES_ON_DEVICE | MMDX_OUT_ON_DEVICE, sel, out_palettes);
+    }
+    if (graph_recording() && (set->device != device || s->device != device))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory and the motion "
+                                               "set and the skeleton must have run on this device before");
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    if (mmdx_status r = skeleton_to_device(s, device)) return r;
+    graph_note_handle(model, &set->pin);
+    graph_note_handle(model, &s->pin);
+    InstanceList list;
+    uint32_t cells;
+    if (mmdx_status r = set_list_in(set, sel, ni, live_host, st, &list, &cells)) return r;
+    if (cells == 0) return MMDX_OK;
+    const BoneTrackParams tp = set_bone_params(set, cells);
+    SkeletonParams fp;
+    fp.morph = nullptr;
+    fp.poses = nullptr;
+    fp.out = out_palettes;
+    fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
+    fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
+    fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
+    fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
+    fp.nb = pl.nb; fp.ni = cells;
+    HIP_TRY(launch_motion_fk_blend_set_select(tp, fp, blend_operands_device(set, a), list, st));
+    s->last_solve = SolveShape{}; s->last_solve.solver = 2;
+    if (!(sel->flags & MMDX_SELECT_ON_DEVICE)) HIP_TRY(wait_stream(st));
+    return MMDX_OK;
+}
+
+extern "C" {
+
+mmdx_status mmdx_motion_set_blend_bones_time_select(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args,
+                                                    const mmdx_instance_select *select, float *out_poses) {
+    return set_blend_bones_select(set, model, args, select, out_poses);
+}
+
+mmdx_status mmdx_motion_set_blend_morphs_time_select(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args,
+                                                     const mmdx_instance_select *select, float *out_weights) {
+    return set_blend_morphs_select(set, model, args, select, out_weights);
+}
+
+mmdx_status mmdx_skeleton_solve_motion_set_blend_time_select(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model,
+                                                             const mmdx_motion_blend_args *args, const mmdx_instance_select *select,
+                                                             float *out_palettes) {
+    return skeleton_solve_motion_set_blend_select(s, set, model, args, select, out_palettes);
+}
+
+}  // extern "C"

@@ -251,27 +251,7 @@ __global__ __launch_bounds__(kRigThreads) void skeleton_fk_kernel(const Skeleton
     fk_bone(p, [&](uint32_t k) { return pose[k]; }, i, bone, reinterpret_cast<float4 *>(p.out) + idx * 4);
 }
 
-// ---- which instance a lane works on ------------------------------------------------------------------------------------------
-// `cell` indexes what a call keeps per instance in its own scratch (the ordered solver's state, the bone-morph state: p.ni cells,
-// instance fastest), `row` the caller's arrays (poses, rates, palettes).  The plain calls: cell k is instance k and so is its row.
-// mmdx_skeleton_solve_select: cell k is LIST POSITION k -- an id listed twice gets two cells, two solves and the same bytes twice --
-// and the row is ids[k]; positions behind min(*count, capacity) and ids that are no row of the arrays are dead.  p.ni is the number of
-// cells: the instance count of a plain call, the list's capacity of a select call.  The plain kernels derive cell = row = instance
-// themselves, as they always did; the select forms go through ListedInstances.
-struct Lane {
-    uint32_t cell, row;
-    bool live;
-};
-struct ListedInstances {
-    InstanceList l;
-    // (the same address in every lane: one scalar load per wave, once per kernel)
-    __device__ __forceinline__ uint32_t used(uint32_t cells) const { return l.count ? min(*l.count, cells) : cells; }
-    __device__ __forceinline__ Lane lane(uint32_t k, uint32_t used) const {
-        const bool in = k < used;
-        const uint32_t id = in ? l.ids[k] : 0u;
-        return {k, id, in && id < l.n_rows};
-    }
-};
+// ---- which instance a lane works on: Lane / ListedInstances, instance_list.hpp ---------------------------------------------------
 
 // skeleton_fk_kernel for the listed instances: one thread per (list position, bone); the bone morphs' state by position, the pose
 // and the palette row by id.  Workgroups wholly behind the count leave first.
@@ -286,6 +266,37 @@ __global__ __launch_bounds__(kRigThreads) void skeleton_fk_select_kernel(const S
     if (!ln.live) return;
     const float4 *pose = reinterpret_cast<const float4 *>(p.poses) + size_t(ln.row) * p.nb * 2;
     fk_bone(p, [&](uint32_t j) { return pose[j]; }, ln.cell, bone, reinterpret_cast<float4 *>(p.out) + (size_t(ln.row) * p.nb + bone) * 4);
+}
+
+// bone_track_blend_set_kernel for the listed instances (mmdx_motion_set_blend_bones_time_select): one thread per (list position,
+// bone), p.ni = the list's capacity.  A wave spans list positions when nb is no multiple of 64, so the id -- and with it weight,
+// clip ids and clocks -- is per lane; operand rows and the pose row are addressed by the id, nothing is kept per position.  The
+// evaluation is the plain kernel's, call for call.  Workgroups wholly behind the count leave first.
+template <class Clock>
+__global__ __launch_bounds__(kRigThreads) void bone_track_blend_set_select_kernel(const BoneTrackParams p, const BlendOperands o,
+                                                                                  const InstanceList list) {
+    const ListedInstances sel = {list};
+    const uint32_t used = sel.used(p.ni);
+    const size_t idx = size_t(blockIdx.x) * kRigThreads + threadIdx.x;
+    if (size_t(blockIdx.x) * kRigThreads >= size_t(used) * p.nb) return;
+    if (idx >= size_t(used) * p.nb) return;
+    const uint32_t k = uint32_t(idx / p.nb), bone = uint32_t(idx - size_t(k) * p.nb);
+    const Lane ln = sel.lane(k, used);
+    if (!ln.live) return;
+    const uint32_t i = ln.row;
+    const float w = o.weights[i];
+    const uint32_t side = blend_side(w);
+    const bool first_b = side == kBlendB;
+    float4 t, q;
+    eval_clip_pose(p, (first_b ? o.clips_b : o.clips_a)[i], o.n_clips, clock_of<Clock>(nullptr, first_b ? o.times_b : o.times_a, i), bone, t, q);
+    if (side == kBlendMix) {
+        float4 tb, qb;
+        eval_clip_pose(p, o.clips_b[i], o.n_clips, clock_of<Clock>(nullptr, o.times_b, i), bone, tb, qb);
+        blend_pose(t, q, tb, qb, w);
+    }
+    float4 *out = reinterpret_cast<float4 *>(p.out) + (size_t(i) * p.nb + bone) * 2;
+    out[0] = t;
+    out[1] = q;
 }
 
 // Bone tracks -> palette in ONE launch (mmdx_skeleton_solve_motion on a parallel-FK skeleton): a workgroup is one instance; its
@@ -372,6 +383,46 @@ __global__ __launch_bounds__(1024) void motion_fk_blend_set_kernel(const BoneTra
             float4 *out = reinterpret_cast<float4 *>(t0.out) + (size_t(i) * p.nb + b) * 2;
             out[0] = tr; out[1] = q;
         }
+    }
+    __syncthreads();
+    for (uint32_t bone = threadIdx.x; bone < p.nb; bone += blockDim.x)
+        fk_bone(p, [&](uint32_t k) { return pose_lds[k]; }, i, bone, reinterpret_cast<float4 *>(p.out) + (size_t(i) * p.nb + bone) * 4);
+}
+
+// motion_fk_blend_set_kernel for the listed instances (mmdx_skeleton_solve_motion_set_blend_time_select): a workgroup is one LIST
+// POSITION (p.ni = the list's capacity).  *count, the id and the five operands of its row are workgroup-uniform loads (the same
+// address in every lane: scalar loads).  A workgroup behind the count, or whose id is no row, returns BEFORE the barrier: the
+// condition is uniform over the workgroup, so no lane of a live workgroup skips it.  Operands and the palette row by id; the blend in
+// registers, the poses in LDS, eval_clip_pose / blend_pose / fk_bone as in the plain kernel.
+template <class Clock>
+__global__ __launch_bounds__(1024) void motion_fk_blend_set_select_kernel(const BoneTrackParams t0, const SkeletonParams p, const BlendOperands o,
+                                                                          const InstanceList list) {
+    extern __shared__ float4 pose_lds[];                 // [nb][2]
+    const ListedInstances sel = {list};
+    const Lane ln = sel.lane(blockIdx.x, sel.used(p.ni));
+    if (!ln.live) return;
+    const uint32_t i = ln.row;
+    const float w = o.weights[i];
+    const uint32_t side = blend_side(w);
+    const bool first_b = side == kBlendB, mix = side == kBlendMix;
+    const uint32_t clip0 = (first_b ? o.clips_b : o.clips_a)[i];
+    const Clock clk0 = clock_of<Clock>(nullptr, first_b ? o.times_b : o.times_a, i);
+    uint32_t clip1 = 0xFFFFFFFFu;
+    Clock clk1 = clk0;
+    if (mix) {
+        clip1 = o.clips_b[i];
+        clk1 = clock_of<Clock>(nullptr, o.times_b, i);
+    }
+    for (uint32_t b = threadIdx.x; b < p.nb; b += blockDim.x) {
+        float4 tr, q;
+        eval_clip_pose(t0, clip0, o.n_clips, clk0, b, tr, q);
+        if (mix) {
+            float4 tb, qb;
+            eval_clip_pose(t0, clip1, o.n_clips, clk1, b, tb, qb);
+            blend_pose(tr, q, tb, qb, w);
+        }
+        pose_lds[2 * b] = tr;
+        pose_lds[2 * b + 1] = q;
     }
     __syncthreads();
     for (uint32_t bone = threadIdx.x; bone < p.nb; bone += blockDim.x)
@@ -1230,6 +1281,26 @@ hipError_t launch_motion_fk_blend_set(const BoneTrackParams &t, const SkeletonPa
     if (lds > kMotionFkMaxLds) return hipErrorInvalidValue;                  // callers check: the two-launch path takes over
     const uint32_t threads = std::min<uint32_t>(1024u, (p.nb + 63u) / 64u * 64u);
     hipLaunchKernelGGL(motion_fk_blend_set_kernel<TimeClock>, dim3(p.ni), dim3(threads), lds, stream, t, p, o);
+    return hipGetLastError();
+}
+
+// the select forms of the two above: sized from p.ni = the list's capacity, one thread per (list position, bone) / one workgroup per
+// list position
+hipError_t launch_bone_track_blend_set_select(const BoneTrackParams &p, const BlendOperands &o, const InstanceList &list, hipStream_t stream) {
+    const size_t n = size_t(p.ni) * p.nb;
+    if (n == 0) return hipSuccess;
+    const dim3 grid(uint32_t((n + kRigThreads - 1) / kRigThreads));
+    hipLaunchKernelGGL(bone_track_blend_set_select_kernel<TimeClock>, grid, dim3(kRigThreads), 0, stream, p, o, list);
+    return hipGetLastError();
+}
+
+hipError_t launch_motion_fk_blend_set_select(const BoneTrackParams &t, const SkeletonParams &p, const BlendOperands &o,
+                                             const InstanceList &list, hipStream_t stream) {
+    if (p.ni == 0 || p.nb == 0) return hipSuccess;
+    const size_t lds = size_t(p.nb) * 32;
+    if (lds > kMotionFkMaxLds) return hipErrorInvalidValue;                  // callers check: the two-launch path takes over
+    const uint32_t threads = std::min<uint32_t>(1024u, (p.nb + 63u) / 64u * 64u);
+    hipLaunchKernelGGL(motion_fk_blend_set_select_kernel<TimeClock>, dim3(p.ni), dim3(threads), lds, stream, t, p, o, list);
     return hipGetLastError();
 }
 

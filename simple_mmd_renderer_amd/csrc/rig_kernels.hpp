@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "instance_list.hpp"
 #include "rig.hpp"
 
 namespace mmdx {
@@ -31,15 +32,16 @@ hipError_t launch_bone_morph(const BoneMorphParams &p, hipStream_t stream);
 hipError_t launch_physics_override(const PhysicsParams &p, hipStream_t stream);
 // mmdx_skeleton_solve_select: the select forms of the one-step solve's kernels.  Their parameter blocks are the plain ones with
 // ni = the list's CAPACITY (state and bone-morph cells are per list position); the list travels as a kernel argument of its own.
-struct InstanceList {
-    const uint32_t *ids;                        // [capacity], device memory
-    const uint32_t *count;                      // device memory; the first min(*count, capacity) ids are used; nullptr = all
-    uint32_t n_rows;                            // NI: rows of poses / rates / palettes; an id >= n_rows is skipped
-};
+// (InstanceList: instance_list.hpp)
 hipError_t launch_skeleton_fk_select(const SkeletonParams &p, const InstanceList &list, hipStream_t stream);
 hipError_t launch_bone_morph_select(const BoneMorphParams &p, const InstanceList &list, hipStream_t stream);
 hipError_t launch_skeleton_ordered_select(const SerialParams &p, const uint8_t *round_coop, const InstanceList &list, hipStream_t stream,
                                           SolveShape *shape);
+// mmdx_motion_set_blend_bones_time_select / mmdx_skeleton_solve_motion_set_blend_time_select: the select forms of the two blend
+// kernels.  p.ni / t.ni = the list's capacity; operand rows, pose rows and palette rows are addressed by id (list.n_rows of them).
+hipError_t launch_bone_track_blend_set_select(const BoneTrackParams &p, const BlendOperands &o, const InstanceList &list, hipStream_t stream);
+hipError_t launch_motion_fk_blend_set_select(const BoneTrackParams &t, const SkeletonParams &p, const BlendOperands &o,
+                                             const InstanceList &list, hipStream_t stream);
 
 // api.cpp: the device and stream a motion / rig call runs on -- the model's own when a (device) model
 // is given, so that the deform call that follows is ordered after it; else the selected device's

@@ -468,10 +468,36 @@ public:
     void BlendTimeMorphRates(const mmdx_motion_blend_args &operands, float *out_rates) {
         check(mmdx_motion_set_blend_morphs_time(set_, poser_.handle(), &operands, out_rates));
     }
+    // The same for a listed subset of the crowd (mmdx.h, the *_blend_*_time_select calls): only the first *count (NULL = n_ids)
+    // instances of ids are evaluated, their rows bit for bit the plain call's; every other row of the output keeps its bytes, so a
+    // crowd's track evaluation costs what is in view.  The clocks still advance for everyone (Animator::Advance).  ids / count are
+    // device memory (what mmdx_cull_bounds wrote; asynchronous on the poser's stream) or, with list_on_device = false, host memory.
+    void BlendTimePalettes(const mmdx_motion_blend_args &operands, const uint32_t *ids, const uint32_t *count, uint32_t n_ids,
+                           float *out_palettes, bool list_on_device = true) {
+        const mmdx_instance_select s = select(ids, count, n_ids, list_on_device);
+        check(mmdx_skeleton_solve_motion_set_blend_time_select(poser_.skeleton(), set_, poser_.handle(), &operands, &s, out_palettes));
+    }
+    void BlendTimePoses(const mmdx_motion_blend_args &operands, const uint32_t *ids, const uint32_t *count, uint32_t n_ids,
+                        float *out_poses, bool list_on_device = true) {
+        const mmdx_instance_select s = select(ids, count, n_ids, list_on_device);
+        check(mmdx_motion_set_blend_bones_time_select(set_, poser_.handle(), &operands, &s, out_poses));
+    }
+    void BlendTimeMorphRates(const mmdx_motion_blend_args &operands, const uint32_t *ids, const uint32_t *count, uint32_t n_ids,
+                             float *out_rates, bool list_on_device = true) {
+        const mmdx_instance_select s = select(ids, count, n_ids, list_on_device);
+        check(mmdx_motion_set_blend_morphs_time_select(set_, poser_.handle(), &operands, &s, out_rates));
+    }
     mmdx_motion_set_t handle() const { return set_; }
     Poser &poser() const { return poser_; }
 
 private:
+    static mmdx_instance_select select(const uint32_t *ids, const uint32_t *count, uint32_t n_ids, bool on_device) {
+        mmdx_instance_select s{};
+        s.struct_size = sizeof(s);
+        s.flags = on_device ? uint32_t(MMDX_SELECT_ON_DEVICE) : 0u;
+        s.ids = ids; s.count = count; s.n_ids = n_ids;
+        return s;
+    }
     static uint32_t flags(bool on_device) { return on_device ? uint32_t(MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE) : 0u; }
     Poser &poser_;
     mmdx_motion_set_t set_ = nullptr;

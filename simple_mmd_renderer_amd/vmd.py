@@ -256,6 +256,15 @@ def blend_args_device(n_instances, clips_a_ptr, times_a_ptr, clips_b_ptr, times_
                            TIMES_ON_DEVICE | api.OUT_ON_DEVICE)
 
 
+def instance_select(ids_ptr, n_ids: int, count_ptr=None, on_device=True) -> "api.InstanceSelect":
+    """mmdx_instance_select over a u32 list (capacity n_ids, the first *count_ptr in use; None = all) in device or host memory."""
+    s = api.InstanceSelect()
+    s.struct_size = C.sizeof(api.InstanceSelect)
+    s.flags = api.SELECT_ON_DEVICE if on_device else 0
+    s.ids, s.count, s.n_ids = ids_ptr, count_ptr, n_ids
+    return s
+
+
 class MotionSet:
     """A bank of clips bound to one model (mmdx_motion_set_t): every instance of a crowd plays its own clip, clips[i], at its own
     frame or time.  bone_motions / morph_motions: sequences of BoneMotion / MorphMotion, one per clip, at least one of the two;
@@ -351,6 +360,26 @@ class MotionSet:
         """The same for morph rates: out f32[NI][NM] resident in HBM."""
         args = blend_args_device(n_instances, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr)
         api.check(api.lib().mmdx_motion_set_blend_morphs_time(self.h, model.h if model is not None else None, C.byref(args), out_ptr))
+
+    # -- the cross-fade for a listed subset of the crowd (mmdx_motion_set_blend_*_time_select) ---------------------------
+    def blend_bones_time_select_device(self, n_instances: int, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr,
+                                       out_ptr, ids_ptr, n_ids: int, count_ptr=None, model=None, select_on_device=True) -> None:
+        """blend_bones_time_device for the instances in the u32 list at ids_ptr only (capacity n_ids, the first *count_ptr in use;
+        count_ptr None = all n_ids): the operand arrays and out f32[NI][NB][8] keep [n_instances] rows, every row that is not
+        listed keeps its bytes.  List and count in device memory (asynchronous) or, with select_on_device=False, in host memory
+        (the call returns when its work is done)."""
+        args = blend_args_device(n_instances, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr)
+        s = instance_select(ids_ptr, n_ids, count_ptr, select_on_device)
+        api.check(api.lib().mmdx_motion_set_blend_bones_time_select(self.h, model.h if model is not None else None, C.byref(args),
+                                                                    C.byref(s), out_ptr))
+
+    def blend_morphs_time_select_device(self, n_instances: int, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr,
+                                        out_ptr, ids_ptr, n_ids: int, count_ptr=None, model=None, select_on_device=True) -> None:
+        """The same for morph rates: out f32[NI][NM] resident in HBM."""
+        args = blend_args_device(n_instances, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr)
+        s = instance_select(ids_ptr, n_ids, count_ptr, select_on_device)
+        api.check(api.lib().mmdx_motion_set_blend_morphs_time_select(self.h, model.h if model is not None else None, C.byref(args),
+                                                                     C.byref(s), out_ptr))
 
     def clip_frames(self) -> np.ndarray:
         """u32 [n_clips]: the largest key frame of every clip over the sides the set has (Motion::GetLength of those tracks);
@@ -756,6 +785,47 @@ class Skeleton:
         try:
             self.solve_select_device(ni, d_pose.ptr, d_out.ptr, d_ids.ptr, ids.size, d_cnt.ptr if d_cnt else None, model,
                                      d_w.ptr if d_w else None, shared)
+            api.check(api.lib().mmdx_sync(model.h) if model is not None else api.lib().mmdx_device_synchronize())
+            return d_out.download((ni, self.nb, 16), np.float32)
+        finally:
+            for b in bufs:
+                b.free()
+
+    # -- tracks and solve for a listed subset of the crowd (mmdx_skeleton_solve_motion_set_blend_time_select) ----------------
+    def solve_motion_set_blend_time_select_device(self, motion_set: "MotionSet", n_instances: int, clips_a_ptr, times_a_ptr,
+                                                  clips_b_ptr, times_b_ptr, weights_ptr, out_ptr, ids_ptr, n_ids: int, count_ptr=None,
+                                                  model=None, select_on_device=True) -> None:
+        """solve_motion_set_blend_time_device for the instances in the u32 list at ids_ptr only (capacity n_ids, the first
+        *count_ptr in use; count_ptr None = all n_ids); every palette row that is not listed keeps its bytes.  List and count in
+        device memory (asynchronous) or, with select_on_device=False, in host memory (the call returns when its work is done)."""
+        args = blend_args_device(n_instances, clips_a_ptr, times_a_ptr, clips_b_ptr, times_b_ptr, weights_ptr)
+        s = instance_select(ids_ptr, n_ids, count_ptr, select_on_device)
+        api.check(api.lib().mmdx_skeleton_solve_motion_set_blend_time_select(self.h, motion_set.h, model.h if model is not None else None,
+                                                                             C.byref(args), C.byref(s), out_ptr))
+
+    def solve_motion_set_blend_time_select(self, motion_set: "MotionSet", clips_a, times_a, clips_b, times_b, weights, ids, count=None,
+                                           model=None, out=None) -> np.ndarray:
+        """Host convenience in the style of solve_select: uploads the five operand arrays [NI], the id list and `out` (the palettes
+        [NI, NB, 16] as they stand before the call; zeros when None), evaluates and solves the first `count` (None = all) listed
+        instances and downloads the WHOLE palette array."""
+        from .engine import DeviceBuffer
+        args, keep = blend_args_host(clips_a, times_a, clips_b, times_b, weights)
+        ca, cb, ta, tb, w = keep
+        ni = args.n_instances
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        before = np.zeros((ni, self.nb, 16), np.float32) if out is None else np.ascontiguousarray(out, np.float32)
+        assert before.shape == (ni, self.nb, 16)
+        bufs = [DeviceBuffer.from_numpy(a) for a in (ca, ta, cb, tb, w)] + [DeviceBuffer.from_numpy(before), DeviceBuffer(max(ids.nbytes, 4))]
+        d_out, d_ids = bufs[5], bufs[6]
+        if ids.size:
+            d_ids.upload(ids)
+        d_cnt = None
+        if count is not None:
+            d_cnt = DeviceBuffer.from_numpy(np.array([count], np.uint32))
+            bufs.append(d_cnt)
+        try:
+            self.solve_motion_set_blend_time_select_device(motion_set, ni, *[b.ptr for b in bufs[:5]], d_out.ptr, d_ids.ptr, ids.size,
+                                                           d_cnt.ptr if d_cnt else None, model)
             api.check(api.lib().mmdx_sync(model.h) if model is not None else api.lib().mmdx_device_synchronize())
             return d_out.download((ni, self.nb, 16), np.float32)
         finally:
