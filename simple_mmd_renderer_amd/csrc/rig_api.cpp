@@ -1,9 +1,15 @@
 // rig_api.cpp -- C ABI of the bone-track and skeleton entry points (include/mmdx.h) over the HIP runtime.
 // Static tables (keys, curve tables, chains) are uploaded on first use per device; per-call operands may
 // live on the host (copied through handle-owned scratch) or in HBM.  No CPU fallback.
+//
+// Every device call is the same sequence, and every step of it is one function of this file, defined ahead of the entry points:
+//   check the arguments (nothing here needs the device) -> resolve_stream -> refuse what a recording cannot hold (refuse_recording)
+//   -> *_to_device -> graph_note_handle -> stage host operands (*_in) -> the parameter block (*_params) -> route_out -> launch ->
+//   finish.  A track + solve call on a skeleton that needs two launches (two_launches) sizes a pose scratch and makes two such calls.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <memory>
 #include <new>
 #include <string>
@@ -57,15 +63,48 @@ struct Buf {
     }
 };
 
+void release(const std::vector<Buf *> &bufs) {
+    for (Buf *b : bufs) b->release();
+}
+
+// The key and curve tables of bone tracks in device memory: one motion's, or a set's clips laid end to end (rig.hpp).
+struct BoneTables {
+    Buf key_off, key_frame, key_tr, key_rot, key_curve, lut;
+    mmdx_status upload(const BoneMotionHost &h) {
+        HIP_TRY(key_off.upload(h.key_off));
+        HIP_TRY(key_frame.upload(h.key_frame));
+        HIP_TRY(key_tr.upload(h.key_tr));
+        HIP_TRY(key_rot.upload(h.key_rot));
+        HIP_TRY(key_curve.upload(h.key_curve));
+        HIP_TRY(lut.upload(h.lut));
+        return MMDX_OK;
+    }
+    // `ni`: instances, or the list positions of a select call; clock and output are the call's to fill in
+    BoneTrackParams params(uint32_t nb, uint32_t ni) const {
+        BoneTrackParams p;
+        p.key_off = static_cast<const uint32_t *>(key_off.ptr);
+        p.key_frame = static_cast<const uint32_t *>(key_frame.ptr);
+        p.key_tr = static_cast<const float *>(key_tr.ptr);
+        p.key_rot = static_cast<const float *>(key_rot.ptr);
+        p.key_curve = static_cast<const uint32_t *>(key_curve.ptr);
+        p.lut = static_cast<const float *>(lut.ptr);
+        p.frames = nullptr; p.out = nullptr; p.times = nullptr;
+        p.nb = nb; p.ni = ni;
+        return p;
+    }
+};
+
 }  // namespace
 
 struct mmdx_bone_motion_s {
     BoneMotionHost host;
     int device = -1;
-    Buf key_off, key_frame, key_tr, key_rot, key_curve, lut, frames_in, out;
+    BoneTables t;
+    Buf frames_in, out;
     GraphPin pin;                                         // recorded graphs that hold these buffers' addresses
+    std::vector<Buf *> all() { return {&t.key_off, &t.key_frame, &t.key_tr, &t.key_rot, &t.key_curve, &t.lut, &frames_in, &out}; }
     mmdx_bone_motion_s() {
-        for (Buf *b : {&key_off, &key_frame, &key_tr, &key_rot, &key_curve, &lut, &frames_in, &out}) b->pin = &pin;
+        for (Buf *b : all()) b->pin = &pin;
     }
 };
 
@@ -83,16 +122,12 @@ struct mmdx_skeleton_s {
     const float *pre_morph = nullptr;
     SolveShape last_solve;                                // what the last successful solve launched (mmdx_debug_last_solve_shape)
     GraphPin pin;                                         // recorded graphs that hold these buffers' addresses
-    mmdx_skeleton_s() {
-        for (Buf *b : {&local_offset, &neg_rest, &chain_off, &chain, &poses_in, &out, &order, &bones, &iks, &links, &events, &rounds,
-                       &state, &apps, &app_chain, &rates_in, &morph_state, &over_bone, &over_strict, &over_skin, &sel_in})
-            b->pin = &pin;
+    std::vector<Buf *> all() {
+        return {&local_offset, &neg_rest, &chain_off, &chain, &poses_in, &out, &order, &bones, &iks, &links, &events, &rounds, &state,
+                &apps, &app_chain, &rates_in, &morph_state, &over_bone, &over_strict, &over_skin, &sel_in};
     }
-    void release_all() {
-        for (Buf *b : {&local_offset, &neg_rest, &chain_off, &chain, &poses_in, &out, &order, &bones, &iks, &links, &events, &rounds,
-                       &state,
-                       &apps, &app_chain, &rates_in, &morph_state, &over_bone, &over_strict, &over_skin, &sel_in})
-            b->release();
+    mmdx_skeleton_s() {
+        for (Buf *b : all()) b->pin = &pin;
     }
 };
 
@@ -101,7 +136,7 @@ struct mmdx_motion_set_s {
     MotionSetHost host;
     std::vector<uint32_t> clip_frames;                              // [n_clips] largest key frame of each clip (mmdx_motion_set_clip_frames)
     int device = -1;
-    Buf key_off, key_frame, key_tr, key_rot, key_curve, lut;        // bone side
+    BoneTables t;                                                   // bone side
     Buf m_key_off, m_frames, m_weights;                             // morph side
     Buf clips_in, clock_in;                                         // host operands: 4 + 8 bytes per instance
     Buf blend_in;                                                   // host operands of a blend call: 28 bytes per instance
@@ -110,8 +145,8 @@ struct mmdx_motion_set_s {
     std::vector<uint32_t> sel_host;                                 // ... its source, alive until the copy has left it
     GraphPin pin;                                                   // recorded graphs that hold these buffers' addresses
     std::vector<Buf *> all() {
-        return {&key_off, &key_frame, &key_tr, &key_rot, &key_curve, &lut, &m_key_off, &m_frames, &m_weights, &clips_in, &clock_in,
-                &blend_in, &poses, &out, &sel_in};
+        return {&t.key_off, &t.key_frame, &t.key_tr, &t.key_rot, &t.key_curve, &t.lut, &m_key_off, &m_frames, &m_weights, &clips_in,
+                &clock_in, &blend_in, &poses, &out, &sel_in};
     }
     mmdx_motion_set_s() {
         for (Buf *b : all()) b->pin = &pin;
@@ -120,54 +155,21 @@ struct mmdx_motion_set_s {
 
 const std::vector<uint32_t> &mmdx::motion_set_clip_frames(const mmdx_motion_set_s *set) { return set->clip_frames; }
 
-// static tables of a motion / a skeleton -> the device they are about to run on (once per device)
+// ---- static tables of a motion / a skeleton / a set -> the device they are about to run on (once per device) --------------------
 static mmdx_status motion_to_device(mmdx_bone_motion_t m, int device) {
     if (m->device == device) return MMDX_OK;
     if (graph_pinned(&m->pin)) return hip_status(hipErrorIllegalState, "moving a bone motion to another device");
-    const BoneMotionHost &h = m->host;
-    for (Buf *b : {&m->key_off, &m->key_frame, &m->key_tr, &m->key_rot, &m->key_curve, &m->lut, &m->frames_in, &m->out})
-        b->release();
-    HIP_TRY(m->key_off.upload(h.key_off));
-    HIP_TRY(m->key_frame.upload(h.key_frame));
-    HIP_TRY(m->key_tr.upload(h.key_tr));
-    HIP_TRY(m->key_rot.upload(h.key_rot));
-    HIP_TRY(m->key_curve.upload(h.key_curve));
-    HIP_TRY(m->lut.upload(h.lut));
+    release(m->all());
+    if (mmdx_status r = m->t.upload(m->host)) return r;
     m->device = device;
     return MMDX_OK;
 }
-static BoneTrackParams motion_params(mmdx_bone_motion_t m, uint32_t n_instances) {
-    BoneTrackParams p;
-    p.key_off = static_cast<const uint32_t *>(m->key_off.ptr);
-    p.key_frame = static_cast<const uint32_t *>(m->key_frame.ptr);
-    p.key_tr = static_cast<const float *>(m->key_tr.ptr);
-    p.key_rot = static_cast<const float *>(m->key_rot.ptr);
-    p.key_curve = static_cast<const uint32_t *>(m->key_curve.ptr);
-    p.lut = static_cast<const float *>(m->lut.ptr);
-    p.frames = nullptr; p.out = nullptr; p.times = nullptr;
-    p.nb = m->host.nb; p.ni = n_instances;
-    return p;
-}
-// the instant of every instance -> the kernel parameters: frame numbers (uint32_t) or, with `time`, seconds (double).  Host
-// operands go through the motion's scratch, sized 8 bytes per instance whenever it grows (room for either).
-static mmdx_status motion_clock_in(mmdx_bone_motion_t m, const void *clock, bool time, uint32_t n_instances, uint32_t flags,
-                                   hipStream_t st, BoneTrackParams &p) {
-    const void *dev = clock;
-    if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
-        const size_t bytes = size_t(n_instances) * (time ? 8 : 4);
-        if (m->frames_in.bytes < bytes) HIP_TRY(m->frames_in.ensure(size_t(n_instances) * 8));
-        HIP_TRY(hipMemcpyAsync(m->frames_in.ptr, clock, bytes, hipMemcpyHostToDevice, st));
-        dev = m->frames_in.ptr;
-    }
-    if (time) p.times = static_cast<const double *>(dev);
-    else p.frames = static_cast<const uint32_t *>(dev);
-    return MMDX_OK;
-}
+
 static mmdx_status skeleton_to_device(mmdx_skeleton_t s, int device) {
     if (s->device == device) return MMDX_OK;
     if (graph_pinned(&s->pin)) return hip_status(hipErrorIllegalState, "moving a skeleton to another device");
     const SkeletonPlan &pl = s->plan;
-    s->release_all();
+    release(s->all());
     HIP_TRY(s->apps.upload(pl.apps));
     HIP_TRY(s->app_chain.upload(pl.app_chain));
     if (pl.serial) {
@@ -187,28 +189,583 @@ static mmdx_status skeleton_to_device(mmdx_skeleton_t s, int device) {
     return MMDX_OK;
 }
 
+static mmdx_status set_to_device(mmdx_motion_set_t set, int device) {
+    if (set->device == device) return MMDX_OK;
+    if (graph_pinned(&set->pin)) return hip_status(hipErrorIllegalState, "moving a motion set to another device");
+    const MotionSetHost &h = set->host;
+    release(set->all());
+    if (h.has_bones)
+        if (mmdx_status r = set->t.upload(h.bones)) return r;
+    if (h.has_morphs) {
+        HIP_TRY(set->m_key_off.upload(h.morph_key_off));
+        HIP_TRY(set->m_frames.upload(h.morph_frames));
+        HIP_TRY(set->m_weights.upload(h.morph_weights));
+    }
+    set->device = device;
+    return MMDX_OK;
+}
+
+// ---- what a recording cannot hold ------------------------------------------------------------------------------------------------
+// While a graph is being recorded a call may neither copy from the host nor allocate: `flags` must hold every *_ON_DEVICE bit in
+// `need`, and the static tables of every handle must be on `device` already (`ran_on`: the handles' device fields).
+static mmdx_status refuse_recording(uint32_t flags, uint32_t need, int device, std::initializer_list<int> ran_on, const char *text) {
+    if (!graph_recording()) return MMDX_OK;
+    bool recordable = (flags & need) == need;
+    for (int d : ran_on) recordable = recordable && d == device;
+    return recordable ? MMDX_OK : fail(MMDX_ERR_INVALID_ARGUMENT, text);
+}
+
+static const uint32_t kClockAndOut = MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;      // (MMDX_TIMES_ON_DEVICE is the same bit)
+static const char *const kSkeletonRecording = "while a graph is being recorded every operand must be in device memory, the "
+                                              "skeleton must have run on this device before, and physics overrides "
+                                              "(host lists) are not recordable";
+static const char *const kSetRecording = "while a graph is being recorded every operand must be in device memory and the motion set "
+                                         "must have run on this device before";
+static const char *const kSetSkeletonRecording = "while a graph is being recorded every operand must be in device memory and the "
+                                                 "motion set and the skeleton must have run on this device before";
+
+// Append bones / IK (the ordered solver), or a skeleton too large for the LDS pose table of the one-launch kernels: a track + solve
+// call takes two launches -- the track call into a pose scratch of the motion (its `out`) or the set (its `poses`), then the solve.
+static bool two_launches(const SkeletonPlan &pl) { return pl.serial || size_t(pl.nb) * 32 > kMotionFkMaxLds; }
+
+// ... and growing that scratch is an allocation: a recording refuses, anything else moves the tables and sizes it.  (The one call
+// on a single motion, skeleton_solve_motion, spells the same three steps out on m->out; it never asked for the device.)
+static mmdx_status set_pose_scratch(mmdx_motion_set_t set, int device, size_t bytes, float **poses) {
+    if (graph_recording() && (set->poses.bytes < bytes || set->device != device))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "run the call once before recording: it sizes the motion set's pose buffer");
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    HIP_TRY(set->poses.ensure(bytes));
+    *poses = static_cast<float *>(set->poses.ptr);
+    return MMDX_OK;
+}
+
+static size_t pose_bytes(uint32_t ni, uint32_t nb) { return size_t(ni) * nb * MMDX_POSE_FLOATS * sizeof(float); }
+static size_t palette_bytes(uint32_t ni, uint32_t nb) { return size_t(ni) * nb * 16 * sizeof(float); }
+
+// ---- host operands -> device addresses, through handle-owned scratch in stream order --------------------------------------------
+// the instant of every instance -> the kernel parameters: frame numbers (uint32_t) or, with `time`, seconds (double).  Host
+// operands go through the motion's scratch, sized 8 bytes per instance whenever it grows (room for either).
+static mmdx_status motion_clock_in(mmdx_bone_motion_t m, const void *clock, bool time, uint32_t n_instances, uint32_t flags,
+                                   hipStream_t st, BoneTrackParams &p) {
+    const void *dev = clock;
+    if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
+        const size_t bytes = size_t(n_instances) * (time ? 8 : 4);
+        if (m->frames_in.bytes < bytes) HIP_TRY(m->frames_in.ensure(size_t(n_instances) * 8));
+        HIP_TRY(hipMemcpyAsync(m->frames_in.ptr, clock, bytes, hipMemcpyHostToDevice, st));
+        dev = m->frames_in.ptr;
+    }
+    if (time) p.times = static_cast<const double *>(dev);
+    else p.frames = static_cast<const uint32_t *>(dev);
+    return MMDX_OK;
+}
+
+// clip ids and the instant of every instance -> device addresses: the clips, and the clock in `*frames` or, with `time`, `*times`
+// (the two clock fields of a parameter block).  MMDX_FRAMES_ON_DEVICE covers both operands; host operands go through the set's
+// scratch (4 + 8 bytes per instance, room for frames or times).
+static mmdx_status set_operands_in(mmdx_motion_set_t set, const uint32_t *clips, const void *clock, bool time, uint32_t n_instances,
+                                   uint32_t flags, hipStream_t st, const uint32_t **dev_clips, const uint32_t **frames,
+                                   const double **times) {
+    *dev_clips = clips;
+    if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
+        HIP_TRY(set->clips_in.ensure(size_t(n_instances) * 4));
+        HIP_TRY(set->clock_in.ensure(size_t(n_instances) * 8));
+        HIP_TRY(hipMemcpyAsync(set->clips_in.ptr, clips, size_t(n_instances) * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(set->clock_in.ptr, clock, size_t(n_instances) * (time ? 8 : 4), hipMemcpyHostToDevice, st));
+        *dev_clips = static_cast<const uint32_t *>(set->clips_in.ptr);
+        clock = set->clock_in.ptr;
+    }
+    if (time) *times = static_cast<const double *>(clock);
+    else *frames = static_cast<const uint32_t *>(clock);
+    return MMDX_OK;
+}
+
+// the five operand arrays of a blend call that are in device memory already (all a select form takes) ...
+static BlendOperands blend_operands_device(mmdx_motion_set_t set, const mmdx_motion_blend_args *a) {
+    BlendOperands o;
+    o.clips_a = a->clips_a; o.clips_b = a->clips_b;
+    o.times_a = a->times_a; o.times_b = a->times_b;
+    o.weights = a->weights;
+    o.n_clips = set->host.n_clips;
+    return o;
+}
+
+// ... and wherever they are: MMDX_TIMES_ON_DEVICE covers all five; host operands go through the set's scratch (times_a, times_b,
+// clips_a, clips_b, weights laid end to end: 28 bytes per instance).
+static mmdx_status blend_operands_in(mmdx_motion_set_t set, const mmdx_motion_blend_args *a, hipStream_t st, BlendOperands *o) {
+    *o = blend_operands_device(set, a);
+    if (a->flags & MMDX_TIMES_ON_DEVICE) return MMDX_OK;
+    const size_t n = a->n_instances;
+    HIP_TRY(set->blend_in.ensure(n * 28));
+    char *base = static_cast<char *>(set->blend_in.ptr);
+    const struct { const void *src; size_t off, bytes; } parts[5] = {{a->times_a, 0, n * 8},       {a->times_b, n * 8, n * 8},
+                                                                     {a->clips_a, n * 16, n * 4}, {a->clips_b, n * 20, n * 4},
+                                                                     {a->weights, n * 24, n * 4}};
+    for (const auto &p : parts) HIP_TRY(hipMemcpyAsync(base + p.off, p.src, p.bytes, hipMemcpyHostToDevice, st));
+    o->times_a = reinterpret_cast<const double *>(base);
+    o->times_b = reinterpret_cast<const double *>(base + n * 8);
+    o->clips_a = reinterpret_cast<const uint32_t *>(base + n * 16);
+    o->clips_b = reinterpret_cast<const uint32_t *>(base + n * 20);
+    o->weights = reinterpret_cast<const float *>(base + n * 24);
+    return MMDX_OK;
+}
+
+// the list of a select call -> device addresses: a device list as it is; a host list through the handle's scratch (`sel_in`, its
+// source `sel_host` alive until the copy has left it), count word first.  `cells` = list positions the launch is sized from -- state
+// and bone-morph cells are per LIST POSITION --: the capacity of a device list, the ids in use of a host list.
+static mmdx_status list_in(Buf &sel_in, std::vector<uint32_t> &sel_host, const mmdx_instance_select *sel, uint32_t n_instances,
+                           uint32_t live_host, hipStream_t st, InstanceList *list, uint32_t *cells) {
+    *list = InstanceList{sel->ids, sel->count, n_instances};
+    if (sel->flags & MMDX_SELECT_ON_DEVICE) {
+        *cells = sel->n_ids;
+        return MMDX_OK;
+    }
+    *cells = live_host;
+    if (live_host == 0) return MMDX_OK;
+    HIP_TRY(sel_in.ensure((size_t(live_host) + 1) * 4));
+    sel_host.resize(size_t(live_host) + 1);
+    sel_host[0] = live_host;
+    std::copy(sel->ids, sel->ids + live_host, sel_host.begin() + 1);
+    HIP_TRY(hipMemcpyAsync(sel_in.ptr, sel_host.data(), sel_host.size() * 4, hipMemcpyHostToDevice, st));
+    list->count = static_cast<const uint32_t *>(sel_in.ptr);
+    list->ids = list->count + 1;
+    return MMDX_OK;
+}
+
+// ---- parameter blocks from a handle ----------------------------------------------------------------------------------------------
+static SkeletonParams fk_params(mmdx_skeleton_t s, uint32_t ni, const float *poses, const float *morph, float *out) {
+    SkeletonParams fp;
+    fp.morph = morph;
+    fp.poses = poses; fp.out = out;
+    fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
+    fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
+    fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
+    fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
+    fp.nb = s->plan.nb; fp.ni = ni;
+    return fp;
+}
+
+static MorphTrackParams set_morph_params(mmdx_motion_set_t set, uint32_t ni) {
+    MorphTrackParams t;
+    t.key_off = static_cast<const uint32_t *>(set->m_key_off.ptr);
+    t.key_frames = static_cast<const uint32_t *>(set->m_frames.ptr);
+    t.key_weights = static_cast<const float *>(set->m_weights.ptr);
+    t.nm = set->host.nm; t.ni = ni;
+    t.frames = nullptr; t.times = nullptr; t.out = nullptr;
+    return t;
+}
+
+static void note_fk_solve(mmdx_skeleton_t s) {
+    s->last_solve = SolveShape{};
+    s->last_solve.solver = 2;
+}
+
+// ---- where the results go, and the end of a call ---------------------------------------------------------------------------------
+struct OutRoute {
+    float *dev = nullptr;        // what the kernel writes: the caller's array (MMDX_OUT_ON_DEVICE) or a handle's scratch
+    float *host = nullptr;       // the caller's host array `finish` copies the scratch to
+    size_t bytes = 0;
+};
+
+static mmdx_status route_out(uint32_t flags, float *caller_out, size_t bytes, Buf &scratch, OutRoute *o) {
+    *o = OutRoute{caller_out, nullptr, bytes};
+    if (flags & MMDX_OUT_ON_DEVICE) return MMDX_OK;
+    HIP_TRY(scratch.ensure(bytes));
+    *o = OutRoute{static_cast<float *>(scratch.ptr), caller_out, bytes};
+    return MMDX_OK;
+}
+
+// results bound for the host are copied out and waited for; results that stay on the device are waited for only when the call
+// `borrowed` a host operand or a host list, which must be consumed before returning
+static mmdx_status finish(uint32_t flags, bool borrowed, hipStream_t st, const OutRoute &o) {
+    if (!(flags & MMDX_OUT_ON_DEVICE)) {
+        if (o.bytes) HIP_TRY(hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(wait_stream(st));
+    } else if (borrowed) {
+        HIP_TRY(wait_stream(st));
+    }
+    return MMDX_OK;
+}
+
+// ---- the solve -------------------------------------------------------------------------------------------------------------------
+// From "the poses are at a device address" on: the bone-morph pass (`rates`: device rates, or null for none), then the ordered solver
+// or parallel FK, for all `cells` instances (`list` null) or for the `cells` positions of `list`.
+// passes: bit 0 = reset + bone morphs + pre-physics list, bit 1 = (physics overrides +) post-physics list
+static mmdx_status solve_on_device(mmdx_skeleton_t s, uint32_t cells, const InstanceList *list, const float *poses, const float *rates,
+                                   bool shared_rates, float *out, uint32_t passes, hipStream_t st) {
+    const SkeletonPlan &pl = s->plan;
+    // bone morphs first: per-bone morph_translation_ / morph_rotation_ of every instance
+    const float *morph_state = (passes & 1u) ? nullptr : s->pre_morph;
+    if (rates) {
+        HIP_TRY(s->morph_state.ensure(size_t(cells) * pl.nb * kMorphStateFloats * sizeof(float)));
+        BoneMorphParams mp;
+        mp.rates = rates;
+        mp.apps = static_cast<const BoneMorphApp *>(s->apps.ptr);
+        mp.chain = static_cast<const float *>(s->app_chain.ptr);
+        mp.out = static_cast<float *>(s->morph_state.ptr);
+        mp.napps = uint32_t(pl.apps.size()); mp.nb = pl.nb; mp.ni = cells; mp.nm = pl.nm; mp.shared = shared_rates ? 1u : 0u;
+        HIP_TRY(list ? launch_bone_morph_select(mp, *list, st) : launch_bone_morph(mp, st));
+        morph_state = mp.out;
+    }
+    if (!pl.serial) {
+        const SkeletonParams fp = fk_params(s, cells, poses, morph_state, out);
+        HIP_TRY(list ? launch_skeleton_fk_select(fp, *list, st) : launch_skeleton_fk(fp, st));
+        note_fk_solve(s);
+        return MMDX_OK;
+    }
+    HIP_TRY(s->state.ensure(size_t(cells) * pl.nb * kSerialStateFloats * sizeof(float)));
+    SerialParams sp;
+    sp.morph = morph_state;
+    sp.poses = poses; sp.out = out;
+    sp.state = static_cast<float *>(s->state.ptr);
+    sp.order = static_cast<const uint32_t *>(s->order.ptr);
+    sp.bones = static_cast<const BoneRec *>(s->bones.ptr);
+    sp.iks = static_cast<const IkRec *>(s->iks.ptr);
+    sp.links = static_cast<const LinkRec *>(s->links.ptr);
+    sp.events = static_cast<const uint32_t *>(s->events.ptr);
+    sp.rounds = static_cast<const RoundRec *>(s->rounds.ptr);
+    sp.nb = pl.nb; sp.ni = cells; sp.n_pre = pl.n_pre;
+    sp.n_rounds_pre = pl.n_rounds_pre; sp.n_rounds = uint32_t(pl.rounds.size());
+    sp.fast_slots = pl.fast_slots;
+    sp.windows = pl.windows;
+    sp.passes = passes;
+    sp.nested = pl.nested_ik ? 1u : 0u;
+    const uint8_t *coop = pl.round_coop.empty() ? nullptr : pl.round_coop.data();
+    HIP_TRY(list ? launch_skeleton_ordered_select(sp, coop, *list, st, &s->last_solve) : launch_skeleton_ordered(sp, coop, st, &s->last_solve));
+    // a pre step leaves what its post step re-reads; after any other solve the scratch a pending pre step left is gone
+    if (passes == 1u) { s->pre_instances = cells; s->pre_poses = poses; s->pre_morph = morph_state; }
+    else s->pre_instances = 0;
+    return MMDX_OK;
+}
+
+// mmdx_skeleton_solve / _morphed / _pre / _post (passes: as above)
 static mmdx_status skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
                                   const float *morph_weights, uint32_t flags, float *out_palettes, uint32_t passes,
-                                  const mmdx_physics_overrides *ov);
-static mmdx_status skeleton_solve_select(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
-                                         const float *morph_weights, uint32_t flags, const mmdx_instance_select *sel,
-                                         float *out_palettes);
+                                  const mmdx_physics_overrides *ov) {
+    if (!s || (!poses && (passes & 1u)) || !out_palettes || !n_instances)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const SkeletonPlan &pl = s->plan;
+    const bool morphs = (passes & 1u) && morph_weights && !pl.apps.empty();
+    const bool overrides = (passes & 2u) && ov && ov->n_bones;
+    const uint32_t need = MMDX_OUT_ON_DEVICE | ((passes & 1u) ? uint32_t(MMDX_POSES_ON_DEVICE) : 0u) |
+                          (morphs ? uint32_t(MMDX_WEIGHTS_ON_DEVICE) : 0u);
+    if (graph_recording() && ov && ov->n_bones) return fail(MMDX_ERR_INVALID_ARGUMENT, kSkeletonRecording);
+    if (mmdx_status r = refuse_recording(flags, need, device, {s->device}, kSkeletonRecording)) return r;
+    if (mmdx_status r = skeleton_to_device(s, device)) return r;
+    graph_note_handle(model, &s->pin);
+    const float *dev_poses = poses;
+    if (!(passes & 1u)) {
+        dev_poses = s->pre_poses;                    // the post-physics list re-reads the poses the pre step solved:
+                                                     // they must still be there (device poses are the caller's to keep)
+    } else if (!(flags & MMDX_POSES_ON_DEVICE)) {
+        const size_t in_bytes = pose_bytes(n_instances, pl.nb);
+        HIP_TRY(s->poses_in.ensure(in_bytes));
+        if (in_bytes) HIP_TRY(hipMemcpyAsync(s->poses_in.ptr, poses, in_bytes, hipMemcpyHostToDevice, st));
+        dev_poses = static_cast<const float *>(s->poses_in.ptr);
+    }
+    OutRoute o;
+    if (mmdx_status r = route_out(flags, out_palettes, palette_bytes(n_instances, pl.nb), s->out, &o)) return r;
+    const bool shared = (flags & MMDX_WEIGHTS_SHARED) != 0;
+    const float *rates = morphs ? morph_weights : nullptr;
+    const bool borrowed_rates = morphs && !(flags & MMDX_WEIGHTS_ON_DEVICE);
+    if (borrowed_rates) {
+        const size_t rate_bytes = size_t(shared ? 1 : n_instances) * pl.nm * sizeof(float);
+        HIP_TRY(s->rates_in.ensure(rate_bytes));
+        HIP_TRY(hipMemcpyAsync(s->rates_in.ptr, morph_weights, rate_bytes, hipMemcpyHostToDevice, st));
+        rates = static_cast<const float *>(s->rates_in.ptr);
+    }
+    if (overrides) {                                  // the reactor's writes, between the two lists
+        HIP_TRY(s->state.ensure(size_t(n_instances) * pl.nb * kSerialStateFloats * sizeof(float)));
+        PhysicsParams pp;
+        std::vector<uint32_t> ob(ov->bone, ov->bone + ov->n_bones);
+        std::vector<uint8_t> os(ov->n_bones, 0);
+        for (uint32_t k = 0; ov->strict && k < ov->n_bones; ++k) os[k] = ov->strict[k] ? 1 : 0;
+        HIP_TRY(s->over_bone.ensure(ob.size() * 4));
+        HIP_TRY(s->over_strict.ensure(os.size()));
+        HIP_TRY(hipMemcpyAsync(s->over_bone.ptr, ob.data(), ob.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s->over_strict.ptr, os.data(), os.size(), hipMemcpyHostToDevice, st));
+        const size_t xf_bytes = size_t(n_instances) * ov->n_bones * 64;
+        if (flags & MMDX_OVERRIDES_ON_DEVICE) {
+            pp.skinning = ov->skinning;
+        } else {
+            HIP_TRY(s->over_skin.ensure(xf_bytes));
+            HIP_TRY(hipMemcpyAsync(s->over_skin.ptr, ov->skinning, xf_bytes, hipMemcpyHostToDevice, st));
+            pp.skinning = static_cast<const float *>(s->over_skin.ptr);
+        }
+        HIP_TRY(hipStreamSynchronize(st));        // ob / os are locals: the copies above must have read them
+        pp.bone = static_cast<const uint32_t *>(s->over_bone.ptr);
+        pp.strict = static_cast<const uint8_t *>(s->over_strict.ptr);
+        pp.out = o.dev;
+        pp.state = static_cast<float *>(s->state.ptr);
+        pp.bones = static_cast<const BoneRec *>(s->bones.ptr);
+        pp.k = ov->n_bones; pp.nb = pl.nb; pp.ni = n_instances;
+        HIP_TRY(launch_physics_override(pp, st));
+    }
+    if (mmdx_status r = solve_on_device(s, n_instances, nullptr, dev_poses, rates, shared, o.dev, passes, st)) return r;
+    return finish(flags, !(flags & MMDX_POSES_ON_DEVICE) || borrowed_rates, st, o);
+}
+
+// The list of a select call (mmdx_skeleton_solve_select, the *_blend_*_time_select calls), decided without the device: `plain` names
+// the calls that take every instance; `live_host` = the ids of a host list that are in use.
+static mmdx_status check_instance_list(const mmdx_instance_select *sel, uint32_t n_instances, const char *plain, uint32_t &live_host) {
+    if (!sel) return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("select is NULL (") + plain + ")");
+    if (sel->struct_size != sizeof(mmdx_instance_select))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.struct_size mismatch");
+    if (sel->flags & ~uint32_t(MMDX_SELECT_ON_DEVICE))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown bits in mmdx_instance_select.flags");
+    if (sel->reserved0 != 0) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.reserved0 must be 0");
+    if (sel->n_ids && !sel->ids) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids is NULL");
+    if (sel->flags & MMDX_SELECT_ON_DEVICE) {
+        if ((reinterpret_cast<uintptr_t>(sel->ids) | reinterpret_cast<uintptr_t>(sel->count)) & 3)
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "device ids / count of mmdx_instance_select must be 4-byte aligned");
+        return MMDX_OK;
+    }
+    if (graph_recording())
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded the instance list must be in device memory "
+                                               "(MMDX_SELECT_ON_DEVICE)");
+    live_host = sel->count ? std::min(*sel->count, sel->n_ids) : sel->n_ids;
+    for (uint32_t j = 0; j < live_host; ++j)
+        if (sel->ids[j] >= n_instances)
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids[" + std::to_string(j) + "] = " +
+                                                   std::to_string(sel->ids[j]) + " is not below n_instances");
+    return MMDX_OK;
+}
+
+// mmdx_skeleton_solve_select: mmdx_skeleton_solve_morphed for the listed instances (include/mmdx.h, rules 1-10).  Everything that can
+// be decided without the device comes first, in the header's order.
+static mmdx_status check_select_args(mmdx_skeleton_t s, uint32_t n_instances, const float *poses, const float *morph_weights,
+                                     uint32_t flags, const mmdx_instance_select *sel, const float *out_palettes, uint32_t &live_host) {
+    if (!s || !poses || !out_palettes || !n_instances) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    const uint32_t need = MMDX_POSES_ON_DEVICE | MMDX_OUT_ON_DEVICE | (morph_weights ? uint32_t(MMDX_WEIGHTS_ON_DEVICE) : 0u);
+    if ((flags & need) != need)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_skeleton_solve_select takes device operands only: pass MMDX_POSES_ON_DEVICE | "
+                                               "MMDX_OUT_ON_DEVICE, and MMDX_WEIGHTS_ON_DEVICE with morph_weights");
+    if (flags & ~uint32_t(MMDX_POSES_ON_DEVICE | MMDX_OUT_ON_DEVICE | MMDX_WEIGHTS_ON_DEVICE | MMDX_WEIGHTS_SHARED))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    return check_instance_list(sel, n_instances, "mmdx_skeleton_solve / _morphed solve every instance", live_host);
+}
+
+// ---- one motion ------------------------------------------------------------------------------------------------------------------
+// mmdx_bone_motion_eval / _eval_time: frames (uint32_t) or, with `time`, seconds (double)
 static mmdx_status bone_motion_eval(mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances, const void *clock, bool time,
-                                    uint32_t flags, float *out_poses);
+                                    uint32_t flags, float *out_poses) {
+    if (!m || !clock || !out_poses || !n_instances)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    if (mmdx_status r = refuse_recording(flags, kClockAndOut, device, {m->device},
+                                         "while a graph is being recorded every operand must be in device memory and the "
+                                         "motion must have run on this device before"))
+        return r;
+    if (mmdx_status r = motion_to_device(m, device)) return r;
+    graph_note_handle(model, &m->pin);
+    BoneTrackParams p = m->t.params(m->host.nb, n_instances);
+    if (mmdx_status r = motion_clock_in(m, clock, time, n_instances, flags, st, p)) return r;
+    OutRoute o;
+    if (mmdx_status r = route_out(flags, out_poses, pose_bytes(n_instances, p.nb), m->out, &o)) return r;
+    p.out = o.dev;
+    HIP_TRY(launch_bone_track_eval(p, st));
+    return finish(flags, !(flags & MMDX_FRAMES_ON_DEVICE), st, o);
+}
+
+// mmdx_skeleton_solve_motion / _time: frames (uint32_t) or, with `time`, seconds (double)
 static mmdx_status skeleton_solve_motion(mmdx_skeleton_t s, mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
-                                         const void *clock, bool time, uint32_t flags, float *out_palettes);
+                                         const void *clock, bool time, uint32_t flags, float *out_palettes) {
+    if (!s || !m || !clock || !out_palettes || !n_instances)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    if (m->host.nb != s->plan.nb)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "the motion was bound to " + std::to_string(m->host.nb) + " bones, the skeleton has " +
+                                               std::to_string(s->plan.nb));
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const SkeletonPlan &pl = s->plan;
+    if (two_launches(pl)) {
+        const size_t bytes = pose_bytes(n_instances, pl.nb);
+        if (graph_recording() && m->out.bytes < bytes)
+            return fail(MMDX_ERR_INVALID_ARGUMENT, "run the call once before recording: it sizes the motion's pose buffer");
+        if (mmdx_status r = motion_to_device(m, device)) return r;
+        HIP_TRY(m->out.ensure(bytes));
+        float *poses = static_cast<float *>(m->out.ptr);
+        if (mmdx_status r = bone_motion_eval(m, model, n_instances, clock, time, (flags & MMDX_FRAMES_ON_DEVICE) | MMDX_OUT_ON_DEVICE, poses))
+            return r;
+        return mmdx_skeleton_solve(s, model, n_instances, poses, MMDX_POSES_ON_DEVICE | (flags & MMDX_OUT_ON_DEVICE), out_palettes);
+    }
+    if (mmdx_status r = refuse_recording(flags, kClockAndOut, device, {m->device, s->device},
+                                         "while a graph is being recorded every operand must be in device memory and the motion "
+                                         "and the skeleton must have run on this device before"))
+        return r;
+    if (mmdx_status r = motion_to_device(m, device)) return r;
+    if (mmdx_status r = skeleton_to_device(s, device)) return r;
+    graph_note_handle(model, &m->pin);
+    graph_note_handle(model, &s->pin);
+    BoneTrackParams tp = m->t.params(pl.nb, n_instances);
+    if (mmdx_status r = motion_clock_in(m, clock, time, n_instances, flags, st, tp)) return r;
+    OutRoute o;
+    if (mmdx_status r = route_out(flags, out_palettes, palette_bytes(n_instances, pl.nb), s->out, &o)) return r;
+    HIP_TRY(launch_motion_fk(tp, fk_params(s, n_instances, nullptr, nullptr, o.dev), st));
+    note_fk_solve(s);
+    return finish(flags, !(flags & MMDX_FRAMES_ON_DEVICE), st, o);
+}
 
+// ---- motion sets -----------------------------------------------------------------------------------------------------------------
+// Everything about a set call that can be decided without the device, in one place and before the first HIP call: NULLs, the
+// instance count, flag bits, NaN in host times (check_time_args), the side the set was created without, host clip ids.
+static mmdx_status set_check_args(mmdx_motion_set_t set, bool bone_side, uint32_t n_instances, const uint32_t *clips, const void *clock,
+                                  bool time, uint32_t flags, const float *out) {
+    if (!set || !clips || !clock || !out || !n_instances) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    const uint32_t allowed = MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
+    if (time) {
+        if (mmdx_status r = check_time_args(static_cast<const double *>(clock), n_instances, flags, allowed)) return r;
+    } else if (flags & ~allowed) {
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    }
+    if (bone_side ? !set->host.has_bones : !set->host.has_morphs)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("this motion set was created without ") + (bone_side ? "bone" : "morph") + " motions");
+    if (!(flags & MMDX_FRAMES_ON_DEVICE))
+        for (uint32_t i = 0; i < n_instances; ++i)
+            if (clips[i] >= set->host.n_clips && clips[i] != MMDX_CLIP_NONE)
+                return fail(MMDX_ERR_BAD_INDEX, "clips[" + std::to_string(i) + "] = " + std::to_string(clips[i]) + ": the set has " +
+                                                std::to_string(set->host.n_clips) + " clips");
+    return MMDX_OK;
+}
+
+static mmdx_status skeleton_matches_set(mmdx_skeleton_t s, mmdx_motion_set_t set) {
+    if (set->host.bones.nb != s->plan.nb)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "the motion set was bound to " + std::to_string(set->host.bones.nb) +
+                                               " bones, the skeleton has " + std::to_string(s->plan.nb));
+    return MMDX_OK;
+}
+
+// mmdx_motion_set_eval_bones / _time: frames (uint32_t) or, with `time`, seconds (double)
 static mmdx_status set_eval_bones(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
-                                  const void *clock, bool time, uint32_t flags, float *out_poses);
-static mmdx_status set_eval_morphs(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
-                                   const void *clock, bool time, uint32_t flags, float *out_weights);
-static mmdx_status skeleton_solve_motion_set(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
-                                             const uint32_t *clips, const void *clock, bool time, uint32_t flags, float *out_palettes);
+                                  const void *clock, bool time, uint32_t flags, float *out_poses) {
+    if (mmdx_status r = set_check_args(set, true, n_instances, clips, clock, time, flags, out_poses)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    if (mmdx_status r = refuse_recording(flags, kClockAndOut, device, {set->device}, kSetRecording)) return r;
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    BoneTrackParams p = set->t.params(set->host.bones.nb, n_instances);
+    const uint32_t *dev_clips;
+    if (mmdx_status r = set_operands_in(set, clips, clock, time, n_instances, flags, st, &dev_clips, &p.frames, &p.times)) return r;
+    OutRoute o;
+    if (mmdx_status r = route_out(flags, out_poses, pose_bytes(n_instances, p.nb), set->out, &o)) return r;
+    p.out = o.dev;
+    HIP_TRY(launch_bone_track_eval_set(p, dev_clips, set->host.n_clips, st));
+    return finish(flags, !(flags & MMDX_FRAMES_ON_DEVICE), st, o);
+}
 
-static mmdx_status set_blend_bones(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args, float *out_poses);
-static mmdx_status set_blend_morphs(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args, float *out_weights);
-static mmdx_status skeleton_solve_motion_set_blend(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model,
-                                                   const mmdx_motion_blend_args *args, float *out_palettes);
+// mmdx_motion_set_eval_morphs / _time
+static mmdx_status set_eval_morphs(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
+                                   const void *clock, bool time, uint32_t flags, float *out_weights) {
+    if (mmdx_status r = set_check_args(set, false, n_instances, clips, clock, time, flags, out_weights)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    if (mmdx_status r = refuse_recording(flags, kClockAndOut, device, {set->device}, kSetRecording)) return r;
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    MorphTrackParams t = set_morph_params(set, n_instances);
+    const uint32_t *dev_clips;
+    if (mmdx_status r = set_operands_in(set, clips, clock, time, n_instances, flags, st, &dev_clips, &t.frames, &t.times)) return r;
+    OutRoute o;
+    if (mmdx_status r = route_out(flags, out_weights, size_t(n_instances) * t.nm * sizeof(float), set->out, &o)) return r;
+    t.out = o.dev;
+    HIP_TRY(launch_morph_track_eval_set(t, dev_clips, set->host.n_clips, st));
+    return finish(flags, !(flags & MMDX_FRAMES_ON_DEVICE), st, o);
+}
+
+// mmdx_skeleton_solve_motion_set / _time
+static mmdx_status skeleton_solve_motion_set(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
+                                             const uint32_t *clips, const void *clock, bool time, uint32_t flags, float *out_palettes) {
+    if (!s) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    if (mmdx_status r = set_check_args(set, true, n_instances, clips, clock, time, flags, out_palettes)) return r;
+    if (mmdx_status r = skeleton_matches_set(s, set)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const SkeletonPlan &pl = s->plan;
+    if (two_launches(pl)) {
+        float *poses;
+        if (mmdx_status r = set_pose_scratch(set, device, pose_bytes(n_instances, pl.nb), &poses)) return r;
+        if (mmdx_status r = set_eval_bones(set, model, n_instances, clips, clock, time, (flags & MMDX_FRAMES_ON_DEVICE) | MMDX_OUT_ON_DEVICE,
+                                           poses))
+            return r;
+        return mmdx_skeleton_solve(s, model, n_instances, poses, MMDX_POSES_ON_DEVICE | (flags & MMDX_OUT_ON_DEVICE), out_palettes);
+    }
+    if (mmdx_status r = refuse_recording(flags, kClockAndOut, device, {set->device, s->device}, kSetSkeletonRecording)) return r;
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    if (mmdx_status r = skeleton_to_device(s, device)) return r;
+    graph_note_handle(model, &set->pin);
+    graph_note_handle(model, &s->pin);
+    BoneTrackParams tp = set->t.params(pl.nb, n_instances);
+    const uint32_t *dev_clips;
+    if (mmdx_status r = set_operands_in(set, clips, clock, time, n_instances, flags, st, &dev_clips, &tp.frames, &tp.times)) return r;
+    OutRoute o;
+    if (mmdx_status r = route_out(flags, out_palettes, palette_bytes(n_instances, pl.nb), s->out, &o)) return r;
+    HIP_TRY(launch_motion_fk_set(tp, fk_params(s, n_instances, nullptr, nullptr, o.dev), dev_clips, set->host.n_clips, st));
+    note_fk_solve(s);
+    return finish(flags, !(flags & MMDX_FRAMES_ON_DEVICE), st, o);
+}
+
+// ---- cross-fade between two clips of a set (mmdx_motion_set_blend_*_time, mmdx_skeleton_solve_motion_set_blend_time) ---------------
+// Everything about a blend call that can be decided without the device, before the first HIP call, in two parts: the header (NULLs,
+// struct_size) ...
+static mmdx_status blend_check_header(mmdx_motion_set_t set, const mmdx_motion_blend_args *a, const float *out) {
+    if (!set || !a || !out) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (a->struct_size != sizeof(mmdx_motion_blend_args)) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_motion_blend_args.struct_size mismatch");
+    return MMDX_OK;
+}
+
+// ... and the operands: their NULLs, the instance count, flag bits, the side the set was created without, and -- for host operands --
+// clip ids of both arrays, NaN times and NaN weights.
+static mmdx_status blend_check_operands(mmdx_motion_set_t set, bool bone_side, const mmdx_motion_blend_args *a) {
+    if (!a->clips_a || !a->clips_b || !a->times_a || !a->times_b || !a->weights || !a->n_instances)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
+    if (a->flags & ~uint32_t(MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    if (bone_side ? !set->host.has_bones : !set->host.has_morphs)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("this motion set was created without ") + (bone_side ? "bone" : "morph") + " motions");
+    if (a->flags & MMDX_TIMES_ON_DEVICE) return MMDX_OK;
+    const struct { const char *name; const uint32_t *clips; const double *times; } sides[2] = {{"a", a->clips_a, a->times_a},
+                                                                                                 {"b", a->clips_b, a->times_b}};
+    for (const auto &s : sides)
+        for (uint32_t i = 0; i < a->n_instances; ++i)
+            if (s.clips[i] >= set->host.n_clips && s.clips[i] != MMDX_CLIP_NONE)
+                return fail(MMDX_ERR_BAD_INDEX, std::string("clips_") + s.name + "[" + std::to_string(i) + "] = " + std::to_string(s.clips[i]) +
+                                                ": the set has " + std::to_string(set->host.n_clips) + " clips");
+    for (const auto &s : sides)
+        for (uint32_t i = 0; i < a->n_instances; ++i)
+            if (s.times[i] != s.times[i])
+                return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("times_") + s.name + "[" + std::to_string(i) + "] is NaN");
+    for (uint32_t i = 0; i < a->n_instances; ++i)
+        if (a->weights[i] != a->weights[i]) return fail(MMDX_ERR_INVALID_ARGUMENT, "weights[" + std::to_string(i) + "] is NaN");
+    return MMDX_OK;
+}
+
+static mmdx_status blend_check_args(mmdx_motion_set_t set, bool bone_side, const mmdx_motion_blend_args *a, const float *out) {
+    if (mmdx_status r = blend_check_header(set, a, out)) return r;
+    return blend_check_operands(set, bone_side, a);
+}
+
+// The select forms (mmdx_motion_set_blend_*_time_select, mmdx_skeleton_solve_motion_set_blend_time_select; include/mmdx.h, rules
+// 1-10) take device operands only, and say so ahead of the operand part, which reads host operands when MMDX_TIMES_ON_DEVICE is
+// absent; unknown flag bits are reported ahead of that.
+static mmdx_status blend_select_check(mmdx_motion_set_t set, bool bone_side, const mmdx_motion_blend_args *a,
+                                      const mmdx_instance_select *sel, const float *out, uint32_t &live_host) {
+    if (mmdx_status r = blend_check_header(set, a, out)) return r;
+    if (a->flags & ~uint32_t(MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    const uint32_t need = MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
+    if ((a->flags & need) != need)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "the select form of a blend call takes device operands only: pass MMDX_TIMES_ON_DEVICE | "
+                                               "MMDX_OUT_ON_DEVICE");
+    if (mmdx_status r = blend_check_operands(set, bone_side, a)) return r;
+    return check_instance_list(sel, a->n_instances, "the calls without _select evaluate every instance", live_host);
+}
 
 extern "C" {
 
@@ -244,20 +801,17 @@ mmdx_status mmdx_bone_motion_eval(mmdx_bone_motion_t m, mmdx_model_t model, uint
 
 mmdx_status mmdx_bone_motion_eval_time(mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
                                        const double *times, uint32_t flags, float *out_poses) {
-    if (!m || !times || !out_poses || !n_instances)
+    if (!m || !times || !out_poses || !n_instances)              // ahead of check_time_args, which reads `times`
         return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
     if (mmdx_status r = check_time_args(times, n_instances, flags, MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) return r;
     return bone_motion_eval(m, model, n_instances, times, true, flags, out_poses);
 }
 
-
 void mmdx_bone_motion_destroy(mmdx_bone_motion_t m) {
     if (!m) return;
     graph_drop_handle(&m->pin);
     if (m->device >= 0) (void)hipSetDevice(m->device);
-    for (Buf *b : {&m->key_off, &m->key_frame, &m->key_tr, &m->key_rot, &m->key_curve, &m->lut, &m->frames_in,
-                   &m->out})
-        b->release();
+    release(m->all());
     delete m;
 }
 
@@ -306,6 +860,14 @@ mmdx_status mmdx_debug_last_solve_shape(mmdx_skeleton_t s, mmdx_debug_solve_shap
     return MMDX_OK;
 }
 
+void mmdx_skeleton_destroy(mmdx_skeleton_t s) {
+    if (!s) return;
+    graph_drop_handle(&s->pin);
+    if (s->device >= 0) (void)hipSetDevice(s->device);
+    release(s->all());
+    delete s;
+}
+
 mmdx_status mmdx_skeleton_solve_motion(mmdx_skeleton_t s, mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
                                        const uint32_t *frames, uint32_t flags, float *out_palettes) {
     return skeleton_solve_motion(s, m, model, n_instances, frames, false, flags, out_palettes);
@@ -313,7 +875,7 @@ mmdx_status mmdx_skeleton_solve_motion(mmdx_skeleton_t s, mmdx_bone_motion_t m, 
 
 mmdx_status mmdx_skeleton_solve_motion_time(mmdx_skeleton_t s, mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
                                             const double *times, uint32_t flags, float *out_palettes) {
-    if (!s || !m || !times || !out_palettes || !n_instances)
+    if (!s || !m || !times || !out_palettes || !n_instances)     // ahead of check_time_args, which reads `times`
         return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
     if (mmdx_status r = check_time_args(times, n_instances, flags, MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) return r;
     return skeleton_solve_motion(s, m, model, n_instances, times, true, flags, out_palettes);
@@ -333,7 +895,24 @@ mmdx_status mmdx_skeleton_solve_morphed(mmdx_skeleton_t s, mmdx_model_t model, u
 mmdx_status mmdx_skeleton_solve_select(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
                                        const float *morph_weights, uint32_t flags, const mmdx_instance_select *select,
                                        float *out_palettes) {
-    return skeleton_solve_select(s, model, n_instances, poses, morph_weights, flags, select, out_palettes);
+    uint32_t live_host = 0;
+    if (mmdx_status r = check_select_args(s, n_instances, poses, morph_weights, flags, select, out_palettes, live_host)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    if (mmdx_status r = refuse_recording(0, 0, device, {s->device},
+                                         "while a graph is being recorded the skeleton must have run on this device before"))
+        return r;
+    if (mmdx_status r = skeleton_to_device(s, device)) return r;
+    graph_note_handle(model, &s->pin);
+    InstanceList list;
+    uint32_t cells;
+    if (mmdx_status r = list_in(s->sel_in, s->sel_host, select, n_instances, live_host, st, &list, &cells)) return r;
+    if (cells == 0) return MMDX_OK;                                 // an empty list writes nothing
+    const float *rates = s->plan.apps.empty() ? nullptr : morph_weights;
+    if (mmdx_status r = solve_on_device(s, cells, &list, poses, rates, (flags & MMDX_WEIGHTS_SHARED) != 0, out_palettes, 3u, st)) return r;
+    // results on the device: waits when the list was borrowed -- it is consumed then, and the results are there
+    return finish(flags, !(select->flags & MMDX_SELECT_ON_DEVICE), st, OutRoute{});
 }
 
 mmdx_status mmdx_skeleton_solve_pre(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
@@ -408,7 +987,7 @@ void mmdx_motion_set_destroy(mmdx_motion_set_t set) {
     if (!set) return;
     graph_drop_handle(&set->pin);
     if (set->device >= 0) (void)hipSetDevice(set->device);
-    for (Buf *b : set->all()) b->release();
+    release(set->all());
     delete set;
 }
 
@@ -444,929 +1023,148 @@ mmdx_status mmdx_skeleton_solve_motion_set_time(mmdx_skeleton_t s, mmdx_motion_s
 
 mmdx_status mmdx_motion_set_blend_bones_time(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args,
                                              float *out_poses) {
-    return set_blend_bones(set, model, args, out_poses);
+    if (mmdx_status r = blend_check_args(set, true, args, out_poses)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    if (mmdx_status r = refuse_recording(args->flags, kClockAndOut, device, {set->device}, kSetRecording)) return r;
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    BoneTrackParams p = set->t.params(set->host.bones.nb, args->n_instances);
+    BlendOperands ops;
+    if (mmdx_status r = blend_operands_in(set, args, st, &ops)) return r;
+    OutRoute o;
+    if (mmdx_status r = route_out(args->flags, out_poses, pose_bytes(args->n_instances, p.nb), set->out, &o)) return r;
+    p.out = o.dev;
+    HIP_TRY(launch_bone_track_blend_set(p, ops, st));
+    return finish(args->flags, !(args->flags & MMDX_TIMES_ON_DEVICE), st, o);
 }
 
 mmdx_status mmdx_motion_set_blend_morphs_time(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args,
                                               float *out_weights) {
-    return set_blend_morphs(set, model, args, out_weights);
+    if (mmdx_status r = blend_check_args(set, false, args, out_weights)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    if (mmdx_status r = refuse_recording(args->flags, kClockAndOut, device, {set->device}, kSetRecording)) return r;
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    MorphTrackParams t = set_morph_params(set, args->n_instances);
+    BlendOperands ops;
+    if (mmdx_status r = blend_operands_in(set, args, st, &ops)) return r;
+    OutRoute o;
+    if (mmdx_status r = route_out(args->flags, out_weights, size_t(args->n_instances) * t.nm * sizeof(float), set->out, &o)) return r;
+    t.out = o.dev;
+    HIP_TRY(launch_morph_track_blend_set(t, ops, st));
+    return finish(args->flags, !(args->flags & MMDX_TIMES_ON_DEVICE), st, o);
 }
 
 mmdx_status mmdx_skeleton_solve_motion_set_blend_time(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model,
                                                       const mmdx_motion_blend_args *args, float *out_palettes) {
-    return skeleton_solve_motion_set_blend(s, set, model, args, out_palettes);
-}
-
-}  // extern "C"
-
-// passes: bit 0 = reset + bone morphs + pre-physics list, bit 1 = (physics overrides +) post-physics list
-static mmdx_status skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
-                                  const float *morph_weights, uint32_t flags, float *out_palettes, uint32_t passes,
-                                  const mmdx_physics_overrides *ov) {
-    if (!s || (!poses && (passes & 1u)) || !out_palettes || !n_instances)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
-    int device;
-    hipStream_t st;
-    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
-    const SkeletonPlan &pl = s->plan;
-    if (graph_recording()) {
-        const uint32_t need = MMDX_OUT_ON_DEVICE | ((passes & 1u) ? uint32_t(MMDX_POSES_ON_DEVICE) : 0u) |
-                              ((passes & 1u) && morph_weights && !pl.apps.empty() ? uint32_t(MMDX_WEIGHTS_ON_DEVICE) : 0u);
-        if ((flags & need) != need || s->device != device || (ov && ov->n_bones))
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory, the "
-                                                   "skeleton must have run on this device before, and physics overrides "
-                                                   "(host lists) are not recordable");
-    }
-    if (mmdx_status r = skeleton_to_device(s, device)) return r;
-    graph_note_handle(model, &s->pin);
-    struct { const float *poses; float *out; } p;
-    const size_t in_bytes = size_t(n_instances) * pl.nb * MMDX_POSE_FLOATS * sizeof(float);
-    const size_t out_bytes = size_t(n_instances) * pl.nb * 16 * sizeof(float);
-    if (!(passes & 1u)) {
-        p.poses = s->pre_poses;                      // the post-physics list re-reads the poses the pre step solved:
-                                                     // they must still be there (device poses are the caller's to keep)
-    } else if (flags & MMDX_POSES_ON_DEVICE) {
-        p.poses = poses;
-    } else {
-        HIP_TRY(s->poses_in.ensure(in_bytes));
-        if (in_bytes) HIP_TRY(hipMemcpyAsync(s->poses_in.ptr, poses, in_bytes, hipMemcpyHostToDevice, st));
-        p.poses = static_cast<const float *>(s->poses_in.ptr);
-    }
-    if (flags & MMDX_OUT_ON_DEVICE) {
-        p.out = out_palettes;
-    } else {
-        HIP_TRY(s->out.ensure(out_bytes));
-        p.out = static_cast<float *>(s->out.ptr);
-    }
-    // bone morphs first: per-bone morph_translation_ / morph_rotation_ of every instance
-    const float *morph_state = (passes & 1u) ? nullptr : s->pre_morph;
-    bool borrowed_rates = false;
-    if ((passes & 1u) && morph_weights && !pl.apps.empty()) {
-        const bool shared = (flags & MMDX_WEIGHTS_SHARED) != 0;
-        const size_t rate_bytes = size_t(shared ? 1 : n_instances) * pl.nm * sizeof(float);
-        BoneMorphParams mp;
-        if (flags & MMDX_WEIGHTS_ON_DEVICE) {
-            mp.rates = morph_weights;
-        } else {
-            HIP_TRY(s->rates_in.ensure(rate_bytes));
-            HIP_TRY(hipMemcpyAsync(s->rates_in.ptr, morph_weights, rate_bytes, hipMemcpyHostToDevice, st));
-            mp.rates = static_cast<const float *>(s->rates_in.ptr);
-            borrowed_rates = true;
-        }
-        HIP_TRY(s->morph_state.ensure(size_t(n_instances) * pl.nb * kMorphStateFloats * sizeof(float)));
-        mp.apps = static_cast<const BoneMorphApp *>(s->apps.ptr);
-        mp.chain = static_cast<const float *>(s->app_chain.ptr);
-        mp.out = static_cast<float *>(s->morph_state.ptr);
-        mp.napps = uint32_t(pl.apps.size()); mp.nb = pl.nb; mp.ni = n_instances; mp.nm = pl.nm; mp.shared = shared ? 1u : 0u;
-        HIP_TRY(launch_bone_morph(mp, st));
-        morph_state = mp.out;
-    }
-    if (pl.serial) {
-        HIP_TRY(s->state.ensure(size_t(n_instances) * pl.nb * kSerialStateFloats * sizeof(float)));
-        SerialParams sp;
-        sp.morph = morph_state;
-        sp.poses = p.poses; sp.out = p.out;
-        sp.state = static_cast<float *>(s->state.ptr);
-        sp.order = static_cast<const uint32_t *>(s->order.ptr);
-        sp.bones = static_cast<const BoneRec *>(s->bones.ptr);
-        sp.iks = static_cast<const IkRec *>(s->iks.ptr);
-        sp.links = static_cast<const LinkRec *>(s->links.ptr);
-        sp.events = static_cast<const uint32_t *>(s->events.ptr);
-        sp.rounds = static_cast<const RoundRec *>(s->rounds.ptr);
-        sp.nb = pl.nb; sp.ni = n_instances; sp.n_pre = pl.n_pre;
-        sp.n_rounds_pre = pl.n_rounds_pre; sp.n_rounds = uint32_t(pl.rounds.size());
-        sp.fast_slots = pl.fast_slots;
-        sp.windows = pl.windows;
-        sp.passes = passes;
-        sp.nested = pl.nested_ik ? 1u : 0u;
-        bool borrowed_over = false;
-        if ((passes & 2u) && ov && ov->n_bones) {     // the reactor's writes, between the two lists
-            PhysicsParams pp;
-            std::vector<uint32_t> ob(ov->bone, ov->bone + ov->n_bones);
-            std::vector<uint8_t> os(ov->n_bones, 0);
-            for (uint32_t k = 0; ov->strict && k < ov->n_bones; ++k) os[k] = ov->strict[k] ? 1 : 0;
-            HIP_TRY(s->over_bone.ensure(ob.size() * 4));
-            HIP_TRY(s->over_strict.ensure(os.size()));
-            HIP_TRY(hipMemcpyAsync(s->over_bone.ptr, ob.data(), ob.size() * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(s->over_strict.ptr, os.data(), os.size(), hipMemcpyHostToDevice, st));
-            const size_t xf_bytes = size_t(n_instances) * ov->n_bones * 64;
-            if (flags & MMDX_OVERRIDES_ON_DEVICE) {
-                pp.skinning = ov->skinning;
-            } else {
-                HIP_TRY(s->over_skin.ensure(xf_bytes));
-                HIP_TRY(hipMemcpyAsync(s->over_skin.ptr, ov->skinning, xf_bytes, hipMemcpyHostToDevice, st));
-                pp.skinning = static_cast<const float *>(s->over_skin.ptr);
-            }
-            HIP_TRY(hipStreamSynchronize(st));        // ob / os are locals: the copies above must have read them
-            borrowed_over = false;
-            pp.bone = static_cast<const uint32_t *>(s->over_bone.ptr);
-            pp.strict = static_cast<const uint8_t *>(s->over_strict.ptr);
-            pp.out = p.out; pp.state = sp.state; pp.bones = sp.bones;
-            pp.k = ov->n_bones; pp.nb = pl.nb; pp.ni = n_instances;
-            HIP_TRY(launch_physics_override(pp, st));
-        }
-        (void)borrowed_over;
-        HIP_TRY(launch_skeleton_ordered(sp, pl.round_coop.empty() ? nullptr : pl.round_coop.data(), st, &s->last_solve));
-        if (passes == 1u) { s->pre_instances = n_instances; s->pre_poses = p.poses; s->pre_morph = morph_state; }
-        else s->pre_instances = 0;
-    } else {
-        SkeletonParams fp;
-        fp.morph = morph_state;
-        fp.poses = p.poses; fp.out = p.out;
-        fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
-        fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
-        fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
-        fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
-        fp.nb = pl.nb; fp.ni = n_instances;
-        HIP_TRY(launch_skeleton_fk(fp, st));
-        s->last_solve = SolveShape{}; s->last_solve.solver = 2;
-    }
-    if (!(flags & MMDX_OUT_ON_DEVICE)) {
-        if (out_bytes) HIP_TRY(hipMemcpyAsync(out_palettes, p.out, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if (!(flags & MMDX_POSES_ON_DEVICE) || borrowed_rates) {
-        HIP_TRY(wait_stream(st));   // borrowed host poses / rates must be consumed before returning
-    }
-    return MMDX_OK;
-}
-
-static mmdx_status check_instance_list(const mmdx_instance_select *sel, uint32_t n_instances, const char *plain, uint32_t &live_host);
-
-// mmdx_skeleton_solve_select: mmdx_skeleton_solve_morphed for the listed instances (include/mmdx.h, rules 1-10).  Everything that can
-// be decided without the device comes first, in the header's order; `live_host` = the ids of a host list that are in use.
-static mmdx_status check_select_args(mmdx_skeleton_t s, uint32_t n_instances, const float *poses, const float *morph_weights,
-                                     uint32_t flags, const mmdx_instance_select *sel, const float *out_palettes, uint32_t &live_host) {
-    if (!s || !poses || !out_palettes || !n_instances) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
-    const uint32_t need = MMDX_POSES_ON_DEVICE | MMDX_OUT_ON_DEVICE | (morph_weights ? uint32_t(MMDX_WEIGHTS_ON_DEVICE) : 0u);
-    if ((flags & need) != need)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_skeleton_solve_select takes device operands only: pass MMDX_POSES_ON_DEVICE | "
-                                               "MMDX_OUT_ON_DEVICE, and MMDX_WEIGHTS_ON_DEVICE with morph_weights");
-    if (flags & ~uint32_t(MMDX_POSES_ON_DEVICE | MMDX_OUT_ON_DEVICE | MMDX_WEIGHTS_ON_DEVICE | MMDX_WEIGHTS_SHARED))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
-    return check_instance_list(sel, n_instances, "mmdx_skeleton_solve / _morphed solve every instance", live_host);
-}
-
-// The list of a select call (mmdx_skeleton_solve_select, the *_blend_*_time_select calls), decided without the device: `plain` names
-// the calls that take every instance; `live_host` = the ids of a host list that are in use.
-static mmdx_status check_instance_list(const mmdx_instance_select *sel, uint32_t n_instances, const char *plain, uint32_t &live_host) {
-    if (!sel) return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("select is NULL (") + plain + ")");
-    if (sel->struct_size != sizeof(mmdx_instance_select))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.struct_size mismatch");
-    if (sel->flags & ~uint32_t(MMDX_SELECT_ON_DEVICE))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown bits in mmdx_instance_select.flags");
-    if (sel->reserved0 != 0) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.reserved0 must be 0");
-    if (sel->n_ids && !sel->ids) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids is NULL");
-    if (sel->flags & MMDX_SELECT_ON_DEVICE) {
-        if ((reinterpret_cast<uintptr_t>(sel->ids) | reinterpret_cast<uintptr_t>(sel->count)) & 3)
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "device ids / count of mmdx_instance_select must be 4-byte aligned");
-        return MMDX_OK;
-    }
-    if (graph_recording())
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded the instance list must be in device memory "
-                                               "(MMDX_SELECT_ON_DEVICE)");
-    live_host = sel->count ? std::min(*sel->count, sel->n_ids) : sel->n_ids;
-    for (uint32_t j = 0; j < live_host; ++j)
-        if (sel->ids[j] >= n_instances)
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids[" + std::to_string(j) + "] = " +
-                                                   std::to_string(sel->ids[j]) + " is not below n_instances");
-    return MMDX_OK;
-}
-
-static mmdx_status skeleton_solve_select(mmdx_skeleton_t s, mmdx_model_t model, uint32_t n_instances, const float *poses,
-                                         const float *morph_weights, uint32_t flags, const mmdx_instance_select *sel,
-                                         float *out_palettes) {
-    uint32_t live_host = 0;
-    if (mmdx_status r = check_select_args(s, n_instances, poses, morph_weights, flags, sel, out_palettes, live_host)) return r;
-    int device;
-    hipStream_t st;
-    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
-    const SkeletonPlan &pl = s->plan;
-    const bool host_list = !(sel->flags & MMDX_SELECT_ON_DEVICE);
-    if (graph_recording() && s->device != device)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded the skeleton must have run on this device before");
-    if (mmdx_status r = skeleton_to_device(s, device)) return r;
-    graph_note_handle(model, &s->pin);
-    // state and bone-morph cells are per LIST POSITION: the capacity of a device list, the ids in use of a host list
-    const uint32_t cells = host_list ? live_host : sel->n_ids;
-    if (cells == 0) return MMDX_OK;                                 // an empty list writes nothing
-    InstanceList list = {sel->ids, sel->count, n_instances};
-    if (host_list) {                                                // through the skeleton's scratch in stream order, count word first
-        HIP_TRY(s->sel_in.ensure((size_t(cells) + 1) * 4));
-        s->sel_host.resize(size_t(cells) + 1);
-        s->sel_host[0] = cells;
-        std::copy(sel->ids, sel->ids + cells, s->sel_host.begin() + 1);
-        HIP_TRY(hipMemcpyAsync(s->sel_in.ptr, s->sel_host.data(), s->sel_host.size() * 4, hipMemcpyHostToDevice, st));
-        list.count = static_cast<const uint32_t *>(s->sel_in.ptr);
-        list.ids = list.count + 1;
-    }
-    const float *morph_state = nullptr;
-    if (morph_weights && !pl.apps.empty()) {
-        HIP_TRY(s->morph_state.ensure(size_t(cells) * pl.nb * kMorphStateFloats * sizeof(float)));
-        BoneMorphParams mp;
-        mp.rates = morph_weights;
-        mp.apps = static_cast<const BoneMorphApp *>(s->apps.ptr);
-        mp.chain = static_cast<const float *>(s->app_chain.ptr);
-        mp.out = static_cast<float *>(s->morph_state.ptr);
-        mp.napps = uint32_t(pl.apps.size()); mp.nb = pl.nb; mp.ni = cells; mp.nm = pl.nm;
-        mp.shared = (flags & MMDX_WEIGHTS_SHARED) ? 1u : 0u;
-        HIP_TRY(launch_bone_morph_select(mp, list, st));
-        morph_state = mp.out;
-    }
-    if (pl.serial) {
-        HIP_TRY(s->state.ensure(size_t(cells) * pl.nb * kSerialStateFloats * sizeof(float)));
-        SerialParams sp;
-        sp.morph = morph_state;
-        sp.poses = poses; sp.out = out_palettes;
-        sp.state = static_cast<float *>(s->state.ptr);
-        sp.order = static_cast<const uint32_t *>(s->order.ptr);
-        sp.bones = static_cast<const BoneRec *>(s->bones.ptr);
-        sp.iks = static_cast<const IkRec *>(s->iks.ptr);
-        sp.links = static_cast<const LinkRec *>(s->links.ptr);
-        sp.events = static_cast<const uint32_t *>(s->events.ptr);
-        sp.rounds = static_cast<const RoundRec *>(s->rounds.ptr);
-        sp.nb = pl.nb; sp.ni = cells; sp.n_pre = pl.n_pre;
-        sp.n_rounds_pre = pl.n_rounds_pre; sp.n_rounds = uint32_t(pl.rounds.size());
-        sp.fast_slots = pl.fast_slots;
-        sp.windows = pl.windows;
-        sp.passes = 3u;
-        sp.nested = pl.nested_ik ? 1u : 0u;
-        HIP_TRY(launch_skeleton_ordered_select(sp, pl.round_coop.empty() ? nullptr : pl.round_coop.data(), list, st, &s->last_solve));
-        s->pre_instances = 0;                                       // (the scratch a pending pre step left is gone, as after mmdx_skeleton_solve)
-    } else {
-        SkeletonParams fp;
-        fp.morph = morph_state;
-        fp.poses = poses; fp.out = out_palettes;
-        fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
-        fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
-        fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
-        fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
-        fp.nb = pl.nb; fp.ni = cells;
-        HIP_TRY(launch_skeleton_fk_select(fp, list, st));
-        s->last_solve = SolveShape{}; s->last_solve.solver = 2;
-    }
-    if (host_list) HIP_TRY(wait_stream(st));                        // the borrowed list is consumed and the results are there
-    return MMDX_OK;
-}
-
-extern "C" void mmdx_skeleton_destroy(mmdx_skeleton_t s) {
-    if (!s) return;
-    graph_drop_handle(&s->pin);
-    if (s->device >= 0) (void)hipSetDevice(s->device);
-    s->release_all();
-    delete s;
-}
-
-// mmdx_bone_motion_eval / _eval_time: frames (uint32_t) or, with `time`, seconds (double)
-static mmdx_status bone_motion_eval(mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances, const void *clock, bool time,
-                                    uint32_t flags, float *out_poses) {
-    if (!m || !clock || !out_poses || !n_instances)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
-    int device;
-    hipStream_t st;
-    if (mmdx_status s = resolve_stream(model, &device, &st)) return s;
-    const BoneMotionHost &h = m->host;
-    if (graph_recording() && ((flags & (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) != (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE) ||
-                              m->device != device))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory and the "
-                                               "motion must have run on this device before");
-    if (mmdx_status r = motion_to_device(m, device)) return r;
-    graph_note_handle(model, &m->pin);
-    BoneTrackParams p = motion_params(m, n_instances);
-    if (mmdx_status r = motion_clock_in(m, clock, time, n_instances, flags, st, p)) return r;
-    const size_t out_bytes = size_t(n_instances) * h.nb * MMDX_POSE_FLOATS * sizeof(float);
-    if (flags & MMDX_OUT_ON_DEVICE) {
-        p.out = out_poses;
-    } else {
-        HIP_TRY(m->out.ensure(out_bytes));
-        p.out = static_cast<float *>(m->out.ptr);
-    }
-    HIP_TRY(launch_bone_track_eval(p, st));
-    if (!(flags & MMDX_OUT_ON_DEVICE)) {
-        if (out_bytes) HIP_TRY(hipMemcpyAsync(out_poses, p.out, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
-        HIP_TRY(wait_stream(st));   // borrowed host frames / times must be consumed before returning
-    }
-    return MMDX_OK;
-}
-
-// mmdx_skeleton_solve_motion / _time: frames (uint32_t) or, with `time`, seconds (double)
-static mmdx_status skeleton_solve_motion(mmdx_skeleton_t s, mmdx_bone_motion_t m, mmdx_model_t model, uint32_t n_instances,
-                                         const void *clock, bool time, uint32_t flags, float *out_palettes) {
-    if (!s || !m || !clock || !out_palettes || !n_instances)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
-    if (m->host.nb != s->plan.nb)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "the motion was bound to " + std::to_string(m->host.nb) + " bones, the skeleton has " +
-                                               std::to_string(s->plan.nb));
-    int device;
-    hipStream_t st;
-    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
-    const SkeletonPlan &pl = s->plan;
-    const size_t pose_bytes = size_t(n_instances) * pl.nb * MMDX_POSE_FLOATS * sizeof(float);
-    if (pl.serial || size_t(pl.nb) * 32 > kMotionFkMaxLds) {
-        // append bones / IK (the ordered solver) or a skeleton too large for the LDS pose table: the two launches, the poses in the
-        // motion's scratch buffer
-        if (graph_recording() && m->out.bytes < pose_bytes)
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "run the call once before recording: it sizes the motion's pose buffer");
-        if (mmdx_status r = motion_to_device(m, device)) return r;
-        HIP_TRY(m->out.ensure(pose_bytes));
-        if (mmdx_status r = bone_motion_eval(m, model, n_instances, clock, time, (flags & MMDX_FRAMES_ON_DEVICE) | MMDX_OUT_ON_DEVICE,
-                                             static_cast<float *>(m->out.ptr)))
-            return r;
-        return mmdx_skeleton_solve(s, model, n_instances, static_cast<const float *>(m->out.ptr),
-                                   MMDX_POSES_ON_DEVICE | (flags & MMDX_OUT_ON_DEVICE), out_palettes);
-    }
-    if (graph_recording() && ((flags & (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) != (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE) ||
-                              m->device != device || s->device != device))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory and the motion "
-                                               "and the skeleton must have run on this device before");
-    if (mmdx_status r = motion_to_device(m, device)) return r;
-    if (mmdx_status r = skeleton_to_device(s, device)) return r;
-    graph_note_handle(model, &m->pin);
-    graph_note_handle(model, &s->pin);
-    BoneTrackParams tp = motion_params(m, n_instances);
-    if (mmdx_status r = motion_clock_in(m, clock, time, n_instances, flags, st, tp)) return r;
-    const size_t out_bytes = size_t(n_instances) * pl.nb * 16 * sizeof(float);
-    SkeletonParams fp;
-    fp.morph = nullptr;
-    fp.poses = nullptr;
-    if (flags & MMDX_OUT_ON_DEVICE) {
-        fp.out = out_palettes;
-    } else {
-        HIP_TRY(s->out.ensure(out_bytes));
-        fp.out = static_cast<float *>(s->out.ptr);
-    }
-    fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
-    fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
-    fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
-    fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
-    fp.nb = pl.nb; fp.ni = n_instances;
-    HIP_TRY(launch_motion_fk(tp, fp, st));
-    s->last_solve = SolveShape{}; s->last_solve.solver = 2;
-    if (!(flags & MMDX_OUT_ON_DEVICE)) {
-        HIP_TRY(hipMemcpyAsync(out_palettes, fp.out, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
-        HIP_TRY(wait_stream(st));                    // the borrowed host frame numbers / times must be consumed before returning
-    }
-    return MMDX_OK;
-}
-
-// ---- motion sets -----------------------------------------------------------------------------------------------------------------
-// Everything about a set call that can be decided without the device, in one place and before the first HIP call: NULLs, the
-// instance count, flag bits, NaN in host times (check_time_args), the side the set was created without, host clip ids.
-static mmdx_status set_check_args(mmdx_motion_set_t set, bool bone_side, uint32_t n_instances, const uint32_t *clips, const void *clock,
-                                  bool time, uint32_t flags, const float *out) {
-    if (!set || !clips || !clock || !out || !n_instances) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
-    const uint32_t allowed = MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
-    if (time) {
-        if (mmdx_status r = check_time_args(static_cast<const double *>(clock), n_instances, flags, allowed)) return r;
-    } else if (flags & ~allowed) {
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
-    }
-    if (bone_side ? !set->host.has_bones : !set->host.has_morphs)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("this motion set was created without ") + (bone_side ? "bone" : "morph") + " motions");
-    if (!(flags & MMDX_FRAMES_ON_DEVICE))
-        for (uint32_t i = 0; i < n_instances; ++i)
-            if (clips[i] >= set->host.n_clips && clips[i] != MMDX_CLIP_NONE)
-                return fail(MMDX_ERR_BAD_INDEX, "clips[" + std::to_string(i) + "] = " + std::to_string(clips[i]) + ": the set has " +
-                                                std::to_string(set->host.n_clips) + " clips");
-    return MMDX_OK;
-}
-
-static mmdx_status set_to_device(mmdx_motion_set_t set, int device) {
-    if (set->device == device) return MMDX_OK;
-    if (graph_pinned(&set->pin)) return hip_status(hipErrorIllegalState, "moving a motion set to another device");
-    const MotionSetHost &h = set->host;
-    for (Buf *b : set->all()) b->release();
-    if (h.has_bones) {
-        HIP_TRY(set->key_off.upload(h.bones.key_off));
-        HIP_TRY(set->key_frame.upload(h.bones.key_frame));
-        HIP_TRY(set->key_tr.upload(h.bones.key_tr));
-        HIP_TRY(set->key_rot.upload(h.bones.key_rot));
-        HIP_TRY(set->key_curve.upload(h.bones.key_curve));
-        HIP_TRY(set->lut.upload(h.bones.lut));
-    }
-    if (h.has_morphs) {
-        HIP_TRY(set->m_key_off.upload(h.morph_key_off));
-        HIP_TRY(set->m_frames.upload(h.morph_frames));
-        HIP_TRY(set->m_weights.upload(h.morph_weights));
-    }
-    set->device = device;
-    return MMDX_OK;
-}
-
-static BoneTrackParams set_bone_params(mmdx_motion_set_t set, uint32_t n_instances) {
-    BoneTrackParams p;
-    p.key_off = static_cast<const uint32_t *>(set->key_off.ptr);
-    p.key_frame = static_cast<const uint32_t *>(set->key_frame.ptr);
-    p.key_tr = static_cast<const float *>(set->key_tr.ptr);
-    p.key_rot = static_cast<const float *>(set->key_rot.ptr);
-    p.key_curve = static_cast<const uint32_t *>(set->key_curve.ptr);
-    p.lut = static_cast<const float *>(set->lut.ptr);
-    p.frames = nullptr; p.out = nullptr; p.times = nullptr;
-    p.nb = set->host.bones.nb; p.ni = n_instances;
-    return p;
-}
-
-// clip ids and the instant of every instance -> device addresses.  MMDX_FRAMES_ON_DEVICE covers both; host operands go through the
-// set's scratch (4 + 8 bytes per instance, room for frames or times) in stream order.
-static mmdx_status set_operands_in(mmdx_motion_set_t set, const uint32_t *clips, const void *clock, bool time, uint32_t n_instances,
-                                   uint32_t flags, hipStream_t st, const uint32_t **dev_clips, const void **dev_clock) {
-    *dev_clips = clips;
-    *dev_clock = clock;
-    if (flags & MMDX_FRAMES_ON_DEVICE) return MMDX_OK;
-    HIP_TRY(set->clips_in.ensure(size_t(n_instances) * 4));
-    HIP_TRY(set->clock_in.ensure(size_t(n_instances) * 8));
-    HIP_TRY(hipMemcpyAsync(set->clips_in.ptr, clips, size_t(n_instances) * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(set->clock_in.ptr, clock, size_t(n_instances) * (time ? 8 : 4), hipMemcpyHostToDevice, st));
-    *dev_clips = static_cast<const uint32_t *>(set->clips_in.ptr);
-    *dev_clock = set->clock_in.ptr;
-    return MMDX_OK;
-}
-
-static const char *const kSetRecording = "while a graph is being recorded every operand must be in device memory and the motion set "
-                                         "must have run on this device before";
-
-// mmdx_motion_set_eval_bones / _time: frames (uint32_t) or, with `time`, seconds (double)
-static mmdx_status set_eval_bones(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
-                                  const void *clock, bool time, uint32_t flags, float *out_poses) {
-    if (mmdx_status r = set_check_args(set, true, n_instances, clips, clock, time, flags, out_poses)) return r;
-    int device;
-    hipStream_t st;
-    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
-    const uint32_t on_device = MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
-    if (graph_recording() && ((flags & on_device) != on_device || set->device != device)) return fail(MMDX_ERR_INVALID_ARGUMENT, kSetRecording);
-    if (mmdx_status r = set_to_device(set, device)) return r;
-    graph_note_handle(model, &set->pin);
-    BoneTrackParams p = set_bone_params(set, n_instances);
-    const uint32_t *dev_clips;
-    const void *dev_clock;
-    if (mmdx_status r = set_operands_in(set, clips, clock, time, n_instances, flags, st, &dev_clips, &dev_clock)) return r;
-    if (time) p.times = static_cast<const double *>(dev_clock);
-    else p.frames = static_cast<const uint32_t *>(dev_clock);
-    const size_t out_bytes = size_t(n_instances) * p.nb * MMDX_POSE_FLOATS * sizeof(float);
-    if (flags & MMDX_OUT_ON_DEVICE) {
-        p.out = out_poses;
-    } else {
-        HIP_TRY(set->out.ensure(out_bytes));
-        p.out = static_cast<float *>(set->out.ptr);
-    }
-    HIP_TRY(launch_bone_track_eval_set(p, dev_clips, set->host.n_clips, st));
-    if (!(flags & MMDX_OUT_ON_DEVICE)) {
-        if (out_bytes) HIP_TRY(hipMemcpyAsync(out_poses, p.out, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
-        HIP_TRY(wait_stream(st));   // borrowed host clip ids and frames / times must be consumed before returning
-    }
-    return MMDX_OK;
-}
-
-// mmdx_motion_set_eval_morphs / _time
-static mmdx_status set_eval_morphs(mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances, const uint32_t *clips,
-                                   const void *clock, bool time, uint32_t flags, float *out_weights) {
-    if (mmdx_status r = set_check_args(set, false, n_instances, clips, clock, time, flags, out_weights)) return r;
-    int device;
-    hipStream_t st;
-    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
-    const uint32_t on_device = MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
-    if (graph_recording() && ((flags & on_device) != on_device || set->device != device)) return fail(MMDX_ERR_INVALID_ARGUMENT, kSetRecording);
-    if (mmdx_status r = set_to_device(set, device)) return r;
-    graph_note_handle(model, &set->pin);
-    MorphTrackParams t;
-    t.key_off = static_cast<const uint32_t *>(set->m_key_off.ptr);
-    t.key_frames = static_cast<const uint32_t *>(set->m_frames.ptr);
-    t.key_weights = static_cast<const float *>(set->m_weights.ptr);
-    t.nm = set->host.nm; t.ni = n_instances;
-    t.frames = nullptr; t.times = nullptr;
-    const uint32_t *dev_clips;
-    const void *dev_clock;
-    if (mmdx_status r = set_operands_in(set, clips, clock, time, n_instances, flags, st, &dev_clips, &dev_clock)) return r;
-    if (time) t.times = static_cast<const double *>(dev_clock);
-    else t.frames = static_cast<const uint32_t *>(dev_clock);
-    const size_t out_bytes = size_t(n_instances) * t.nm * sizeof(float);
-    if (flags & MMDX_OUT_ON_DEVICE) {
-        t.out = out_weights;
-    } else {
-        HIP_TRY(set->out.ensure(out_bytes));
-        t.out = static_cast<float *>(set->out.ptr);
-    }
-    HIP_TRY(launch_morph_track_eval_set(t, dev_clips, set->host.n_clips, st));
-    if (!(flags & MMDX_OUT_ON_DEVICE)) {
-        if (out_bytes) HIP_TRY(hipMemcpyAsync(out_weights, t.out, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
-        HIP_TRY(wait_stream(st));   // borrowed host clip ids and frames / times must be consumed before returning
-    }
-    return MMDX_OK;
-}
-
-// mmdx_skeleton_solve_motion_set / _time
-static mmdx_status skeleton_solve_motion_set(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model, uint32_t n_instances,
-                                             const uint32_t *clips, const void *clock, bool time, uint32_t flags, float *out_palettes) {
-    if (!s) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
-    if (mmdx_status r = set_check_args(set, true, n_instances, clips, clock, time, flags, out_palettes)) return r;
-    if (set->host.bones.nb != s->plan.nb)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "the motion set was bound to " + std::to_string(set->host.bones.nb) +
-                                               " bones, the skeleton has " + std::to_string(s->plan.nb));
-    int device;
-    hipStream_t st;
-    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
-    const SkeletonPlan &pl = s->plan;
-    const size_t pose_bytes = size_t(n_instances) * pl.nb * MMDX_POSE_FLOATS * sizeof(float);
-    if (pl.serial || size_t(pl.nb) * 32 > kMotionFkMaxLds) {
-        // append bones / IK (the ordered solver) or a skeleton too large for the LDS pose table: the two launches, the poses in the
-        // set's scratch buffer
-        if (graph_recording() && (set->poses.bytes < pose_bytes || set->device != device))
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "run the call once before recording: it sizes the motion set's pose buffer");
-        if (mmdx_status r = set_to_device(set, device)) return r;
-        HIP_TRY(set->poses.ensure(pose_bytes));
-        if (mmdx_status r = set_eval_bones(set, model, n_instances, clips, clock, time, (flags & MMDX_FRAMES_ON_DEVICE) | MMDX_OUT_ON_DEVICE,
-                                           static_cast<float *>(set->poses.ptr)))
-            return r;
-        return mmdx_skeleton_solve(s, model, n_instances, static_cast<const float *>(set->poses.ptr),
-                                   MMDX_POSES_ON_DEVICE | (flags & MMDX_OUT_ON_DEVICE), out_palettes);
-    }
-    const uint32_t on_device = MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
-    if (graph_recording() && ((flags & on_device) != on_device || set->device != device || s->device != device))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory and the motion "
-                                               "set and the skeleton must have run on this device before");
-    if (mmdx_status r = set_to_device(set, device)) return r;
-    if (mmdx_status r = skeleton_to_device(s, device)) return r;
-    graph_note_handle(model, &set->pin);
-    graph_note_handle(model, &s->pin);
-    BoneTrackParams tp = set_bone_params(set, n_instances);
-    const uint32_t *dev_clips;
-    const void *dev_clock;
-    if (mmdx_status r = set_operands_in(set, clips, clock, time, n_instances, flags, st, &dev_clips, &dev_clock)) return r;
-    if (time) tp.times = static_cast<const double *>(dev_clock);
-    else tp.frames = static_cast<const uint32_t *>(dev_clock);
-    const size_t out_bytes = size_t(n_instances) * pl.nb * 16 * sizeof(float);
-    SkeletonParams fp;
-    fp.morph = nullptr;
-    fp.poses = nullptr;
-    if (flags & MMDX_OUT_ON_DEVICE) {
-        fp.out = out_palettes;
-    } else {
-        HIP_TRY(s->out.ensure(out_bytes));
-        fp.out = static_cast<float *>(s->out.ptr);
-    }
-    fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
-    fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
-    fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
-    fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
-    fp.nb = pl.nb; fp.ni = n_instances;
-    HIP_TRY(launch_motion_fk_set(tp, fp, dev_clips, set->host.n_clips, st));
-    s->last_solve = SolveShape{}; s->last_solve.solver = 2;
-    if (!(flags & MMDX_OUT_ON_DEVICE)) {
-        HIP_TRY(hipMemcpyAsync(out_palettes, fp.out, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
-        HIP_TRY(wait_stream(st));                    // the borrowed host clip ids and clocks must be consumed before returning
-    }
-    return MMDX_OK;
-}
-
-// ---- cross-fade between two clips of a set (mmdx_motion_set_blend_*_time, mmdx_skeleton_solve_motion_set_blend_time) ---------------
-// Everything about a blend call that can be decided without the device, before the first HIP call: NULLs, struct_size, the
-// instance count, flag bits, the side the set was created without, and -- for host operands -- clip ids of both arrays, NaN
-// times and NaN weights.
-static mmdx_status blend_check_args(mmdx_motion_set_t set, bool bone_side, const mmdx_motion_blend_args *a, const float *out) {
-    if (!set || !a || !out) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (a->struct_size != sizeof(mmdx_motion_blend_args)) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_motion_blend_args.struct_size mismatch");
-    if (!a->clips_a || !a->clips_b || !a->times_a || !a->times_b || !a->weights || !a->n_instances)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
-    if (a->flags & ~uint32_t(MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
-    if (bone_side ? !set->host.has_bones : !set->host.has_morphs)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("this motion set was created without ") + (bone_side ? "bone" : "morph") + " motions");
-    if (a->flags & MMDX_TIMES_ON_DEVICE) return MMDX_OK;
-    const struct { const char *name; const uint32_t *clips; const double *times; } sides[2] = {{"a", a->clips_a, a->times_a},
-                                                                                                 {"b", a->clips_b, a->times_b}};
-    for (const auto &s : sides)
-        for (uint32_t i = 0; i < a->n_instances; ++i)
-            if (s.clips[i] >= set->host.n_clips && s.clips[i] != MMDX_CLIP_NONE)
-                return fail(MMDX_ERR_BAD_INDEX, std::string("clips_") + s.name + "[" + std::to_string(i) + "] = " + std::to_string(s.clips[i]) +
-                                                ": the set has " + std::to_string(set->host.n_clips) + " clips");
-    for (const auto &s : sides)
-        for (uint32_t i = 0; i < a->n_instances; ++i)
-            if (s.times[i] != s.times[i])
-                return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("times_") + s.name + "[" + std::to_string(i) + "] is NaN");
-    for (uint32_t i = 0; i < a->n_instances; ++i)
-        if (a->weights[i] != a->weights[i]) return fail(MMDX_ERR_INVALID_ARGUMENT, "weights[" + std::to_string(i) + "] is NaN");
-    return MMDX_OK;
-}
-
-// the five operand arrays -> device addresses.  MMDX_TIMES_ON_DEVICE covers all five; host operands go through the set's scratch
-// (times_a, times_b, clips_a, clips_b, weights laid end to end: 28 bytes per instance) in stream order.
-static mmdx_status blend_operands_in(mmdx_motion_set_t set, const mmdx_motion_blend_args *a, hipStream_t st, BlendOperands *o) {
-    o->clips_a = a->clips_a; o->clips_b = a->clips_b;
-    o->times_a = a->times_a; o->times_b = a->times_b;
-    o->weights = a->weights;
-    o->n_clips = set->host.n_clips;
-    if (a->flags & MMDX_TIMES_ON_DEVICE) return MMDX_OK;
-    const size_t n = a->n_instances;
-    HIP_TRY(set->blend_in.ensure(n * 28));
-    char *base = static_cast<char *>(set->blend_in.ptr);
-    const struct { const void *src; size_t off, bytes; } parts[5] = {{a->times_a, 0, n * 8},       {a->times_b, n * 8, n * 8},
-                                                                     {a->clips_a, n * 16, n * 4}, {a->clips_b, n * 20, n * 4},
-                                                                     {a->weights, n * 24, n * 4}};
-    for (const auto &p : parts) HIP_TRY(hipMemcpyAsync(base + p.off, p.src, p.bytes, hipMemcpyHostToDevice, st));
-    o->times_a = reinterpret_cast<const double *>(base);
-    o->times_b = reinterpret_cast<const double *>(base + n * 8);
-    o->clips_a = reinterpret_cast<const uint32_t *>(base + n * 16);
-    o->clips_b = reinterpret_cast<const uint32_t *>(base + n * 20);
-    o->weights = reinterpret_cast<const float *>(base + n * 24);
-    return MMDX_OK;
-}
-
-// results bound for the host are copied out and waited for; borrowed host operands must be consumed before returning
-static mmdx_status blend_finish(uint32_t flags, hipStream_t st, float *host_out, const float *dev_out, size_t out_bytes) {
-    if (!(flags & MMDX_OUT_ON_DEVICE)) {
-        if (out_bytes) HIP_TRY(hipMemcpyAsync(host_out, dev_out, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if (!(flags & MMDX_TIMES_ON_DEVICE)) {
-        HIP_TRY(wait_stream(st));
-    }
-    return MMDX_OK;
-}
-
-// mmdx_motion_set_blend_bones_time
-static mmdx_status set_blend_bones(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *a, float *out_poses) {
-    if (mmdx_status r = blend_check_args(set, true, a, out_poses)) return r;
-    int device;
-    hipStream_t st;
-    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
-    const uint32_t on_device = MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
-    if (graph_recording() && ((a->flags & on_device) != on_device || set->device != device)) return fail(MMDX_ERR_INVALID_ARGUMENT, kSetRecording);
-    if (mmdx_status r = set_to_device(set, device)) return r;
-    graph_note_handle(model, &set->pin);
-    BoneTrackParams p = set_bone_params(set, a->n_instances);
-    BlendOperands o;
-    if (mmdx_status r = blend_operands_in(set, a, st, &o)) return r;
-    const size_t out_bytes = size_t(a->n_instances) * p.nb * MMDX_POSE_FLOATS * sizeof(float);
-    if (a->flags & MMDX_OUT_ON_DEVICE) {
-        p.out = out_poses;
-    } else {
-        HIP_TRY(set->out.ensure(out_bytes));
-        p.out = static_cast<float *>(set->out.ptr);
-    }
-    HIP_TRY(launch_bone_track_blend_set(p, o, st));
-    return blend_finish(a->flags, st, out_poses, p.out, out_bytes);
-}
-
-// mmdx_motion_set_blend_morphs_time
-static mmdx_status set_blend_morphs(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *a, float *out_weights) {
-    if (mmdx_status r = blend_check_args(set, false, a, out_weights)) return r;
-    int device;
-    hipStream_t st;
-    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
-    const uint32_t on_device = MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
-    if (graph_recording() && ((a->flags & on_device) != on_device || set->device != device)) return fail(MMDX_ERR_INVALID_ARGUMENT, kSetRecording);
-    if (mmdx_status r = set_to_device(set, device)) return r;
-    graph_note_handle(model, &set->pin);
-    MorphTrackParams t;
-    t.key_off = static_cast<const uint32_t *>(set->m_key_off.ptr);
-    t.key_frames = static_cast<const uint32_t *>(set->m_frames.ptr);
-    t.key_weights = static_cast<const float *>(set->m_weights.ptr);
-    t.nm = set->host.nm; t.ni = a->n_instances;
-    t.frames = nullptr; t.times = nullptr;
-    BlendOperands o;
-    if (mmdx_status r = blend_operands_in(set, a, st, &o)) return r;
-    const size_t out_bytes = size_t(a->n_instances) * t.nm * sizeof(float);
-    if (a->flags & MMDX_OUT_ON_DEVICE) {
-        t.out = out_weights;
-    } else {
-        HIP_TRY(set->out.ensure(out_bytes));
-        t.out = static_cast<float *>(set->out.ptr);
-    }
-    HIP_TRY(launch_morph_track_blend_set(t, o, st));
-    return blend_finish(a->flags, st, out_weights, t.out, out_bytes);
-}
-
-// mmdx_skeleton_solve_motion_set_blend_time
-static mmdx_status skeleton_solve_motion_set_blend(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model,
-                                                   const mmdx_motion_blend_args *a, float *out_palettes) {
     if (!s) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (mmdx_status r = blend_check_args(set, true, a, out_palettes)) return r;
-    if (set->host.bones.nb != s->plan.nb)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "the motion set was bound to " + std::to_string(set->host.bones.nb) +
-                                               " bones, the skeleton has " + std::to_string(s->plan.nb));
+    if (mmdx_status r = blend_check_args(set, true, args, out_palettes)) return r;
+    if (mmdx_status r = skeleton_matches_set(s, set)) return r;
     int device;
     hipStream_t st;
     if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
     const SkeletonPlan &pl = s->plan;
-    const uint32_t ni = a->n_instances;
-    const size_t pose_bytes = size_t(ni) * pl.nb * MMDX_POSE_FLOATS * sizeof(float);
-    if (pl.serial || size_t(pl.nb) * 32 > kMotionFkMaxLds) {
-        // append bones / IK (the ordered solver) or a skeleton too large for the LDS pose table: the blend track kernel into the
-        // set's scratch buffer, then the solve
-        if (graph_recording() && (set->poses.bytes < pose_bytes || set->device != device))
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "run the call once before recording: it sizes the motion set's pose buffer");
-        if (mmdx_status r = set_to_device(set, device)) return r;
-        HIP_TRY(set->poses.ensure(pose_bytes));
-        mmdx_motion_blend_args to_scratch = *a;
-        to_scratch.flags = (a->flags & MMDX_TIMES_ON_DEVICE) | MMDX_OUT_ON_DEVICE;
-        if (mmdx_status r = set_blend_bones(set, model, &to_scratch, static_cast<float *>(set->poses.ptr))) return r;
-        return mmdx_skeleton_solve(s, model, ni, static_cast<const float *>(set->poses.ptr),
-                                   MMDX_POSES_ON_DEVICE | (a->flags & MMDX_OUT_ON_DEVICE), out_palettes);
+    const uint32_t ni = args->n_instances;
+    if (two_launches(pl)) {                                         // the blend track call, then the solve
+        float *poses;
+        if (mmdx_status r = set_pose_scratch(set, device, pose_bytes(ni, pl.nb), &poses)) return r;
+        mmdx_motion_blend_args to_scratch = *args;
+        to_scratch.flags = (args->flags & MMDX_TIMES_ON_DEVICE) | MMDX_OUT_ON_DEVICE;
+        if (mmdx_status r = mmdx_motion_set_blend_bones_time(set, model, &to_scratch, poses)) return r;
+        return mmdx_skeleton_solve(s, model, ni, poses, MMDX_POSES_ON_DEVICE | (args->flags & MMDX_OUT_ON_DEVICE), out_palettes);
     }
-    const uint32_t on_device = MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
-    if (graph_recording() && ((a->flags & on_device) != on_device || set->device != device || s->device != device))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory and the motion "
-                                               "set and the skeleton must have run on this device before");
+    if (mmdx_status r = refuse_recording(args->flags, kClockAndOut, device, {set->device, s->device}, kSetSkeletonRecording)) return r;
     if (mmdx_status r = set_to_device(set, device)) return r;
     if (mmdx_status r = skeleton_to_device(s, device)) return r;
     graph_note_handle(model, &set->pin);
     graph_note_handle(model, &s->pin);
-    const BoneTrackParams tp = set_bone_params(set, ni);
-    BlendOperands o;
-    if (mmdx_status r = blend_operands_in(set, a, st, &o)) return r;
-    const size_t out_bytes = size_t(ni) * pl.nb * 16 * sizeof(float);
-    SkeletonParams fp;
-    fp.morph = nullptr;
-    fp.poses = nullptr;
-    if (a->flags & MMDX_OUT_ON_DEVICE) {
-        fp.out = out_palettes;
-    } else {
-        HIP_TRY(s->out.ensure(out_bytes));
-        fp.out = static_cast<float *>(s->out.ptr);
-    }
-    fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
-    fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
-    fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
-    fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
-    fp.nb = pl.nb; fp.ni = ni;
-    HIP_TRY(launch_motion_fk_blend_set(tp, fp, o, st));
-    s->last_solve = SolveShape{}; s->last_solve.solver = 2;
-    return blend_finish(a->flags, st, out_palettes, fp.out, out_bytes);
+    const BoneTrackParams tp = set->t.params(pl.nb, ni);
+    BlendOperands ops;
+    if (mmdx_status r = blend_operands_in(set, args, st, &ops)) return r;
+    OutRoute o;
+    if (mmdx_status r = route_out(args->flags, out_palettes, palette_bytes(ni, pl.nb), s->out, &o)) return r;
+    HIP_TRY(launch_motion_fk_blend_set(tp, fk_params(s, ni, nullptr, nullptr, o.dev), ops, st));
+    note_fk_solve(s);
+    return finish(args->flags, !(args->flags & MMDX_TIMES_ON_DEVICE), st, o);
 }
 
-// ---- the cross-fade for the listed instances (mmdx_motion_set_blend_*_time_select, mmdx_skeleton_solve_motion_set_blend_time_select;
-// include/mmdx.h, rules 1-10) -----------------------------------------------------------------------------------------------------------
-// Everything that can be decided without the device, before the first HIP call.  The device-resident form is checked ahead of
-// blend_check_args, which reads host operands when MMDX_TIMES_ON_DEVICE is absent; the rest of the operand checks are its own.
-static mmdx_status blend_select_check(mmdx_motion_set_t set, bool bone_side, const mmdx_motion_blend_args *a,
-                                      const mmdx_instance_select *sel, const float *out, uint32_t &live_host) {
-    if (!set || !a || !out) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (a->struct_size != sizeof(mmdx_motion_blend_args)) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_motion_blend_args.struct_size mismatch");
-    if (a->flags & ~uint32_t(MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
-    const uint32_t need = MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;
-    if ((a->flags & need) != need)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "the select form of a blend call takes device operands only: pass MMDX_TIMES_ON_DEVICE | "
-                                               "MMDX_OUT_ON_DEVICE");
-    if (mmdx_status r = blend_check_args(set, bone_side, a, out)) return r;
-    return check_instance_list(sel, a->n_instances, "the calls without _select evaluate every instance", live_host);
-}
-
-// the list -> device addresses: a device list as it is; a host list through the set's scratch in stream order, count word first.
-// `cells` = list positions the launch is sized from: the capacity of a device list, the ids in use of a host list.
-static mmdx_status set_list_in(mmdx_motion_set_t set, const mmdx_instance_select *sel, uint32_t n_instances, uint32_t live_host,
-                               hipStream_t st, InstanceList *list, uint32_t *cells) {
-    *list = InstanceList{sel->ids, sel->count, n_instances};
-    if (sel->flags & MMDX_SELECT_ON_DEVICE) {
-        *cells = sel->n_ids;
-        return MMDX_OK;
-    }
-    *cells = live_host;
-    if (live_host == 0) return MMDX_OK;
-    HIP_TRY(set->sel_in.ensure((size_t(live_host) + 1) * 4));
-    set->sel_host.resize(size_t(live_host) + 1);
-    set->sel_host[0] = live_host;
-    std::copy(sel->ids, sel->ids + live_host, set->sel_host.begin() + 1);
-    HIP_TRY(hipMemcpyAsync(set->sel_in.ptr, set->sel_host.data(), set->sel_host.size() * 4, hipMemcpyHostToDevice, st));
-    list->count = static_cast<const uint32_t *>(set->sel_in.ptr);
-    list->ids = list->count + 1;
-    return MMDX_OK;
-}
-
-static BlendOperands blend_operands_device(mmdx_motion_set_t set, const mmdx_motion_blend_args *a) {
-    BlendOperands o;
-    o.clips_a = a->clips_a; o.clips_b = a->clips_b;
-    o.times_a = a->times_a; o.times_b = a->times_b;
-    o.weights = a->weights;
-    o.n_clips = set->host.n_clips;
-    return o;
-}
-
-// mmdx_motion_set_blend_bones_time_select
-static mmdx_status set_blend_bones_select(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *a,
-                                          const mmdx_instance_select *sel, float *out_poses) {
-    uint32_t live_host = 0;
-    if (mmdx_status r = blend_select_check(set, true, a, sel, out_poses, live_host)) return r;
-    int device;
-    hipStream_t st;
-    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
-    if (graph_recording() && set->device != device) return fail(MMDX_ERR_INVALID_ARGUMENT, kSetRecording);
-    if (mmdx_status r = set_to_device(set, device)) return r;
-    graph_note_handle(model, &set->pin);
-    InstanceList list;
-    uint32_t cells;
-    if (mmdx_status r = set_list_in(set, sel, a->n_instances, live_host, st, &list, &cells)) return r;
-    if (cells == 0) return MMDX_OK;                                 // an empty list writes nothing
-    BoneTrackParams p = set_bone_params(set, cells);
-    p.out = out_poses;
-    HIP_TRY(launch_bone_track_blend_set_select(p, blend_operands_device(set, a), list, st));
-    if (!(sel->flags & MMDX_SELECT_ON_DEVICE)) HIP_TRY(wait_stream(st));   // the borrowed list is consumed and the results are there
-    return MMDX_OK;
-}
-
-// mmdx_motion_set_blend_morphs_time_select
-static mmdx_status set_blend_morphs_select(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *a,
-                                           const mmdx_instance_select *sel, float *out_weights) {
-    uint32_t live_host = 0;
-    if (mmdx_status r = blend_select_check(set, false, a, sel, out_weights, live_host)) return r;
-    int device;
-    hipStream_t st;
-    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
-    if (graph_recording() && set->device != device) return fail(MMDX_ERR_INVALID_ARGUMENT, kSetRecording);
-    if (mmdx_status r = set_to_device(set, device)) return r;
-    graph_note_handle(model, &set->pin);
-    InstanceList list;
-    uint32_t cells;
-    if (mmdx_status r = set_list_in(set, sel, a->n_instances, live_host, st, &list, &cells)) return r;
-    if (cells == 0) return MMDX_OK;
-    MorphTrackParams t;
-    t.key_off = static_cast<const uint32_t *>(set->m_key_off.ptr);
-    t.key_frames = static_cast<const uint32_t *>(set->m_frames.ptr);
-    t.key_weights = static_cast<const float *>(set->m_weights.ptr);
-    t.nm = set->host.nm; t.ni = cells;
-    t.frames = nullptr; t.times = nullptr;
-    t.out = out_weights;
-    HIP_TRY(launch_morph_track_blend_set_select(t, blend_operands_device(set, a), list, st));
-    if (!(sel->flags & MMDX_SELECT_ON_DEVICE)) HIP_TRY(wait_stream(st));
-    return MMDX_OK;
-}
-
-// mmdx_skeleton_solve_motion_set_blend_time_select
-static mmdx_status skeleton_solve_motion_set_blend_select(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model,
-                                                          const mmdx_motion_blend_args *a, const mmdx_instance_select *sel,
-                                                          float *out_palettes) {
-    if (!s) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
-    uint32_t live_host = 0;
-    if (mmdx_status r = blend_select_check(set, true, a, sel, out_palettes, live_host)) return r;
-    if (set->host.bones.nb != s->plan.nb)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "the motion set was bound to " + std::to_string(set->host.bones.nb) +
-                                               " bones, the skeleton has " + std::to_string(s->plan.nb));
-    int device;
-    hipStream_t st;
-    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
-    const SkeletonPlan &pl = s->plan;
-    const uint32_t ni = a->n_instances;
-    if (pl.serial || size_t(pl.nb) * 32 > kMotionFkMaxLds) {
-        // append bones / IK (the ordered solver) or a skeleton too large for the LDS pose table: the blend select into the set's pose
-        // scratch -- [NI] rows, addressed by id -- then the select solve with the same list
-        const size_t pose_bytes = size_t(ni) * pl.nb * MMDX_POSE_FLOATS * sizeof(float);
-        if (graph_recording() && (set->poses.bytes < pose_bytes || set->device != device))
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "run the call once before recording: it sizes the motion set's pose buffer");
-        if (mmdx_status r = set_to_device(set, device)) return r;
-        HIP_TRY(set->poses.ensure(pose_bytes));
-        if (mmdx_status r = set_blend_bones_select(set, model, a, sel, static_cast<float *>(set->poses.ptr))) return r;
-        return mmdx_skeleton_solve_select(s, model, ni, static_cast<const float *>(set->poses.ptr), nullptr,
-                                          MMDX_POSES_ON_DEVICE | MMDX_OUT_ON_DEVICE, sel, out_palettes);
-    }
-    if (graph_recording() && (set->device != device || s->device != device))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory and the motion "
-                                               "set and the skeleton must have run on this device before");
-    if (mmdx_status r = set_to_device(set, device)) return r;
-    if (mmdx_status r = skeleton_to_device(s, device)) return r;
-    graph_note_handle(model, &set->pin);
-    graph_note_handle(model, &s->pin);
-    InstanceList list;
-    uint32_t cells;
-    if (mmdx_status r = set_list_in(set, sel, ni, live_host, st, &list, &cells)) return r;
-    if (cells == 0) return MMDX_OK;
-    const BoneTrackParams tp = set_bone_params(set, cells);
-    SkeletonParams fp;
-    fp.morph = nullptr;
-    fp.poses = nullptr;
-    fp.out = out_palettes;
-    fp.local_offset = static_cast<const float *>(s->local_offset.ptr);
-    fp.neg_rest = static_cast<const float *>(s->neg_rest.ptr);
-    fp.chain_off = static_cast<const uint32_t *>(s->chain_off.ptr);
-    fp.chain = static_cast<const uint32_t *>(s->chain.ptr);
-    fp.nb = pl.nb; fp.ni = cells;
-    HIP_TRY(launch_motion_fk_blend_set_select(tp, fp, blend_operands_device(set, a), list, st));
-    s->last_solve = SolveShape{}; s->last_solve.solver = 2;
-    if (!(sel->flags & MMDX_SELECT_ON_DEVICE)) HIP_TRY(wait_stream(st));
-    return MMDX_OK;
-}
-
-extern "C" {
-
+// ---- the cross-fade for the listed instances: device operands and output; a borrowed host list is waited for at the end -----------
 mmdx_status mmdx_motion_set_blend_bones_time_select(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args,
                                                     const mmdx_instance_select *select, float *out_poses) {
-    return set_blend_bones_select(set, model, args, select, out_poses);
+    uint32_t live_host = 0;
+    if (mmdx_status r = blend_select_check(set, true, args, select, out_poses, live_host)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    if (mmdx_status r = refuse_recording(0, 0, device, {set->device}, kSetRecording)) return r;
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    InstanceList list;
+    uint32_t cells;
+    if (mmdx_status r = list_in(set->sel_in, set->sel_host, select, args->n_instances, live_host, st, &list, &cells)) return r;
+    if (cells == 0) return MMDX_OK;                                 // an empty list writes nothing
+    BoneTrackParams p = set->t.params(set->host.bones.nb, cells);
+    p.out = out_poses;
+    HIP_TRY(launch_bone_track_blend_set_select(p, blend_operands_device(set, args), list, st));
+    return finish(args->flags, !(select->flags & MMDX_SELECT_ON_DEVICE), st, OutRoute{});
 }
 
 mmdx_status mmdx_motion_set_blend_morphs_time_select(mmdx_motion_set_t set, mmdx_model_t model, const mmdx_motion_blend_args *args,
                                                      const mmdx_instance_select *select, float *out_weights) {
-    return set_blend_morphs_select(set, model, args, select, out_weights);
+    uint32_t live_host = 0;
+    if (mmdx_status r = blend_select_check(set, false, args, select, out_weights, live_host)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    if (mmdx_status r = refuse_recording(0, 0, device, {set->device}, kSetRecording)) return r;
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    InstanceList list;
+    uint32_t cells;
+    if (mmdx_status r = list_in(set->sel_in, set->sel_host, select, args->n_instances, live_host, st, &list, &cells)) return r;
+    if (cells == 0) return MMDX_OK;
+    MorphTrackParams t = set_morph_params(set, cells);
+    t.out = out_weights;
+    HIP_TRY(launch_morph_track_blend_set_select(t, blend_operands_device(set, args), list, st));
+    return finish(args->flags, !(select->flags & MMDX_SELECT_ON_DEVICE), st, OutRoute{});
 }
 
 mmdx_status mmdx_skeleton_solve_motion_set_blend_time_select(mmdx_skeleton_t s, mmdx_motion_set_t set, mmdx_model_t model,
                                                              const mmdx_motion_blend_args *args, const mmdx_instance_select *select,
                                                              float *out_palettes) {
-    return skeleton_solve_motion_set_blend_select(s, set, model, args, select, out_palettes);
+    if (!s) return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    uint32_t live_host = 0;
+    if (mmdx_status r = blend_select_check(set, true, args, select, out_palettes, live_host)) return r;
+    if (mmdx_status r = skeleton_matches_set(s, set)) return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    const SkeletonPlan &pl = s->plan;
+    const uint32_t ni = args->n_instances;
+    if (two_launches(pl)) {
+        // the blend select into the set's pose scratch -- [NI] rows, addressed by id -- then the select solve with the same list
+        float *poses;
+        if (mmdx_status r = set_pose_scratch(set, device, pose_bytes(ni, pl.nb), &poses)) return r;
+        if (mmdx_status r = mmdx_motion_set_blend_bones_time_select(set, model, args, select, poses)) return r;
+        return mmdx_skeleton_solve_select(s, model, ni, poses, nullptr, MMDX_POSES_ON_DEVICE | MMDX_OUT_ON_DEVICE, select, out_palettes);
+    }
+    if (mmdx_status r = refuse_recording(0, 0, device, {set->device, s->device}, kSetSkeletonRecording)) return r;
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    if (mmdx_status r = skeleton_to_device(s, device)) return r;
+    graph_note_handle(model, &set->pin);
+    graph_note_handle(model, &s->pin);
+    InstanceList list;
+    uint32_t cells;
+    if (mmdx_status r = list_in(set->sel_in, set->sel_host, select, ni, live_host, st, &list, &cells)) return r;
+    if (cells == 0) return MMDX_OK;
+    const BoneTrackParams tp = set->t.params(pl.nb, cells);
+    HIP_TRY(launch_motion_fk_blend_set_select(tp, fk_params(s, cells, nullptr, nullptr, out_palettes), blend_operands_device(set, args), list, st));
+    note_fk_solve(s);
+    return finish(args->flags, !(select->flags & MMDX_SELECT_ON_DEVICE), st, OutRoute{});
 }
 
 }  // extern "C"
