@@ -14,7 +14,7 @@
 #include "anim_kernels.hpp"
 #include "error.hpp"
 #include "graph_pin.hpp"
-#include "rig_kernels.hpp"
+#include "host_runtime.hpp"
 
 using namespace mmdx;
 
@@ -22,12 +22,6 @@ static_assert(kAnimClipNone == MMDX_CLIP_NONE && kAnimNoRequest == MMDX_ANIM_NO_
 static_assert(kAnimLoop == MMDX_ANIM_LOOP && kAnimHold == MMDX_ANIM_HOLD && kAnimThen == MMDX_ANIM_THEN, "anim_math.hpp restates mmdx.h");
 
 namespace {
-
-#define HIP_TRY(expr)                                            \
-    do {                                                         \
-        hipError_t e_ = (expr);                                  \
-        if (e_ != hipSuccess) return hip_status(e_, #expr);      \
-    } while (0)
 
 constexpr size_t kStateBytes = 3 * 8 + 8 * 4;     // per instance: three f64 arrays, eight 4-byte arrays
 constexpr size_t kTableBytes = 8 + 3 * 4;         // per clip: length, mode, next, fade
@@ -89,7 +83,7 @@ mmdx_status state_to_device(mmdx_animator_t a, int device) {
     HIP_TRY(hipMalloc(&d, req_at + ni * kRequestBytes));
     if (hipError_t e = hipMemcpy(d, h, bytes, hipMemcpyHostToDevice)) {
         (void)hipFree(d);
-        return hip_status(e, "hipMemcpy of the animator's initial state");
+        return hip_fail(e, "hipMemcpy of the animator's initial state");
     }
     char *b = static_cast<char *>(d);
     AnimArrays &s = a->arrays;

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -37,17 +38,6 @@ hipError_t g_prepare_status[16];
 // Streams of this thread that are recording a graph (hipStreamCaptureModeThreadLocal: begin and end happen on one thread,
 // mmdx_graph_end enforces it): while > 0 nothing on this thread may allocate, copy from the host or wait.
 thread_local int tl_recording_depth = 0;
-
-
-template <typename T>
-hipError_t upload(DevBuf &b, const std::vector<T> &v, uint64_t &total) {
-    const size_t n = std::max<size_t>(v.size() * sizeof(T), 16);  // never a null stream pointer
-    hipError_t e = b.ensure(n);
-    if (e != hipSuccess) return e;
-    total += n;
-    if (!v.empty()) return hipMemcpy(b.ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    return hipSuccess;
-}
 
 }  // namespace
 
@@ -148,36 +138,38 @@ hipError_t copy_in(mmdx_model_s *m, void *dst, const void *src, PtrKind kind, si
 
 
 
+// every static stream and the two buffers of the shared morph pass; their sizes are mmdx_model_info.device_bytes
 mmdx_status upload_model(mmdx_model_s *m) {
     Plan &p = m->plan;
-    uint64_t &t = m->device_bytes;
-    HIP_TRY(upload(m->tiles, p.tiles, t));
-    if (p.f16) HIP_TRY(upload(m->spos, p.spos16, t)); else HIP_TRY(upload(m->spos, p.spos, t));
-    HIP_TRY(upload(m->snrm, p.snrm, t));
-    HIP_TRY(upload(m->suv, p.suv, t));
-    HIP_TRY(upload(m->perm, p.perm, t));
-    HIP_TRY(upload(m->skin1, p.skin1, t));
-    HIP_TRY(upload(m->skin2_ids, p.skin2_ids, t));
-    HIP_TRY(upload(m->skin2_w, p.skin2_w, t));
-    HIP_TRY(upload(m->skin4_ids, p.skin4_ids, t));
-    HIP_TRY(upload(m->skin4_w, p.skin4_w, t));
-    HIP_TRY(upload(m->bone_list, p.bone_list, t));
-    HIP_TRY(upload(m->ell, p.ell, t));
-    if (p.f16) HIP_TRY(upload(m->entries, p.entries16, t)); else HIP_TRY(upload(m->entries, p.entries, t));
-    HIP_TRY(upload(m->slot_top, p.slot_top, t));
-    HIP_TRY(upload(m->chain_off, p.chain_off, t));
-    HIP_TRY(upload(m->chain_rate, p.chain_rate, t));
-    HIP_TRY(upload(m->bone_boxes, bone_box_device_table(p), t));
+    HIP_TRY(m->tiles.upload(p.tiles));
+    if (p.f16) HIP_TRY(m->spos.upload(p.spos16)); else HIP_TRY(m->spos.upload(p.spos));
+    HIP_TRY(m->snrm.upload(p.snrm));
+    HIP_TRY(m->suv.upload(p.suv));
+    HIP_TRY(m->perm.upload(p.perm));
+    HIP_TRY(m->skin1.upload(p.skin1));
+    HIP_TRY(m->skin2_ids.upload(p.skin2_ids));
+    HIP_TRY(m->skin2_w.upload(p.skin2_w));
+    HIP_TRY(m->skin4_ids.upload(p.skin4_ids));
+    HIP_TRY(m->skin4_w.upload(p.skin4_w));
+    HIP_TRY(m->bone_list.upload(p.bone_list));
+    HIP_TRY(m->ell.upload(p.ell));
+    if (p.f16) HIP_TRY(m->entries.upload(p.entries16)); else HIP_TRY(m->entries.upload(p.entries));
+    HIP_TRY(m->slot_top.upload(p.slot_top));
+    HIP_TRY(m->chain_off.upload(p.chain_off));
+    HIP_TRY(m->chain_rate.upload(p.chain_rate));
+    HIP_TRY(m->bone_boxes.upload(bone_box_device_table(p)));
     if (p.ns) {
         HIP_TRY(m->morphed.ensure(size_t(p.nv) * 12));
-        t += size_t(p.nv) * 12;
         // which rates `morphed` was last computed from (kernels.hpp, RatesSeen): nothing yet
         const size_t seen_bytes = (size_t(kSeenRates) + p.nm) * 4;
         HIP_TRY(m->seen.ensure(seen_bytes));
         HIP_TRY(hipMemset(m->seen.ptr, 0, seen_bytes));
         HIP_TRY(hipStreamSynchronize(nullptr));
-        t += seen_bytes;
     }
+    for (const DevBuf *b : {&m->tiles, &m->spos, &m->snrm, &m->suv, &m->perm, &m->skin1, &m->skin2_ids, &m->skin2_w, &m->skin4_ids,
+                            &m->skin4_w, &m->bone_list, &m->ell, &m->entries, &m->slot_top, &m->chain_off, &m->chain_rate,
+                            &m->bone_boxes, &m->morphed, &m->seen})
+        m->device_bytes += b->bytes;
     return MMDX_OK;
 }
 
@@ -215,7 +207,7 @@ size_t out_bytes_b(uint32_t layout, uint64_t nvi) {
 mmdx_status mmdx::hip_fail(hipError_t e, const char *what) {
     // leave no sticky error behind for the next call
     (void)hipGetLastError();
-    // the two refusals of DevBuf::ensure / rig_api's Buf::ensure (no HIP call failed)
+    // the two refusals of DevBuf::ensure (no HIP call failed)
     if (e == hipErrorIllegalState)
         return fail(MMDX_ERR_INVALID_ARGUMENT, std::string(what) + ": a scratch buffer of this handle would have to grow, but a recorded "
                     "graph (mmdx_graph_*) holds its address -- destroy the graph first, or size the buffers with an un-recorded call of "
@@ -245,15 +237,24 @@ LaunchOverrides &mmdx::launch_overrides() {
     return o;
 }
 
+// The device side of a morph motion (vmd.cpp keeps the pointer and knows nothing of HIP): its tables, and the scratch of callers
+// with host operands -- `frames_in` grows to 8 bytes per instance, room for the double times of mmdx_morph_motion_eval_time.
+struct mmdx::MorphMotionDevice {
+    DevBuf key_off, frames, weights, frames_in, out;
+    int device = -1;
+    GraphPin pin;                 // recorded graphs that hold these addresses
+    std::array<DevBuf *, 5> all() { return {&key_off, &frames, &weights, &frames_in, &out}; }
+    MorphMotionDevice() {
+        for (DevBuf *b : all()) b->pin = &pin;
+        out.floor = 16;
+    }
+};
+
 void mmdx::morph_motion_release_device(MorphMotionDevice &d) {
     graph_drop_handle(&d.pin);               // graphs that hold these addresses can no longer be replayed
     if (d.device >= 0) (void)hipSetDevice(d.device);
-    for (void **p : {&d.key_off, &d.frames, &d.weights, &d.frames_in, &d.out}) {
-        device_free_or_defer(*p);
-        *p = nullptr;
-    }
-    d.frames_in_bytes = d.out_bytes = 0;
-    d.device = -1;
+    for (DevBuf *b : d.all()) b->release();
+    delete &d;
 }
 
 // A stream that is recording takes calls from the recording thread only: the "nothing may allocate / copy from the host / wait"
@@ -262,6 +263,21 @@ static mmdx_status recording_thread_check(mmdx_model_t model) {
     if (model && model->capturing && model->capture_thread != std::this_thread::get_id())
         return fail(MMDX_ERR_INVALID_ARGUMENT, "this model's stream is recording a graph on another thread: recorded calls must come "
                                                "from the thread that called mmdx_graph_begin");
+    return MMDX_OK;
+}
+
+static mmdx_status refuse_host_only(mmdx_model_t m) {
+    if (m->device < 0)
+        return fail(MMDX_ERR_NO_DEVICE, "model was created with MMDX_CREATE_HOST_ONLY: nothing to run on "
+                                        "(this engine has no CPU fallback)");
+    return MMDX_OK;
+}
+
+mmdx_status mmdx::model_call_begin(mmdx_model_t m, uint32_t flags, uint32_t need, const char *text) {
+    if (mmdx_status st = refuse_host_only(m)) return st;
+    if (mmdx_status st = recording_thread_check(m)) return st;
+    if (mmdx_status st = refuse_recording(flags, need, m->device, {}, text)) return st;
+    HIP_TRY(hipSetDevice(m->device));
     return MMDX_OK;
 }
 
@@ -276,7 +292,6 @@ mmdx_status mmdx::resolve_stream(mmdx_model_t model, int *device, hipStream_t *s
     HIP_TRY(hipSetDevice(*device));
     return MMDX_OK;
 }
-mmdx_status mmdx::hip_status(hipError_t e, const char *what) { return hip_fail(e, what); }
 bool mmdx::graph_recording() { return tl_recording_depth > 0; }
 // hipFree is one of the calls the runtime refuses on a thread whose stream is recording (it would also invalidate the recording):
 // a handle destroyed in that window parks its blocks here, mmdx_graph_end frees them.
@@ -510,15 +525,11 @@ struct OutputRoute {
     size_t bytes_a = 0, bytes_b = 0, off_b = 0; // the two arrays; the second one's offset in the bounce buffer
 };
 
-// the instance list of a select call: validated in full before anything is enqueued
+// the instance list of a select call: validated in full before anything is enqueued.  The shared cuts (host_runtime.hpp), with this
+// call's own checks between them.
 static mmdx_status validate_select(mmdx_model_t m, const mmdx_deform_args *a, const mmdx_instance_select *sel, uint32_t &live_host) {
     const Plan &p = m->plan;
-    if (sel->struct_size != sizeof(mmdx_instance_select))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.struct_size mismatch");
-    if (sel->flags & ~uint32_t(MMDX_SELECT_ON_DEVICE))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown bits in mmdx_instance_select.flags");
-    if (sel->reserved0 != 0) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.reserved0 must be 0");
-    if (sel->n_ids && !sel->ids) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids is NULL");
+    if (mmdx_status st = list_header_check(sel)) return st;
     // the GPU-resident crowd form only: a staging or bounce copy of the outputs moves whole arrays and cannot leave the
     // instances outside a list untouched
     const uint32_t need = MMDX_PALETTE_ON_DEVICE | MMDX_OUT_ON_DEVICE |
@@ -526,25 +537,13 @@ static mmdx_status validate_select(mmdx_model_t m, const mmdx_deform_args *a, co
     if ((a->flags & need) != need)
         return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_deform_batched_select takes device operands only: pass MMDX_PALETTE_ON_DEVICE | "
                                                "MMDX_OUT_ON_DEVICE, and MMDX_WEIGHTS_ON_DEVICE with morph_weights");
-    if (sel->flags & MMDX_SELECT_ON_DEVICE) {
-        if ((reinterpret_cast<uintptr_t>(sel->ids) | reinterpret_cast<uintptr_t>(sel->count)) & 3)
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "device ids / count of mmdx_instance_select must be 4-byte aligned");
-        return MMDX_OK;
-    }
-    if (m->capturing)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded the instance list must be in device memory "
-                                               "(MMDX_SELECT_ON_DEVICE)");
+    if (mmdx_status st = list_placement_check(sel, m->capturing)) return st;
     void *unused = nullptr;
-    if ((sel->n_ids && classify_pointer(sel->ids, &unused) == PtrKind::Device) ||
-        (sel->count && classify_pointer(sel->count, &unused) == PtrKind::Device))
+    if (!(sel->flags & MMDX_SELECT_ON_DEVICE) && ((sel->n_ids && classify_pointer(sel->ids, &unused) == PtrKind::Device) ||
+                                                  (sel->count && classify_pointer(sel->count, &unused) == PtrKind::Device)))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "ids / count of mmdx_instance_select point to device memory: pass "
                                                "MMDX_SELECT_ON_DEVICE");
-    live_host = sel->count ? std::min(*sel->count, sel->n_ids) : sel->n_ids;
-    for (uint32_t j = 0; j < live_host; ++j)
-        if (sel->ids[j] >= a->n_instances)
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids[" + std::to_string(j) + "] = " +
-                                                   std::to_string(sel->ids[j]) + " is not below n_instances");
-    return MMDX_OK;
+    return host_list_check(sel, a->n_instances, live_host);
 }
 
 static mmdx_status validate_call(mmdx_model_t m, const mmdx_deform_args *a, const float *out_bounds, const mmdx_instance_select *sel,
@@ -552,9 +551,7 @@ static mmdx_status validate_call(mmdx_model_t m, const mmdx_deform_args *a, cons
     if (!m || !a) return fail(MMDX_ERR_INVALID_ARGUMENT, "model / args is NULL");
     if (a->struct_size != sizeof(mmdx_deform_args))
         return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_deform_args.struct_size mismatch");
-    if (m->device < 0)
-        return fail(MMDX_ERR_NO_DEVICE, "model was created with MMDX_CREATE_HOST_ONLY: nothing to run on "
-                                        "(this engine has no CPU fallback)");
+    if (mmdx_status st = refuse_host_only(m)) return st;
     const Plan &p = m->plan;
     const uint32_t ni = a->n_instances, layout = a->out_layout;
     if (ni == 0) return fail(MMDX_ERR_INVALID_ARGUMENT, "n_instances must be >= 1");
@@ -600,13 +597,13 @@ static mmdx_status validate_call(mmdx_model_t m, const mmdx_deform_args *a, cons
         return fail(MMDX_ERR_INVALID_ARGUMENT, "device out_bounds must be 4-byte aligned");
     if (out_bounds && !(a->flags & MMDX_OUT_ON_DEVICE) && classify_pointer(out_bounds, &map_unused) == PtrKind::Device)
         return fail(MMDX_ERR_INVALID_ARGUMENT, "out_bounds points to device memory: pass MMDX_OUT_ON_DEVICE");
-    if (m->capturing) {
-        if (mmdx_status rst = recording_thread_check(m)) return rst;
-        const uint32_t need = MMDX_PALETTE_ON_DEVICE | MMDX_OUT_ON_DEVICE | (p.ns ? uint32_t(MMDX_WEIGHTS_ON_DEVICE) : 0u);
-        if ((a->flags & need) != need)
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory");
-        if (m->profile) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_profile_enable and graph recording exclude each other");
-    }
+    // (the host-only refusal answered further up, where this call has always had it.  Only a recording of THIS model's stream
+    // refuses host operands here: a thread that records another model's graph may still deform this one from the host.)
+    const uint32_t need = MMDX_PALETTE_ON_DEVICE | MMDX_OUT_ON_DEVICE | (p.ns ? uint32_t(MMDX_WEIGHTS_ON_DEVICE) : 0u);
+    if (mmdx_status st = model_call_begin(m, a->flags, m->capturing ? need : 0u,
+                                          "while a graph is being recorded every operand must be in device memory"))
+        return st;
+    if (m->capturing && m->profile) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_profile_enable and graph recording exclude each other");
     return MMDX_OK;
 }
 
@@ -658,15 +655,8 @@ static mmdx_status stage_select(mmdx_model_t m, const mmdx_instance_select *sel,
     dp.sel_interleave = launch_overrides().select_interleave != 0 ? 1u : 0u;
     if (sel->flags & MMDX_SELECT_ON_DEVICE) {
         dp.sel_ids = sel->ids; dp.sel_count = sel->count;
-    } else if (sel->n_ids) {
-        HIP_TRY(m->sel.ensure((size_t(sel->n_ids) + 1) * 4));
-        m->sel_host.resize(size_t(sel->n_ids) + 1);
-        m->sel_host[0] = live_host;
-        std::memcpy(m->sel_host.data() + 1, sel->ids, size_t(sel->n_ids) * 4);
-        // (pageable source: the copy has left the host vector when the call returns)
-        HIP_TRY(hipMemcpyAsync(m->sel.ptr, m->sel_host.data(), m->sel_host.size() * 4, hipMemcpyHostToDevice, m->stream));
-        dp.sel_count = static_cast<const uint32_t *>(m->sel.ptr);
-        dp.sel_ids = dp.sel_count + 1;
+    } else if (sel->n_ids) {                    // all n_ids ids travel: the kernel is sized from the capacity
+        return stage_list(m->sel, m->sel_host, sel->ids, sel->n_ids, live_host, m->stream, &dp.sel_count, &dp.sel_ids);
     }
     return MMDX_OK;
 }
@@ -962,8 +952,7 @@ static void record_launch_shape(mmdx_model_t m, const DeformCall &c, const Launc
 static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, float *out_bounds,
                                   const mmdx_instance_select *sel = nullptr) {
     CallPointers cp;
-    if (mmdx_status s = validate_call(m, a, out_bounds, sel, cp)) return s;
-    HIP_TRY(hipSetDevice(m->device));
+    if (mmdx_status s = validate_call(m, a, out_bounds, sel, cp)) return s;       // ends in model_call_begin: the device is selected
     hipEvent_t *pev;
     if (mmdx_status s = profile_events(m, pev)) return s;
     DeformParams dp = static_params(*m);
@@ -1038,79 +1027,52 @@ mmdx_status mmdx_sync(mmdx_model_t m) {
 
 
 // ---- VMD morph motion: device-side evaluation ----------------------------------------------------
-// mmdx_morph_motion_eval / _eval_time: frames (uint32_t) or, with `time`, seconds (double)
+// the tables of a motion -> the device it is about to run on (once per device)
+static mmdx_status morph_to_device(MorphMotionDevice &d, const MorphMotionHost &h, int device) {
+    if (d.device == device) return MMDX_OK;
+    if (graph_pinned(&d.pin)) return fail(MMDX_ERR_INVALID_ARGUMENT, "this motion's device tables are held by a recorded graph: destroy the graph before moving it to another device");
+    for (DevBuf *b : d.all()) b->release();
+    HIP_TRY(d.key_off.upload(h.key_off, size_t(h.nm) + 1));
+    HIP_TRY(d.frames.upload(h.frames, h.nkeys));
+    HIP_TRY(d.weights.upload(h.weights, h.nkeys));
+    d.device = device;
+    return MMDX_OK;
+}
+
+// mmdx_morph_motion_eval / _eval_time: frames (uint32_t) or, with `time`, seconds (double).  The sequence of bone_motion_eval
+// (rig_api.cpp), with this call's own two refusals of a recording, each in its own words and place: host operands ahead of
+// resolve_stream, a motion that never ran on the device behind it.
 static mmdx_status morph_motion_eval(mmdx_morph_motion_t mm, mmdx_model_t model, uint32_t n_instances, const void *clock, bool time,
                                      uint32_t flags, float *out_weights) {
     if (!mm || !clock || !out_weights || !n_instances)
         return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
-    if (tl_recording_depth > 0 && (flags & (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) != (MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded every operand must be in device memory");
-    if (mmdx_status rst = recording_thread_check(model)) return rst;
+    if (mmdx_status r = refuse_recording(flags, MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE, 0, {},
+                                         "while a graph is being recorded every operand must be in device memory"))
+        return r;
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    MorphMotionDevice *&dev = morph_motion_device(mm);
+    if (!dev && !(dev = new (std::nothrow) MorphMotionDevice)) return fail(MMDX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    MorphMotionDevice &d = *dev;
+    if (mmdx_status r = refuse_recording(0, 0, device, {d.device},
+                                         "first use of this motion on the device: run the sequence once before recording it"))
+        return r;
     const MorphMotionHost h = morph_motion_host(mm);
-    MorphMotionDevice &d = morph_motion_device(mm);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(MMDX_ERR_NO_DEVICE, "no HIP device available (morph tracks are evaluated on the GPU)");
-    const int device = model && model->device >= 0 ? model->device : current_device();
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t st = model && model->device >= 0 ? model->stream : nullptr;
-    if (d.device != device) {
-        if (tl_recording_depth > 0) return fail(MMDX_ERR_INVALID_ARGUMENT, "first use of this motion on the device: run the sequence once before recording it");
-        if (graph_pinned(&d.pin)) return fail(MMDX_ERR_INVALID_ARGUMENT, "this motion's device tables are held by a recorded graph: destroy the graph before moving it to another device");
-        morph_motion_release_device(d);
-        HIP_TRY(hipMalloc(&d.key_off, (size_t(h.nm) + 1) * 4));
-        HIP_TRY(hipMalloc(&d.frames, std::max<size_t>(size_t(h.nkeys) * 4, 16)));
-        HIP_TRY(hipMalloc(&d.weights, std::max<size_t>(size_t(h.nkeys) * 4, 16)));
-        HIP_TRY(hipMemcpy(d.key_off, h.key_off, (size_t(h.nm) + 1) * 4, hipMemcpyHostToDevice));
-        if (h.nkeys) {
-            HIP_TRY(hipMemcpy(d.frames, h.frames, size_t(h.nkeys) * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d.weights, h.weights, size_t(h.nkeys) * 4, hipMemcpyHostToDevice));
-        }
-        d.device = device;
-    }
+    if (mmdx_status r = morph_to_device(d, h, device)) return r;
     graph_note_handle(model, &d.pin);
     MorphTrackParams t;
-    t.key_off = static_cast<const uint32_t *>(d.key_off);
-    t.key_frames = static_cast<const uint32_t *>(d.frames);
-    t.key_weights = static_cast<const float *>(d.weights);
+    t.key_off = static_cast<const uint32_t *>(d.key_off.ptr);
+    t.key_frames = static_cast<const uint32_t *>(d.frames.ptr);
+    t.key_weights = static_cast<const float *>(d.weights.ptr);
     t.nm = h.nm; t.ni = n_instances;
     t.frames = nullptr; t.times = nullptr;
-    const void *dev_clock = clock;
-    if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
-        const size_t clock_bytes = size_t(n_instances) * (time ? 8 : 4);
-        if (d.frames_in_bytes < clock_bytes) {      // grows to 8 bytes per instance: room for frames or times
-            if (graph_pinned(&d.pin)) return hip_fail(hipErrorIllegalState, "morph motion frame scratch");
-            if (d.frames_in) (void)hipFree(d.frames_in);
-            d.frames_in = nullptr; d.frames_in_bytes = 0;
-            HIP_TRY(hipMalloc(&d.frames_in, size_t(n_instances) * 8));
-            d.frames_in_bytes = size_t(n_instances) * 8;
-        }
-        HIP_TRY(hipMemcpyAsync(d.frames_in, clock, clock_bytes, hipMemcpyHostToDevice, st));
-        dev_clock = d.frames_in;
-    }
-    if (time) t.times = static_cast<const double *>(dev_clock);
-    else t.frames = static_cast<const uint32_t *>(dev_clock);
-    const size_t out_bytes = size_t(n_instances) * h.nm * 4;
-    if (flags & MMDX_OUT_ON_DEVICE) {
-        t.out = out_weights;
-    } else {
-        if (d.out_bytes < out_bytes) {
-            if (graph_pinned(&d.pin)) return hip_fail(hipErrorIllegalState, "morph motion output scratch");
-            if (d.out) (void)hipFree(d.out);
-            d.out = nullptr; d.out_bytes = 0;
-            HIP_TRY(hipMalloc(&d.out, std::max<size_t>(out_bytes, 16)));
-            d.out_bytes = std::max<size_t>(out_bytes, 16);
-        }
-        t.out = static_cast<float *>(d.out);
-    }
+    if (mmdx_status r = clock_in(d.frames_in, "morph motion frame scratch", clock, time, n_instances, flags, st, &t.frames, &t.times)) return r;
+    OutRoute o;
+    if (mmdx_status r = route_out(flags, out_weights, size_t(n_instances) * h.nm * 4, d.out, &o, "morph motion output scratch")) return r;
+    t.out = o.dev;
     HIP_TRY(launch_morph_track_eval(t, st));
-    if (!(flags & MMDX_OUT_ON_DEVICE)) {
-        if (out_bytes) HIP_TRY(hipMemcpyAsync(out_weights, t.out, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
-        HIP_TRY(wait_stream(st));   // borrowed host frames / times must be consumed before returning
-    }
-    return MMDX_OK;
+    return finish(flags, !(flags & MMDX_FRAMES_ON_DEVICE), st, o);
 }
 
 mmdx_status mmdx_morph_motion_eval(mmdx_morph_motion_t mm, mmdx_model_t model, uint32_t n_instances,

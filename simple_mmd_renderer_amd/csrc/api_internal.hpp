@@ -1,5 +1,6 @@
-// api_internal.hpp -- what api.cpp (the drop-in boundary, include/mmdx.h) and bench_api.cpp (the measurement / A-B entry points,
-// include/mmdx_bench.h) share: the model handle, its device buffers, the error mapping and the launch-shape overrides.
+// api_internal.hpp -- what api.cpp (the drop-in boundary, include/mmdx.h), bench_api.cpp (the measurement / A-B entry points,
+// include/mmdx_bench.h) and the other files of calls on a model share: the model handle and the launch-shape overrides.  The host
+// plumbing (error mapping, device buffer, call steps) is host_runtime.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,41 +15,12 @@
 #include "../../include/mmdx_bench.h"
 #include "error.hpp"
 #include "graph_pin.hpp"
+#include "host_runtime.hpp"
 #include "kernels.hpp"
 #include "launch_shape.hpp"
 #include "plan.hpp"
-#include "rig_kernels.hpp"
 
 namespace mmdx {
-
-// HIP error -> status + message (also clears the runtime's sticky error)
-mmdx_status hip_fail(hipError_t e, const char *what);
-
-#define HIP_TRY(expr)                                          \
-    do {                                                       \
-        hipError_t e_ = (expr);                                \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr);      \
-    } while (0)
-
-struct DevBuf {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    const GraphPin *pin = nullptr;           // per-call scratch of a handle: may not move while a recorded graph holds it
-    hipError_t ensure(size_t need) {
-        if (need <= bytes) return hipSuccess;
-        if (graph_recording()) return hipErrorStreamCaptureUnsupported;   // run the sequence once un-captured first
-        if (graph_pinned(pin)) return hipErrorIllegalState;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr; bytes = 0;
-        hipError_t e = hipMalloc(&ptr, need);
-        if (e == hipSuccess) bytes = need;
-        return e;
-    }
-    void release() {
-        device_free_or_defer(ptr);
-        ptr = nullptr; bytes = 0;
-    }
-};
 
 // The launch-shape overrides (launch_shape.hpp), as the environment sets them
 LaunchOverrides read_launch_overrides();

@@ -3,7 +3,6 @@
 #include <cmath>
 #include <cstring>
 #include <string>
-#include <thread>
 
 #include "api_internal.hpp"
 #include "cull_kernels.hpp"
@@ -55,12 +54,7 @@ mmdx_status mmdx_cull_bounds(mmdx_model_t m, const mmdx_cull_args *a) {
     if (dev_bits & 3) return fail(MMDX_ERR_INVALID_ARGUMENT, "device pointers of mmdx_cull_args must be 4-byte aligned");
     if (!view_dev)
         if (mmdx_status s = validate_view(*a->view)) return s;
-    if (m->device < 0)
-        return fail(MMDX_ERR_NO_DEVICE, "model was created with MMDX_CREATE_HOST_ONLY: nothing to run on (this engine has no CPU fallback)");
-    if (m->capturing && m->capture_thread != std::this_thread::get_id())
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "this model's stream is recording a graph on another thread: recorded calls must come "
-                                               "from the thread that called mmdx_graph_begin");
-    HIP_TRY(hipSetDevice(m->device));
+    if (mmdx_status r = model_call_begin(m, 0, 0, nullptr)) return r;      // (a host view is read here, at the call: recordable)
     const CullShape shape = plan_cull_launch(ni, cull_overrides());
     if (shape.scratch_bytes) HIP_TRY(m->cull.ensure(shape.scratch_bytes));
     const CullLaunch call{a->bounds, view_dev ? a->view : nullptr, view_dev ? nullptr : a->view, a->out_ids, a->out_counts, a->out_levels,

@@ -4,7 +4,6 @@
 #include <cmath>
 #include <cstring>
 #include <string>
-#include <thread>
 
 #include "api_internal.hpp"
 #include "pbounds_kernels.hpp"
@@ -71,32 +70,19 @@ extern "C" mmdx_status mmdx_palette_bounds(mmdx_model_t m, const mmdx_palette_bo
         return fail(MMDX_ERR_UNSUPPORTED, "mmdx_palette_bounds: " + std::to_string(m->plan.n_nonconvex) +
                                               " vertices of this model have a negative skin weight (n_nonconvex): a box of bone boxes "
                                               "does not contain them");
-    if (m->device < 0)
-        return fail(MMDX_ERR_NO_DEVICE, "model was created with MMDX_CREATE_HOST_ONLY: nothing to run on (this engine has no CPU fallback)");
-    if (m->capturing && m->capture_thread != std::this_thread::get_id())
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "this model's stream is recording a graph on another thread: recorded calls must come "
-                                               "from the thread that called mmdx_graph_begin");
-    if (graph_recording() && (a->flags & on_device) != on_device)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded palettes and out_bounds must both be in device memory");
-    HIP_TRY(hipSetDevice(m->device));
+    if (mmdx_status r = model_call_begin(m, a->flags, on_device,
+                                         "while a graph is being recorded palettes and out_bounds must both be in device memory"))
+        return r;
     hipStream_t st = m->stream;
     PBoundsLaunch p{a->palettes, static_cast<const float *>(m->bone_boxes.ptr), a->out_bounds, ni, nb, uint32_t(m->plan.box_bone.size()),
                     m->plan.box_eps, a->morph_scale, a->pos_scale};
     if (!(a->flags & MMDX_PALETTE_ON_DEVICE)) {
-        HIP_TRY(m->pbounds_in.ensure(pal_bytes));
-        HIP_TRY(hipMemcpyAsync(m->pbounds_in.ptr, a->palettes, pal_bytes, hipMemcpyHostToDevice, st));
+        if (mmdx_status r = stage_in(m->pbounds_in, a->palettes, pal_bytes, st)) return r;
         p.palettes = static_cast<const float *>(m->pbounds_in.ptr);
     }
-    if (!(a->flags & MMDX_OUT_ON_DEVICE)) {
-        HIP_TRY(m->pbounds_out.ensure(out_bytes));
-        p.out = static_cast<float *>(m->pbounds_out.ptr);
-    }
+    OutRoute o;
+    if (mmdx_status r = route_out(a->flags, a->out_bounds, out_bytes, m->pbounds_out, &o)) return r;
+    p.out = o.dev;
     HIP_TRY(launch_palette_bounds(p, st));
-    if (!(a->flags & MMDX_OUT_ON_DEVICE)) {
-        HIP_TRY(hipMemcpyAsync(a->out_bounds, p.out, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if ((a->flags & on_device) != on_device) {
-        HIP_TRY(wait_stream(st));   // borrowed host palettes must be consumed before returning
-    }
-    return MMDX_OK;
+    return finish(a->flags, (a->flags & on_device) != on_device, st, o);   // borrowed: host palettes
 }

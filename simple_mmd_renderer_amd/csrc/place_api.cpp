@@ -1,7 +1,6 @@
 // place_api.cpp -- mmdx_palette_place (include/mmdx.h): argument validation on the host, host operands through the model's scratch
 // the way mmdx_skeleton_solve takes them, and the launch (place_kernels.hip) on the handle's stream.
 #include <string>
-#include <thread>
 
 #include "api_internal.hpp"
 #include "place_kernels.hpp"
@@ -44,38 +43,23 @@ extern "C" mmdx_status mmdx_palette_place(mmdx_model_t m, const mmdx_place_args 
         return fail(MMDX_ERR_INVALID_ARGUMENT, "device placements must be 4-byte aligned");
     if (ni > kPlaceMaxInstances || place_chunks(nb) > 65535u)
         return fail(MMDX_ERR_UNSUPPORTED, "mmdx_palette_place: more than 2^23 instances or 2^22 bones in one call");
-    if (m->device < 0)
-        return fail(MMDX_ERR_NO_DEVICE, "model was created with MMDX_CREATE_HOST_ONLY: nothing to run on (this engine has no CPU fallback)");
-    if (m->capturing && m->capture_thread != std::this_thread::get_id())
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "this model's stream is recording a graph on another thread: recorded calls must come "
-                                               "from the thread that called mmdx_graph_begin");
-    if (graph_recording() && (a->flags & on_device) != on_device)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded palettes, placements and out_palettes must all be in "
-                                               "device memory");
-    HIP_TRY(hipSetDevice(m->device));
+    if (mmdx_status r = model_call_begin(m, a->flags, on_device, "while a graph is being recorded palettes, placements and "
+                                                                 "out_palettes must all be in device memory"))
+        return r;
     if (!nb) return MMDX_OK;
     hipStream_t st = m->stream;
     PlaceLaunch p{a->palettes, a->placements, a->out_palettes, ni, nb, matrix};
     if (!(a->flags & MMDX_PALETTE_ON_DEVICE)) {
-        HIP_TRY(m->place_in.ensure(pal_bytes));
-        HIP_TRY(hipMemcpyAsync(m->place_in.ptr, a->palettes, pal_bytes, hipMemcpyHostToDevice, st));
+        if (mmdx_status r = stage_in(m->place_in, a->palettes, pal_bytes, st)) return r;
         p.palettes = static_cast<const float *>(m->place_in.ptr);
     }
     if (!(a->flags & MMDX_PLACE_ON_DEVICE)) {
-        HIP_TRY(m->place_w.ensure(place_bytes));
-        HIP_TRY(hipMemcpyAsync(m->place_w.ptr, a->placements, place_bytes, hipMemcpyHostToDevice, st));
+        if (mmdx_status r = stage_in(m->place_w, a->placements, place_bytes, st)) return r;
         p.placements = static_cast<const float *>(m->place_w.ptr);
     }
-    if (!(a->flags & MMDX_OUT_ON_DEVICE)) {
-        HIP_TRY(m->place_out.ensure(pal_bytes));
-        p.out = static_cast<float *>(m->place_out.ptr);
-    }
+    OutRoute o;
+    if (mmdx_status r = route_out(a->flags, a->out_palettes, pal_bytes, m->place_out, &o)) return r;
+    p.out = o.dev;
     HIP_TRY(launch_palette_place(p, st));
-    if (!(a->flags & MMDX_OUT_ON_DEVICE)) {
-        HIP_TRY(hipMemcpyAsync(a->out_palettes, p.out, pal_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if ((a->flags & on_device) != on_device) {
-        HIP_TRY(wait_stream(st));   // borrowed host palettes / placements must be consumed before returning
-    }
-    return MMDX_OK;
+    return finish(a->flags, (a->flags & on_device) != on_device, st, o);   // borrowed: host palettes / placements
 }

@@ -2,7 +2,8 @@
 // Static tables (keys, curve tables, chains) are uploaded on first use per device; per-call operands may
 // live on the host (copied through handle-owned scratch) or in HBM.  No CPU fallback.
 //
-// Every device call is the same sequence, and every step of it is one function of this file, defined ahead of the entry points:
+// Every device call is the same sequence, and every step of it is one function, defined ahead of the entry points here or -- the
+// steps other files share: refuse_recording, stage_in, clock_in, route_out, finish, the list checks -- in host_runtime.hpp:
 //   check the arguments (nothing here needs the device) -> resolve_stream -> refuse what a recording cannot hold (refuse_recording)
 //   -> *_to_device -> graph_note_handle -> stage host operands (*_in) -> the parameter block (*_params) -> route_out -> launch ->
 //   finish.  A track + solve call on a skeleton that needs two launches (two_launches) sizes a pose scratch and makes two such calls.
@@ -20,6 +21,7 @@
 #include "anim_kernels.hpp"
 #include "error.hpp"
 #include "graph_pin.hpp"
+#include "host_runtime.hpp"
 #include "kernels.hpp"
 #include "motion_blend.hpp"
 #include "rig.hpp"
@@ -31,45 +33,13 @@ using namespace mmdx;
 
 namespace {
 
-#define HIP_TRY(expr)                                            \
-    do {                                                         \
-        hipError_t e_ = (expr);                                  \
-        if (e_ != hipSuccess) return hip_status(e_, #expr);      \
-    } while (0)
-
-struct Buf {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    const GraphPin *pin = nullptr;           // the owning handle's: a buffer a recorded graph holds may not move
-    hipError_t ensure(size_t need) {
-        need = std::max<size_t>(need, 16);
-        if (need <= bytes) return hipSuccess;
-        if (graph_recording()) return hipErrorStreamCaptureUnsupported;   // run the sequence once un-captured first
-        if (graph_pinned(pin)) return hipErrorIllegalState;                 // (hip_status turns both into a clear message)
-        release();
-        hipError_t e = hipMalloc(&ptr, need);
-        if (e == hipSuccess) bytes = need;
-        return e;
-    }
-    template <typename T>
-    hipError_t upload(const std::vector<T> &v) {
-        hipError_t e = ensure(v.size() * sizeof(T));
-        if (e != hipSuccess || v.empty()) return e;
-        return hipMemcpy(ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    }
-    void release() {
-        device_free_or_defer(ptr);
-        ptr = nullptr; bytes = 0;
-    }
-};
-
-void release(const std::vector<Buf *> &bufs) {
-    for (Buf *b : bufs) b->release();
+void release(const std::vector<DevBuf *> &bufs) {
+    for (DevBuf *b : bufs) b->release();
 }
 
 // The key and curve tables of bone tracks in device memory: one motion's, or a set's clips laid end to end (rig.hpp).
 struct BoneTables {
-    Buf key_off, key_frame, key_tr, key_rot, key_curve, lut;
+    DevBuf key_off, key_frame, key_tr, key_rot, key_curve, lut;
     mmdx_status upload(const BoneMotionHost &h) {
         HIP_TRY(key_off.upload(h.key_off));
         HIP_TRY(key_frame.upload(h.key_frame));
@@ -100,34 +70,34 @@ struct mmdx_bone_motion_s {
     BoneMotionHost host;
     int device = -1;
     BoneTables t;
-    Buf frames_in, out;
+    DevBuf frames_in, out;
     GraphPin pin;                                         // recorded graphs that hold these buffers' addresses
-    std::vector<Buf *> all() { return {&t.key_off, &t.key_frame, &t.key_tr, &t.key_rot, &t.key_curve, &t.lut, &frames_in, &out}; }
+    std::vector<DevBuf *> all() { return {&t.key_off, &t.key_frame, &t.key_tr, &t.key_rot, &t.key_curve, &t.lut, &frames_in, &out}; }
     mmdx_bone_motion_s() {
-        for (Buf *b : all()) b->pin = &pin;
+        for (DevBuf *b : all()) { b->pin = &pin; b->floor = 16; }    // (the floor: host_runtime.hpp)
     }
 };
 
 struct mmdx_skeleton_s {
     SkeletonPlan plan;
     int device = -1;
-    Buf local_offset, neg_rest, chain_off, chain, poses_in, out;
-    Buf order, bones, iks, links, events, rounds, state;  // ordered solver
-    Buf apps, app_chain, rates_in, morph_state;           // bone morphs
-    Buf over_bone, over_strict, over_skin;                // physics seam: the reactor's writes of one frame
-    Buf sel_in;                                           // mmdx_skeleton_solve_select with a host list: {live count, ids[live]}
+    DevBuf local_offset, neg_rest, chain_off, chain, poses_in, out;
+    DevBuf order, bones, iks, links, events, rounds, state;  // ordered solver
+    DevBuf apps, app_chain, rates_in, morph_state;           // bone morphs
+    DevBuf over_bone, over_strict, over_skin;                // physics seam: the reactor's writes of one frame
+    DevBuf sel_in;                                           // mmdx_skeleton_solve_select with a host list: {live count, ids[live]}
     std::vector<uint32_t> sel_host;                       // ... its source, alive until the copy has left it
     uint32_t pre_instances = 0;                           // instances of the last mmdx_skeleton_solve_pre (0: none pending)
     const float *pre_poses = nullptr;                     // the poses that call solved (device address)
     const float *pre_morph = nullptr;
     SolveShape last_solve;                                // what the last successful solve launched (mmdx_debug_last_solve_shape)
     GraphPin pin;                                         // recorded graphs that hold these buffers' addresses
-    std::vector<Buf *> all() {
+    std::vector<DevBuf *> all() {
         return {&local_offset, &neg_rest, &chain_off, &chain, &poses_in, &out, &order, &bones, &iks, &links, &events, &rounds, &state,
                 &apps, &app_chain, &rates_in, &morph_state, &over_bone, &over_strict, &over_skin, &sel_in};
     }
     mmdx_skeleton_s() {
-        for (Buf *b : all()) b->pin = &pin;
+        for (DevBuf *b : all()) { b->pin = &pin; b->floor = 16; }    // (the floor: host_runtime.hpp)
     }
 };
 
@@ -137,19 +107,19 @@ struct mmdx_motion_set_s {
     std::vector<uint32_t> clip_frames;                              // [n_clips] largest key frame of each clip (mmdx_motion_set_clip_frames)
     int device = -1;
     BoneTables t;                                                   // bone side
-    Buf m_key_off, m_frames, m_weights;                             // morph side
-    Buf clips_in, clock_in;                                         // host operands: 4 + 8 bytes per instance
-    Buf blend_in;                                                   // host operands of a blend call: 28 bytes per instance
-    Buf poses, out;                                                 // the two-launch palette path's poses; results bound for the host
-    Buf sel_in;                                                     // a *_blend_*_time_select call with a host list: {live count, ids[live]}
+    DevBuf m_key_off, m_frames, m_weights;                             // morph side
+    DevBuf clips_in, clock_in;                                         // host operands: 4 + 8 bytes per instance
+    DevBuf blend_in;                                                   // host operands of a blend call: 28 bytes per instance
+    DevBuf poses, out;                                                 // the two-launch palette path's poses; results bound for the host
+    DevBuf sel_in;                                                     // a *_blend_*_time_select call with a host list: {live count, ids[live]}
     std::vector<uint32_t> sel_host;                                 // ... its source, alive until the copy has left it
     GraphPin pin;                                                   // recorded graphs that hold these buffers' addresses
-    std::vector<Buf *> all() {
+    std::vector<DevBuf *> all() {
         return {&t.key_off, &t.key_frame, &t.key_tr, &t.key_rot, &t.key_curve, &t.lut, &m_key_off, &m_frames, &m_weights, &clips_in,
                 &clock_in, &blend_in, &poses, &out, &sel_in};
     }
     mmdx_motion_set_s() {
-        for (Buf *b : all()) b->pin = &pin;
+        for (DevBuf *b : all()) { b->pin = &pin; b->floor = 16; }    // (the floor: host_runtime.hpp)
     }
 };
 
@@ -158,7 +128,7 @@ const std::vector<uint32_t> &mmdx::motion_set_clip_frames(const mmdx_motion_set_
 // ---- static tables of a motion / a skeleton / a set -> the device they are about to run on (once per device) --------------------
 static mmdx_status motion_to_device(mmdx_bone_motion_t m, int device) {
     if (m->device == device) return MMDX_OK;
-    if (graph_pinned(&m->pin)) return hip_status(hipErrorIllegalState, "moving a bone motion to another device");
+    if (graph_pinned(&m->pin)) return hip_fail(hipErrorIllegalState, "moving a bone motion to another device");
     release(m->all());
     if (mmdx_status r = m->t.upload(m->host)) return r;
     m->device = device;
@@ -167,7 +137,7 @@ static mmdx_status motion_to_device(mmdx_bone_motion_t m, int device) {
 
 static mmdx_status skeleton_to_device(mmdx_skeleton_t s, int device) {
     if (s->device == device) return MMDX_OK;
-    if (graph_pinned(&s->pin)) return hip_status(hipErrorIllegalState, "moving a skeleton to another device");
+    if (graph_pinned(&s->pin)) return hip_fail(hipErrorIllegalState, "moving a skeleton to another device");
     const SkeletonPlan &pl = s->plan;
     release(s->all());
     HIP_TRY(s->apps.upload(pl.apps));
@@ -191,7 +161,7 @@ static mmdx_status skeleton_to_device(mmdx_skeleton_t s, int device) {
 
 static mmdx_status set_to_device(mmdx_motion_set_t set, int device) {
     if (set->device == device) return MMDX_OK;
-    if (graph_pinned(&set->pin)) return hip_status(hipErrorIllegalState, "moving a motion set to another device");
+    if (graph_pinned(&set->pin)) return hip_fail(hipErrorIllegalState, "moving a motion set to another device");
     const MotionSetHost &h = set->host;
     release(set->all());
     if (h.has_bones)
@@ -205,16 +175,7 @@ static mmdx_status set_to_device(mmdx_motion_set_t set, int device) {
     return MMDX_OK;
 }
 
-// ---- what a recording cannot hold ------------------------------------------------------------------------------------------------
-// While a graph is being recorded a call may neither copy from the host nor allocate: `flags` must hold every *_ON_DEVICE bit in
-// `need`, and the static tables of every handle must be on `device` already (`ran_on`: the handles' device fields).
-static mmdx_status refuse_recording(uint32_t flags, uint32_t need, int device, std::initializer_list<int> ran_on, const char *text) {
-    if (!graph_recording()) return MMDX_OK;
-    bool recordable = (flags & need) == need;
-    for (int d : ran_on) recordable = recordable && d == device;
-    return recordable ? MMDX_OK : fail(MMDX_ERR_INVALID_ARGUMENT, text);
-}
-
+// ---- what a recording cannot hold (refuse_recording: host_runtime.hpp) ------------------------------------------------------------
 static const uint32_t kClockAndOut = MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE;      // (MMDX_TIMES_ON_DEVICE is the same bit)
 static const char *const kSkeletonRecording = "while a graph is being recorded every operand must be in device memory, the "
                                               "skeleton must have run on this device before, and physics overrides "
@@ -243,22 +204,7 @@ static size_t pose_bytes(uint32_t ni, uint32_t nb) { return size_t(ni) * nb * MM
 static size_t palette_bytes(uint32_t ni, uint32_t nb) { return size_t(ni) * nb * 16 * sizeof(float); }
 
 // ---- host operands -> device addresses, through handle-owned scratch in stream order --------------------------------------------
-// the instant of every instance -> the kernel parameters: frame numbers (uint32_t) or, with `time`, seconds (double).  Host
-// operands go through the motion's scratch, sized 8 bytes per instance whenever it grows (room for either).
-static mmdx_status motion_clock_in(mmdx_bone_motion_t m, const void *clock, bool time, uint32_t n_instances, uint32_t flags,
-                                   hipStream_t st, BoneTrackParams &p) {
-    const void *dev = clock;
-    if (!(flags & MMDX_FRAMES_ON_DEVICE)) {
-        const size_t bytes = size_t(n_instances) * (time ? 8 : 4);
-        if (m->frames_in.bytes < bytes) HIP_TRY(m->frames_in.ensure(size_t(n_instances) * 8));
-        HIP_TRY(hipMemcpyAsync(m->frames_in.ptr, clock, bytes, hipMemcpyHostToDevice, st));
-        dev = m->frames_in.ptr;
-    }
-    if (time) p.times = static_cast<const double *>(dev);
-    else p.frames = static_cast<const uint32_t *>(dev);
-    return MMDX_OK;
-}
-
+// (one operand: stage_in; the clock of one motion: clock_in -- both in host_runtime.hpp)
 // clip ids and the instant of every instance -> device addresses: the clips, and the clock in `*frames` or, with `time`, `*times`
 // (the two clock fields of a parameter block).  MMDX_FRAMES_ON_DEVICE covers both operands; host operands go through the set's
 // scratch (4 + 8 bytes per instance, room for frames or times).
@@ -312,7 +258,7 @@ static mmdx_status blend_operands_in(mmdx_motion_set_t set, const mmdx_motion_bl
 // the list of a select call -> device addresses: a device list as it is; a host list through the handle's scratch (`sel_in`, its
 // source `sel_host` alive until the copy has left it), count word first.  `cells` = list positions the launch is sized from -- state
 // and bone-morph cells are per LIST POSITION --: the capacity of a device list, the ids in use of a host list.
-static mmdx_status list_in(Buf &sel_in, std::vector<uint32_t> &sel_host, const mmdx_instance_select *sel, uint32_t n_instances,
+static mmdx_status list_in(DevBuf &sel_in, std::vector<uint32_t> &sel_host, const mmdx_instance_select *sel, uint32_t n_instances,
                            uint32_t live_host, hipStream_t st, InstanceList *list, uint32_t *cells) {
     *list = InstanceList{sel->ids, sel->count, n_instances};
     if (sel->flags & MMDX_SELECT_ON_DEVICE) {
@@ -321,14 +267,7 @@ static mmdx_status list_in(Buf &sel_in, std::vector<uint32_t> &sel_host, const m
     }
     *cells = live_host;
     if (live_host == 0) return MMDX_OK;
-    HIP_TRY(sel_in.ensure((size_t(live_host) + 1) * 4));
-    sel_host.resize(size_t(live_host) + 1);
-    sel_host[0] = live_host;
-    std::copy(sel->ids, sel->ids + live_host, sel_host.begin() + 1);
-    HIP_TRY(hipMemcpyAsync(sel_in.ptr, sel_host.data(), sel_host.size() * 4, hipMemcpyHostToDevice, st));
-    list->count = static_cast<const uint32_t *>(sel_in.ptr);
-    list->ids = list->count + 1;
-    return MMDX_OK;
+    return stage_list(sel_in, sel_host, sel->ids, live_host, live_host, st, &list->count, &list->ids);
 }
 
 // ---- parameter blocks from a handle ----------------------------------------------------------------------------------------------
@@ -357,33 +296,6 @@ static MorphTrackParams set_morph_params(mmdx_motion_set_t set, uint32_t ni) {
 static void note_fk_solve(mmdx_skeleton_t s) {
     s->last_solve = SolveShape{};
     s->last_solve.solver = 2;
-}
-
-// ---- where the results go, and the end of a call ---------------------------------------------------------------------------------
-struct OutRoute {
-    float *dev = nullptr;        // what the kernel writes: the caller's array (MMDX_OUT_ON_DEVICE) or a handle's scratch
-    float *host = nullptr;       // the caller's host array `finish` copies the scratch to
-    size_t bytes = 0;
-};
-
-static mmdx_status route_out(uint32_t flags, float *caller_out, size_t bytes, Buf &scratch, OutRoute *o) {
-    *o = OutRoute{caller_out, nullptr, bytes};
-    if (flags & MMDX_OUT_ON_DEVICE) return MMDX_OK;
-    HIP_TRY(scratch.ensure(bytes));
-    *o = OutRoute{static_cast<float *>(scratch.ptr), caller_out, bytes};
-    return MMDX_OK;
-}
-
-// results bound for the host are copied out and waited for; results that stay on the device are waited for only when the call
-// `borrowed` a host operand or a host list, which must be consumed before returning
-static mmdx_status finish(uint32_t flags, bool borrowed, hipStream_t st, const OutRoute &o) {
-    if (!(flags & MMDX_OUT_ON_DEVICE)) {
-        if (o.bytes) HIP_TRY(hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(wait_stream(st));
-    } else if (borrowed) {
-        HIP_TRY(wait_stream(st));
-    }
-    return MMDX_OK;
 }
 
 // ---- the solve -------------------------------------------------------------------------------------------------------------------
@@ -460,9 +372,7 @@ static mmdx_status skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_
         dev_poses = s->pre_poses;                    // the post-physics list re-reads the poses the pre step solved:
                                                      // they must still be there (device poses are the caller's to keep)
     } else if (!(flags & MMDX_POSES_ON_DEVICE)) {
-        const size_t in_bytes = pose_bytes(n_instances, pl.nb);
-        HIP_TRY(s->poses_in.ensure(in_bytes));
-        if (in_bytes) HIP_TRY(hipMemcpyAsync(s->poses_in.ptr, poses, in_bytes, hipMemcpyHostToDevice, st));
+        if (mmdx_status r = stage_in(s->poses_in, poses, pose_bytes(n_instances, pl.nb), st)) return r;
         dev_poses = static_cast<const float *>(s->poses_in.ptr);
     }
     OutRoute o;
@@ -471,9 +381,7 @@ static mmdx_status skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_
     const float *rates = morphs ? morph_weights : nullptr;
     const bool borrowed_rates = morphs && !(flags & MMDX_WEIGHTS_ON_DEVICE);
     if (borrowed_rates) {
-        const size_t rate_bytes = size_t(shared ? 1 : n_instances) * pl.nm * sizeof(float);
-        HIP_TRY(s->rates_in.ensure(rate_bytes));
-        HIP_TRY(hipMemcpyAsync(s->rates_in.ptr, morph_weights, rate_bytes, hipMemcpyHostToDevice, st));
+        if (mmdx_status r = stage_in(s->rates_in, morph_weights, size_t(shared ? 1 : n_instances) * pl.nm * sizeof(float), st)) return r;
         rates = static_cast<const float *>(s->rates_in.ptr);
     }
     if (overrides) {                                  // the reactor's writes, between the two lists
@@ -490,8 +398,7 @@ static mmdx_status skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_
         if (flags & MMDX_OVERRIDES_ON_DEVICE) {
             pp.skinning = ov->skinning;
         } else {
-            HIP_TRY(s->over_skin.ensure(xf_bytes));
-            HIP_TRY(hipMemcpyAsync(s->over_skin.ptr, ov->skinning, xf_bytes, hipMemcpyHostToDevice, st));
+            if (mmdx_status r = stage_in(s->over_skin, ov->skinning, xf_bytes, st)) return r;
             pp.skinning = static_cast<const float *>(s->over_skin.ptr);
         }
         HIP_TRY(hipStreamSynchronize(st));        // ob / os are locals: the copies above must have read them
@@ -511,26 +418,9 @@ static mmdx_status skeleton_solve(mmdx_skeleton_t s, mmdx_model_t model, uint32_
 // the calls that take every instance; `live_host` = the ids of a host list that are in use.
 static mmdx_status check_instance_list(const mmdx_instance_select *sel, uint32_t n_instances, const char *plain, uint32_t &live_host) {
     if (!sel) return fail(MMDX_ERR_INVALID_ARGUMENT, std::string("select is NULL (") + plain + ")");
-    if (sel->struct_size != sizeof(mmdx_instance_select))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.struct_size mismatch");
-    if (sel->flags & ~uint32_t(MMDX_SELECT_ON_DEVICE))
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown bits in mmdx_instance_select.flags");
-    if (sel->reserved0 != 0) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.reserved0 must be 0");
-    if (sel->n_ids && !sel->ids) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids is NULL");
-    if (sel->flags & MMDX_SELECT_ON_DEVICE) {
-        if ((reinterpret_cast<uintptr_t>(sel->ids) | reinterpret_cast<uintptr_t>(sel->count)) & 3)
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "device ids / count of mmdx_instance_select must be 4-byte aligned");
-        return MMDX_OK;
-    }
-    if (graph_recording())
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "while a graph is being recorded the instance list must be in device memory "
-                                               "(MMDX_SELECT_ON_DEVICE)");
-    live_host = sel->count ? std::min(*sel->count, sel->n_ids) : sel->n_ids;
-    for (uint32_t j = 0; j < live_host; ++j)
-        if (sel->ids[j] >= n_instances)
-            return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_instance_select.ids[" + std::to_string(j) + "] = " +
-                                                   std::to_string(sel->ids[j]) + " is not below n_instances");
-    return MMDX_OK;
+    if (mmdx_status r = list_header_check(sel)) return r;
+    if (mmdx_status r = list_placement_check(sel, graph_recording())) return r;      // this THREAD records: these calls may have no model
+    return host_list_check(sel, n_instances, live_host);
 }
 
 // mmdx_skeleton_solve_select: mmdx_skeleton_solve_morphed for the listed instances (include/mmdx.h, rules 1-10).  Everything that can
@@ -563,7 +453,7 @@ static mmdx_status bone_motion_eval(mmdx_bone_motion_t m, mmdx_model_t model, ui
     if (mmdx_status r = motion_to_device(m, device)) return r;
     graph_note_handle(model, &m->pin);
     BoneTrackParams p = m->t.params(m->host.nb, n_instances);
-    if (mmdx_status r = motion_clock_in(m, clock, time, n_instances, flags, st, p)) return r;
+    if (mmdx_status r = clock_in(m->frames_in, "bone motion clock scratch", clock, time, n_instances, flags, st, &p.frames, &p.times)) return r;
     OutRoute o;
     if (mmdx_status r = route_out(flags, out_poses, pose_bytes(n_instances, p.nb), m->out, &o)) return r;
     p.out = o.dev;
@@ -603,7 +493,7 @@ static mmdx_status skeleton_solve_motion(mmdx_skeleton_t s, mmdx_bone_motion_t m
     graph_note_handle(model, &m->pin);
     graph_note_handle(model, &s->pin);
     BoneTrackParams tp = m->t.params(pl.nb, n_instances);
-    if (mmdx_status r = motion_clock_in(m, clock, time, n_instances, flags, st, tp)) return r;
+    if (mmdx_status r = clock_in(m->frames_in, "bone motion clock scratch", clock, time, n_instances, flags, st, &tp.frames, &tp.times)) return r;
     OutRoute o;
     if (mmdx_status r = route_out(flags, out_palettes, palette_bytes(n_instances, pl.nb), s->out, &o)) return r;
     HIP_TRY(launch_motion_fk(tp, fk_params(s, n_instances, nullptr, nullptr, o.dev), st));

@@ -82,13 +82,13 @@ struct mmdx_morph_motion_s {
     uint32_t nm = 0, n_mapped = 0;
     std::vector<uint32_t> key_off, frames;                // [nm+1], [K]
     std::vector<float> weights;                           // [K]
-    mmdx::MorphMotionDevice dev;                          // uploaded lazily by the first eval
+    mmdx::MorphMotionDevice *dev = nullptr;               // created and uploaded by the first eval (api.cpp)
 };
 
 const mmdx::MorphMotionHost mmdx::morph_motion_host(const mmdx_morph_motion_s *m) {
     return {m->nm, m->key_off.data(), m->frames.data(), m->weights.data(), uint32_t(m->frames.size())};
 }
-mmdx::MorphMotionDevice &mmdx::morph_motion_device(mmdx_morph_motion_s *m) { return m->dev; }
+mmdx::MorphMotionDevice *&mmdx::morph_motion_device(mmdx_morph_motion_s *m) { return m->dev; }
 mmdx::VmdBoneTracks mmdx::vmd_bone_tracks(const mmdx_vmd_s *v) {
     return {&v->bone_names, &v->bone_off, v->bone_keys.data()};
 }
@@ -272,7 +272,7 @@ mmdx_status mmdx_morph_motion_get_info(mmdx_morph_motion_t mm, uint32_t *n_morph
 
 void mmdx_morph_motion_destroy(mmdx_morph_motion_t mm) {
     if (!mm) return;
-    mmdx::morph_motion_release_device(mm->dev);
+    if (mm->dev) mmdx::morph_motion_release_device(*mm->dev);
     delete mm;
 }
 

@@ -7,7 +7,6 @@
 #include <vector>
 
 #include "../../include/mmdx.h"
-#include "graph_pin.hpp"
 
 namespace mmdx {
 
@@ -19,18 +18,11 @@ struct MorphMotionHost {          // keyframes of every model morph, model-morph
     uint32_t nkeys;
 };
 
-struct MorphMotionDevice {        // owned by api.cpp (hipMalloc / hipFree)
-    void *key_off = nullptr, *frames = nullptr, *weights = nullptr;
-    void *frames_in = nullptr, *out = nullptr;   // per-call scratch for host-pointer callers (frames_in: 8 bytes per instance,
-                                                 // room for the double times of mmdx_morph_motion_eval_time)
-    size_t frames_in_bytes = 0, out_bytes = 0;
-    int device = -1;
-    GraphPin pin;                 // recorded graphs that hold these addresses
-};
+struct MorphMotionDevice;         // the tables and scratch in device memory: defined, created on first use and deleted by api.cpp
 
 const MorphMotionHost morph_motion_host(const mmdx_morph_motion_s *m);
-MorphMotionDevice &morph_motion_device(mmdx_morph_motion_s *m);
-void morph_motion_release_device(MorphMotionDevice &d);   // api.cpp
+MorphMotionDevice *&morph_motion_device(mmdx_morph_motion_s *m);
+void morph_motion_release_device(MorphMotionDevice &d);   // api.cpp: frees the buffers and the object itself
 
 struct VmdBoneTracks {            // views into a parsed motion, valid until mmdx_vmd_destroy
     const std::vector<std::string> *names;    // UTF-8, track order
