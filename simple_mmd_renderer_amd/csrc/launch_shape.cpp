@@ -95,10 +95,13 @@ mmdx_status plan_deform_launch(const Plan &p, const DeformCall &c, const LaunchO
         for (uint32_t k = 16; k >= 4 && !g; k -= 4)
             if (pack_lds_bytes(k, p.max_tile_bones, p.ns, &so, &wo, &mo) <= half) g = k;
         if (!g && pack_lds_bytes(4, p.max_tile_bones, p.ns, &so, &wo, &mo) <= kLdsPerCu) g = 4;
-        if (ov.group > 0) g = std::max(uint32_t(ov.group) / 4 * 4, 4u);
         if (g) {
             g = std::min(g, (ni + 3) / 4 * 4);
             while (g > 4 && uint64_t(p.ntiles) * ((ni + g - 1) / g) < 1536) g -= 4;     // keep 256 CUs x 3 workgroups busy twice over
+        }
+        // (forced last, as for the tile kernel above: a forced group is not shrunk to fill the chip)
+        if (ov.group > 0) g = std::max(uint32_t(ov.group) / 4 * 4, 4u);
+        if (g) {
             s.group = g;
             lds = pack_lds_bytes(g, p.max_tile_bones, p.ns, &s.stage_off, &s.w_off, &s.mp_off);
             if (lds > kLdsPerCu) pack = false;
