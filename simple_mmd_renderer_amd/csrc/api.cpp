@@ -675,72 +675,28 @@ static mmdx_status stage_palettes(mmdx_model_t m, const mmdx_deform_args *a, Ptr
     return MMDX_OK;
 }
 
-// The morph mode of a call (kMorph*), and whether its shared morph pass can be left out
-struct MorphMode {
-    int morph = kMorphNone;
-    bool shared = false;             // one set of rates for the call
-    bool autoskip = false;           // MMDX_MORPH_AUTOSKIP
-    bool unchanged = false;          // the shared rates are those `morphed` was computed from: by the caller's word, or found equal here
-    bool host_skip = false;          // ... found equal here: the host-side comparison
-    bool host_rates_call = false;    // a crowd's shared rates, in host memory, that take the morph pass
-};
-
-// A decision only: reads the handle's record of what `morphed` holds, changes nothing
-static mmdx_status choose_morph_mode(const mmdx_model_s *m, const mmdx_deform_args *a, const mmdx_instance_select *sel, MorphMode &mm) {
-    const Plan &p = m->plan;
-    const uint32_t ni = a->n_instances;
-    const bool shared = mm.shared = (a->flags & MMDX_WEIGHTS_SHARED) != 0 || ni == 1;
-    // Morph mode.  Shared rates: a single frame and SMALL crowds with one facial state gather the morphs inside the deform
-    // kernel (every workgroup repeats its tile's walk; no separate launch: 8.8 vs 10.1 us for 2 instances of the 50k
-    // model, break-even at 8, tools/archive/probes/shared_ab.py); larger crowds run the morph pass once, in front (257 vs 269 us for
-    // 1024 instances) -- or not at all when the caller declares the rates unchanged since the last such call.
-    bool unchanged = shared && ni > 1 && (a->flags & MMDX_MORPH_UNCHANGED);
-    if (unchanged && !m->morphed_valid)
-        return fail(MMDX_ERR_INVALID_ARGUMENT, "MMDX_MORPH_UNCHANGED without an earlier MMDX_WEIGHTS_SHARED crowd call on this model");
-    const int sf = launch_overrides().shared_fused;          // 0: never for crowds, 1: small crowds (default), 2: always
-    // The same without the caller's promise: vertex_images_ depends on morph_rates_ only (poser_impl.inl:362-386), so a crowd call
-    // whose shared rates are, bit for bit, those of the morph pass whose result this handle still holds needs no morph pass.
-    // Rates in HOST memory are compared here (memcmp with the copy kept of the last pass's), the launch and the upload are skipped;
-    // rates in DEVICE memory are compared by morph_apply_kernel itself, which then skips its walk (RatesSeen, kernels.hpp).
-    const bool autoskip = mm.autoskip = launch_overrides().morph_autoskip != 0;
-    const bool crowd_pass = p.ns && shared && ni > 1 && !(p.ns <= kMaxFusedSlots && (sf == 2 || (sf == 1 && ni <= 8)));
-    const bool host_rates_call = crowd_pass && !unchanged && !(a->flags & MMDX_WEIGHTS_ON_DEVICE);
-    if (host_rates_call && autoskip && m->morphed_valid && m->host_rates_valid && m->host_rates.size() == p.nm &&
-        std::memcmp(m->host_rates.data(), a->morph_weights, size_t(p.nm) * 4) == 0) {
-        unchanged = mm.host_skip = true;
-    }
-    // (a select call with an empty list launches no deform kernel: its shared rates take the morph pass, so that the positions
-    // later MMDX_MORPH_UNCHANGED calls rely on are there)
-    const bool gather_in_kernel = ni == 1 || (p.ns <= kMaxFusedSlots && !unchanged && (sf == 2 || (sf == 1 && ni <= 8)) &&
-                                              !(sel && sel->n_ids == 0));
-    if (p.ns) mm.morph = shared ? (gather_in_kernel ? kMorphFused1 : kMorphShared) : kMorphFused4;
-    mm.unchanged = unchanged; mm.host_rates_call = host_rates_call;
-    return MMDX_OK;
-}
-
-// Morph mode + slot weights: decides the call's morph mode (`morph`, kMorph*), uploads the rates, runs the flatten / shared morph
-// pass where the mode has one, and fills the morph fields of `dp`.  The handle's record of what `morphed` holds (morphed_valid,
-// host_rates, the device-side RatesSeen) is written here and nowhere else.
+// The morph step: takes a replay's news into the handle's record, plans (plan_morph_pass, launch_shape.hpp: the morph mode, the pass
+// in front of the deform kernel, what becomes of the records), then does what the plan says -- uploads the rates, launches the pass,
+// fills the morph fields of `dp`.  The handle's record of what `morphed` holds (morphed_valid, host_rates) is written in one block
+// behind the last launch: a call that fails in here leaves the record it found.
 static mmdx_status run_morph_pass(mmdx_model_t m, const mmdx_deform_args *a, const mmdx_instance_select *sel, PtrKind kind_w,
-                                  hipEvent_t *pev, DeformParams &dp, int &morph) {
+                                  hipEvent_t *pev, DeformParams &dp, MorphPlan &pl) {
     const Plan &p = m->plan;
     const KernelSet &ks = kernel_set((p.flags & MMDX_CREATE_FAST_MATH) != 0);
-    const uint32_t ni = a->n_instances;
     hipStream_t st = m->stream;
     if (m->pin.replayed.exchange(false, std::memory_order_acq_rel)) m->host_rates_valid = false;   // a graph replay ran a morph pass
-    MorphMode mm;
-    if (mmdx_status s = choose_morph_mode(m, a, sel, mm)) return s;
-    if (mm.host_skip) ++m->host_skips;
-    morph = mm.morph;
-    const bool shared = mm.shared, autoskip = mm.autoskip, unchanged = mm.unchanged, host_rates_call = mm.host_rates_call;
-    if (morph == kMorphNone) return MMDX_OK;
-    const uint32_t niw = shared ? 1u : (sel ? sel->n_ids : ni);     // (select, per-instance rates: one row per list position)
-    const float *rates_dev;
-    if ((a->flags & MMDX_WEIGHTS_ON_DEVICE) || unchanged) {
-        rates_dev = a->morph_weights;                     // (unchanged: never read)
-    } else {
-        HIP_TRY(m->rates.ensure(size_t(niw) * p.nm * 4));
-        HIP_TRY(copy_in(m, m->rates.ptr, a->morph_weights, kind_w, size_t(niw) * p.nm * 4, kBounceInBytes / 2, st));
+    const LaunchOverrides &ov = launch_overrides();
+    const MorphCall call{p.ns, p.nm, a->n_instances, a->flags, sel != nullptr, sel ? sel->n_ids : 0u, ov.shared_fused, ov.morph_autoskip,
+                         a->morph_weights};
+    std::string err;
+    if (mmdx_status s = plan_morph_pass(call, {m->morphed_valid, m->host_rates_valid, m->host_rates.data(), m->host_rates.size()}, pl, err))
+        return fail(s, err);
+    if (pl.host_skip) ++m->host_skips;
+    if (pl.morph == kMorphNone) return MMDX_OK;
+    const float *rates_dev = a->morph_weights;            // (a pass that is left out never reads them)
+    if (pl.upload) {
+        HIP_TRY(m->rates.ensure(size_t(pl.niw) * p.nm * 4));
+        HIP_TRY(copy_in(m, m->rates.ptr, a->morph_weights, kind_w, size_t(pl.niw) * p.nm * 4, kBounceInBytes / 2, st));
         rates_dev = static_cast<const float *>(m->rates.ptr);
     }
     FlattenParams f{};
@@ -748,45 +704,41 @@ static mmdx_status run_morph_pass(mmdx_model_t m, const mmdx_deform_args *a, con
     f.slot_top = static_cast<const uint32_t *>(m->slot_top.ptr);
     f.chain_off = static_cast<const uint32_t *>(m->chain_off.ptr);
     f.chain_rate = static_cast<const float *>(m->chain_rate.ptr);
-    f.nm = p.nm; f.ns = p.ns; f.niw = niw;
-    f.quad = morph == kMorphFused4 ? 1u : 0u;
-    f.seen = nullptr;
-    if (sel && !shared) { f.sel_ids = dp.sel_ids; f.sel_count = dp.sel_count; f.sel_ni = ni; }
-    const size_t rows = f.quad ? size_t((niw + 3) / 4) * 4 : niw;
-    HIP_TRY(m->wslot.ensure(rows * (size_t(p.ns) + 1) * 4));
+    f.nm = p.nm; f.ns = p.ns; f.niw = pl.niw;
+    f.quad = pl.quad ? 1u : 0u;
+    if (pl.select_rows) { f.sel_ids = dp.sel_ids; f.sel_count = dp.sel_count; f.sel_ni = a->n_instances; }
+    HIP_TRY(m->wslot.ensure(pl.wslot_rows * (size_t(p.ns) + 1) * 4));
     f.out = static_cast<float *>(m->wslot.ptr);
+    uint32_t *seen = static_cast<uint32_t *>(m->seen.ptr);
+    if (pl.seen == MorphPlan::kSeenCompared) f.seen = seen;
+    if (pl.seen == MorphPlan::kSeenClearedByDeform) dp.morph_seen = seen;
     if (pev) HIP_TRY(hipEventRecord(pev[2], st));
     dp.wslot = f.out;
-    dp.morphed = static_cast<float *>(m->morphed.ptr);
-    if (morph == kMorphShared && unchanged) {
-        // nothing to launch: `morphed` holds the positions
-    } else if (morph == kMorphShared && p.ns <= kMaxFusedSlots) {
-        if (autoskip) f.seen = static_cast<uint32_t *>(m->seen.ptr);
-        HIP_TRY(ks.launch_morph_apply(p.f16, dp, &f, st));      // flatten fused in: one launch
-    } else if (morph == kMorphFused1) {
-        if (ni > 1) dp.morph_seen = static_cast<uint32_t *>(m->seen.ptr);   // it overwrites `morphed`: the record is void after it
-        // A single frame (ni == 1) leaves the model's kept positions alone: they belong to the last SHARED CROWD call
-        // (MMDX_MORPH_UNCHANGED is documented against that one), whichever kernel the frame takes.
-        if (ni == 1) dp.morphed = nullptr;
-        dp.fused_rates = rates_dev;                           // flatten inside the deform kernel
+    dp.morphed = pl.withhold_morphed ? nullptr : static_cast<float *>(m->morphed.ptr);
+    switch (pl.pass) {
+    case MorphPlan::kNoPass:
+        break;
+    case MorphPlan::kFusedApply:
+        HIP_TRY(ks.launch_morph_apply(p.f16, dp, &f, st));
+        break;
+    case MorphPlan::kFlattenApply:
+        HIP_TRY(launch_flatten(f, st));
+        HIP_TRY(ks.launch_morph_apply(p.f16, dp, nullptr, st));
+        HIP_TRY(hipMemsetAsync(seen, 0, 4, st));
+        break;
+    case MorphPlan::kFlatten:
+        HIP_TRY(launch_flatten(f, st));
+        break;
+    case MorphPlan::kGather:                              // flatten inside the deform kernel
+        dp.fused_rates = rates_dev;
         dp.slot_top = f.slot_top; dp.chain_off = f.chain_off; dp.chain_rate = f.chain_rate;
         dp.nm = p.nm;
-    } else {
-        HIP_TRY(launch_flatten(f, st));
-        if (morph == kMorphShared) {
-            HIP_TRY(ks.launch_morph_apply(p.f16, dp, nullptr, st));
-            HIP_TRY(hipMemsetAsync(m->seen.ptr, 0, 4, st));       // this (rare: > 8192 slots) pass keeps no record of its rates
-        }
-    }
-    // the host's own record: the rates of the pass `morphed` now holds, when they were host memory
-    if (morph == kMorphShared && !unchanged) {
-        m->host_rates_valid = host_rates_call;
-        if (host_rates_call) m->host_rates.assign(a->morph_weights, a->morph_weights + p.nm);
-    } else if (morph == kMorphFused1 && ni > 1) {
-        m->host_rates_valid = false;
+        break;
     }
     if (pev) HIP_TRY(hipEventRecord(pev[3], st));
-    if (morph == kMorphShared || (morph == kMorphFused1 && ni > 1)) m->morphed_valid = true;   // kept by either path
+    m->morphed_valid = pl.morphed_valid;
+    if (pl.host_rates == MorphPlan::kRatesStored) m->host_rates.assign(a->morph_weights, a->morph_weights + p.nm);
+    if (pl.host_rates != MorphPlan::kRatesKept) m->host_rates_valid = pl.host_rates == MorphPlan::kRatesStored;
     return MMDX_OK;
 }
 
@@ -961,11 +913,11 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
     if (sel)
         if (mmdx_status s = stage_select(m, sel, cp.sel_live_host, dp)) return s;
     if (mmdx_status s = stage_palettes(m, a, cp.kind_pal, dp)) return s;
-    int morph;
-    if (mmdx_status s = run_morph_pass(m, a, sel, cp.kind_w, pev, dp, morph)) return s;
+    MorphPlan mp;
+    if (mmdx_status s = run_morph_pass(m, a, sel, cp.kind_w, pev, dp, mp)) return s;
     OutputRoute route;
     if (mmdx_status s = route_outputs(m, a, cp, dp, route)) return s;
-    const DeformCall call{a->out_layout, a->n_instances, sel ? sel->n_ids : a->n_instances, a->flags, morph, out_bounds != nullptr,
+    const DeformCall call{a->out_layout, a->n_instances, sel ? sel->n_ids : a->n_instances, a->flags, mp.morph, out_bounds != nullptr,
                           sel != nullptr, route.out_dev, route.direct || route.bounce, route.bytes_a + route.bytes_b};
     LaunchShape shape;
     std::string err;
@@ -974,7 +926,7 @@ static mmdx_status deform_batched(mmdx_model_t m, const mmdx_deform_args *a, flo
     float *bounds_dev = nullptr;
     if (mmdx_status s = launch_planned(m, call, shape, out_bounds, pev, dp, bounds_dev)) return s;
     record_launch_shape(m, call, shape, dp);
-    const bool host_inputs = !(a->flags & MMDX_PALETTE_ON_DEVICE) || (morph != kMorphNone && !(a->flags & MMDX_WEIGHTS_ON_DEVICE)) ||
+    const bool host_inputs = !(a->flags & MMDX_PALETTE_ON_DEVICE) || (mp.morph != kMorphNone && !(a->flags & MMDX_WEIGHTS_ON_DEVICE)) ||
                              (sel && !(sel->flags & MMDX_SELECT_ON_DEVICE) && sel->n_ids);
     return copy_out(m, a, route, cp.pitch, dp, out_bounds, bounds_dev, host_inputs);
 }

@@ -130,7 +130,6 @@ struct KernelSet {
 const KernelSet &kernels();         // kernels.hip
 const KernelSet &kernels_fast();    // kernels_fast.hip
 inline const KernelSet &kernel_set(bool fast) { return fast ? kernels_fast() : kernels(); }
-constexpr uint32_t kMaxFusedSlots = 8192;
 // pitch: vertices from one instance's piece to the next (0 = nv)
 hipError_t launch_pattern_fill(void *a, void *b, uint32_t nv, uint32_t ni, uint32_t bpva, uint32_t bpvb,
                                hipStream_t stream, uint32_t pitch = 0);

@@ -3,6 +3,7 @@
 #include "launch_shape.hpp"
 
 #include <algorithm>
+#include <cstring>
 
 namespace mmdx {
 
@@ -149,6 +150,77 @@ mmdx_status plan_deform_launch(const Plan &p, const DeformCall &c, const LaunchO
     } else {
         s.kernel = LaunchShape::kDeform;
     }
+    return MMDX_OK;
+}
+
+mmdx_status plan_morph_pass(const MorphCall &c, const MorphRecord &rec, MorphPlan &pl, std::string &err) {
+    pl = MorphPlan{};
+    pl.morphed_valid = rec.morphed_valid;
+    const uint32_t ni = c.ni;
+    const bool shared = (c.flags & MMDX_WEIGHTS_SHARED) != 0 || ni == 1;      // one set of rates for the call
+    const bool promised = shared && ni > 1 && (c.flags & MMDX_MORPH_UNCHANGED);
+    if (promised && !rec.morphed_valid) {
+        err = "MMDX_MORPH_UNCHANGED without an earlier MMDX_WEIGHTS_SHARED crowd call on this model";
+        return MMDX_ERR_INVALID_ARGUMENT;
+    }
+    if (!c.ns) return MMDX_OK;                                  // kMorphNone: nothing to upload, launch or remember
+    pl.upload = !(c.flags & MMDX_WEIGHTS_ON_DEVICE) && !promised;
+    pl.niw = pl.wslot_rows = 1;
+    if (!shared) {
+        pl.morph = kMorphFused4;
+        pl.pass = MorphPlan::kFlatten;
+        pl.quad = true;
+        pl.select_rows = c.select;
+        pl.niw = c.select ? c.n_ids : ni;                       // (select: one row per list position)
+        pl.wslot_rows = (pl.niw + 3) / 4 * 4;
+        return MMDX_OK;
+    }
+    if (ni == 1) {
+        // A single frame leaves the model's kept positions alone: they belong to the last SHARED CROWD call (MMDX_MORPH_UNCHANGED
+        // is documented against that one), whichever kernel the frame takes.
+        pl.morph = kMorphFused1;
+        pl.pass = MorphPlan::kGather;
+        pl.withhold_morphed = true;
+        return MMDX_OK;
+    }
+    // A crowd with one facial state.  SMALL crowds gather the morphs inside the deform kernel like a single frame (every workgroup
+    // repeats its tile's walk; no separate launch: 8.8 vs 10.1 us for 2 instances of the 50k model, break-even at 8,
+    // tools/archive/probes/shared_ab.py); larger crowds run the morph pass once, in front (257 vs 269 us for 1024 instances) -- or
+    // not at all when the caller declares the rates unchanged since the last such call.
+    // shared_fused: 0 never for crowds, 1 small crowds (default), 2 always.
+    const bool small = c.ns <= kMaxFusedSlots && (c.shared_fused == 2 || (c.shared_fused == 1 && ni <= 8));
+    pl.morphed_valid = true;                                    // kept by either path
+    // (a select call with an empty list launches no deform kernel: its shared rates take the morph pass, so that the positions
+    // later MMDX_MORPH_UNCHANGED calls rely on are there)
+    if (small && !promised && !(c.select && c.n_ids == 0)) {
+        pl.morph = kMorphFused1;
+        pl.pass = MorphPlan::kGather;
+        pl.seen = MorphPlan::kSeenClearedByDeform;              // it overwrites `morphed`: neither record describes it afterwards
+        pl.host_rates = MorphPlan::kRatesVoid;
+        return MMDX_OK;
+    }
+    pl.morph = kMorphShared;
+    // The same as the caller's promise, without it: vertex_images_ depends on morph_rates_ only (poser_impl.inl:362-386), so a crowd
+    // call whose shared rates are, bit for bit, those of the morph pass whose result this handle still holds needs no morph pass.
+    // Rates in HOST memory are compared here (with the copy kept of the last pass's), the launch and the upload are skipped; rates
+    // in DEVICE memory are compared by morph_apply_kernel itself, which then skips its walk (RatesSeen, kernels.hpp).
+    // Only crowds past the small size keep and consult the host's copy (a small crowd gets here with a promise or an empty list).
+    const bool host_rates_call = !small && !promised && !(c.flags & MMDX_WEIGHTS_ON_DEVICE);
+    pl.host_skip = host_rates_call && c.morph_autoskip != 0 && rec.morphed_valid && rec.host_rates_valid && rec.n_host_rates == c.nm &&
+                   std::memcmp(rec.host_rates, c.rates, size_t(c.nm) * 4) == 0;
+    if (promised || pl.host_skip) {                             // nothing to launch: `morphed` holds the positions
+        pl.upload = false;
+        return MMDX_OK;
+    }
+    if (c.ns <= kMaxFusedSlots) {
+        pl.pass = MorphPlan::kFusedApply;
+        pl.seen = c.morph_autoskip != 0 ? MorphPlan::kSeenCompared : MorphPlan::kSeenUntouched;
+    } else {
+        pl.pass = MorphPlan::kFlattenApply;
+        pl.seen = MorphPlan::kSeenClearedByMemset;              // this (rare: > 8192 slots) pass keeps no record of its rates
+    }
+    // the host's own record: the rates of the pass `morphed` now holds, when they were host memory
+    pl.host_rates = host_rates_call ? MorphPlan::kRatesStored : MorphPlan::kRatesVoid;
     return MMDX_OK;
 }
 

@@ -1,6 +1,6 @@
 // launch_shape.hpp -- the shape of one deform launch (threads, store flavour, group size, LDS layout, which kernel), decided from
 // values alone: no handle, no HIP call, no environment.  Pure C++17 like plan.cpp, so every heuristic in it can be swept on a machine
-// without a GPU (tests/test_launch_shape.py).
+// without a GPU (tests/test_launch_shape.py).  Below it, the morph step of the same call (plan_morph_pass, tests/test_morph_plan.py).
 #pragma once
 
 #include <cstddef>
@@ -56,5 +56,68 @@ struct LaunchShape {
 
 // MMDX_OK and `shape`, or MMDX_ERR_UNSUPPORTED and `err` when a workgroup would need more LDS than a CU has.
 mmdx_status plan_deform_launch(const Plan &p, const DeformCall &c, const LaunchOverrides &ov, LaunchShape &shape, std::string &err);
+
+// ---- the morph step of the same call: which morph mode (DeformCall::morph), which launches in front of the deform kernel, and what
+// the handle knows afterwards about the positions it keeps.  A handle keeps ONE buffer of morphed positions (`morphed`), and two
+// records of the rates it was computed from: the host's (MorphRecord) and the device's (RatesSeen, kernels.hpp).  The rules
+// (tests/test_morph_plan.py sweeps them and proves the records sound over every short sequence of calls):
+//   * morph == kMorphNone iff the model has no slot; per-instance rates are kMorphFused4 and never touch `morphed` or a record;
+//   * a single frame (ni == 1) is kMorphFused1, gathers in its kernel and is never handed `morphed` (withhold_morphed);
+//   * a crowd with one set of rates either gathers in the deform kernel (kMorphFused1, pass kGather) or reads `morphed`
+//     (kMorphShared); kMorphShared with pass kNoPass reads what an earlier call left there, which takes the caller's word
+//     (MMDX_MORPH_UNCHANGED, refused unless morphed_valid) or the host's comparison (host_skip);
+//   * what a pass leaves behind:   pass           `morphed`        device record                host record      morphed_valid
+//                                  kNoPass        kept             untouched                    kept             kept
+//                                  kFlatten       kept             untouched                    kept             kept
+//                                  kGather, ni=1  kept             untouched                    kept             kept
+//                                  kGather, crowd the call's       cleared by the deform kernel void             true
+//                                  kFusedApply    the call's       compared, then = the call's  stored* or void  true
+//                                                                  (untouched without autoskip)
+//                                  kFlattenApply  the call's       cleared by a memset          stored* or void  true
+//     (* stored: the rates came from host memory and the crowd is past the small-crowd size; the copy is what later host-rates
+//     calls are compared with);
+//   * the host record is only ever trusted together with morphed_valid, with autoskip on, and by a call that would store it.
+struct MorphRecord {
+    bool morphed_valid;         // `morphed` holds the result of a crowd's morph pass or gather
+    bool host_rates_valid;      // ... and host_rates are the rates it was computed from
+    const float *host_rates;
+    size_t n_host_rates;
+};
+
+struct MorphCall {
+    uint32_t ns, nm;            // the model's slots and morphs
+    uint32_t ni, flags;         // mmdx_deform_args (MMDX_WEIGHTS_SHARED, MMDX_MORPH_UNCHANGED and MMDX_WEIGHTS_ON_DEVICE are read)
+    bool select;                // a select call ...
+    uint32_t n_ids;             // ... and its list's capacity
+    int shared_fused, morph_autoskip;   // LaunchOverrides
+    const float *rates;         // mmdx_deform_args.morph_weights; read (nm floats) only without MMDX_WEIGHTS_ON_DEVICE
+};
+
+struct MorphPlan {
+    enum Pass {
+        kNoPass,                // nothing in front of the deform kernel
+        kFusedApply,            // morph_apply_kernel with the flatten fused in: one launch
+        kFlattenApply,          // flatten, morph_apply_kernel, and a memset of the device record's valid word
+        kFlatten,               // flatten alone: the slot weights of per-instance rates
+        kGather                 // none either: the deform kernel flattens and gathers (DeformParams::fused_rates)
+    };
+    enum Seen { kSeenUntouched, kSeenCompared, kSeenClearedByDeform, kSeenClearedByMemset };
+    enum HostRates { kRatesKept, kRatesStored, kRatesVoid };
+    int morph;                  // kMorph*
+    Pass pass;
+    bool upload;                // the call's rates go to the handle's scratch first (niw rows of nm)
+    uint32_t niw;               // rows of rates: 1 shared; per-instance the instances, or the list positions of a select call
+    uint32_t wslot_rows;        // rows of ns + 1 slot weights the scratch must hold (niw, in whole quads for kMorphFused4)
+    bool quad;                  // flatten writes instance quads (kMorphFused4)
+    bool select_rows;           // flatten takes row j from rates[sel_ids[j]]
+    Seen seen;                  // the device record
+    bool withhold_morphed;      // dp.morphed = nullptr
+    bool host_skip;             // kNoPass because the host found the rates equal to the recorded ones (counted in host_skips)
+    bool morphed_valid;         // the handle's record after the call ...
+    HostRates host_rates;       // ... and its copy of the rates: as before, = the call's, or void
+};
+
+// MMDX_OK and `plan`, or MMDX_ERR_INVALID_ARGUMENT and `err`: MMDX_MORPH_UNCHANGED on a crowd whose handle holds no positions.
+mmdx_status plan_morph_pass(const MorphCall &c, const MorphRecord &rec, MorphPlan &plan, std::string &err);
 
 }  // namespace mmdx

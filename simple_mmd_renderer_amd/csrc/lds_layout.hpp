@@ -26,6 +26,9 @@ enum : int {
     kMorphSelect = 16   // kernels.hip only: ORed into deform_kernel's morph-mode template argument for the flavour of
                         // mmdx_deform_batched_select (modes 16..19 in kernel listings)
 };
+// Most slots whose weights a kernel evaluates itself, into LDS (morph_apply_kernel with the flatten fused in, the kMorphFused1
+// gather of a crowd); models past it take the separate flatten launch (launch_shape.cpp, plan_morph_pass)
+constexpr uint32_t kMaxFusedSlots = 8192;
 
 // LDS staging images of one tile's output range (bytes; all multiples of 16)
 constexpr uint32_t kSoaImgBytes = (kTileVerts * 3 + 4) * 4;        // f32 xyz + alignment slack

@@ -239,7 +239,7 @@ def test_oracle_equals_libmmd_on_long_rows(oracle, kind):
 
 # ---- CPU: the planner ----------------------------------------------------------------------------------------------------------------
 def morph_mode(ns, shared, ni, shared_fused):
-    """choose_morph_mode (csrc/api.cpp) for a call that promises nothing about its rates; ns <= 8192."""
+    """plan_morph_pass (csrc/launch_shape.cpp) for a call that promises nothing about its rates; ns <= 8192."""
     if not ns:
         return NONE
     if not (shared or ni == 1):
@@ -249,7 +249,7 @@ def morph_mode(ns, shared, ni, shared_fused):
 
 def test_planner_gives_every_case_its_shape(hip_lib, planner):
     """Every GPU case through tests/launch_shape_driver.cpp: the claimed kernel, threads (the frame kernel's come from
-    MMDX_FRAME_THREADS, past the planner) and group; the morph mode from choose_morph_mode restated; per-instance cases at least
+    MMDX_FRAME_THREADS, past the planner) and group; the morph mode from plan_morph_pass restated; per-instance cases at least
     two packs per workgroup."""
     scalars = {}
     calls = []
