@@ -72,7 +72,9 @@ extern "C" {
  *    MMDX_ANIM_DT_ON_DEVICE (new entry points, structures and a flag bit no other call accepts; nothing existing changes).
  *    mmdx_motion_set_blend_bones_time_select, mmdx_motion_set_blend_morphs_time_select and
  *    mmdx_skeleton_solve_motion_set_blend_time_select (new entry points over the existing mmdx_motion_blend_args and
- *    mmdx_instance_select; nothing existing changes). */
+ *    mmdx_instance_select; nothing existing changes).
+ *    mmdx_pose_blend and mmdx_rate_blend with mmdx_row_blend_args, MMDX_MASK_NONE and MMDX_BLEND_A_ON_DEVICE / _B_ / _PARAMS_, and
+ *    mmdx_skeleton_subtree_mask (new entry points, a structure and three flag bits no other call accepts; nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -840,7 +842,7 @@ MMDX_API mmdx_status mmdx_skeleton_solve_motion_set_time(mmdx_skeleton_t skeleto
  * Host operands are checked before the first HIP call: a clip id >= n_clips other than MMDX_CLIP_NONE in either array returns
  * MMDX_ERR_BAD_INDEX, a NaN time or weight MMDX_ERR_INVALID_ARGUMENT.  Device operands follow the rules above (a NaN time takes
  * the first key).  flags: MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE, unknown bits rejected; MMDX_TIMES_ON_DEVICE makes ALL FIVE
- * operand arrays device pointers.  Only the time clock is offered; more than two clips stay with the caller; advancing and wrapping
+ * operand arrays device pointers.  Only the time clock is offered; more than two clips and per-bone weights are mmdx_pose_blend's (below); advancing and wrapping
  * the clocks, the fade weight and the hand-over at the end of a fade are mmdx_animator_advance's (below).  Stream, device,
  * first-use upload, graph recording and pinning as for mmdx_skeleton_solve_motion_set_time: run the call once before recording it. */
 typedef struct mmdx_motion_blend_args {
@@ -1224,6 +1226,80 @@ MMDX_API mmdx_status mmdx_skeleton_solve_motion_set_blend_time_select(mmdx_skele
                                                                       const mmdx_motion_blend_args *args,
                                                                       const mmdx_instance_select *select,
                                                                       float *out_palettes /* [NI][NB][16] */);
+
+/* ---- Layers: the masked blend of two evaluated pose or rate arrays, per bone / per morph ------------------------------------------
+ * The cross-fade above applies one weight to a whole row.  A layer -- the upper body waves while the legs keep walking, the face
+ * follows a talk clip while the body dances -- needs a weight per bone.  mmdx_pose_blend takes two pose arrays A and B
+ * [NI][row_items][MMDX_POSE_FLOATS] that any track call wrote (a cross-fading base from one animator, a layer from another), a weight
+ * per instance and a mask row per instance, and writes per item the cross-fade's blend at the effective weight weight x mask[item];
+ * mmdx_rate_blend does the same for two morph-rate arrays [NI][row_items].  The result goes to mmdx_skeleton_solve / _solve_select
+ * (and the deform) as poses and rates always did; calling again with a third array gives a third layer.
+ *
+ * For instance i and item j, with m = mask_ids ? mask_ids[i] : MMDX_MASK_NONE:
+ *   mask value         mv = 1.0f for m == MMDX_MASK_NONE, masks[m][j] for m < n_masks, 0.0f for any other device id (the row is A)
+ *   effective weight   e = weights[i] * mv, one binary32 multiply: without a mask e is exactly weights[i]
+ *   !(e >= 1e-7f)      item j of out is A's item, every bit (the fourth translation float and NaNs copied as they are); B's item is
+ *                      not read
+ *   e > 1.0f - 1e-7f   item j is B's item, every bit; A's item is not read (with out == a it is simply overwritten)
+ *   otherwise          the cross-fade's arithmetic above (translation, rotation, morph rate) with w = e, unfused; fourth translation
+ *                      float 0.  Bit-identical to libmmd's operations; only the sign and payload of a NaN in a mixed item are not
+ *                      part of the contract.
+ * Two consequences callers may rely on:
+ *  - B MAY BE UNINITIALISED WHERE IT IS NOT NEEDED: rows of B whose instance has weights[i] == 0 (or a device NaN weight), and items
+ *    whose mask value is 0, may hold anything and influence no written byte.  The layer's tracks can therefore be evaluated with the
+ *    *_select track calls for the instances that wear the layer only.
+ *  - THE NO-MASK CALL EQUALS THE SET'S BLEND: with mask_ids == NULL, A the rows mmdx_motion_set_eval_bones_time writes for (clips_a,
+ *    times_a) and B those for (clips_b, times_b), mmdx_pose_blend writes bit for bit what mmdx_motion_set_blend_bones_time writes for
+ *    the same operands; the same holds for mmdx_rate_blend against mmdx_motion_set_blend_morphs_time.
+ * `model` supplies the device, the stream, graph recording and the scratch of host operands, as for mmdx_palette_place; row_items is
+ * explicit and need not be the model's bone or morph count.  The call is asynchronous on the model's stream and records into
+ * mmdx_graph_begin / _end (every operand in device memory then; a replay reads a, b, weights, mask_ids, masks and the list afresh).
+ *  - In place: out == a and out == b are both allowed, a lane reads its own items of A and B before it stores.  Any other overlap
+ *    among a, b and out (a overlapping b included), and weights, mask_ids or masks overlapping out, are MMDX_ERR_INVALID_ARGUMENT.
+ *    With out == a, a row whose weight is 0 or NaN already holds its result and is not touched at all: a crowd in which few instances
+ *    wear a layer pays for those instances only.
+ *  - select (NULL = every instance) follows mmdx_instance_select as mmdx_deform_batched_select states it: the first min(*count, n_ids)
+ *    ids are used; a device id >= NI is skipped, a host id >= NI fails before anything is launched; an id listed twice costs twice
+ *    and stores the same bytes (with a separate out; in place list an id once, a second blend of the row would start from what the
+ *    first one wrote); no byte of a row that is not listed is written, and its operand rows may hold anything; a host list
+ *    is copied through scratch of the model and refused while a graph is being recorded.  With a list, a, b and out must be device
+ *    memory (the staging copies of host rows move whole arrays): anything else is MMDX_ERR_INVALID_ARGUMENT.
+ *  - An operand without its *_ON_DEVICE flag is host memory, copied per call through scratch of the model, and the call returns when
+ *    the work is done.  Host operands are checked before the first HIP call: a mask id >= n_masks other than MMDX_MASK_NONE is
+ *    MMDX_ERR_BAD_INDEX, a NaN weight or mask value MMDX_ERR_INVALID_ARGUMENT; any other host mask value (negative, above 1) is used
+ *    as given, like a device one.
+ *  - Device pose arrays must be 16-byte aligned; device rate arrays, weights, mask_ids and masks 4-byte aligned.
+ *  - n_instances == 0 or row_items == 0 is MMDX_OK and launches nothing.  NULL model / args / a / b / weights / out, masks == NULL
+ *    with mask_ids and n_masks > 0, a struct_size mismatch of either structure, an unknown flag bit and reserved0 != 0 are
+ *    MMDX_ERR_INVALID_ARGUMENT; a MMDX_CREATE_HOST_ONLY model is MMDX_ERR_NO_DEVICE (after validation).  Models created with
+ *    MMDX_CREATE_FAST_MATH run the same, uncontracted kernels. */
+#define MMDX_MASK_NONE 0xFFFFFFFFu            /* no mask: every item's mask value is 1.0f */
+enum {
+    MMDX_BLEND_A_ON_DEVICE = 1u << 11,        /* a is a device pointer (else host, copied per call)                                */
+    MMDX_BLEND_B_ON_DEVICE = 1u << 12,        /* b is a device pointer                                                             */
+    MMDX_BLEND_PARAMS_ON_DEVICE = 1u << 13    /* weights, mask_ids and masks are device pointers, read when the kernel RUNS        */
+};
+typedef struct mmdx_row_blend_args {
+    uint32_t struct_size, flags;        /* = sizeof(mmdx_row_blend_args); the three above | MMDX_OUT_ON_DEVICE, any other bit:
+                                           MMDX_ERR_INVALID_ARGUMENT                                                               */
+    uint32_t n_instances, row_items;    /* NI; NB (poses) or NM (rates)                                                            */
+    const float *a, *b;                 /* poses [NI][row_items][MMDX_POSE_FLOATS]; rates [NI][row_items]                          */
+    const float *weights;               /* [NI]                                                                                    */
+    const uint32_t *mask_ids;           /* [NI] or NULL = MMDX_MASK_NONE for everyone                                              */
+    const float *masks;                 /* [n_masks][row_items]; may be NULL when n_masks == 0                                     */
+    uint32_t n_masks, reserved0;        /* reserved0 must be 0                                                                     */
+    float *out;                         /* same shape as a; may be == a or == b                                                    */
+} mmdx_row_blend_args;
+MMDX_API mmdx_status mmdx_pose_blend(mmdx_model_t model, const mmdx_row_blend_args *args,
+                                     const mmdx_instance_select *select /* NULL = every instance */);
+MMDX_API mmdx_status mmdx_rate_blend(mmdx_model_t model, const mmdx_row_blend_args *args,
+                                     const mmdx_instance_select *select /* NULL = every instance */);
+/* A mask row from the hierarchy, on the host (no device needed): out_mask[b] = inside when b or any ancestor of b is in roots, else
+ * outside.  Ancestors are followed through the parent array the skeleton was created from, as mmdx_skeleton_desc.parent defines it: a
+ * parent outside [0, NB) ends the chain, which is followed for at most NB steps.  n_roots == 0 fills `outside`; a root >= NB is
+ * MMDX_ERR_BAD_INDEX (nothing is written); NULL skeleton / out_mask, and NULL roots with n_roots > 0, are MMDX_ERR_INVALID_ARGUMENT. */
+MMDX_API mmdx_status mmdx_skeleton_subtree_mask(mmdx_skeleton_t skeleton, uint32_t n_roots, const uint32_t *roots, float inside,
+                                                float outside, float *out_mask /* [NB] host */);
 MMDX_API void mmdx_skeleton_destroy(mmdx_skeleton_t skeleton);
 /* Fills `desc` with pointers into `pmx` (valid until mmdx_pmx_destroy): rest positions, parents, transform
  * levels, flag words, append and IK tables exactly as the file states them (PmxReader,

@@ -27,6 +27,9 @@ CULL_VIEW_ON_DEVICE = 1  # mmdx_cull_args.flags: view is a device pointer, read 
 PLACE_ON_DEVICE, PLACE_MATRIX = 256, 512     # mmdx_place_args.flags (with PALETTE_ON_DEVICE / OUT_ON_DEVICE): placements is a device
 #                                              pointer; placements[i] is a 16-float matrix instead of an 8-float pose
 POSE_FLOATS = 8          # MMDX_POSE_FLOATS: translation xyz, 0, quaternion xyzw
+MASK_NONE = 0xFFFFFFFF   # MMDX_MASK_NONE: no mask, every item's mask value is 1.0f (mmdx_pose_blend / mmdx_rate_blend)
+BLEND_A_ON_DEVICE, BLEND_B_ON_DEVICE, BLEND_PARAMS_ON_DEVICE = 1 << 11, 1 << 12, 1 << 13   # mmdx_row_blend_args.flags (with OUT_ON_DEVICE):
+#                                              a, b, and {weights, mask_ids, masks} are device pointers
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
@@ -77,6 +80,13 @@ class PlaceArgs(C.Structure):
     """mmdx_place_args: palettes x per-instance world matrices (mmdx_palette_place)."""
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("reserved0", C.c_uint32),
                 ("palettes", C.c_void_p), ("placements", C.c_void_p), ("out_palettes", C.c_void_p)]
+
+
+class RowBlendArgs(C.Structure):
+    """mmdx_row_blend_args: two pose or rate arrays, a weight and a mask row per instance (mmdx_pose_blend / mmdx_rate_blend)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("row_items", C.c_uint32),
+                ("a", C.c_void_p), ("b", C.c_void_p), ("weights", C.c_void_p), ("mask_ids", C.c_void_p), ("masks", C.c_void_p),
+                ("n_masks", C.c_uint32), ("reserved0", C.c_uint32), ("out", C.c_void_p)]
 
 
 class BoneBoxInfo(C.Structure):
@@ -257,6 +267,11 @@ SIGNATURES = {
     "mmdx_skeleton_solve_pre": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                             C.c_void_p]),
     "mmdx_skeleton_solve_post": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    # the masked blend of two evaluated arrays: (model, mmdx_row_blend_args*, mmdx_instance_select* or NULL); and a mask row from the
+    # hierarchy: (skeleton, n_roots, roots, inside, outside, out_mask)
+    "mmdx_pose_blend": (C.c_int32, [C.c_void_p, C.POINTER(RowBlendArgs), C.POINTER(InstanceSelect)]),
+    "mmdx_rate_blend": (C.c_int32, [C.c_void_p, C.POINTER(RowBlendArgs), C.POINTER(InstanceSelect)]),
+    "mmdx_skeleton_subtree_mask": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
     "mmdx_skeleton_destroy": (None, [C.c_void_p]),
     "mmdx_graph_begin": (C.c_int32, [C.c_void_p]),
     "mmdx_graph_end": (C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -181,7 +181,8 @@ void free_model(mmdx_model_s *m) {
                           &m->skin2_w, &m->skin4_ids, &m->skin4_w, &m->bone_list, &m->ell,
                           &m->entries, &m->slot_top, &m->chain_off, &m->chain_rate, &m->pal, &m->rates,
                           &m->wslot, &m->morphed, &m->seen, &m->out_a, &m->out_b, &m->bnd, &m->sel, &m->cull,
-                          &m->place_in, &m->place_w, &m->place_out, &m->bone_boxes, &m->pbounds_in, &m->pbounds_out})
+                          &m->place_in, &m->place_w, &m->place_out, &m->bone_boxes, &m->pbounds_in, &m->pbounds_out,
+                          &m->blend_a, &m->blend_b, &m->blend_p, &m->blend_out, &m->blend_sel})
             b->release();
         if (m->bounce) (void)hipHostFree(m->bounce);
         if (m->bounce_in) (void)hipHostFree(m->bounce_in);

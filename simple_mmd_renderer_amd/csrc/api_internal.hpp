@@ -61,6 +61,10 @@ struct mmdx_model_s {
     mmdx::DevBuf place_in, place_w, place_out;   // mmdx_palette_place with host operands: palettes, placements, result
     mmdx::DevBuf bone_boxes;                     // static: the bone-box table of mmdx_palette_bounds (pbounds_kernels.hpp row layout)
     mmdx::DevBuf pbounds_in, pbounds_out;        // mmdx_palette_bounds with host operands: palettes, result
+    mmdx::DevBuf blend_a, blend_b, blend_p, blend_out;   // mmdx_pose_blend / mmdx_rate_blend with host operands: A, B, {weights, mask
+                                                         // ids, masks}, result
+    mmdx::DevBuf blend_sel;                      // ... with a host list: {live count, ids[live]}
+    std::vector<uint32_t> blend_sel_host;        // ... its source, alive until the copy has left it
     bool morphed_valid = false;     // `morphed` holds the result of a shared morph pass (MMDX_MORPH_UNCHANGED)
     std::vector<float> host_rates;  // ... and the host's copy of those rates when they came from host memory
     bool host_rates_valid = false;
@@ -74,7 +78,7 @@ struct mmdx_model_s {
     mmdx_debug_launch_shape last_shape{};     // ... and the rest of its shape (mmdx_debug_last_launch_shape); struct_size unused
     mmdx_model_s() {
         for (mmdx::DevBuf *b : {&pal, &rates, &wslot, &morphed, &out_a, &out_b, &bnd, &sel, &cull, &place_in, &place_w, &place_out, &pbounds_in,
-                                 &pbounds_out}) b->pin = &pin;
+                                 &pbounds_out, &blend_a, &blend_b, &blend_p, &blend_out, &blend_sel}) b->pin = &pin;
     }
     // page-locked bounce buffer for small outputs bound for pageable host memory (see mmdx_deform_batched)
     void *bounce = nullptr, *bounce_dev = nullptr;  // host address, device-side address

@@ -1,5 +1,5 @@
 // host_runtime.hpp -- the host plumbing every C-ABI file (api.cpp, rig_api.cpp, anim_api.cpp, place_api.cpp, pbounds_api.cpp,
-// cull_api.cpp, bench_api.cpp) takes from one place: the runtime services api.cpp defines, HIP_TRY, the device buffer, and the
+// cull_api.cpp, row_blend_api.cpp, bench_api.cpp) takes from one place: the runtime services api.cpp defines, HIP_TRY, the device buffer, and the
 // named steps a call is built from -- what a recording refuses, the preamble of a call on a model, the instance-list checks and
 // stager, the host round trip (stage_in / clock_in / route_out / finish).  No device code, no launch declarations.
 #pragma once

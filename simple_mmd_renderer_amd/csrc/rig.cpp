@@ -316,6 +316,7 @@ mmdx_status build_skeleton(const mmdx_skeleton_desc &d, SkeletonPlan &out, std::
     };
     for (uint32_t b = 0; b < nb; ++b)
         if (parent_of(b) == int64_t(b)) return bad(MMDX_ERR_INVALID_ARGUMENT, "bone " + std::to_string(b) + " is its own parent");
+    if (nb) out.parent.assign(d.parent, d.parent + nb);
     out.local_offset.resize(size_t(nb) * 4, 0.0f);
     out.neg_rest.resize(size_t(nb) * 4, 0.0f);
     for (uint32_t b = 0; b < nb; ++b) {

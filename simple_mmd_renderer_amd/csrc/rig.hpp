@@ -120,6 +120,7 @@ struct SkeletonPlan {
     uint32_t n_ik = 0, n_links = 0, n_append = 0, fast_slots = 0, n_fast = 0;
     bool serial = false;                        // IK or append bones present: the ordered solver, not parallel FK
     std::vector<uint32_t> order;                // evaluation sequence: pre-physics sorted, then post-physics sorted
+    std::vector<int32_t> parent;                // [nb] mmdx_skeleton_desc.parent as given (mmdx_skeleton_subtree_mask walks it)
     // parallel FK
     std::vector<float> local_offset;            // [nb][4] rest position relative to the parent (or absolute)
     std::vector<float> neg_rest;                // [nb][4] -rest position: translation row of the global offset

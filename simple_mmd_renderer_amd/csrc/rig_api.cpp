@@ -19,6 +19,7 @@
 #include "../../include/mmdx.h"
 #include "../../include/mmdx_bench.h"
 #include "anim_kernels.hpp"
+#include "bone_mask.hpp"
 #include "error.hpp"
 #include "graph_pin.hpp"
 #include "host_runtime.hpp"
@@ -737,6 +738,17 @@ mmdx_status mmdx_skeleton_get_info(mmdx_skeleton_t s, mmdx_skeleton_info *info) 
     info->n_solve_rounds = uint32_t(s->plan.rounds.size());
     info->n_ik_rounds_16_lanes = 0;
     for (uint8_t c : s->plan.round_coop) info->n_ik_rounds_16_lanes += (c && !s->plan.nested_ik) ? 1u : 0u;
+    return MMDX_OK;
+}
+
+// a mask row of mmdx_pose_blend from the hierarchy (bone_mask.hpp): host only, no device
+mmdx_status mmdx_skeleton_subtree_mask(mmdx_skeleton_t s, uint32_t n_roots, const uint32_t *roots, float inside, float outside,
+                                       float *out_mask) {
+    if (!s || !out_mask || (n_roots && !roots)) return fail(MMDX_ERR_INVALID_ARGUMENT, "skeleton / out_mask / roots is NULL");
+    const int64_t bad = subtree_mask(s->plan.parent.data(), s->plan.nb, roots, n_roots, inside, outside, out_mask);
+    if (bad >= 0)
+        return fail(MMDX_ERR_BAD_INDEX, "roots[" + std::to_string(bad) + "] = " + std::to_string(roots[bad]) + " is not a bone of the skeleton (" +
+                                        std::to_string(s->plan.nb) + " bones)");
     return MMDX_OK;
 }
 

@@ -487,10 +487,49 @@ public:
         const mmdx_instance_select s = select(ids, count, n_ids, list_on_device);
         check(mmdx_motion_set_blend_morphs_time_select(set_, poser_.handle(), &operands, &s, out_rates));
     }
+    // Layers (mmdx.h, mmdx_pose_blend / mmdx_rate_blend): out[i][item] = the cross-fade's blend of a[i][item] and b[i][item] at
+    // weights[i] * masks[mask_ids[i]][item] -- the upper body from one animator over the legs of another, a talking face over a
+    // dancing body.  a, b, out are [n][row_items][8] poses (BlendPoses) or [n][row_items] rates (BlendRates); out may be a or b;
+    // mask_ids may be NULL (no masks: the cross-fade itself) and holds MMDX_MASK_NONE for an instance without one.  Items whose
+    // effective weight is below 1e-7 never read b, so the layer's rows need evaluating for the instances that wear it only.  Host
+    // arrays by default; with on_device = true everything is device memory and the call is asynchronous on the poser's stream
+    // (recordable); ids / count / n_ids then restrict it to a listed subset (NULL ids = everyone), every other row keeps its bytes.
+    void BlendPoses(uint32_t n, uint32_t row_items, const float *a, const float *b, const float *weights, const uint32_t *mask_ids,
+                    const float *masks, uint32_t n_masks, float *out, bool on_device = false, const uint32_t *ids = nullptr,
+                    const uint32_t *count = nullptr, uint32_t n_ids = 0, bool list_on_device = true) {
+        const mmdx_row_blend_args r = row_blend_args(n, row_items, a, b, weights, mask_ids, masks, n_masks, out, on_device);
+        const mmdx_instance_select s = select(ids, count, n_ids, list_on_device);
+        check(mmdx_pose_blend(poser_.handle(), &r, ids ? &s : nullptr));
+    }
+    void BlendRates(uint32_t n, uint32_t row_items, const float *a, const float *b, const float *weights, const uint32_t *mask_ids,
+                    const float *masks, uint32_t n_masks, float *out, bool on_device = false, const uint32_t *ids = nullptr,
+                    const uint32_t *count = nullptr, uint32_t n_ids = 0, bool list_on_device = true) {
+        const mmdx_row_blend_args r = row_blend_args(n, row_items, a, b, weights, mask_ids, masks, n_masks, out, on_device);
+        const mmdx_instance_select s = select(ids, count, n_ids, list_on_device);
+        check(mmdx_rate_blend(poser_.handle(), &r, ids ? &s : nullptr));
+    }
+    // A mask row for BlendPoses from the hierarchy (mmdx_skeleton_subtree_mask, host only): `inside` for every bone that is one of
+    // roots or has one among its ancestors, `outside` for the rest.
+    std::vector<float> SubtreeMask(const std::vector<uint32_t> &roots, float inside = 1.0f, float outside = 0.0f) const {
+        std::vector<float> mask(poser_.bone_names().size());
+        check(mmdx_skeleton_subtree_mask(poser_.skeleton(), uint32_t(roots.size()), roots.data(), inside, outside, mask.data()));
+        return mask;
+    }
     mmdx_motion_set_t handle() const { return set_; }
     Poser &poser() const { return poser_; }
 
 private:
+    static mmdx_row_blend_args row_blend_args(uint32_t n, uint32_t row_items, const float *a, const float *b, const float *weights,
+                                              const uint32_t *mask_ids, const float *masks, uint32_t n_masks, float *out, bool on_device) {
+        mmdx_row_blend_args r{};
+        r.struct_size = sizeof(r);
+        r.flags = on_device ? uint32_t(MMDX_BLEND_A_ON_DEVICE | MMDX_BLEND_B_ON_DEVICE | MMDX_BLEND_PARAMS_ON_DEVICE | MMDX_OUT_ON_DEVICE) : 0u;
+        r.n_instances = n; r.row_items = row_items;
+        r.a = a; r.b = b; r.weights = weights;
+        r.mask_ids = mask_ids; r.masks = masks; r.n_masks = n_masks;
+        r.out = out;
+        return r;
+    }
     static mmdx_instance_select select(const uint32_t *ids, const uint32_t *count, uint32_t n_ids, bool on_device) {
         mmdx_instance_select s{};
         s.struct_size = sizeof(s);

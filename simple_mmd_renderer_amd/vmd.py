@@ -265,6 +265,69 @@ def instance_select(ids_ptr, n_ids: int, count_ptr=None, on_device=True) -> "api
     return s
 
 
+# ---- layers: the masked blend of two evaluated pose or rate arrays (mmdx_pose_blend / mmdx_rate_blend) -----------------------
+MASK_NONE = api.MASK_NONE                # MMDX_MASK_NONE: this instance blends every item at its full weight
+
+
+def _blend_rows_host(fn, a, b, weights, masks, mask_ids, model, item_floats):
+    a = np.ascontiguousarray(a, np.float32)
+    b = np.ascontiguousarray(b, np.float32)
+    if a.shape != b.shape or a.ndim != (3 if item_floats > 1 else 2) or (item_floats > 1 and a.shape[2] != item_floats):
+        raise ValueError("a and b must have one shape: [NI, items, 8] for poses, [NI, items] for rates")
+    ni, items = a.shape[0], a.shape[1]
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if w.size != ni:
+        raise ValueError("one weight per instance")
+    keep = [a, b, w]
+    args = api.RowBlendArgs(C.sizeof(api.RowBlendArgs), 0, ni, items, a.ctypes.data, b.ctypes.data, w.ctypes.data, None, None, 0, 0, None)
+    if mask_ids is not None:
+        ids = np.ascontiguousarray(mask_ids, np.uint32).reshape(-1)
+        if ids.size != ni:
+            raise ValueError("one mask id per instance")
+        m = np.ascontiguousarray(masks if masks is not None else np.zeros((0, items)), np.float32).reshape(-1, items)
+        keep += [ids, m]
+        args.mask_ids, args.masks, args.n_masks = ids.ctypes.data, m.ctypes.data if m.size else None, m.shape[0]
+    out = np.empty_like(a)
+    args.out = out.ctypes.data
+    api.check(fn(model.h if model is not None else None, C.byref(args), None))
+    return out
+
+
+def blend_poses(a, b, weights, masks=None, mask_ids=None, model=None) -> np.ndarray:
+    """Host convenience (mmdx_pose_blend; `model` is required: it supplies the device and stream): poses a, b f32 [NI, items, 8],
+    weights [NI], masks f32 [n_masks, items] and mask_ids u32 [NI] (MASK_NONE = no mask; None = nobody has one) -> poses f32
+    [NI, items, 8]: per item the cross-fade's blend at weights[i] * masks[mask_ids[i]][item]."""
+    return _blend_rows_host(api.lib().mmdx_pose_blend, a, b, weights, masks, mask_ids, model, POSE_FLOATS)
+
+
+def blend_rates(a, b, weights, masks=None, mask_ids=None, model=None) -> np.ndarray:
+    """The same for morph rates (mmdx_rate_blend): a, b f32 [NI, items] -> f32 [NI, items]."""
+    return _blend_rows_host(api.lib().mmdx_rate_blend, a, b, weights, masks, mask_ids, model, 1)
+
+
+def _blend_rows_device(fn, n_instances, row_items, a_ptr, b_ptr, weights_ptr, out_ptr, masks_ptr, n_masks, mask_ids_ptr, model, select):
+    args = api.RowBlendArgs(C.sizeof(api.RowBlendArgs),
+                            api.BLEND_A_ON_DEVICE | api.BLEND_B_ON_DEVICE | api.BLEND_PARAMS_ON_DEVICE | api.OUT_ON_DEVICE,
+                            n_instances, row_items, a_ptr, b_ptr, weights_ptr, mask_ids_ptr, masks_ptr, n_masks, 0, out_ptr)
+    api.check(fn(model.h if model is not None else None, C.byref(args), C.byref(select) if select is not None else None))
+
+
+def blend_poses_device(n_instances: int, row_items: int, a_ptr, b_ptr, weights_ptr, out_ptr, masks_ptr=None, n_masks: int = 0,
+                       mask_ids_ptr=None, model=None, select=None) -> None:
+    """a, b, out f32[NI][row_items][8] (out may be a or b), weights f32[NI], mask_ids u32[NI] (or None) and masks
+    f32[n_masks][row_items] resident in HBM; asynchronous on the model's stream.  select: an instance_select(...) -- only the listed
+    instances are blended, every other row of out keeps its bytes."""
+    _blend_rows_device(api.lib().mmdx_pose_blend, n_instances, row_items, a_ptr, b_ptr, weights_ptr, out_ptr, masks_ptr, n_masks,
+                       mask_ids_ptr, model, select)
+
+
+def blend_rates_device(n_instances: int, row_items: int, a_ptr, b_ptr, weights_ptr, out_ptr, masks_ptr=None, n_masks: int = 0,
+                       mask_ids_ptr=None, model=None, select=None) -> None:
+    """The same for morph rates: a, b, out f32[NI][row_items]."""
+    _blend_rows_device(api.lib().mmdx_rate_blend, n_instances, row_items, a_ptr, b_ptr, weights_ptr, out_ptr, masks_ptr, n_masks,
+                       mask_ids_ptr, model, select)
+
+
 class MotionSet:
     """A bank of clips bound to one model (mmdx_motion_set_t): every instance of a crowd plays its own clip, clips[i], at its own
     frame or time.  bone_motions / morph_motions: sequences of BoneMotion / MorphMotion, one per clip, at least one of the two;
@@ -612,6 +675,15 @@ class Skeleton:
         d = {k: int(getattr(s, k)) for k, _ in api.DebugSolveShape._fields_ if k not in ("struct_size", "reserved0")}
         d["solver"] = api.DEBUG_SOLVERS[d["solver"]]
         return d
+
+    def subtree_mask(self, roots, inside: float = 1.0, outside: float = 0.0) -> np.ndarray:
+        """A mask row for blend_poses from the hierarchy (mmdx_skeleton_subtree_mask, host only): f32 [NB] holding `inside` for
+        every bone that is one of `roots` or has one among its ancestors, `outside` for the rest."""
+        r = np.ascontiguousarray(roots, np.uint32).reshape(-1)
+        out = np.empty(self.nb, np.float32)
+        api.check(api.lib().mmdx_skeleton_subtree_mask(self.h, r.size, r.ctypes.data if r.size else None, inside, outside,
+                                                       out.ctypes.data))
+        return out
 
     def solve(self, poses, model=None, morph_weights=None) -> np.ndarray:
         """Host convenience: poses f32 [NI, NB, 8] (+ morph rates [NI, NM] or shared [NM]) -> palettes
