@@ -74,7 +74,9 @@ extern "C" {
  *    mmdx_skeleton_solve_motion_set_blend_time_select (new entry points over the existing mmdx_motion_blend_args and
  *    mmdx_instance_select; nothing existing changes).
  *    mmdx_pose_blend and mmdx_rate_blend with mmdx_row_blend_args, MMDX_MASK_NONE and MMDX_BLEND_A_ON_DEVICE / _B_ / _PARAMS_, and
- *    mmdx_skeleton_subtree_mask (new entry points, a structure and three flag bits no other call accepts; nothing existing changes). */
+ *    mmdx_skeleton_subtree_mask (new entry points, a structure and three flag bits no other call accepts; nothing existing changes).
+ *    mmdx_animator_root_motion with mmdx_root_motion_args and MMDX_ROOT_X / _Y / _Z, mmdx_bone_motion_in_place, and
+ *    mmdx_bone_motion_get_keys with mmdx_bone_motion_keys (three new entry points and two structures; nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -653,6 +655,21 @@ MMDX_API mmdx_status mmdx_vmd_bind_bones(mmdx_vmd_t vmd, uint32_t n_bones,
 MMDX_API mmdx_status mmdx_bone_motion_get_info(mmdx_bone_motion_t motion, uint32_t *n_bones,
                                                uint32_t *n_mapped, uint32_t *n_keys,
                                                uint32_t *n_curves);
+/* The host key tables of a bound motion, as mmdx_vmd_bind_bones / mmdx_bone_motion_in_place built them and as they are uploaded on
+ * first use: what each model bone received from the file (an adopter can look at what was bound; the tests compare an in-place
+ * copy with its source byte for byte).  Host only.  The pointers are the handle's own arrays, read-only, valid until
+ * mmdx_bone_motion_destroy.  NULL motion / out or a struct_size mismatch: MMDX_ERR_INVALID_ARGUMENT. */
+typedef struct mmdx_bone_motion_keys {
+    uint32_t struct_size;            /* = sizeof(mmdx_bone_motion_keys), set by the caller                                         */
+    uint32_t n_bones, n_keys, n_curves;
+    const uint32_t *key_off;         /* [n_bones + 1]: the keys of bone b are key_off[b] .. key_off[b + 1]                         */
+    const uint32_t *key_frame;       /* [n_keys], ascending inside a bone                                                          */
+    const float *key_tr;             /* [n_keys][4]: translation xyz, 0                                                            */
+    const float *key_rot;            /* [n_keys][4]: quaternion xyzw                                                               */
+    const uint32_t *key_curve;       /* [n_keys][4]: curve table id for x, y, z, rotation; 0xFFFFFFFF = linear                     */
+    const float *lut;                /* [n_curves][32]: the presampled curves                                                      */
+} mmdx_bone_motion_keys;
+MMDX_API mmdx_status mmdx_bone_motion_get_keys(mmdx_bone_motion_t motion, mmdx_bone_motion_keys *out);
 /* out_poses[i][b][MMDX_POSE_FLOATS] = local pose of model bone b at frames[i].  Stream and device as
  * for mmdx_morph_motion_eval.  flags: MMDX_FRAMES_ON_DEVICE | MMDX_OUT_ON_DEVICE. */
 MMDX_API mmdx_status mmdx_bone_motion_eval(mmdx_bone_motion_t motion, mmdx_model_t model,
@@ -996,6 +1013,63 @@ MMDX_API mmdx_status mmdx_animator_request(mmdx_animator_t animator, mmdx_model_
                                            const uint32_t *clips, const float *fades, const double *start_times, uint32_t flags);
 /* flags: MMDX_ANIM_DT_ON_DEVICE or 0; unknown bits are rejected. */
 MMDX_API mmdx_status mmdx_animator_advance(mmdx_animator_t animator, mmdx_model_t model, const double *dt, uint32_t flags);
+
+/* ---- Root motion: the animator walks its crowd through the world -----------------------------------------------------------------
+ * mmdx_animator_root_motion adds, to every instance's placement (the pose form of mmdx_palette_place, in device memory), the
+ * displacement the playing clips give a root bone during the step that mmdx_animator_advance is ABOUT to take: call it BEFORE
+ * advance, with the same dt, on the state advance is about to step.  It reads the animator's arrays and writes only
+ * placements[i][0..2]; the fourth float, the quaternion and every animator array keep their bytes.
+ *
+ * `set` is any bone-sided set with the animator's clip count (another count: MMDX_ERR_INVALID_ARGUMENT); it need not be the set the
+ * poses come from.  The intended cheap form: bind every VMD to the single name of the root bone (mmdx_vmd_bind_bones with one
+ * name) -- a one-bone bank, root_bone = 0 -- so the call reads a few keys per instance whatever the model's bone count.
+ *
+ * The arithmetic is part of the contract, like advance's: IEEE operations only, unfused.  R(c, t) is the translation in the row
+ * that mmdx_motion_set_eval_bones_time writes for (clip c, time t, bone root_bone), {0,0,0} when c >= n_clips.  A NaN dt writes
+ * nothing.  Otherwise, for every instance i, with the state as it stands before advance:
+ *   1. s = double(speed) * dt                                      (step 1 of advance)
+ *   2. the displacement of a side (c, t0):  raw = t0 + s;  t1 = wrap(c, raw)   (advance's wrap, above)
+ *        the wrap did not fold (a HOLD / THEN clamp included):  D = R(c,t1) - R(c,t0)
+ *        it folded:                                             D = (R(c,near) - R(c,t0)) + (R(c,t1) - R(c,far))
+ *            with near = L(c), far = 0.0 when raw >= L(c); near = 0.0, far = L(c) otherwise (a negative step).  Further whole
+ *            laps inside one step are not counted, just as `loops` counts one.
+ *        Each - and + is libmmd's Vector3D operator: per component, binary32, in the order written.
+ *   3. D_a = the displacement of (clips_a, times_a); D_b = that of (clips_b, times_b) when fade_rate > 0, else {+0,+0,+0}
+ *   4. blend with the weight before the step, w = weights[i], by the cross-fade's rules (mmdx_motion_blend_args):
+ *        !(w >= 1e-7f): D = D_a, and side b is neither evaluated nor read;  w > 1.0f - 1e-7f: D = D_b, side a is not evaluated;
+ *        otherwise D.c = D_a.c * (1.0f - w) + D_b.c * w per component
+ *   5. a component whose bit is absent from `axes` becomes +0.0f (a select, not a multiply)
+ *   6. M = ToRotateMatrix of placements[i][4..7] as in mmdx_palette_place (the quaternion is not normalised);
+ *      d = rotate(D, M) (L/util/math_impl.inl:1032-1038): d.c = D.x*M[0][c] + D.y*M[1][c] + D.z*M[2][c], left to right;
+ *      placements[i][c] = placements[i][c] + d.c
+ * There are no other short circuits: NaN and infinity propagate as IEEE gives them (a NaN's sign and payload are outside the
+ * contract, as in mmdx_palette_place).  Clip changes advance makes in its step 4 (a request, a THEN successor, a switch at once)
+ * contribute nothing: the new clip starts at its t0.  Turning is out of scope (no rotation deltas, no matrix-form placements, no
+ * select form: a culled character keeps walking, as its clock keeps running).
+ *
+ * NULL animator / set / args / dt / placements, a struct_size mismatch, unknown flag or axes bits, a misaligned device dt (8) or
+ * placements (4), a set without a bone side and a host NaN dt are MMDX_ERR_INVALID_ARGUMENT; root_bone >= the set's bone count is
+ * MMDX_ERR_BAD_INDEX.  Device, stream and graph rules are advance's: asynchronous on `model`'s stream, a model of another device
+ * than the animator's is refused, recordable after one unrecorded run (a host dt is frozen into the recording), and both the
+ * animator and the set are pinned by a graph that holds them.
+ *
+ * mmdx_bone_motion_in_place (host only) is the other half: a copy of `src` in which the translation of every key of `bone` is
+ * +0.0f on the axes named, everything else byte for byte the same.  The zeroed channels evaluate to zero at every time (the lerp
+ * of two zeros), so a set made of such motions gives the poses whose motion has been taken out, through every existing call --
+ * the one-launch blend solve included -- at no per-frame cost; the whole-model shift is what the placement then carries.  This is
+ * a faithful split only when every moved bone descends from `bone` (the adopter's choice of root, such as PMX's "mother" bone); the call does
+ * not check it.  NULL src / out and unknown axes bits: MMDX_ERR_INVALID_ARGUMENT; bone >= the motion's bone count: MMDX_ERR_BAD_INDEX. */
+enum { MMDX_ROOT_X = 1u, MMDX_ROOT_Y = 2u, MMDX_ROOT_Z = 4u };
+typedef struct mmdx_root_motion_args {
+    uint32_t struct_size, flags;   /* = sizeof(mmdx_root_motion_args); flags: MMDX_ANIM_DT_ON_DEVICE or 0, other bits rejected      */
+    uint32_t root_bone;            /* a bone of `set` (< its n_bones)                                                              */
+    uint32_t axes;                 /* MMDX_ROOT_X | _Y | _Z; bits outside rejected; 0 allowed (nothing moves)                      */
+    const double *dt;              /* as mmdx_animator_advance: a host value, or a device double with the flag                     */
+    float *placements;             /* DEVICE, [NI][MMDX_POSE_FLOATS], the pose form of mmdx_palette_place; 4-byte aligned          */
+} mmdx_root_motion_args;
+MMDX_API mmdx_status mmdx_animator_root_motion(mmdx_animator_t animator, mmdx_motion_set_t set, mmdx_model_t model,
+                                               const mmdx_root_motion_args *args);
+MMDX_API mmdx_status mmdx_bone_motion_in_place(mmdx_bone_motion_t src, uint32_t bone, uint32_t axes, mmdx_bone_motion_t *out_motion);
 
 /* ---- where every instance stands: palette x world matrix ----------------------------------------------------------------------
  * Every palette the solves above write is in model space.  mmdx_palette_place multiplies each skinning matrix of instance i on the

@@ -89,6 +89,21 @@ class RowBlendArgs(C.Structure):
                 ("n_masks", C.c_uint32), ("reserved0", C.c_uint32), ("out", C.c_void_p)]
 
 
+ROOT_X, ROOT_Y, ROOT_Z = 1, 2, 4          # MMDX_ROOT_*: the axes of mmdx_animator_root_motion / mmdx_bone_motion_in_place
+
+
+class RootMotionArgs(C.Structure):
+    """mmdx_root_motion_args: the root bone, the axes, the step and the placements of mmdx_animator_root_motion."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("root_bone", C.c_uint32), ("axes", C.c_uint32),
+                ("dt", C.c_void_p), ("placements", C.c_void_p)]
+
+
+class BoneMotionKeys(C.Structure):
+    """mmdx_bone_motion_keys: the host key tables of a bound bone motion (mmdx_bone_motion_get_keys)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_bones", C.c_uint32), ("n_keys", C.c_uint32), ("n_curves", C.c_uint32),
+                ("key_off", _u32p), ("key_frame", _u32p), ("key_tr", _f32p), ("key_rot", _f32p), ("key_curve", _u32p), ("lut", _f32p)]
+
+
 class BoneBoxInfo(C.Structure):
     """mmdx_bone_box_info: the scalars of a model's bone-box table (mmdx_model_get_bone_boxes)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_boxes", C.c_uint32), ("n_nonconvex", C.c_uint32), ("max_vertex_entries", C.c_uint32),
@@ -259,6 +274,10 @@ SIGNATURES = {
     "mmdx_animator_get_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmdx_animator_request": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "mmdx_animator_advance": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    # root motion: (animator, set, model, mmdx_root_motion_args*); (bone motion, bone, axes, out)
+    "mmdx_animator_root_motion": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RootMotionArgs)]),
+    "mmdx_bone_motion_in_place": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "mmdx_bone_motion_get_keys": (C.c_int32, [C.c_void_p, C.POINTER(BoneMotionKeys)]),
     "mmdx_skeleton_solve_morphed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),
     # (skeleton, model, n_instances, poses, morph_weights, flags, mmdx_instance_select*, out)

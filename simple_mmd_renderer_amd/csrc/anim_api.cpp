@@ -12,12 +12,16 @@
 
 #include "../../include/mmdx.h"
 #include "anim_kernels.hpp"
+#include "api_internal.hpp"
 #include "error.hpp"
 #include "graph_pin.hpp"
 #include "host_runtime.hpp"
+#include "rig_kernels.hpp"
+#include "root_math.hpp"
 
 using namespace mmdx;
 
+static_assert(kRootX == MMDX_ROOT_X && kRootY == MMDX_ROOT_Y && kRootZ == MMDX_ROOT_Z, "root_math.hpp restates mmdx.h");
 static_assert(kAnimClipNone == MMDX_CLIP_NONE && kAnimNoRequest == MMDX_ANIM_NO_REQUEST, "anim_math.hpp restates mmdx.h");
 static_assert(kAnimLoop == MMDX_ANIM_LOOP && kAnimHold == MMDX_ANIM_HOLD && kAnimThen == MMDX_ANIM_THEN, "anim_math.hpp restates mmdx.h");
 
@@ -366,6 +370,43 @@ mmdx_status mmdx_animator_advance(mmdx_animator_t a, mmdx_model_t model, const d
     if (mmdx_status r = state_to_device(a, device)) return r;
     graph_note_handle(model, &a->pin);
     HIP_TRY(launch_animator_advance(a->arrays, a->table, on_device ? 0.0 : *dt, on_device ? dt : nullptr, st));
+    return MMDX_OK;
+}
+
+mmdx_status mmdx_animator_root_motion(mmdx_animator_t a, mmdx_motion_set_t set, mmdx_model_t model, const mmdx_root_motion_args *args) {
+    if (!a || !set || !args) return fail(MMDX_ERR_INVALID_ARGUMENT, "animator / set / args is NULL");
+    if (args->struct_size != sizeof(mmdx_root_motion_args)) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_root_motion_args.struct_size mismatch");
+    if (!args->dt || !args->placements) return fail(MMDX_ERR_INVALID_ARGUMENT, "dt / placements is NULL");
+    if (args->flags & ~uint32_t(MMDX_ANIM_DT_ON_DEVICE)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    if (args->axes & ~uint32_t(MMDX_ROOT_X | MMDX_ROOT_Y | MMDX_ROOT_Z)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown axes bits");
+    const SetBoneSide side = motion_set_bone_side(set);
+    if (!side.has_bones) return fail(MMDX_ERR_INVALID_ARGUMENT, "this motion set was created without bone motions");
+    if (side.n_clips != a->n_clips)
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "the set has " + std::to_string(side.n_clips) + " clips, the animator's table " +
+                                               std::to_string(a->n_clips));
+    if (args->root_bone >= side.nb)
+        return fail(MMDX_ERR_BAD_INDEX, "root_bone = " + std::to_string(args->root_bone) + ": the set has " + std::to_string(side.nb) + " bones");
+    if (reinterpret_cast<uintptr_t>(args->placements) & 3) return fail(MMDX_ERR_INVALID_ARGUMENT, "placements must be 4-byte aligned");
+    const bool on_device = (args->flags & MMDX_ANIM_DT_ON_DEVICE) != 0;
+    if (on_device) {
+        if (reinterpret_cast<uintptr_t>(args->dt) & 7) return fail(MMDX_ERR_INVALID_ARGUMENT, "a device dt must be 8-byte aligned");
+    } else if (is_nan(*args->dt)) {
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "dt is NaN");
+    }
+    int device;
+    hipStream_t st;
+    if (mmdx_status r = resolve_stream(model, &device, &st)) return r;
+    if (mmdx_status r = refuse_recording(0, 0, device, {side.device},
+                                         "while a graph is being recorded the motion set must have run on this device before"))
+        return r;
+    if (mmdx_status r = state_to_device(a, device)) return r;
+    BoneTrackParams p;
+    if (mmdx_status r = motion_set_bone_tables(set, model, device, &p)) return r;
+    graph_note_handle(model, &a->pin);
+    const AnimArrays &s = a->arrays;
+    const RootMotionParams rp{s.clips_a, s.clips_b, s.times_a, s.times_b, s.weights, s.speed, s.fade_rate, s.ni, a->table,
+                              args->root_bone, args->axes, args->placements};
+    HIP_TRY(launch_animator_root_motion(p, rp, on_device ? 0.0 : *args->dt, on_device ? args->dt : nullptr, st));
     return MMDX_OK;
 }
 

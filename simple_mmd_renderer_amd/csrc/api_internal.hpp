@@ -19,6 +19,7 @@
 #include "kernels.hpp"
 #include "launch_shape.hpp"
 #include "plan.hpp"
+#include "rig.hpp"
 
 namespace mmdx {
 
@@ -31,6 +32,16 @@ std::vector<float> bone_box_device_table(const Plan &p);   // pbounds_api.cpp: t
 // average ms of `iters` store-pattern launches on the default stream (after one warm-up launch); bench_api.cpp
 hipError_t time_store_pattern(void *a, void *b, uint32_t nv, uint32_t ni, uint32_t bpva, uint32_t bpvb, int iters, float *avg_ms,
                               uint32_t pitch = 0);   // pitch: vertices from one instance to the next (0 = nv)
+// rig_api.cpp, the owner of the motion-set handle, for mmdx_animator_root_motion (anim_api.cpp): what a set says about its bone
+// side without the device ...
+struct SetBoneSide {
+    bool has_bones;
+    uint32_t n_clips, nb;
+    int device;                                 // where its tables are, -1 = nowhere yet
+};
+SetBoneSide motion_set_bone_side(const mmdx_motion_set_s *set);
+// ... and its bone tables on `device` as a parameter block (clock and output fields empty), the set noted in `model`'s recording
+mmdx_status motion_set_bone_tables(mmdx_motion_set_s *set, mmdx_model_t model, int device, BoneTrackParams *p);
 
 }  // namespace mmdx
 

@@ -19,6 +19,7 @@
 #include "../../include/mmdx.h"
 #include "../../include/mmdx_bench.h"
 #include "anim_kernels.hpp"
+#include "api_internal.hpp"
 #include "bone_mask.hpp"
 #include "error.hpp"
 #include "graph_pin.hpp"
@@ -173,6 +174,17 @@ static mmdx_status set_to_device(mmdx_motion_set_t set, int device) {
         HIP_TRY(set->m_weights.upload(h.morph_weights));
     }
     set->device = device;
+    return MMDX_OK;
+}
+
+SetBoneSide mmdx::motion_set_bone_side(const mmdx_motion_set_s *set) {
+    return {set->host.has_bones, set->host.n_clips, set->host.has_bones ? set->host.bones.nb : 0u, set->device};
+}
+
+mmdx_status mmdx::motion_set_bone_tables(mmdx_motion_set_s *set, mmdx_model_t model, int device, BoneTrackParams *p) {
+    if (mmdx_status r = set_to_device(set, device)) return r;
+    graph_note_handle(model, &set->pin);
+    *p = set->t.params(set->host.bones.nb, 0);
     return MMDX_OK;
 }
 
@@ -696,6 +708,42 @@ mmdx_status mmdx_bone_motion_eval_time(mmdx_bone_motion_t m, mmdx_model_t model,
         return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or n_instances == 0");
     if (mmdx_status r = check_time_args(times, n_instances, flags, MMDX_TIMES_ON_DEVICE | MMDX_OUT_ON_DEVICE)) return r;
     return bone_motion_eval(m, model, n_instances, times, true, flags, out_poses);
+}
+
+mmdx_status mmdx_bone_motion_in_place(mmdx_bone_motion_t src, uint32_t bone, uint32_t axes, mmdx_bone_motion_t *out) {
+    if (!out) return fail(MMDX_ERR_INVALID_ARGUMENT, "out_motion is NULL");
+    *out = nullptr;
+    if (!src) return fail(MMDX_ERR_INVALID_ARGUMENT, "motion is NULL");
+    if (axes & ~uint32_t(MMDX_ROOT_X | MMDX_ROOT_Y | MMDX_ROOT_Z)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown axes bits");
+    if (bone >= src->host.nb)
+        return fail(MMDX_ERR_BAD_INDEX, "bone = " + std::to_string(bone) + ": the motion is bound to " + std::to_string(src->host.nb) + " bones");
+    try {
+        std::unique_ptr<mmdx_bone_motion_s> m(new mmdx_bone_motion_s);
+        m->host = src->host;                                 // the tables only: the copy uploads its own on first use
+        for (uint32_t k = m->host.key_off[bone]; k < m->host.key_off[bone + 1]; ++k)
+            for (uint32_t c = 0; c < 3; ++c)
+                if (axes & (1u << c)) m->host.key_tr[size_t(k) * 4 + c] = 0.0f;
+        *out = m.release();
+    } catch (const std::bad_alloc &) {
+        return fail(MMDX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    }
+    return MMDX_OK;
+}
+
+mmdx_status mmdx_bone_motion_get_keys(mmdx_bone_motion_t m, mmdx_bone_motion_keys *out) {
+    if (!m || !out || out->struct_size != sizeof(mmdx_bone_motion_keys))
+        return fail(MMDX_ERR_INVALID_ARGUMENT, "NULL argument or mmdx_bone_motion_keys.struct_size mismatch");
+    const BoneMotionHost &h = m->host;
+    out->n_bones = h.nb;
+    out->n_keys = uint32_t(h.key_frame.size());
+    out->n_curves = uint32_t(h.lut.size() / kCurveSamples);
+    out->key_off = h.key_off.data();
+    out->key_frame = h.key_frame.data();
+    out->key_tr = h.key_tr.data();
+    out->key_rot = h.key_rot.data();
+    out->key_curve = h.key_curve.data();
+    out->lut = h.lut.data();
+    return MMDX_OK;
 }
 
 void mmdx_bone_motion_destroy(mmdx_bone_motion_t m) {

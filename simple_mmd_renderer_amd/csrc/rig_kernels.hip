@@ -9,6 +9,7 @@
 #include "motion_clock.hpp"
 #include "rig.hpp"
 #include "rig_kernels.hpp"
+#include "root_math.hpp"
 #include "solve_shape.hpp"
 
 #include <atomic>
@@ -1203,7 +1204,74 @@ __global__ __launch_bounds__(kBoneMorphThreads) void physics_override_kernel(con
     }
 }
 
+// ---- root motion (mmdx_animator_root_motion; include/mmdx.h states the arithmetic, root_math.hpp holds it) ------------------------
+// The displacement the playing clips give the root bone during the step mmdx_animator_advance is about to take, rotated by the
+// instance's heading and added to placements[i][0..2].  An instance needs up to eight track evaluations -- two sides, each at t0,
+// t1 and, when the step crosses a loop seam, at both ends of the seam -- and each is a chain of dependent loads (the key search)
+// that the compiler does not overlap with another one inlined into the same lane.  So:
+//   eight lanes per instance   lane = side * 4 + {t0, t1, near, far}; eight instances per wave, 64 per workgroup.  Every lane runs at
+//                              most one eval_bone_pose<TimeClock>, and none where the value is not needed: a side the weight does
+//                              not read (its clip id and clock are not loaded either), near / far without a fold, an id outside
+//                              the bank (R = 0).
+//   the group's first lane     collects the seven other translations and side b's fold flag with __shfl inside its eight lanes
+//                              (groups leave whole at the array's end, so every lane it reads from is alive), then does steps 2-6
+//                              in the stated order and stores 12 bytes.  The fourth float and the quaternion are never written.
+//   clip table, dt             read as animator_advance_kernel reads them; a NaN dt returns before any store.
+constexpr uint32_t kRootLanes = 8, kRootThreads = 512;
+static_assert(kRootSideA == kBlendA && kRootSideB == kBlendB && kRootSideMix == kBlendMix, "root_math.hpp restates motion_blend.hpp");
+
+struct RootBlendRate {
+    __device__ __forceinline__ float operator()(const float a, const float b, const float w) const { return blend_rate(a, b, w); }
+};
+
+__global__ __launch_bounds__(kRootThreads) void animator_root_motion_kernel(const BoneTrackParams p, const RootMotionParams r, double dt,
+                                                                            const double *dt_dev) {
+    if (dt_dev) dt = *dt_dev;
+    if (dt != dt) return;
+    const size_t tid = size_t(blockIdx.x) * kRootThreads + threadIdx.x;
+    if (tid / kRootLanes >= r.ni) return;                  // a whole group of eight
+    const uint32_t i = uint32_t(tid / kRootLanes), sub = uint32_t(tid % kRootLanes);
+    const uint32_t lane_side = sub / 4, which = sub % 4;
+    const float w = r.weights[i];
+    const uint32_t side = blend_side(w);
+    // side a is read unless the row is B; side b unless the row is A, and only while a fade runs (else its displacement is +0)
+    const bool reads = lane_side == 0 ? side != kBlendB : (side != kBlendA && r.fade_rate[i] > 0.0f);
+    float4 t = make_float4(0.f, 0.f, 0.f, 0.f), q;
+    uint32_t folded = 0;
+    if (reads) {
+        const uint32_t c = (lane_side ? r.clips_b : r.clips_a)[i];
+        const double t0 = (lane_side ? r.times_b : r.times_a)[i];
+        const RootTimes rt = root_times(r.k, c, t0, double(r.speed[i]) * dt);
+        folded = rt.folded;
+        if (c < r.k.n_clips && (which < kRootNear || folded))
+            eval_bone_pose(clip_of(p, c), r.root_bone, TimeClock{root_time_of(rt, which) * 30.0}, t, q);
+    }
+    RootVec at[kRootLanes];
+#pragma unroll
+    for (uint32_t j = 0; j < kRootLanes; ++j) at[j] = {__shfl(t.x, int(j), kRootLanes), __shfl(t.y, int(j), kRootLanes), __shfl(t.z, int(j), kRootLanes)};
+    const uint32_t folded_b = __shfl(folded, 4, kRootLanes);
+    if (sub != 0) return;
+    const RootVec da = root_displacement(at[kRootT0], at[kRootT1], at[kRootNear], at[kRootFar], folded);
+    const RootVec db = root_displacement(at[4 + kRootT0], at[4 + kRootT1], at[4 + kRootNear], at[4 + kRootFar], folded_b);
+    const RootVec d = root_mask(root_blend(da, db, side, w, RootBlendRate{}), r.axes);
+    float *place = r.placements + size_t(i) * 8;
+    float pose[8];
+    pose[0] = place[0]; pose[1] = place[1]; pose[2] = place[2]; pose[3] = 0.f;
+    pose[4] = place[4]; pose[5] = place[5]; pose[6] = place[6]; pose[7] = place[7];
+    root_accumulate(d, pose);
+    place[0] = pose[0]; place[1] = pose[1]; place[2] = pose[2];
+}
+
 }  // namespace
+
+hipError_t launch_animator_root_motion(const BoneTrackParams &p, const RootMotionParams &r, double dt, const double *dt_dev,
+                                       hipStream_t stream) {
+    if (!r.ni) return hipSuccess;
+    constexpr uint32_t per_block = kRootThreads / kRootLanes;
+    hipLaunchKernelGGL(animator_root_motion_kernel, dim3((r.ni + per_block - 1) / per_block), dim3(kRootThreads), 0, stream, p, r, dt,
+                       dt_dev);
+    return hipGetLastError();
+}
 
 hipError_t launch_physics_override(const PhysicsParams &p, hipStream_t stream) {
     if (p.ni == 0 || p.k == 0) return hipSuccess;

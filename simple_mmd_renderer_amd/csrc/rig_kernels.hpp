@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "anim_math.hpp"
 #include "instance_list.hpp"
 #include "rig.hpp"
 
@@ -42,5 +43,19 @@ hipError_t launch_skeleton_ordered_select(const SerialParams &p, const uint8_t *
 hipError_t launch_bone_track_blend_set_select(const BoneTrackParams &p, const BlendOperands &o, const InstanceList &list, hipStream_t stream);
 hipError_t launch_motion_fk_blend_set_select(const BoneTrackParams &t, const SkeletonParams &p, const BlendOperands &o,
                                              const InstanceList &list, hipStream_t stream);
+// mmdx_animator_root_motion.  It lives here, not in anim_kernels.hip, because eval_bone_pose is local to rig_kernels.hip.
+// p: the concatenated bone tables of a set with k.n_clips clips (clock and output fields unused); the seven arrays are the
+// animator's, [ni] each, only read; placements [ni][8], of which [0..2] are updated.  dt / dt_dev as launch_animator_advance.
+struct RootMotionParams {
+    const uint32_t *clips_a, *clips_b;
+    const double *times_a, *times_b;
+    const float *weights, *speed, *fade_rate;
+    uint32_t ni;
+    AnimClips k;
+    uint32_t root_bone, axes;                   // root_bone < p.nb; MMDX_ROOT_X | _Y | _Z
+    float *placements;
+};
+hipError_t launch_animator_root_motion(const BoneTrackParams &p, const RootMotionParams &r, double dt, const double *dt_dev,
+                                       hipStream_t stream);
 
 }  // namespace mmdx

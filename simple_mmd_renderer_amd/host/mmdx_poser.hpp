@@ -359,7 +359,10 @@ private:
 // asynchronous on the poser's stream (and recordable into a graph).  The motions may be destroyed after construction.
 class MotionSet {
 public:
-    MotionSet(const std::vector<const Motion *> &motions, Poser &poser) : poser_(poser) {
+    // in_place_bone >= 0: the set of the motions IN PLACE (mmdx.h, mmdx_bone_motion_in_place) -- every key of that bone loses its
+    // translation on in_place_axes (MMDX_ROOT_X | _Y | _Z), so the poses stay where they are and the placements carry the walk
+    // (Animator::RootMotion with a set that kept it).
+    MotionSet(const std::vector<const Motion *> &motions, Poser &poser, int in_place_bone = -1, uint32_t in_place_axes = 0) : poser_(poser) {
         std::vector<const char *> bn, mn;
         for (const std::string &s : poser.bone_names()) bn.push_back(s.c_str());
         for (const std::string &s : poser.morph_names()) mn.push_back(s.c_str());
@@ -368,6 +371,12 @@ public:
         mmdx_status st = MMDX_OK;
         for (size_t c = 0; c < motions.size() && st == MMDX_OK; ++c) {
             st = mmdx_vmd_bind_bones(motions[c]->handle(), uint32_t(bn.size()), bn.data(), &bones[c]);
+            if (st == MMDX_OK && in_place_bone >= 0) {
+                mmdx_bone_motion_t moving = bones[c];
+                bones[c] = nullptr;
+                st = mmdx_bone_motion_in_place(moving, uint32_t(in_place_bone), in_place_axes, &bones[c]);
+                mmdx_bone_motion_destroy(moving);
+            }
             if (st == MMDX_OK) st = mmdx_vmd_bind_morphs(motions[c]->handle(), uint32_t(mn.size()), mn.data(), &morphs[c]);
         }
         if (st == MMDX_OK) st = mmdx_motion_set_create(uint32_t(motions.size()), bones.data(), morphs.data(), &set_);
@@ -564,6 +573,24 @@ public:
     // one step for every instance, on the poser's stream; a recorded graph freezes dt -- record AdvanceDeviceDt instead
     void Advance(double dt) { check(mmdx_animator_advance(anim_, set_.poser().handle(), &dt, 0)); }
     void AdvanceDeviceDt(const double *dt_device) { check(mmdx_animator_advance(anim_, set_.poser().handle(), dt_device, MMDX_ANIM_DT_ON_DEVICE)); }
+    // Root motion (mmdx.h, mmdx_animator_root_motion): placements [n][8] in device memory, the pose form of PlacePalettes, receive
+    // what the playing clips of `moving` -- a set with this animator's clip count that kept the root's translation -- move bone
+    // root_bone by during the step that Advance is ABOUT to take, turned by each placement's heading.  Call it before Advance with
+    // the same dt, or call Step, which does both in that order.
+    void RootMotion(MotionSet &moving, uint32_t root_bone, uint32_t axes, float *placements_device, double dt) {
+        root_motion(moving, root_bone, axes, placements_device, &dt, 0);
+    }
+    void RootMotionDeviceDt(MotionSet &moving, uint32_t root_bone, uint32_t axes, float *placements_device, const double *dt_device) {
+        root_motion(moving, root_bone, axes, placements_device, dt_device, MMDX_ANIM_DT_ON_DEVICE);
+    }
+    void Step(MotionSet &moving, uint32_t root_bone, uint32_t axes, float *placements_device, double dt) {
+        RootMotion(moving, root_bone, axes, placements_device, dt);
+        Advance(dt);
+    }
+    void StepDeviceDt(MotionSet &moving, uint32_t root_bone, uint32_t axes, float *placements_device, const double *dt_device) {
+        RootMotionDeviceDt(moving, root_bone, axes, placements_device, dt_device);
+        AdvanceDeviceDt(dt_device);
+    }
     // instance ids[j] fades over fades[j] seconds (NULL: at once) to clips[j], started at start_times[j] (NULL: 0); host lists
     void Request(uint32_t n, const uint32_t *ids, const uint32_t *clips, const float *fades = nullptr, const double *start_times = nullptr,
                  bool on_device = false) {
@@ -592,6 +619,14 @@ public:
     mmdx_animator_t handle() const { return anim_; }
 
 private:
+    void root_motion(MotionSet &moving, uint32_t root_bone, uint32_t axes, float *placements, const double *dt, uint32_t flags) {
+        mmdx_root_motion_args a{};
+        a.struct_size = sizeof(a);
+        a.flags = flags;
+        a.root_bone = root_bone; a.axes = axes;
+        a.dt = dt; a.placements = placements;
+        check(mmdx_animator_root_motion(anim_, moving.handle(), set_.poser().handle(), &a));
+    }
     MotionSet &set_;
     uint32_t n_;
     mmdx_animator_t anim_ = nullptr;

@@ -32,7 +32,10 @@ static int crowd(int argc, char **argv) {
         clips_of.push_back(motions.back().get());
     }
     mmdx::MotionSet set(clips_of, *poser);
-    motions.clear();                          // the set copied what it needs
+    // the same motions in place: bone 0 keeps no translation (the walking crowd at the end plays these)
+    const uint32_t all_axes = MMDX_ROOT_X | MMDX_ROOT_Y | MMDX_ROOT_Z;
+    mmdx::MotionSet in_place(clips_of, *poser, 0, all_axes);
+    motions.clear();                          // the sets copied what they need
     const uint32_t nc = set.clip_count();
     std::vector<uint32_t> clips(ni);
     std::vector<double> times(ni);
@@ -74,6 +77,32 @@ static int crowd(int argc, char **argv) {
     animator.GetState(state);
     std::fprintf(stderr, "animated checksum=%016llx clock[0]=%.6f loops[0]=%u\n", (unsigned long long)checksum(palettes.data(), palettes.size() * 4),
                  clock[0], loops[0]);
+    // the crowd walks (root motion): the poses come from the motions in place, and the placements -- in device memory, turned a
+    // little more from one instance to the next -- take what `set` moves bone 0 by in every step.  Step = RootMotion, then Advance.
+    mmdx::Animator walker(in_place, ni);
+    for (uint32_t i = 0; i < ni; ++i) {
+        const float half = 0.05f * float(i);
+        where[8 * i + 5] = half; where[8 * i + 7] = 1.f - half * half;       // a heading about y, not normalised
+    }
+    ids.resize(ni);
+    for (uint32_t i = 0; i < ni; ++i) ids[i] = i;
+    walker.Request(ni, ids.data(), clips.data());
+    void *d_where = nullptr, *d_walk = nullptr;
+    mmdx::check(mmdx_device_malloc(&d_where, where.size() * 4));
+    mmdx::check(mmdx_device_malloc(&d_walk, palettes.size() * 4));
+    mmdx::check(mmdx_memcpy_h2d(d_where, where.data(), where.size() * 4));
+    for (int step = 0; step < 60; ++step) {
+        walker.Step(set, 0, all_axes, static_cast<float *>(d_where), 1.0 / hz);
+        in_place.BlendTimePalettes(walker.operands(), static_cast<float *>(d_walk));
+        in_place.PlacePalettes(ni, static_cast<float *>(d_walk), static_cast<float *>(d_where), static_cast<float *>(d_walk), false, true);
+    }
+    mmdx::check(mmdx_sync(poser->handle()));
+    mmdx::check(mmdx_memcpy_d2h(palettes.data(), d_walk, palettes.size() * 4));
+    mmdx::check(mmdx_memcpy_d2h(where.data(), d_where, where.size() * 4));
+    mmdx::check(mmdx_device_free(d_walk));
+    mmdx::check(mmdx_device_free(d_where));
+    std::fprintf(stderr, "walked checksum=%016llx where=%016llx\n", (unsigned long long)checksum(palettes.data(), palettes.size() * 4),
+                 (unsigned long long)checksum(where.data(), where.size() * 4));
     return 0;
 }
 

@@ -184,10 +184,35 @@ class BoneMotion:
         arr = (C.c_char_p * max(len(enc), 1))(*enc)
         self.h = C.c_void_p()
         api.check(api.lib().mmdx_vmd_bind_bones(vmd.h, len(enc), arr, C.byref(self.h)))
+        self._read_info()
+
+    def _read_info(self):
         nb, mapped, keys, curves = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
         api.check(api.lib().mmdx_bone_motion_get_info(self.h, C.byref(nb), C.byref(mapped), C.byref(keys),
                                                       C.byref(curves)))
         self.nb, self.n_mapped, self.n_keys, self.n_curves = nb.value, mapped.value, keys.value, curves.value
+
+    def in_place(self, bone: int, axes: int) -> "BoneMotion":
+        """A copy of this motion in which the translation of every key of `bone` is +0 on `axes` (api.ROOT_X | ROOT_Y | ROOT_Z;
+        mmdx_bone_motion_in_place): the motion with its root motion taken out, for a crowd whose placements carry it
+        (Animator.root_motion).  Everything else is the same, byte for byte."""
+        out = BoneMotion.__new__(BoneMotion)
+        out.h = C.c_void_p()
+        api.check(api.lib().mmdx_bone_motion_in_place(self.h, bone, axes, C.byref(out.h)))
+        out._read_info()
+        return out
+
+    def keys(self) -> Dict[str, np.ndarray]:
+        """Copies of the host key tables (mmdx_bone_motion_get_keys, for tests): key_off u32 [NB+1], key_frame u32 [K], key_tr
+        f32 [K, 4], key_rot f32 [K, 4], key_curve u32 [K, 4], lut f32 [n_curves, 32]."""
+        k = api.BoneMotionKeys(C.sizeof(api.BoneMotionKeys))
+        api.check(api.lib().mmdx_bone_motion_get_keys(self.h, C.byref(k)))
+
+        def take(p, shape):
+            return np.ctypeslib.as_array(p, shape).copy() if int(np.prod(shape)) else np.zeros(shape, p._type_)
+        return dict(key_off=take(k.key_off, (k.n_bones + 1,)), key_frame=take(k.key_frame, (k.n_keys,)),
+                    key_tr=take(k.key_tr, (k.n_keys, 4)), key_rot=take(k.key_rot, (k.n_keys, 4)),
+                    key_curve=take(k.key_curve, (k.n_keys, 4)), lut=take(k.lut, (k.n_curves, 32)))
 
     def eval(self, frames, model=None) -> np.ndarray:
         """Host convenience: frames [NI] -> poses f32 [NI, NB, 8] (device evaluation + D2H)."""
@@ -521,6 +546,28 @@ class Animator:
     def advance_device_dt(self, dt_ptr, model=None) -> None:
         """The same with dt a device double, read when the kernel runs: a replayed graph rewrites 8 bytes."""
         api.check(api.lib().mmdx_animator_advance(self.h, model.h if model is not None else None, dt_ptr, ANIM_DT_ON_DEVICE))
+
+    def root_motion(self, motion_set: "MotionSet", root_bone: int, axes: int, placements_ptr, dt: Optional[float] = None, dt_ptr=None,
+                    model=None) -> None:
+        """Add to placements f32[NI][8] (device memory, the pose form of mmdx_palette_place) what the playing clips of `motion_set`
+        move bone `root_bone` by during the step advance() is ABOUT to take, rotated by each placement's heading: call it before
+        advance with the same step -- dt, a host value, or dt_ptr, a device double read when the kernel runs.  axes: api.ROOT_X |
+        ROOT_Y | ROOT_Z.  Only placements[i][0..2] are written."""
+        if (dt is None) == (dt_ptr is None):
+            raise ValueError("give one of dt and dt_ptr")
+        host = C.c_double(dt) if dt is not None else None
+        args = api.RootMotionArgs(C.sizeof(api.RootMotionArgs), 0 if dt is not None else ANIM_DT_ON_DEVICE, root_bone, axes,
+                                  C.addressof(host) if dt is not None else dt_ptr, placements_ptr)
+        api.check(api.lib().mmdx_animator_root_motion(self.h, motion_set.h, model.h if model is not None else None, C.byref(args)))
+
+    def step(self, motion_set: "MotionSet", root_bone: int, axes: int, placements_ptr, dt: Optional[float] = None, dt_ptr=None,
+             model=None) -> None:
+        """root_motion, then advance, with one step: the order the header requires, in one call."""
+        self.root_motion(motion_set, root_bone, axes, placements_ptr, dt, dt_ptr, model)
+        if dt is not None:
+            self.advance(dt, model)
+        else:
+            self.advance_device_dt(dt_ptr, model)
 
     def request(self, ids, clips, fades=None, start_times=None, model=None) -> None:
         """Host lists: instance ids[j] fades (fades[j] seconds, default 0 = at once) to clips[j] started at start_times[j]."""
