@@ -76,7 +76,9 @@ extern "C" {
  *    mmdx_pose_blend and mmdx_rate_blend with mmdx_row_blend_args, MMDX_MASK_NONE and MMDX_BLEND_A_ON_DEVICE / _B_ / _PARAMS_, and
  *    mmdx_skeleton_subtree_mask (new entry points, a structure and three flag bits no other call accepts; nothing existing changes).
  *    mmdx_animator_root_motion with mmdx_root_motion_args and MMDX_ROOT_X / _Y / _Z, mmdx_bone_motion_in_place, and
- *    mmdx_bone_motion_get_keys with mmdx_bone_motion_keys (three new entry points and two structures; nothing existing changes). */
+ *    mmdx_bone_motion_get_keys with mmdx_bone_motion_keys (three new entry points and two structures; nothing existing changes).
+ *    mmdx_pose_add and mmdx_rate_add with mmdx_row_add_args and MMDX_REF_NONE (two new entry points and a structure over the
+ *    blend's flag bits; nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -1368,6 +1370,78 @@ MMDX_API mmdx_status mmdx_pose_blend(mmdx_model_t model, const mmdx_row_blend_ar
                                      const mmdx_instance_select *select /* NULL = every instance */);
 MMDX_API mmdx_status mmdx_rate_blend(mmdx_model_t model, const mmdx_row_blend_args *args,
                                      const mmdx_instance_select *select /* NULL = every instance */);
+
+/* ---- Additive layers: a clip's offset from its reference pose, added per bone / per morph ------------------------------------------
+ * The layer call above replaces: at effective weight e a bone moves from A's pose towards B's.  Breathing, a recoil, a lean into a
+ * turn, a nod, "a bit more smile" add instead: the difference between a clip and that clip's reference pose goes on top of whatever
+ * the base does, possibly exaggerated.  mmdx_pose_add takes the base rows A, the layer rows B and a bank of reference rows
+ * refs[n_refs][row_items][MMDX_POSE_FLOATS] (one row per additive clip, chosen per instance by ref_ids), all of them rows that any
+ * track call wrote, and writes A with B's difference from the reference applied at the effective weight, the way libmmd applies a
+ * bone morph; mmdx_rate_add does the same for morph rates [NI][row_items] with refs[n_refs][row_items].  The reference rows need no
+ * call of their own: mmdx_motion_set_eval_bones_time with n_instances = n_clips, clips[i] = i, times[i] = 0 writes refs in exactly
+ * this layout (the same with _eval_morphs_time for rates).
+ *
+ * For instance i and item j (Quaternion and Vector3 operators as libmmd's: L/util/math_impl.inl, L/motion/poser_impl.inl):
+ *  1. effective weight   e = weights[i] * mv, mv exactly as the layers block above defines it (MMDX_MASK_NONE, masks[m][j], or 0 for
+ *                        any other device id): one binary32 multiply.
+ *  2. reference id       r = ref_ids ? ref_ids[i] : MMDX_REF_NONE.  A device r >= n_refs other than MMDX_REF_NONE makes the whole
+ *                        row A; a host one is MMDX_ERR_BAD_INDEX.
+ *  3. !(e >= 1e-7f)      item j of out is A's item, every bit (the fourth translation float and NaNs as they are); neither B's item
+ *                        nor the reference's is read.  This is the bone-morph walk's `rate < 1e-7f` skip (poser_impl.inl:347-353),
+ *                        closed over NaN the way the layers block closes its own.
+ *  4. no upper short circuit: e is used as given; e == 1 adds the whole difference, e > 1 exaggerates it.  Masks above 1 and weights
+ *                        above 1 are legal in host and device memory.
+ *  5. the difference     r == MMDX_REF_NONE: B's item is the difference (d.q = B.q, d.t = B.t), no arithmetic is done on it.
+ *                        With R = refs[r][j]: d.q = B.q * R.q.Inverse() (operator*, Inverse, math_impl.inl:474-477, 510-517: the way
+ *                        the CCD loop extracts a delta, poser_impl.inl:290), d.t = B.t - R.t per channel.
+ *  6. applying it        unfused, in this order: mt = 0.0f + d.t * e per channel; mq = Identity * SLerp(Identity, d.q)[e]
+ *                        (math_impl.inl:1312-1337); out.q = mq * A.q; out.t = mt + A.t; the fourth translation float is 0.
+ *  7. the identity steps 0.0f + and Identity * are kept: they make the item bit for bit what Poser::UpdateMorphTransform
+ *                        (poser_impl.inl:347-353) followed by UpdateBoneTransform (:144-145, morph_rotation_ * rotation_ and
+ *                        morph_translation_ + translation_) computes for a bone whose morph_* received exactly one application
+ *                        (d.t, d.q) at rate e.  Hence: mmdx_pose_add with B the (translation, rotation) rows of a bone morph, no
+ *                        reference and the morph's rate as weight, followed by mmdx_skeleton_solve, gives the palettes of
+ *                        mmdx_skeleton_solve_morphed, value for value (-0 may come out as +0, nothing else differs).
+ *  8. quaternions        are never normalised.  A d.q whose |comega| exceeds 1 makes acos NaN; omega > 1e-7f is then false and
+ *                        SLerp returns Identity, as in libmmd.  acos and sin go through double, as in the bone morphs.
+ *  9. rates              d = (r == MMDX_REF_NONE) ? b : b - ref, then out = a + d * e (vertex_image + offset * rate,
+ *                        poser_impl.inl:344), unfused.
+ * Only the sign and payload of a NaN in a mixed item are not part of the contract.  Negative effective weights are A by rule 3:
+ * there are no subtracting layers.
+ *
+ * Everything else is the layers contract above, word for word: `model`, the stream, graph recording (a replay reads a, b, weights,
+ * mask_ids, masks, ref_ids, refs and the list afresh), select, host operands and their checks, zero sizes, refusals, HOST_ONLY
+ * models, FAST_MATH models running the same uncontracted kernels.  The flags are the blend's; MMDX_BLEND_PARAMS_ON_DEVICE covers
+ * ref_ids and refs as well.  In addition:
+ *  - In place: out == a and out == b are both allowed, a lane reads its items of A, B and R before it stores; a overlapping b, and
+ *    any other overlap among a, b and out, are MMDX_ERR_INVALID_ARGUMENT, and so is ref_ids or refs overlapping out.  With out == a
+ *    a row whose weight is 0 or NaN is not touched, its workgroup returns after reading the weight; items that stay A are neither
+ *    loaded nor stored.
+ *  - B AND THE REFERENCE MAY BE UNINITIALISED wherever e fails the test of rule 3 (and B in rows whose device reference id is out of
+ *    range).
+ *  - ref_ids == NULL means MMDX_REF_NONE for everyone and refs / n_refs are ignored; refs == NULL with ref_ids and n_refs > 0 is
+ *    MMDX_ERR_INVALID_ARGUMENT.  Host ref ids are checked before the first HIP call; host refs are not inspected.
+ *  - Device refs of mmdx_pose_add must be 16-byte aligned; device refs of mmdx_rate_add and device ref_ids 4-byte aligned.
+ *  - reserved0 and reserved1 must be 0. */
+#define MMDX_REF_NONE 0xFFFFFFFFu             /* no reference: B already is a difference */
+typedef struct mmdx_row_add_args {
+    uint32_t struct_size, flags;        /* = sizeof(mmdx_row_add_args); MMDX_BLEND_A_ON_DEVICE | _B_ | _PARAMS_ | MMDX_OUT_ON_DEVICE,
+                                           any other bit: MMDX_ERR_INVALID_ARGUMENT                                                */
+    uint32_t n_instances, row_items;    /* NI; NB (poses) or NM (rates)                                                            */
+    const float *a, *b;                 /* poses [NI][row_items][MMDX_POSE_FLOATS]; rates [NI][row_items]                          */
+    const float *weights;               /* [NI]                                                                                    */
+    const uint32_t *mask_ids;           /* [NI] or NULL = MMDX_MASK_NONE for everyone                                              */
+    const float *masks;                 /* [n_masks][row_items]; may be NULL when n_masks == 0                                     */
+    uint32_t n_masks, reserved0;        /* reserved0 must be 0                                                                     */
+    float *out;                         /* same shape as a; may be == a or == b                                                    */
+    const uint32_t *ref_ids;            /* [NI] or NULL = MMDX_REF_NONE for everyone                                               */
+    const float *refs;                  /* poses [n_refs][row_items][MMDX_POSE_FLOATS]; rates [n_refs][row_items]                  */
+    uint32_t n_refs, reserved1;         /* reserved1 must be 0                                                                     */
+} mmdx_row_add_args;
+MMDX_API mmdx_status mmdx_pose_add(mmdx_model_t model, const mmdx_row_add_args *args,
+                                   const mmdx_instance_select *select /* NULL = every instance */);
+MMDX_API mmdx_status mmdx_rate_add(mmdx_model_t model, const mmdx_row_add_args *args,
+                                   const mmdx_instance_select *select /* NULL = every instance */);
 /* A mask row from the hierarchy, on the host (no device needed): out_mask[b] = inside when b or any ancestor of b is in roots, else
  * outside.  Ancestors are followed through the parent array the skeleton was created from, as mmdx_skeleton_desc.parent defines it: a
  * parent outside [0, NB) ends the chain, which is followed for at most NB steps.  n_roots == 0 fills `outside`; a root >= NB is

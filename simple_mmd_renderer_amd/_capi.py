@@ -30,6 +30,7 @@ POSE_FLOATS = 8          # MMDX_POSE_FLOATS: translation xyz, 0, quaternion xyzw
 MASK_NONE = 0xFFFFFFFF   # MMDX_MASK_NONE: no mask, every item's mask value is 1.0f (mmdx_pose_blend / mmdx_rate_blend)
 BLEND_A_ON_DEVICE, BLEND_B_ON_DEVICE, BLEND_PARAMS_ON_DEVICE = 1 << 11, 1 << 12, 1 << 13   # mmdx_row_blend_args.flags (with OUT_ON_DEVICE):
 #                                              a, b, and {weights, mask_ids, masks} are device pointers
+REF_NONE = 0xFFFFFFFF    # MMDX_REF_NONE: no reference row, B already is a difference (mmdx_pose_add / mmdx_rate_add)
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
@@ -87,6 +88,11 @@ class RowBlendArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("row_items", C.c_uint32),
                 ("a", C.c_void_p), ("b", C.c_void_p), ("weights", C.c_void_p), ("mask_ids", C.c_void_p), ("masks", C.c_void_p),
                 ("n_masks", C.c_uint32), ("reserved0", C.c_uint32), ("out", C.c_void_p)]
+
+
+class RowAddArgs(C.Structure):
+    """mmdx_row_add_args: mmdx_row_blend_args plus the reference rows of an additive layer (mmdx_pose_add / mmdx_rate_add)."""
+    _fields_ = RowBlendArgs._fields_ + [("ref_ids", C.c_void_p), ("refs", C.c_void_p), ("n_refs", C.c_uint32), ("reserved1", C.c_uint32)]
 
 
 ROOT_X, ROOT_Y, ROOT_Z = 1, 2, 4          # MMDX_ROOT_*: the axes of mmdx_animator_root_motion / mmdx_bone_motion_in_place
@@ -291,6 +297,9 @@ SIGNATURES = {
     "mmdx_pose_blend": (C.c_int32, [C.c_void_p, C.POINTER(RowBlendArgs), C.POINTER(InstanceSelect)]),
     "mmdx_rate_blend": (C.c_int32, [C.c_void_p, C.POINTER(RowBlendArgs), C.POINTER(InstanceSelect)]),
     "mmdx_skeleton_subtree_mask": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
+    # additive layers: (model, mmdx_row_add_args*, mmdx_instance_select* or NULL)
+    "mmdx_pose_add": (C.c_int32, [C.c_void_p, C.POINTER(RowAddArgs), C.POINTER(InstanceSelect)]),
+    "mmdx_rate_add": (C.c_int32, [C.c_void_p, C.POINTER(RowAddArgs), C.POINTER(InstanceSelect)]),
     "mmdx_skeleton_destroy": (None, [C.c_void_p]),
     "mmdx_graph_begin": (C.c_int32, [C.c_void_p]),
     "mmdx_graph_end": (C.c_int32, [C.c_void_p, C.POINTER(C.c_void_p)]),

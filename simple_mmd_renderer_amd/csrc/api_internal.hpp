@@ -72,8 +72,8 @@ struct mmdx_model_s {
     mmdx::DevBuf place_in, place_w, place_out;   // mmdx_palette_place with host operands: palettes, placements, result
     mmdx::DevBuf bone_boxes;                     // static: the bone-box table of mmdx_palette_bounds (pbounds_kernels.hpp row layout)
     mmdx::DevBuf pbounds_in, pbounds_out;        // mmdx_palette_bounds with host operands: palettes, result
-    mmdx::DevBuf blend_a, blend_b, blend_p, blend_out;   // mmdx_pose_blend / mmdx_rate_blend with host operands: A, B, {weights, mask
-                                                         // ids, masks}, result
+    mmdx::DevBuf blend_a, blend_b, blend_p, blend_out;   // mmdx_pose_blend / mmdx_rate_blend / mmdx_pose_add / mmdx_rate_add with host
+                                                         // operands: A, B, {weights, mask ids, masks, ref ids, refs}, result
     mmdx::DevBuf blend_sel;                      // ... with a host list: {live count, ids[live]}
     std::vector<uint32_t> blend_sel_host;        // ... its source, alive until the copy has left it
     bool morphed_valid = false;     // `morphed` holds the result of a shared morph pass (MMDX_MORPH_UNCHANGED)

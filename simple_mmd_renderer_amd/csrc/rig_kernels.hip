@@ -10,6 +10,7 @@
 #include "rig.hpp"
 #include "rig_kernels.hpp"
 #include "root_math.hpp"
+#include "row_blend_kernels.hpp"
 #include "solve_shape.hpp"
 
 #include <atomic>
@@ -1262,7 +1263,78 @@ __global__ __launch_bounds__(kRootThreads) void animator_root_motion_kernel(cons
     place[0] = pose[0]; place[1] = pose[1]; place[2] = pose[2];
 }
 
+// ---- additive layers (mmdx_pose_add; include/mmdx.h states the arithmetic) -----------------------------------------------------------
+// Per (instance, item) the difference between B's item and a reference item, applied to A's item at the effective weight e the way a
+// bone morph is: d = (B.q * R.q.Inverse(), B.t - R.t), or B itself without a reference; out = (Identity * SLerp(Identity, d.q)[e]) *
+// A.q and (0 + d.t * e) + A.t.  It lives here, not in row_blend_kernels.hip, because q_mul, q_inverse and q_slerp_from_identity are
+// local to this file and are called, not restated: an item is bit for bit what bone_morph_body.inl and the solver's
+// morph_rotation * rotation make of one application (d.t, d.q) at rate e.
+//   the shape                  is pose_blend_kernel's (row_blend_kernels.hip): one lane per item, blockIdx.x the instance or the list
+//                              position, blockIdx.y a chunk of the row; the list entry, the weight, the mask id and the reference id
+//                              are read once per workgroup (none of them may overlap out); a pose is two 16-byte accesses; no LDS;
+//                              a, b and out are not __restrict__, a lane reads its items of A, B and R before it stores.
+//   loads and stores           an item that stays A -- !(e >= 1e-7f), or a reference id that is neither below n_refs nor kRefNone --
+//                              is neither loaded nor stored with out == a, and is A's 32 bytes copied otherwise; only a mixing lane
+//                              loads B and, under a reference, R.  With out == a a row whose weight is 0 or NaN returns after the
+//                              weight, one whose reference id is out of range after the id.
+//   arithmetic                 a mixing lane runs one d_acos and three d_sin (through double, as the bone morphs do).
+template <bool kSelect>
+__global__ __launch_bounds__(kRowBlendThreads) void pose_add_kernel(const float4 *a, const float4 *b, float4 *out,
+                                                                    const float *__restrict__ weights,
+                                                                    const uint32_t *__restrict__ mask_ids,
+                                                                    const float *__restrict__ masks,
+                                                                    const uint32_t *__restrict__ ref_ids,
+                                                                    const float4 *__restrict__ refs, uint32_t items, uint32_t n_masks,
+                                                                    uint32_t n_refs, const InstanceList list) {
+    uint32_t i;
+    float w;
+    if (!blend_row<kSelect>(list, weights, out == a, i, w)) return;
+    const uint32_t r = ref_ids ? ref_ids[i] : kRefNone;
+    const bool row_is_a = r != kRefNone && r >= n_refs;
+    if (row_is_a && out == a) return;
+    const uint32_t j = blockIdx.y * blockDim.x + threadIdx.x;      // < 65535 * 256: no overflow
+    if (j >= items) return;
+    const float e = effective_weight(w, mask_ids, masks, n_masks, items, i, j);
+    const bool mix = !row_is_a && e >= 1e-7f;
+    if (!mix && out == a) return;
+    const size_t at = (size_t(i) * items + j) * 2;
+    float4 t = a[at], q = a[at + 1];
+    if (mix) {
+        float4 dt = b[at];
+        const float4 bq = b[at + 1];
+        Quat dq = {bq.x, bq.y, bq.z, bq.w};
+        if (r != kRefNone) {
+            const size_t rat = (size_t(r) * items + j) * 2;
+            const float4 rt = refs[rat], rq = refs[rat + 1];
+            dq = q_mul(dq, q_inverse({rq.x, rq.y, rq.z, rq.w}));
+            dt.x = dt.x - rt.x; dt.y = dt.y - rt.y; dt.z = dt.z - rt.z;
+        }
+        const float mx = 0.0f + dt.x * e, my = 0.0f + dt.y * e, mz = 0.0f + dt.z * e;        // morph_translation_ + T * rate
+        const Quat mq = q_mul(q_identity(), q_slerp_from_identity(dq, e));                   // morph_rotation_ * SLerp(Identity, Q)[rate]
+        const Quat oq = q_mul(mq, {q.x, q.y, q.z, q.w});                                    // morph_rotation_ * rotation_
+        t = make_float4(mx + t.x, my + t.y, mz + t.z, 0.0f);                                 // morph_translation_ + translation_
+        q = make_float4(oq.i, oq.j, oq.k, oq.e);
+    }
+    out[at] = t;
+    out[at + 1] = q;
+}
+
 }  // namespace
+
+hipError_t launch_pose_add(const RowAddLaunch &p, const InstanceList *list, uint32_t cells, hipStream_t stream) {
+    const RowBlendLaunch &s = p.rows;
+    const dim3 grid(list ? cells : s.ni, row_blend_chunks(s.items)), block(row_blend_threads(s.items));
+    const float4 *a = reinterpret_cast<const float4 *>(s.a), *b = reinterpret_cast<const float4 *>(s.b);
+    const float4 *refs = reinterpret_cast<const float4 *>(p.refs);
+    float4 *out = reinterpret_cast<float4 *>(s.out);
+    if (list)
+        hipLaunchKernelGGL(pose_add_kernel<true>, grid, block, 0, stream, a, b, out, s.weights, s.mask_ids, s.masks, p.ref_ids, refs,
+                           s.items, s.n_masks, p.n_refs, *list);
+    else
+        hipLaunchKernelGGL(pose_add_kernel<false>, grid, block, 0, stream, a, b, out, s.weights, s.mask_ids, s.masks, p.ref_ids, refs,
+                           s.items, s.n_masks, p.n_refs, InstanceList{nullptr, nullptr, s.ni});
+    return hipGetLastError();
+}
 
 hipError_t launch_animator_root_motion(const BoneTrackParams &p, const RootMotionParams &r, double dt, const double *dt_dev,
                                        hipStream_t stream) {

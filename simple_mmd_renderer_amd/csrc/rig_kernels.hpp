@@ -6,6 +6,7 @@
 #include "anim_math.hpp"
 #include "instance_list.hpp"
 #include "rig.hpp"
+#include "row_blend_kernels.hpp"
 
 namespace mmdx {
 int env_int(const char *name, int dflt);   // api.cpp
@@ -57,5 +58,8 @@ struct RootMotionParams {
 };
 hipError_t launch_animator_root_motion(const BoneTrackParams &p, const RootMotionParams &r, double dt, const double *dt_dev,
                                        hipStream_t stream);
+// mmdx_pose_add.  It lives here, not in row_blend_kernels.hip, because q_mul, q_inverse and q_slerp_from_identity are local to
+// rig_kernels.hip.  Operands and conditions as launch_pose_blend (row_blend_kernels.hpp); refs is not read when n_refs == 0.
+hipError_t launch_pose_add(const RowAddLaunch &p, const InstanceList *list, uint32_t cells, hipStream_t stream);
 
 }  // namespace mmdx

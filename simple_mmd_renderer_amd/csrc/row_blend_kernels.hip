@@ -1,4 +1,4 @@
-// row_blend_kernels.hip -- mmdx_pose_blend / mmdx_rate_blend on gfx950: per (instance, item) the blend of two evaluated rows at the
+// row_blend_kernels.hip -- mmdx_pose_blend / mmdx_rate_blend (and mmdx_rate_add, at the end) on gfx950: per (instance, item) the blend of two evaluated rows at the
 // effective weight weights[i] * mask[item] (include/mmdx.h states the contract).  The arithmetic is blend_side / blend_pose /
 // blend_rate of motion_blend.hpp, called and not restated; this file is built with -ffp-contract=off like the rest, and models
 // created with MMDX_CREATE_FAST_MATH run these same kernels.
@@ -21,30 +21,6 @@
 namespace mmdx {
 
 namespace {
-
-// the row a workgroup works on: false = none (a dead list position, or an in-place row that already holds its result)
-template <bool kSelect>
-__device__ __forceinline__ bool blend_row(const InstanceList &list, const float *__restrict__ weights, bool in_place_a, uint32_t &i,
-                                          float &w) {
-    i = blockIdx.x;
-    if (kSelect) {
-        const ListedInstances li{list};
-        const Lane ln = li.lane(blockIdx.x, li.used(gridDim.x));
-        if (!ln.live) return false;
-        i = ln.row;
-    }
-    w = weights[i];
-    return !(in_place_a && (w == 0.0f || w != w));
-}
-
-// the effective weight of item j of instance i: one binary32 multiply (by 1.0f without a mask: exactly w)
-__device__ __forceinline__ float effective_weight(float w, const uint32_t *__restrict__ mask_ids, const float *__restrict__ masks,
-                                                  uint32_t n_masks, uint32_t items, uint32_t i, uint32_t j) {
-    const uint32_t m = mask_ids ? mask_ids[i] : kMaskNone;
-    float mv = 1.0f;
-    if (m != kMaskNone) mv = m < n_masks ? masks[size_t(m) * items + j] : 0.0f;
-    return w * mv;
-}
 
 template <bool kSelect>
 __global__ __launch_bounds__(kRowBlendThreads) void pose_blend_kernel(const float4 *a, const float4 *b, float4 *out,
@@ -88,6 +64,38 @@ __global__ __launch_bounds__(kRowBlendThreads) void rate_blend_kernel(const floa
     out[at] = r;
 }
 
+// mmdx_rate_add: out = a + d * e with d = b, or b - refs[r] under a reference; the shape, the early returns and the in-place rule are
+// those above.  An item whose effective weight fails e >= 1e-7f, and every item of a row whose reference id is neither below n_refs
+// nor kRefNone, is A's: neither b nor refs is read for it.
+template <bool kSelect>
+__global__ __launch_bounds__(kRowBlendThreads) void rate_add_kernel(const float *a, const float *b, float *out,
+                                                                    const float *__restrict__ weights,
+                                                                    const uint32_t *__restrict__ mask_ids,
+                                                                    const float *__restrict__ masks,
+                                                                    const uint32_t *__restrict__ ref_ids,
+                                                                    const float *__restrict__ refs, uint32_t items, uint32_t n_masks,
+                                                                    uint32_t n_refs, const InstanceList list) {
+    uint32_t i;
+    float w;
+    if (!blend_row<kSelect>(list, weights, out == a, i, w)) return;
+    const uint32_t r = ref_ids ? ref_ids[i] : kRefNone;
+    const bool row_is_a = r != kRefNone && r >= n_refs;
+    if (row_is_a && out == a) return;
+    const uint32_t j = blockIdx.y * blockDim.x + threadIdx.x;
+    if (j >= items) return;
+    const float e = effective_weight(w, mask_ids, masks, n_masks, items, i, j);
+    const bool mix = !row_is_a && e >= 1e-7f;
+    if (!mix && out == a) return;
+    const size_t at = size_t(i) * items + j;
+    float v = a[at];
+    if (mix) {
+        float d = b[at];
+        if (r != kRefNone) d = d - refs[size_t(r) * items + j];
+        v = v + d * e;
+    }
+    out[at] = v;
+}
+
 }  // namespace
 
 hipError_t launch_pose_blend(const RowBlendLaunch &p, const InstanceList *list, uint32_t cells, hipStream_t stream) {
@@ -111,6 +119,18 @@ hipError_t launch_rate_blend(const RowBlendLaunch &p, const InstanceList *list, 
     else
         hipLaunchKernelGGL(rate_blend_kernel<false>, grid, block, 0, stream, p.a, p.b, p.out, p.weights, p.mask_ids, p.masks, p.items,
                            p.n_masks, InstanceList{nullptr, nullptr, p.ni});
+    return hipGetLastError();
+}
+
+hipError_t launch_rate_add(const RowAddLaunch &p, const InstanceList *list, uint32_t cells, hipStream_t stream) {
+    const RowBlendLaunch &q = p.rows;
+    const dim3 grid(list ? cells : q.ni, row_blend_chunks(q.items)), block(row_blend_threads(q.items));
+    if (list)
+        hipLaunchKernelGGL(rate_add_kernel<true>, grid, block, 0, stream, q.a, q.b, q.out, q.weights, q.mask_ids, q.masks, p.ref_ids,
+                           p.refs, q.items, q.n_masks, p.n_refs, *list);
+    else
+        hipLaunchKernelGGL(rate_add_kernel<false>, grid, block, 0, stream, q.a, q.b, q.out, q.weights, q.mask_ids, q.masks, p.ref_ids,
+                           p.refs, q.items, q.n_masks, p.n_refs, InstanceList{nullptr, nullptr, q.ni});
     return hipGetLastError();
 }
 

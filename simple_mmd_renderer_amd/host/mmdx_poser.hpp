@@ -402,6 +402,11 @@ public:
     void SeekFramePalettes(uint32_t n, const uint32_t *clips, const uint32_t *frames, float *out_palettes, bool on_device = false) {
         check(mmdx_skeleton_solve_motion_set(poser_.skeleton(), set_, poser_.handle(), n, clips, frames, flags(on_device), out_palettes));
     }
+    // out_poses[i][bone][8] = the evaluated tracks alone, unsolved: the rows BlendPoses / AddPoses take.  With n = clip_count(),
+    // clips[i] = i and times[i] = 0 these are the reference rows of AddPoses.
+    void SeekTimePoses(uint32_t n, const uint32_t *clips, const double *times, float *out_poses, bool on_device = false) {
+        check(mmdx_motion_set_eval_bones_time(set_, poser_.handle(), n, clips, times, flags(on_device), out_poses));
+    }
     // A poser on its way from one motion to another: instance i is weights[i] of the way from clip clips_a[i] at times_a[i] to
     // clip clips_b[i] at times_b[i] (lerp of the translations, NLerp of the rotations -- what libmmd does between two keys);
     // below 1e-7 the row is clip a's and above 1 - 1e-7 clip b's, bit for bit, and only that clip is evaluated.
@@ -517,6 +522,27 @@ public:
         const mmdx_instance_select s = select(ids, count, n_ids, list_on_device);
         check(mmdx_rate_blend(poser_.handle(), &r, ids ? &s : nullptr));
     }
+    // Additive layers (mmdx.h, mmdx_pose_add / mmdx_rate_add): out[i][item] = a[i][item] with the difference between b[i][item] and
+    // refs[ref_ids[i]][item] applied at weights[i] * masks[mask_ids[i]][item] the way a bone morph is -- breathing, a recoil, a nod on
+    // top of whatever the base plays; weights above 1 exaggerate.  ref_ids may be NULL and holds MMDX_REF_NONE where b already is a
+    // difference.  refs [n_refs][row_items][8] (poses) or [n_refs][row_items] (rates) are the rows SeekTimePoses / SeekTimeMorphRates
+    // write for clips 0 .. n_refs - 1 at time 0.  Everything else as BlendPoses / BlendRates.
+    void AddPoses(uint32_t n, uint32_t row_items, const float *a, const float *b, const float *weights, const uint32_t *mask_ids,
+                  const float *masks, uint32_t n_masks, const uint32_t *ref_ids, const float *refs, uint32_t n_refs, float *out,
+                  bool on_device = false, const uint32_t *ids = nullptr, const uint32_t *count = nullptr, uint32_t n_ids = 0,
+                  bool list_on_device = true) {
+        const mmdx_row_add_args r = row_add_args(n, row_items, a, b, weights, mask_ids, masks, n_masks, ref_ids, refs, n_refs, out, on_device);
+        const mmdx_instance_select s = select(ids, count, n_ids, list_on_device);
+        check(mmdx_pose_add(poser_.handle(), &r, ids ? &s : nullptr));
+    }
+    void AddRates(uint32_t n, uint32_t row_items, const float *a, const float *b, const float *weights, const uint32_t *mask_ids,
+                  const float *masks, uint32_t n_masks, const uint32_t *ref_ids, const float *refs, uint32_t n_refs, float *out,
+                  bool on_device = false, const uint32_t *ids = nullptr, const uint32_t *count = nullptr, uint32_t n_ids = 0,
+                  bool list_on_device = true) {
+        const mmdx_row_add_args r = row_add_args(n, row_items, a, b, weights, mask_ids, masks, n_masks, ref_ids, refs, n_refs, out, on_device);
+        const mmdx_instance_select s = select(ids, count, n_ids, list_on_device);
+        check(mmdx_rate_add(poser_.handle(), &r, ids ? &s : nullptr));
+    }
     // A mask row for BlendPoses from the hierarchy (mmdx_skeleton_subtree_mask, host only): `inside` for every bone that is one of
     // roots or has one among its ancestors, `outside` for the rest.
     std::vector<float> SubtreeMask(const std::vector<uint32_t> &roots, float inside = 1.0f, float outside = 0.0f) const {
@@ -536,6 +562,19 @@ private:
         r.n_instances = n; r.row_items = row_items;
         r.a = a; r.b = b; r.weights = weights;
         r.mask_ids = mask_ids; r.masks = masks; r.n_masks = n_masks;
+        r.out = out;
+        return r;
+    }
+    static mmdx_row_add_args row_add_args(uint32_t n, uint32_t row_items, const float *a, const float *b, const float *weights,
+                                          const uint32_t *mask_ids, const float *masks, uint32_t n_masks, const uint32_t *ref_ids,
+                                          const float *refs, uint32_t n_refs, float *out, bool on_device) {
+        mmdx_row_add_args r{};
+        r.struct_size = sizeof(r);
+        r.flags = on_device ? uint32_t(MMDX_BLEND_A_ON_DEVICE | MMDX_BLEND_B_ON_DEVICE | MMDX_BLEND_PARAMS_ON_DEVICE | MMDX_OUT_ON_DEVICE) : 0u;
+        r.n_instances = n; r.row_items = row_items;
+        r.a = a; r.b = b; r.weights = weights;
+        r.mask_ids = mask_ids; r.masks = masks; r.n_masks = n_masks;
+        r.ref_ids = ref_ids; r.refs = refs; r.n_refs = n_refs;
         r.out = out;
         return r;
     }

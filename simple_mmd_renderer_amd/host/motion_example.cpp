@@ -103,6 +103,24 @@ static int crowd(int argc, char **argv) {
     mmdx::check(mmdx_device_free(d_where));
     std::fprintf(stderr, "walked checksum=%016llx where=%016llx\n", (unsigned long long)checksum(palettes.data(), palettes.size() * 4),
                  (unsigned long long)checksum(where.data(), where.size() * 4));
+    // an additive layer: every instance keeps playing its clip and gets, one and a half times over, what the NEXT clip does half a
+    // second in relative to that clip's own first frame.  The reference rows are the clips at time 0.
+    const uint32_t nb = poser->bone_count(), nm = poser->morph_count();
+    std::vector<uint32_t> every(nc), layer(ni);
+    const std::vector<double> zero(nc, 0.0), half_second(ni, 0.5);
+    for (uint32_t c = 0; c < nc; ++c) every[c] = c;
+    for (uint32_t i = 0; i < ni; ++i) layer[i] = (clips[i] + 1) % nc;
+    std::vector<float> base(size_t(ni) * nb * 8), over(base.size()), refs(size_t(nc) * nb * 8), rate_over(rates.size()), rate_refs(size_t(nc) * nm);
+    set.SeekTimePoses(ni, clips.data(), times.data(), base.data());
+    set.SeekTimePoses(ni, layer.data(), half_second.data(), over.data());
+    set.SeekTimePoses(nc, every.data(), zero.data(), refs.data());
+    set.SeekTimeMorphRates(ni, layer.data(), half_second.data(), rate_over.data());
+    set.SeekTimeMorphRates(nc, every.data(), zero.data(), rate_refs.data());
+    const std::vector<float> more(ni, 1.5f);
+    set.AddPoses(ni, nb, base.data(), over.data(), more.data(), nullptr, nullptr, 0, layer.data(), refs.data(), nc, base.data());
+    set.AddRates(ni, nm, rates.data(), rate_over.data(), more.data(), nullptr, nullptr, 0, layer.data(), rate_refs.data(), nc, rates.data());
+    std::fprintf(stderr, "layered checksum=%016llx rates=%016llx\n", (unsigned long long)checksum(base.data(), base.size() * 4),
+                 (unsigned long long)checksum(rates.data(), rates.size() * 4));
     return 0;
 }
 

@@ -353,6 +353,83 @@ def blend_rates_device(n_instances: int, row_items: int, a_ptr, b_ptr, weights_p
                        mask_ids_ptr, model, select)
 
 
+# ---- additive layers: a clip's offset from its reference pose, added per bone / per morph (mmdx_pose_add / mmdx_rate_add) -----
+REF_NONE = api.REF_NONE                  # MMDX_REF_NONE: this instance's B rows already are differences
+
+
+def _add_rows_host(fn, a, b, weights, masks, mask_ids, refs, ref_ids, model, item_floats):
+    a = np.ascontiguousarray(a, np.float32)
+    b = np.ascontiguousarray(b, np.float32)
+    if a.shape != b.shape or a.ndim != (3 if item_floats > 1 else 2) or (item_floats > 1 and a.shape[2] != item_floats):
+        raise ValueError("a and b must have one shape: [NI, items, 8] for poses, [NI, items] for rates")
+    ni, items = a.shape[0], a.shape[1]
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if w.size != ni:
+        raise ValueError("one weight per instance")
+    keep = [a, b, w]
+    args = api.RowAddArgs(C.sizeof(api.RowAddArgs), 0, ni, items, a.ctypes.data, b.ctypes.data, w.ctypes.data, None, None, 0, 0, None,
+                          None, None, 0, 0)
+    if mask_ids is not None:
+        ids = np.ascontiguousarray(mask_ids, np.uint32).reshape(-1)
+        if ids.size != ni:
+            raise ValueError("one mask id per instance")
+        m = np.ascontiguousarray(masks if masks is not None else np.zeros((0, items)), np.float32).reshape(-1, items)
+        keep += [ids, m]
+        args.mask_ids, args.masks, args.n_masks = ids.ctypes.data, m.ctypes.data if m.size else None, m.shape[0]
+    if ref_ids is not None:
+        rids = np.ascontiguousarray(ref_ids, np.uint32).reshape(-1)
+        if rids.size != ni:
+            raise ValueError("one reference id per instance")
+        r = np.ascontiguousarray(refs if refs is not None else np.zeros((0,) + a.shape[1:]), np.float32)
+        if r.shape[1:] != a.shape[1:]:
+            raise ValueError("refs must be [n_refs, items, 8] for poses, [n_refs, items] for rates")
+        keep += [rids, r]
+        args.ref_ids, args.refs, args.n_refs = rids.ctypes.data, r.ctypes.data if r.size else None, r.shape[0]
+    out = np.empty_like(a)
+    args.out = out.ctypes.data
+    api.check(fn(model.h if model is not None else None, C.byref(args), None))
+    return out
+
+
+def add_poses(a, b, weights, masks=None, mask_ids=None, refs=None, ref_ids=None, model=None) -> np.ndarray:
+    """Host convenience (mmdx_pose_add; `model` is required: it supplies the device and stream): base poses a and layer poses b f32
+    [NI, items, 8], weights [NI], masks / mask_ids as blend_poses, refs f32 [n_refs, items, 8] and ref_ids u32 [NI] (REF_NONE = b
+    already is a difference; None = nobody has a reference) -> poses f32 [NI, items, 8]: per item a with b's difference from its
+    reference row applied at weights[i] * masks[mask_ids[i]][item], the way a bone morph is applied."""
+    return _add_rows_host(api.lib().mmdx_pose_add, a, b, weights, masks, mask_ids, refs, ref_ids, model, POSE_FLOATS)
+
+
+def add_rates(a, b, weights, masks=None, mask_ids=None, refs=None, ref_ids=None, model=None) -> np.ndarray:
+    """The same for morph rates (mmdx_rate_add): a, b f32 [NI, items], refs f32 [n_refs, items] -> a + (b - ref) * e, f32 [NI, items]."""
+    return _add_rows_host(api.lib().mmdx_rate_add, a, b, weights, masks, mask_ids, refs, ref_ids, model, 1)
+
+
+def _add_rows_device(fn, n_instances, row_items, a_ptr, b_ptr, weights_ptr, out_ptr, masks_ptr, n_masks, mask_ids_ptr, refs_ptr, n_refs,
+                     ref_ids_ptr, model, select):
+    args = api.RowAddArgs(C.sizeof(api.RowAddArgs),
+                          api.BLEND_A_ON_DEVICE | api.BLEND_B_ON_DEVICE | api.BLEND_PARAMS_ON_DEVICE | api.OUT_ON_DEVICE,
+                          n_instances, row_items, a_ptr, b_ptr, weights_ptr, mask_ids_ptr, masks_ptr, n_masks, 0, out_ptr,
+                          ref_ids_ptr, refs_ptr, n_refs, 0)
+    api.check(fn(model.h if model is not None else None, C.byref(args), C.byref(select) if select is not None else None))
+
+
+def add_poses_device(n_instances: int, row_items: int, a_ptr, b_ptr, weights_ptr, out_ptr, masks_ptr=None, n_masks: int = 0,
+                     mask_ids_ptr=None, refs_ptr=None, n_refs: int = 0, ref_ids_ptr=None, model=None, select=None) -> None:
+    """a, b, out f32[NI][row_items][8] (out may be a or b), weights f32[NI], mask_ids u32[NI] (or None), masks f32[n_masks][row_items],
+    ref_ids u32[NI] (or None) and refs f32[n_refs][row_items][8] resident in HBM; asynchronous on the model's stream.  refs is what
+    MotionSet.eval_bones_time_device writes for clips 0 .. n_refs - 1 at time 0.  select: an instance_select(...) -- only the listed
+    instances are layered, every other row of out keeps its bytes."""
+    _add_rows_device(api.lib().mmdx_pose_add, n_instances, row_items, a_ptr, b_ptr, weights_ptr, out_ptr, masks_ptr, n_masks,
+                     mask_ids_ptr, refs_ptr, n_refs, ref_ids_ptr, model, select)
+
+
+def add_rates_device(n_instances: int, row_items: int, a_ptr, b_ptr, weights_ptr, out_ptr, masks_ptr=None, n_masks: int = 0,
+                     mask_ids_ptr=None, refs_ptr=None, n_refs: int = 0, ref_ids_ptr=None, model=None, select=None) -> None:
+    """The same for morph rates: a, b, out f32[NI][row_items], refs f32[n_refs][row_items]."""
+    _add_rows_device(api.lib().mmdx_rate_add, n_instances, row_items, a_ptr, b_ptr, weights_ptr, out_ptr, masks_ptr, n_masks,
+                     mask_ids_ptr, refs_ptr, n_refs, ref_ids_ptr, model, select)
+
+
 class MotionSet:
     """A bank of clips bound to one model (mmdx_motion_set_t): every instance of a crowd plays its own clip, clips[i], at its own
     frame or time.  bone_motions / morph_motions: sequences of BoneMotion / MorphMotion, one per clip, at least one of the two;
