@@ -78,7 +78,9 @@ extern "C" {
  *    mmdx_animator_root_motion with mmdx_root_motion_args and MMDX_ROOT_X / _Y / _Z, mmdx_bone_motion_in_place, and
  *    mmdx_bone_motion_get_keys with mmdx_bone_motion_keys (three new entry points and two structures; nothing existing changes).
  *    mmdx_pose_add and mmdx_rate_add with mmdx_row_add_args and MMDX_REF_NONE (two new entry points and a structure over the
- *    blend's flag bits; nothing existing changes). */
+ *    blend's flag bits; nothing existing changes).
+ *    mmdx_animator_root_motion_turn with mmdx_root_turn_args and MMDX_ROOT_NORMALIZE, and mmdx_bone_motion_in_place_turn (two new
+ *    entry points, a structure and a flag bit no other call accepts; nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -1046,8 +1048,9 @@ MMDX_API mmdx_status mmdx_animator_advance(mmdx_animator_t animator, mmdx_model_
  *      placements[i][c] = placements[i][c] + d.c
  * There are no other short circuits: NaN and infinity propagate as IEEE gives them (a NaN's sign and payload are outside the
  * contract, as in mmdx_palette_place).  Clip changes advance makes in its step 4 (a request, a THEN successor, a switch at once)
- * contribute nothing: the new clip starts at its t0.  Turning is out of scope (no rotation deltas, no matrix-form placements, no
- * select form: a culled character keeps walking, as its clock keeps running).
+ * contribute nothing: the new clip starts at its t0.  This call reads the root's translation only and leaves the heading alone;
+ * mmdx_animator_root_motion_turn, below, also applies the root's rotation deltas.  (No matrix-form placements, no
+ * select form: a culled character keeps walking, as its clock keeps running.)
  *
  * NULL animator / set / args / dt / placements, a struct_size mismatch, unknown flag or axes bits, a misaligned device dt (8) or
  * placements (4), a set without a bone side and a host NaN dt are MMDX_ERR_INVALID_ARGUMENT; root_bone >= the set's bone count is
@@ -1072,6 +1075,60 @@ typedef struct mmdx_root_motion_args {
 MMDX_API mmdx_status mmdx_animator_root_motion(mmdx_animator_t animator, mmdx_motion_set_t set, mmdx_model_t model,
                                                const mmdx_root_motion_args *args);
 MMDX_API mmdx_status mmdx_bone_motion_in_place(mmdx_bone_motion_t src, uint32_t bone, uint32_t axes, mmdx_bone_motion_t *out_motion);
+
+/* ---- Root motion that turns: rotation deltas move each placement's heading ---------------------------------------------------------
+ * mmdx_animator_root_motion_turn is mmdx_animator_root_motion for clips whose root also rotates (a walk along a curve, a turn on the
+ * spot): the placement follows the root as a rigid frame.  If every moved bone descends from the root, the original motion is
+ * S_inplace * W_root(t) * W_0 with W_root the root's "world bone" matrix, so the placement must become
+ * W_p(t1) = W_root(t1) * W_root(t0)^-1 * W_p(t0); in quaternions and row vectors that is the arithmetic below (libmmd's product
+ * satisfies M(a * b) = M(b) * M(a)).  The call order (BEFORE advance, same dt), the validation, the device / stream / graph rules and
+ * the pinning are the plain call's, word for word.  It writes placements[i][0..2] and placements[i][4..7]; placements[i][3] and
+ * every animator array keep their bytes.  A NaN dt writes nothing.
+ *
+ * The arithmetic is part of the contract: IEEE binary32 in the order written, unfused.  (T, Q)(c, t) is the translation and the
+ * rotation {x, y, z, w} of the row mmdx_motion_set_eval_bones_time writes for (clip c, time t, bone root_bone); {0,0,0} and
+ * {0,0,0,1} when c >= n_clips.  s, raw, t1, near and far are steps 1-2 of the plain call.  `*` between quaternions is
+ * Quaternion::operator* (L/util/math_impl.inl:510-517), Inverse is :474-477, M(q) is q.ToRotateMatrix() (:540-563, not normalised),
+ * rotate(v, M) is :1032-1038 (three-term sums left to right), - and + on vectors are per component.
+ *   a side (c, t0), no fold:   qi = Q(t0).Inverse();  dq = qi * Q(t1);  D = rotate(T(t1) - T(t0), M(qi))
+ *   a side (c, t0), folded:    qi = Q(t0).Inverse();   dq1 = qi * Q(near);  d1 = rotate(T(near) - T(t0), M(qi))
+ *                              qf = Q(far).Inverse();  dq2 = qf * Q(t1);    d2 = rotate(T(t1) - T(far), M(qf))
+ *                              D = d1 + rotate(d2, M(dq1));  dq = dq1 * dq2
+ *   sides                      (D_a, dq_a) from (clips_a, times_a); (D_b, dq_b) from (clips_b, times_b) when fade_rate > 0, else
+ *                              {+0,+0,+0} and {0,0,0,1}
+ *   blend                      at the weight before the step, by the cross-fade's rules: !(w >= 1e-7f): side a unchanged, side b is
+ *                              neither evaluated nor read;  w > 1.0f - 1e-7f: side b unchanged, side a is not evaluated;  otherwise
+ *                              D.c = D_a.c * (1.0f - w) + D_b.c * w per component and dq = the middle branch of NLerp(dq_a, dq_b)[w]
+ *                              (:1271-1275: the sign of the four-term dot picks a + or a -, then Vector4D::Normalize's
+ *                              1 / float(sqrt(double(sum))))
+ *   axes                       a component of D whose bit is absent from `axes` becomes +0.0f (a select).  D is in the ROOT'S OWN
+ *                              frame at t0, not in the clip's: for a clip that starts turned, X there is not the clip's X
+ *   placement {p, ., h}        p.c = p.c + rotate(D, M(h)).c with M(h) of the heading BEFORE the step;  h' = h * dq;
+ *                              with MMDX_ROOT_NORMALIZE h' = (h * dq).Normalize() (:457-465: s = x*x + y*y + z*z + w*w left to
+ *                              right, n = 1.0f / float(sqrt(double(s))) as math::sqrt does (L/util/math.inl:28-30), four products)
+ * There are no short circuits beyond the blend's: an identity dq is still multiplied (a -0 in the heading may become +0), NaN and
+ * infinity propagate as IEEE gives them.  Without MMDX_ROOT_NORMALIZE the heading's norm drifts by a rounding per step, as any
+ * chained product does; mmdx_palette_place does not normalise either, so a long-lived crowd wants the flag.
+ *
+ * flags: MMDX_ANIM_DT_ON_DEVICE | MMDX_ROOT_NORMALIZE, other bits rejected.  Every refusal of mmdx_animator_root_motion applies with
+ * the same status.  Not here: yaw-only extraction, matrix-form placements, a select form, scale.
+ *
+ * mmdx_bone_motion_in_place_turn (host only) is mmdx_bone_motion_in_place, and in addition every key of `bone` gets the rotation
+ * {+0,+0,+0,1}.  Such a track evaluates to the identity at every time, in every bit: between two keys the weights (1 - lam) + lam
+ * give exactly 1 in binary32 for lam in [0, 1], and the normalisation then multiplies by 1.  A set made of such motions gives the
+ * poses with the root's motion and turning taken out; the placement carries both.  As above, the split is faithful
+ * only when every moved bone descends from `bone`; the call does not check it.  Refusals as mmdx_bone_motion_in_place. */
+enum { MMDX_ROOT_NORMALIZE = 1u << 14 };   /* mmdx_animator_root_motion_turn: normalise the heading after the product */
+typedef struct mmdx_root_turn_args {
+    uint32_t struct_size, flags;   /* = sizeof(mmdx_root_turn_args); MMDX_ANIM_DT_ON_DEVICE | MMDX_ROOT_NORMALIZE or 0             */
+    uint32_t root_bone;            /* a bone of `set` (< its n_bones)                                                              */
+    uint32_t axes;                 /* MMDX_ROOT_X | _Y | _Z, in the root's frame at t0; bits outside rejected; 0 allowed           */
+    const double *dt;              /* as mmdx_animator_advance: a host value, or a device double with the flag                     */
+    float *placements;             /* DEVICE, [NI][MMDX_POSE_FLOATS], the pose form of mmdx_palette_place; 4-byte aligned          */
+} mmdx_root_turn_args;
+MMDX_API mmdx_status mmdx_animator_root_motion_turn(mmdx_animator_t animator, mmdx_motion_set_t set, mmdx_model_t model,
+                                                    const mmdx_root_turn_args *args);
+MMDX_API mmdx_status mmdx_bone_motion_in_place_turn(mmdx_bone_motion_t src, uint32_t bone, uint32_t axes, mmdx_bone_motion_t *out_motion);
 
 /* ---- where every instance stands: palette x world matrix ----------------------------------------------------------------------
  * Every palette the solves above write is in model space.  mmdx_palette_place multiplies each skinning matrix of instance i on the

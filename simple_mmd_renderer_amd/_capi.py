@@ -104,6 +104,14 @@ class RootMotionArgs(C.Structure):
                 ("dt", C.c_void_p), ("placements", C.c_void_p)]
 
 
+ROOT_NORMALIZE = 1 << 14                  # MMDX_ROOT_NORMALIZE: mmdx_animator_root_motion_turn normalises the heading it wrote
+
+
+class RootTurnArgs(C.Structure):
+    """mmdx_root_turn_args: mmdx_root_motion_args' fields, its own type, for mmdx_animator_root_motion_turn."""
+    _fields_ = list(RootMotionArgs._fields_)
+
+
 class BoneMotionKeys(C.Structure):
     """mmdx_bone_motion_keys: the host key tables of a bound bone motion (mmdx_bone_motion_get_keys)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_bones", C.c_uint32), ("n_keys", C.c_uint32), ("n_curves", C.c_uint32),
@@ -283,6 +291,8 @@ SIGNATURES = {
     # root motion: (animator, set, model, mmdx_root_motion_args*); (bone motion, bone, axes, out)
     "mmdx_animator_root_motion": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RootMotionArgs)]),
     "mmdx_bone_motion_in_place": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "mmdx_animator_root_motion_turn": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RootTurnArgs)]),
+    "mmdx_bone_motion_in_place_turn": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "mmdx_bone_motion_get_keys": (C.c_int32, [C.c_void_p, C.POINTER(BoneMotionKeys)]),
     "mmdx_skeleton_solve_morphed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),

@@ -373,11 +373,17 @@ mmdx_status mmdx_animator_advance(mmdx_animator_t a, mmdx_model_t model, const d
     return MMDX_OK;
 }
 
-mmdx_status mmdx_animator_root_motion(mmdx_animator_t a, mmdx_motion_set_t set, mmdx_model_t model, const mmdx_root_motion_args *args) {
+}  // extern "C"
+
+// mmdx_animator_root_motion and mmdx_animator_root_motion_turn: two structs with the same fields, one set of rules.  `turn` picks
+// the kernel that also moves the heading; `allowed` is what the call accepts in flags.
+template <class Args>
+static mmdx_status root_motion_call(mmdx_animator_t a, mmdx_motion_set_t set, mmdx_model_t model, const Args *args, const char *size_error,
+                                    uint32_t allowed, bool turn) {
     if (!a || !set || !args) return fail(MMDX_ERR_INVALID_ARGUMENT, "animator / set / args is NULL");
-    if (args->struct_size != sizeof(mmdx_root_motion_args)) return fail(MMDX_ERR_INVALID_ARGUMENT, "mmdx_root_motion_args.struct_size mismatch");
+    if (args->struct_size != sizeof(Args)) return fail(MMDX_ERR_INVALID_ARGUMENT, size_error);
     if (!args->dt || !args->placements) return fail(MMDX_ERR_INVALID_ARGUMENT, "dt / placements is NULL");
-    if (args->flags & ~uint32_t(MMDX_ANIM_DT_ON_DEVICE)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    if (args->flags & ~allowed) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown flag bits");
     if (args->axes & ~uint32_t(MMDX_ROOT_X | MMDX_ROOT_Y | MMDX_ROOT_Z)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown axes bits");
     const SetBoneSide side = motion_set_bone_side(set);
     if (!side.has_bones) return fail(MMDX_ERR_INVALID_ARGUMENT, "this motion set was created without bone motions");
@@ -406,8 +412,22 @@ mmdx_status mmdx_animator_root_motion(mmdx_animator_t a, mmdx_motion_set_t set, 
     const AnimArrays &s = a->arrays;
     const RootMotionParams rp{s.clips_a, s.clips_b, s.times_a, s.times_b, s.weights, s.speed, s.fade_rate, s.ni, a->table,
                               args->root_bone, args->axes, args->placements};
-    HIP_TRY(launch_animator_root_motion(p, rp, on_device ? 0.0 : *args->dt, on_device ? args->dt : nullptr, st));
+    const double dt = on_device ? 0.0 : *args->dt;
+    const double *dt_dev = on_device ? args->dt : nullptr;
+    if (turn) HIP_TRY(launch_animator_root_turn(p, rp, (args->flags & MMDX_ROOT_NORMALIZE) != 0, dt, dt_dev, st));
+    else HIP_TRY(launch_animator_root_motion(p, rp, dt, dt_dev, st));
     return MMDX_OK;
+}
+
+extern "C" {
+
+mmdx_status mmdx_animator_root_motion(mmdx_animator_t a, mmdx_motion_set_t set, mmdx_model_t model, const mmdx_root_motion_args *args) {
+    return root_motion_call(a, set, model, args, "mmdx_root_motion_args.struct_size mismatch", uint32_t(MMDX_ANIM_DT_ON_DEVICE), false);
+}
+
+mmdx_status mmdx_animator_root_motion_turn(mmdx_animator_t a, mmdx_motion_set_t set, mmdx_model_t model, const mmdx_root_turn_args *args) {
+    return root_motion_call(a, set, model, args, "mmdx_root_turn_args.struct_size mismatch",
+                            uint32_t(MMDX_ANIM_DT_ON_DEVICE | MMDX_ROOT_NORMALIZE), true);
 }
 
 }  // extern "C"

@@ -670,6 +670,31 @@ static mmdx_status blend_select_check(mmdx_motion_set_t set, bool bone_side, con
     return check_instance_list(sel, a->n_instances, "the calls without _select evaluate every instance", live_host);
 }
 
+// mmdx_bone_motion_in_place and _in_place_turn: the copy, with the translations of `bone` zeroed on `axes` and, for the turn form,
+// its rotations replaced by {+0,+0,+0,1}
+static mmdx_status bone_motion_in_place(mmdx_bone_motion_t src, uint32_t bone, uint32_t axes, bool turn, mmdx_bone_motion_t *out) {
+    if (!out) return fail(MMDX_ERR_INVALID_ARGUMENT, "out_motion is NULL");
+    *out = nullptr;
+    if (!src) return fail(MMDX_ERR_INVALID_ARGUMENT, "motion is NULL");
+    if (axes & ~uint32_t(MMDX_ROOT_X | MMDX_ROOT_Y | MMDX_ROOT_Z)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown axes bits");
+    if (bone >= src->host.nb)
+        return fail(MMDX_ERR_BAD_INDEX, "bone = " + std::to_string(bone) + ": the motion is bound to " + std::to_string(src->host.nb) + " bones");
+    try {
+        std::unique_ptr<mmdx_bone_motion_s> m(new mmdx_bone_motion_s);
+        m->host = src->host;                                 // the tables only: the copy uploads its own on first use
+        for (uint32_t k = m->host.key_off[bone]; k < m->host.key_off[bone + 1]; ++k)
+            for (uint32_t c = 0; c < 3; ++c)
+                if (axes & (1u << c)) m->host.key_tr[size_t(k) * 4 + c] = 0.0f;
+        if (turn)
+            for (uint32_t k = m->host.key_off[bone]; k < m->host.key_off[bone + 1]; ++k)
+                for (uint32_t c = 0; c < 4; ++c) m->host.key_rot[size_t(k) * 4 + c] = c == 3 ? 1.0f : 0.0f;
+        *out = m.release();
+    } catch (const std::bad_alloc &) {
+        return fail(MMDX_ERR_OUT_OF_MEMORY, "host allocation failed");
+    }
+    return MMDX_OK;
+}
+
 extern "C" {
 
 mmdx_status mmdx_vmd_bind_bones(mmdx_vmd_t vmd, uint32_t n_bones, const char *const *bone_names,
@@ -711,23 +736,11 @@ mmdx_status mmdx_bone_motion_eval_time(mmdx_bone_motion_t m, mmdx_model_t model,
 }
 
 mmdx_status mmdx_bone_motion_in_place(mmdx_bone_motion_t src, uint32_t bone, uint32_t axes, mmdx_bone_motion_t *out) {
-    if (!out) return fail(MMDX_ERR_INVALID_ARGUMENT, "out_motion is NULL");
-    *out = nullptr;
-    if (!src) return fail(MMDX_ERR_INVALID_ARGUMENT, "motion is NULL");
-    if (axes & ~uint32_t(MMDX_ROOT_X | MMDX_ROOT_Y | MMDX_ROOT_Z)) return fail(MMDX_ERR_INVALID_ARGUMENT, "unknown axes bits");
-    if (bone >= src->host.nb)
-        return fail(MMDX_ERR_BAD_INDEX, "bone = " + std::to_string(bone) + ": the motion is bound to " + std::to_string(src->host.nb) + " bones");
-    try {
-        std::unique_ptr<mmdx_bone_motion_s> m(new mmdx_bone_motion_s);
-        m->host = src->host;                                 // the tables only: the copy uploads its own on first use
-        for (uint32_t k = m->host.key_off[bone]; k < m->host.key_off[bone + 1]; ++k)
-            for (uint32_t c = 0; c < 3; ++c)
-                if (axes & (1u << c)) m->host.key_tr[size_t(k) * 4 + c] = 0.0f;
-        *out = m.release();
-    } catch (const std::bad_alloc &) {
-        return fail(MMDX_ERR_OUT_OF_MEMORY, "host allocation failed");
-    }
-    return MMDX_OK;
+    return bone_motion_in_place(src, bone, axes, false, out);
+}
+
+mmdx_status mmdx_bone_motion_in_place_turn(mmdx_bone_motion_t src, uint32_t bone, uint32_t axes, mmdx_bone_motion_t *out) {
+    return bone_motion_in_place(src, bone, axes, true, out);
 }
 
 mmdx_status mmdx_bone_motion_get_keys(mmdx_bone_motion_t m, mmdx_bone_motion_keys *out) {

@@ -1263,6 +1263,63 @@ __global__ __launch_bounds__(kRootThreads) void animator_root_motion_kernel(cons
     place[0] = pose[0]; place[1] = pose[1]; place[2] = pose[2];
 }
 
+// ---- root motion that turns (mmdx_animator_root_motion_turn; include/mmdx.h states the arithmetic, root_math.hpp holds it) ---------
+// animator_root_motion_kernel's shape and its rules for what is not evaluated, with the root's rotation kept: a lane that does not
+// evaluate holds {0,0,0} and the identity, which is what the header gives an id outside the bank and a side b that is not fading.
+// The group's first lane collects seven translations, seven rotations and side b's fold flag with __shfl, runs the steps in the
+// stated order and stores 12 + 16 bytes; the fourth float is never written.
+struct RootBlendPose {
+    __device__ __forceinline__ RootDelta operator()(const RootDelta a, const RootDelta b, const float w) const {
+        float4 t = make_float4(a.d.x, a.d.y, a.d.z, 0.f), q = make_float4(a.q.x, a.q.y, a.q.z, a.q.w);
+        blend_pose(t, q, make_float4(b.d.x, b.d.y, b.d.z, 0.f), make_float4(b.q.x, b.q.y, b.q.z, b.q.w), w);
+        return {{t.x, t.y, t.z}, {q.x, q.y, q.z, q.w}};
+    }
+};
+
+__global__ __launch_bounds__(kRootThreads) void animator_root_turn_kernel(const BoneTrackParams p, const RootMotionParams r, double dt,
+                                                                          const double *dt_dev, const bool normalize) {
+    if (dt_dev) dt = *dt_dev;
+    if (dt != dt) return;
+    const size_t tid = size_t(blockIdx.x) * kRootThreads + threadIdx.x;
+    if (tid / kRootLanes >= r.ni) return;                  // a whole group of eight
+    const uint32_t i = uint32_t(tid / kRootLanes), sub = uint32_t(tid % kRootLanes);
+    const uint32_t lane_side = sub / 4, which = sub % 4;
+    const float w = r.weights[i];
+    const uint32_t side = blend_side(w);
+    const bool reads = lane_side == 0 ? side != kBlendB : (side != kBlendA && r.fade_rate[i] > 0.0f);
+    float4 t = make_float4(0.f, 0.f, 0.f, 0.f), q = make_float4(0.f, 0.f, 0.f, 1.f);
+    uint32_t folded = 0;
+    if (reads) {
+        const uint32_t c = (lane_side ? r.clips_b : r.clips_a)[i];
+        const double t0 = (lane_side ? r.times_b : r.times_a)[i];
+        const RootTimes rt = root_times(r.k, c, t0, double(r.speed[i]) * dt);
+        folded = rt.folded;
+        if (c < r.k.n_clips && (which < kRootNear || folded))
+            eval_bone_pose(clip_of(p, c), r.root_bone, TimeClock{root_time_of(rt, which) * 30.0}, t, q);
+    }
+    RootVec at[kRootLanes];
+    RootQuat aq[kRootLanes];
+#pragma unroll
+    for (uint32_t j = 0; j < kRootLanes; ++j) {
+        at[j] = {__shfl(t.x, int(j), kRootLanes), __shfl(t.y, int(j), kRootLanes), __shfl(t.z, int(j), kRootLanes)};
+        aq[j] = {__shfl(q.x, int(j), kRootLanes), __shfl(q.y, int(j), kRootLanes), __shfl(q.z, int(j), kRootLanes),
+                 __shfl(q.w, int(j), kRootLanes)};
+    }
+    const uint32_t folded_b = __shfl(folded, 4, kRootLanes);
+    if (sub != 0) return;
+    const RootDelta da = root_turn_side(at, aq, folded);
+    const RootDelta db = root_turn_side(at + 4, aq + 4, folded_b);
+    RootDelta s = root_turn_blend(da, db, side, w, RootBlendPose{});
+    s.d = root_mask(s.d, r.axes);
+    float *place = r.placements + size_t(i) * 8;
+    float pose[8];
+    pose[0] = place[0]; pose[1] = place[1]; pose[2] = place[2]; pose[3] = 0.f;
+    pose[4] = place[4]; pose[5] = place[5]; pose[6] = place[6]; pose[7] = place[7];
+    root_turn_accumulate(s, normalize, pose);
+    place[0] = pose[0]; place[1] = pose[1]; place[2] = pose[2];
+    place[4] = pose[4]; place[5] = pose[5]; place[6] = pose[6]; place[7] = pose[7];
+}
+
 // ---- additive layers (mmdx_pose_add; include/mmdx.h states the arithmetic) -----------------------------------------------------------
 // Per (instance, item) the difference between B's item and a reference item, applied to A's item at the effective weight e the way a
 // bone morph is: d = (B.q * R.q.Inverse(), B.t - R.t), or B itself without a reference; out = (Identity * SLerp(Identity, d.q)[e]) *
@@ -1342,6 +1399,15 @@ hipError_t launch_animator_root_motion(const BoneTrackParams &p, const RootMotio
     constexpr uint32_t per_block = kRootThreads / kRootLanes;
     hipLaunchKernelGGL(animator_root_motion_kernel, dim3((r.ni + per_block - 1) / per_block), dim3(kRootThreads), 0, stream, p, r, dt,
                        dt_dev);
+    return hipGetLastError();
+}
+
+hipError_t launch_animator_root_turn(const BoneTrackParams &p, const RootMotionParams &r, bool normalize, double dt, const double *dt_dev,
+                                     hipStream_t stream) {
+    if (!r.ni) return hipSuccess;
+    constexpr uint32_t per_block = kRootThreads / kRootLanes;
+    hipLaunchKernelGGL(animator_root_turn_kernel, dim3((r.ni + per_block - 1) / per_block), dim3(kRootThreads), 0, stream, p, r, dt,
+                       dt_dev, normalize);
     return hipGetLastError();
 }
 

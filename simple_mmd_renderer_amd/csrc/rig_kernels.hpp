@@ -58,6 +58,9 @@ struct RootMotionParams {
 };
 hipError_t launch_animator_root_motion(const BoneTrackParams &p, const RootMotionParams &r, double dt, const double *dt_dev,
                                        hipStream_t stream);
+// mmdx_animator_root_motion_turn: the same operands; placements[i][0..2] and [4..7] are updated.  normalize: MMDX_ROOT_NORMALIZE.
+hipError_t launch_animator_root_turn(const BoneTrackParams &p, const RootMotionParams &r, bool normalize, double dt, const double *dt_dev,
+                                     hipStream_t stream);
 // mmdx_pose_add.  It lives here, not in row_blend_kernels.hip, because q_mul, q_inverse and q_slerp_from_identity are local to
 // rig_kernels.hip.  Operands and conditions as launch_pose_blend (row_blend_kernels.hpp); refs is not read when n_refs == 0.
 hipError_t launch_pose_add(const RowAddLaunch &p, const InstanceList *list, uint32_t cells, hipStream_t stream);

@@ -1,4 +1,5 @@
-// root_math.hpp -- the arithmetic of mmdx_animator_root_motion (include/mmdx.h states it), once: the gfx950 kernel
+// root_math.hpp -- the arithmetic of mmdx_animator_root_motion and, in the second half, of mmdx_animator_root_motion_turn
+// (include/mmdx.h states both), once: the gfx950 kernel
 // (animator_root_motion_kernel in rig_kernels.hip) and a CPU driver (tests/root_math_driver.cpp) compile these same lines, and
 // tests/root_motion_ref.py restates them in numpy.  IEEE operations only, binary32 in the order written (the clocks are
 // anim_math.hpp's, in double); both builds pass -ffp-contract=off, so nothing is fused.
@@ -8,6 +9,7 @@
 // eval_bone_pose in the kernel and Motion::GetBonePose in the golden rows.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 
 #include "anim_math.hpp"
@@ -92,6 +94,84 @@ MMDX_ROOT_FN void root_accumulate(const RootVec d, float *pose) {
     pose[0] = pose[0] + rx;
     pose[1] = pose[1] + ry;
     pose[2] = pose[2] + rz;
+}
+
+// ---- root motion that turns (mmdx_animator_root_motion_turn; include/mmdx.h states it) -------------------------------------------
+// The same clocks, sides, blend rows and axes select as above; a side is now a pair (D, dq) -- the root's displacement in its own
+// frame at t0 and its rotation delta -- and the placement's heading is multiplied by the blended delta.  The kernel
+// (animator_root_turn_kernel in rig_kernels.hip) and tests/root_turn_math_driver.cpp compile these lines, tests/root_turn_ref.py
+// restates them.  rig_kernels.hip's q_mul / q_inverse are device-only and local to that translation unit, so the three quaternion
+// operations are restated here as root_sub is; the blend of two pairs is motion_blend.hpp's blend_pose, passed in by the caller.
+struct RootQuat {
+    float x, y, z, w;                            // libmmd's i, j, k, e
+};
+struct RootDelta {
+    RootVec d;
+    RootQuat q;
+};
+
+// Quaternion::operator*(const Quaternion &), L/util/math_impl.inl:510-517.  M(a * b) = M(b) * M(a) in the row-vector convention.
+MMDX_ROOT_FN RootQuat root_q_mul(const RootQuat a, const RootQuat q) {
+    RootQuat r;
+    r.x = (a.w * q.x + a.x * q.w + a.y * q.z) - a.z * q.y;
+    r.y = (a.w * q.y + a.y * q.w + a.z * q.x) - a.x * q.z;
+    r.z = (a.w * q.z + a.x * q.y + a.z * q.w) - a.y * q.x;
+    r.w = a.w * q.w - (a.x * q.x + a.y * q.y + a.z * q.z);
+    return r;
+}
+// Quaternion::Inverse, :474-477: Conjugate() (:466-473) * (1 / the squared norm, summed left to right) (operator*(elem_type), :486-493)
+MMDX_ROOT_FN RootQuat root_q_inverse(const RootQuat a) {
+    const float n = 1.0f / (a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w);
+    return {-a.x * n, -a.y * n, -a.z * n, a.w * n};
+}
+// Quaternion::Normalize, :457-465, with Norm (:454-456) and math::sqrt (L/util/math.inl:28-30): float(sqrt(double(sum)))
+MMDX_ROOT_FN RootQuat root_q_normalize(const RootQuat a) {
+    const float s = a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
+    const float n = 1.0f / float(sqrt(double(s)));
+    return {a.x * n, a.y * n, a.z * n, a.w * n};
+}
+// rotate(v, q.ToRotateMatrix()): L/util/math_impl.inl:1032-1038 over :540-563 (place_matrix_from_pose; q is not normalised)
+MMDX_ROOT_FN RootVec root_rotate(const RootVec v, const RootQuat q) {
+    const float pose[8] = {0.0f, 0.0f, 0.0f, 0.0f, q.x, q.y, q.z, q.w};
+    float m[16];
+    place_matrix_from_pose(pose, m);
+    return {v.x * m[0] + v.y * m[4] + v.z * m[8], v.x * m[1] + v.y * m[5] + v.z * m[9], v.x * m[2] + v.y * m[6] + v.z * m[10]};
+}
+
+// One leg from (t0, q0) to (t1, q1): qi = q0.Inverse(); dq = qi * q1; D = rotate(t1 - t0, M(qi))
+MMDX_ROOT_FN RootDelta root_turn_leg(const RootVec t0, const RootQuat q0, const RootVec t1, const RootQuat q1) {
+    const RootQuat qi = root_q_inverse(q0);
+    return {root_rotate(root_sub(t1, t0), qi), root_q_mul(qi, q1)};
+}
+// A side from (T, Q) at its four instants (near / far are not looked at without a fold).  Folded: the leg t0 -> near, then the leg
+// far -> t1 carried into the first one's frame: D = d1 + rotate(d2, M(dq1)), dq = dq1 * dq2.
+MMDX_ROOT_FN RootDelta root_turn_side(const RootVec *t, const RootQuat *q, uint32_t folded) {
+    if (!folded) return root_turn_leg(t[kRootT0], q[kRootT0], t[kRootT1], q[kRootT1]);
+    const RootDelta one = root_turn_leg(t[kRootT0], q[kRootT0], t[kRootNear], q[kRootNear]);
+    const RootDelta two = root_turn_leg(t[kRootFar], q[kRootFar], t[kRootT1], q[kRootT1]);
+    return {root_add(one.d, root_rotate(two.d, one.q)), root_q_mul(one.q, two.q)};
+}
+
+// `side` is blend_side(w); `pose` is blend_pose (motion_blend.hpp) over two pairs: the lerp per channel and NLerp's middle branch
+// with its normalisation.  An end-point row is that side's pair unchanged.
+template <class Pose>
+MMDX_ROOT_FN RootDelta root_turn_blend(const RootDelta a, const RootDelta b, uint32_t side, float w, Pose pose) {
+    if (side == kRootSideA) return a;
+    if (side == kRootSideB) return b;
+    return pose(a, b, w);
+}
+
+// pose = one placement {p, (untouched), h}: p.c = p.c + rotate(D, M(h)).c with the heading BEFORE the step, then h = h * dq and,
+// with `normalize`, its Normalize().  No short circuit for an identity dq.  pose[3] is neither read nor written.
+MMDX_ROOT_FN void root_turn_accumulate(const RootDelta s, bool normalize, float *pose) {
+    const RootQuat h = {pose[4], pose[5], pose[6], pose[7]};
+    const RootVec r = root_rotate(s.d, h);
+    pose[0] = pose[0] + r.x;
+    pose[1] = pose[1] + r.y;
+    pose[2] = pose[2] + r.z;
+    RootQuat n = root_q_mul(h, s.q);
+    if (normalize) n = root_q_normalize(n);
+    pose[4] = n.x; pose[5] = n.y; pose[6] = n.z; pose[7] = n.w;
 }
 
 }  // namespace mmdx

@@ -361,8 +361,10 @@ class MotionSet {
 public:
     // in_place_bone >= 0: the set of the motions IN PLACE (mmdx.h, mmdx_bone_motion_in_place) -- every key of that bone loses its
     // translation on in_place_axes (MMDX_ROOT_X | _Y | _Z), so the poses stay where they are and the placements carry the walk
-    // (Animator::RootMotion with a set that kept it).
-    MotionSet(const std::vector<const Motion *> &motions, Poser &poser, int in_place_bone = -1, uint32_t in_place_axes = 0) : poser_(poser) {
+    // (Animator::RootMotion with a set that kept it).  in_place_turn: mmdx_bone_motion_in_place_turn instead -- the bone's rotation
+    // becomes the identity as well, and the placements carry the turning too (Animator::RootTurn).
+    MotionSet(const std::vector<const Motion *> &motions, Poser &poser, int in_place_bone = -1, uint32_t in_place_axes = 0,
+              bool in_place_turn = false) : poser_(poser) {
         std::vector<const char *> bn, mn;
         for (const std::string &s : poser.bone_names()) bn.push_back(s.c_str());
         for (const std::string &s : poser.morph_names()) mn.push_back(s.c_str());
@@ -374,7 +376,8 @@ public:
             if (st == MMDX_OK && in_place_bone >= 0) {
                 mmdx_bone_motion_t moving = bones[c];
                 bones[c] = nullptr;
-                st = mmdx_bone_motion_in_place(moving, uint32_t(in_place_bone), in_place_axes, &bones[c]);
+                st = in_place_turn ? mmdx_bone_motion_in_place_turn(moving, uint32_t(in_place_bone), in_place_axes, &bones[c])
+                                   : mmdx_bone_motion_in_place(moving, uint32_t(in_place_bone), in_place_axes, &bones[c]);
                 mmdx_bone_motion_destroy(moving);
             }
             if (st == MMDX_OK) st = mmdx_vmd_bind_morphs(motions[c]->handle(), uint32_t(mn.size()), mn.data(), &morphs[c]);
@@ -630,6 +633,21 @@ public:
         RootMotionDeviceDt(moving, root_bone, axes, placements_device, dt_device);
         AdvanceDeviceDt(dt_device);
     }
+    // Root motion that turns (mmdx.h, mmdx_animator_root_motion_turn): the same, and each placement's heading [4..7] is multiplied
+    // by the root's rotation delta; normalize = MMDX_ROOT_NORMALIZE.  `moving` kept the root's translation and rotation; the poses
+    // come from a set built with in_place_turn.
+    void RootTurn(MotionSet &moving, uint32_t root_bone, uint32_t axes, float *placements_device, double dt, bool normalize = false) {
+        root_turn(moving, root_bone, axes, placements_device, &dt, normalize ? uint32_t(MMDX_ROOT_NORMALIZE) : 0u);
+    }
+    void RootTurnDeviceDt(MotionSet &moving, uint32_t root_bone, uint32_t axes, float *placements_device, const double *dt_device,
+                          bool normalize = false) {
+        root_turn(moving, root_bone, axes, placements_device, dt_device,
+                  MMDX_ANIM_DT_ON_DEVICE | (normalize ? uint32_t(MMDX_ROOT_NORMALIZE) : 0u));
+    }
+    void StepTurn(MotionSet &moving, uint32_t root_bone, uint32_t axes, float *placements_device, double dt, bool normalize = false) {
+        RootTurn(moving, root_bone, axes, placements_device, dt, normalize);
+        Advance(dt);
+    }
     // instance ids[j] fades over fades[j] seconds (NULL: at once) to clips[j], started at start_times[j] (NULL: 0); host lists
     void Request(uint32_t n, const uint32_t *ids, const uint32_t *clips, const float *fades = nullptr, const double *start_times = nullptr,
                  bool on_device = false) {
@@ -665,6 +683,14 @@ private:
         a.root_bone = root_bone; a.axes = axes;
         a.dt = dt; a.placements = placements;
         check(mmdx_animator_root_motion(anim_, moving.handle(), set_.poser().handle(), &a));
+    }
+    void root_turn(MotionSet &moving, uint32_t root_bone, uint32_t axes, float *placements, const double *dt, uint32_t flags) {
+        mmdx_root_turn_args a{};
+        a.struct_size = sizeof(a);
+        a.flags = flags;
+        a.root_bone = root_bone; a.axes = axes;
+        a.dt = dt; a.placements = placements;
+        check(mmdx_animator_root_motion_turn(anim_, moving.handle(), set_.poser().handle(), &a));
     }
     MotionSet &set_;
     uint32_t n_;

@@ -5,7 +5,8 @@
 // With `hz` the loop runs at that display rate: step n seeks to n / hz seconds (MotionPlayer::SeekTime) instead of frame n.
 //   ./motion_example --crowd instances hz model.pmx clip0.vmd [clip1.vmd ...]
 // Crowd mode (mmdx::MotionSet): the motions are the clips of one bank, instance i plays clip i % clips at i / hz seconds; one
-// call each gives every instance's palette and morph rates; then mmdx::Animator runs the crowd's clocks on the device for 60 steps.
+// call each gives every instance's palette and morph rates; then mmdx::Animator runs the crowd's clocks on the device for 60 steps,
+// walks it (root motion) and, at the end, walks and turns it (root motion with rotation deltas).
 // Prints per-run checksums so tests can compare with the Python path over the same C ABI.
 #include <cstdio>
 #include <cstdlib>
@@ -35,6 +36,8 @@ static int crowd(int argc, char **argv) {
     // the same motions in place: bone 0 keeps no translation (the walking crowd at the end plays these)
     const uint32_t all_axes = MMDX_ROOT_X | MMDX_ROOT_Y | MMDX_ROOT_Z;
     mmdx::MotionSet in_place(clips_of, *poser, 0, all_axes);
+    // ... and with bone 0's rotation taken out as well (the turning crowd at the very end plays these)
+    mmdx::MotionSet in_place_turn(clips_of, *poser, 0, all_axes, true);
     motions.clear();                          // the sets copied what they need
     const uint32_t nc = set.clip_count();
     std::vector<uint32_t> clips(ni);
@@ -121,6 +124,32 @@ static int crowd(int argc, char **argv) {
     set.AddRates(ni, nm, rates.data(), rate_over.data(), more.data(), nullptr, nullptr, 0, layer.data(), rate_refs.data(), nc, rates.data());
     std::fprintf(stderr, "layered checksum=%016llx rates=%016llx\n", (unsigned long long)checksum(base.data(), base.size() * 4),
                  (unsigned long long)checksum(rates.data(), rates.size() * 4));
+    // the crowd walks and turns (root motion with rotation deltas): the poses come from the motions with bone 0's translation AND
+    // rotation taken out, and each placement follows bone 0 of `set` as a rigid frame -- its heading is multiplied by the bone's
+    // rotation delta and normalised.  StepTurn = RootTurn, then Advance.
+    mmdx::Animator turner(in_place_turn, ni);
+    std::fill(where.begin(), where.end(), 0.f);
+    for (uint32_t i = 0; i < ni; ++i) {
+        const float half = 0.05f * float(i);
+        where[8 * i] = 12.f * float(i); where[8 * i + 5] = half; where[8 * i + 7] = 1.f - half * half;
+    }
+    turner.Request(ni, ids.data(), clips.data());
+    void *d_turn = nullptr;
+    mmdx::check(mmdx_device_malloc(&d_where, where.size() * 4));
+    mmdx::check(mmdx_device_malloc(&d_turn, palettes.size() * 4));
+    mmdx::check(mmdx_memcpy_h2d(d_where, where.data(), where.size() * 4));
+    for (int step = 0; step < 60; ++step) {
+        turner.StepTurn(set, 0, all_axes, static_cast<float *>(d_where), 1.0 / hz, true);
+        in_place_turn.BlendTimePalettes(turner.operands(), static_cast<float *>(d_turn));
+        in_place_turn.PlacePalettes(ni, static_cast<float *>(d_turn), static_cast<float *>(d_where), static_cast<float *>(d_turn), false, true);
+    }
+    mmdx::check(mmdx_sync(poser->handle()));
+    mmdx::check(mmdx_memcpy_d2h(palettes.data(), d_turn, palettes.size() * 4));
+    mmdx::check(mmdx_memcpy_d2h(where.data(), d_where, where.size() * 4));
+    mmdx::check(mmdx_device_free(d_turn));
+    mmdx::check(mmdx_device_free(d_where));
+    std::fprintf(stderr, "turned checksum=%016llx where=%016llx\n", (unsigned long long)checksum(palettes.data(), palettes.size() * 4),
+                 (unsigned long long)checksum(where.data(), where.size() * 4));
     return 0;
 }
 

@@ -202,6 +202,15 @@ class BoneMotion:
         out._read_info()
         return out
 
+    def in_place_turn(self, bone: int, axes: int) -> "BoneMotion":
+        """in_place, and every key of `bone` also gets the rotation {+0,+0,+0,1} (mmdx_bone_motion_in_place_turn): the track evaluates
+        to the identity at every time, for a crowd whose placements carry the turning as well (Animator.root_turn)."""
+        out = BoneMotion.__new__(BoneMotion)
+        out.h = C.c_void_p()
+        api.check(api.lib().mmdx_bone_motion_in_place_turn(self.h, bone, axes, C.byref(out.h)))
+        out._read_info()
+        return out
+
     def keys(self) -> Dict[str, np.ndarray]:
         """Copies of the host key tables (mmdx_bone_motion_get_keys, for tests): key_off u32 [NB+1], key_frame u32 [K], key_tr
         f32 [K, 4], key_rot f32 [K, 4], key_curve u32 [K, 4], lut f32 [n_curves, 32]."""
@@ -637,10 +646,29 @@ class Animator:
                                   C.addressof(host) if dt is not None else dt_ptr, placements_ptr)
         api.check(api.lib().mmdx_animator_root_motion(self.h, motion_set.h, model.h if model is not None else None, C.byref(args)))
 
+    def root_turn(self, motion_set: "MotionSet", root_bone: int, axes: int, placements_ptr, dt: Optional[float] = None, dt_ptr=None,
+                  model=None, normalize: bool = False) -> None:
+        """root_motion for clips whose root also rotates (mmdx_animator_root_motion_turn): the displacement is taken in the root's
+        own frame at the start of the step, and each placement's heading [4..7] is multiplied by the root's rotation delta --
+        normalised afterwards with normalize=True (api.ROOT_NORMALIZE).  placements[i][0..2] and [4..7] are written."""
+        if (dt is None) == (dt_ptr is None):
+            raise ValueError("give one of dt and dt_ptr")
+        host = C.c_double(dt) if dt is not None else None
+        flags = (0 if dt is not None else ANIM_DT_ON_DEVICE) | (api.ROOT_NORMALIZE if normalize else 0)
+        args = api.RootTurnArgs(C.sizeof(api.RootTurnArgs), flags, root_bone, axes, C.addressof(host) if dt is not None else dt_ptr,
+                                placements_ptr)
+        api.check(api.lib().mmdx_animator_root_motion_turn(self.h, motion_set.h, model.h if model is not None else None, C.byref(args)))
+
     def step(self, motion_set: "MotionSet", root_bone: int, axes: int, placements_ptr, dt: Optional[float] = None, dt_ptr=None,
-             model=None) -> None:
-        """root_motion, then advance, with one step: the order the header requires, in one call."""
-        self.root_motion(motion_set, root_bone, axes, placements_ptr, dt, dt_ptr, model)
+             model=None, turn: bool = False, normalize: bool = False) -> None:
+        """root_motion -- root_turn with turn=True, where normalize applies -- then advance, with one step: the order the header
+        requires, in one call."""
+        if turn:
+            self.root_turn(motion_set, root_bone, axes, placements_ptr, dt, dt_ptr, model, normalize)
+        elif normalize:
+            raise ValueError("normalize needs turn=True")
+        else:
+            self.root_motion(motion_set, root_bone, axes, placements_ptr, dt, dt_ptr, model)
         if dt is not None:
             self.advance(dt, model)
         else:
