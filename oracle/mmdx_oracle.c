@@ -560,6 +560,34 @@ static void place(const solve_ctx *c, uint32_t b) {        /* rotation -> local 
 
 static void update_bone(const solve_ctx *c, uint32_t b, int solve_ik);
 
+/* Optional trace of the CCD-IK solves (tests/ik_exits.py steers chains to every way out of the loop with it): one record of
+ * MMDX_IK_TRACE_WORDS words per call of solve_ik_chain, nested solves included, written when the call returns (so an inner
+ * solve's record precedes its outer one's) -- IK bone, clamped loop count, exit kind (0 reached before the loop, 1 reached after
+ * a sweep, 2 ran out of sweeps, 3 loop count 0), sweeps run, the first sweep of the first half (i < loop / 2) and of the second
+ * half that reproduced every link's ik_rot (memcmp of the rotation before and after the link's step: the device's `changed`
+ * predicate), 0xFFFFFFFF for none, whether a link's ik_rot holds a NaN at exit, the link count.  The trace only reads: no
+ * result bit depends on it.  Not thread-safe; off by default. */
+enum { MMDX_IK_TRACE_WORDS = 8 };
+enum { IK_EXIT_BEFORE_LOOP = 0, IK_EXIT_REACHED = 1, IK_EXIT_RAN_OUT = 2, IK_EXIT_LOOP_ZERO = 3 };
+static uint32_t *g_ik_trace;
+static size_t g_ik_trace_cap, g_ik_trace_n;
+void mmdx_oracle_trace_ik(uint32_t *records, size_t capacity) { g_ik_trace = records; g_ik_trace_cap = capacity; g_ik_trace_n = 0; }
+size_t mmdx_oracle_trace_ik_count(void) { return g_ik_trace_n; }
+static void ik_trace_emit(const solve_ctx *c, uint32_t b, uint32_t limit, uint32_t kind, uint32_t sweeps, const uint32_t *repro) {
+    if (!g_ik_trace) return;
+    if (g_ik_trace_n < g_ik_trace_cap) {
+        uint32_t *rec = g_ik_trace + MMDX_IK_TRACE_WORDS * g_ik_trace_n;
+        const uint32_t l0 = c->ik_link_off[b], n = c->ik_link_off[b + 1] - l0;
+        uint32_t nan = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            const quat_t q = c->st[c->ik_link_bone[l0 + i]].ik_rot;
+            if (q.i != q.i || q.j != q.j || q.k != q.k || q.e != q.e) nan = 1;
+        }
+        rec[0] = b; rec[1] = limit; rec[2] = kind; rec[3] = sweeps; rec[4] = repro[0]; rec[5] = repro[1]; rec[6] = nan; rec[7] = n;
+    }
+    ++g_ik_trace_n;
+}
+
 static void solve_ik_chain(const solve_ctx *c, uint32_t b) {
     bone_state_t *st = c->st;
     const uint32_t l0 = c->ik_link_off[b], n = c->ik_link_off[b + 1] - l0;
@@ -572,9 +600,11 @@ static void solve_ik_chain(const solve_ctx *c, uint32_t b) {
     update_bone(c, target, 1);
     memcpy(tgt_pos, st[target].local + 12, 12);
     for (int k = 0; k < 3; ++k) err[k] = ik_pos[k] - tgt_pos[k];
-    if (v3_dot(err, err) < (float)MMDX_EPS_D) return;
+    uint32_t repro[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};           /* trace only */
+    if (v3_dot(err, err) < (float)MMDX_EPS_D) { ik_trace_emit(c, b, limit, IK_EXIT_BEFORE_LOOP, 0, repro); return; }
     const uint32_t ikt = limit / 2;
     for (uint32_t i = 0; i < limit; ++i) {
+        int same = 1;                                           /* trace only: every link step of this sweep left ik_rot's bytes */
         for (uint32_t j = 0; j < n; ++j) {
             /* per-link constants of the Poser ctor (:63-90) */
             const int limited = c->ik_link_limited[l0 + j] != 0;
@@ -622,6 +652,7 @@ static void solve_ik_chain(const solve_ctx *c, uint32_t b) {
             dot = 1.0f < dot ? 1.0f : dot;
             const float ac = f_acos(dot), cap = c->ik_angle[b] * (j + 1);
             const float angle = cap < ac ? cap : ac;
+            const quat_t ik_rot_before = li->ik_rot;
             li->ik_rot = q_mul(axis_to_quat(axis, angle), li->ik_rot);
             if (limited) {
                 quat_t lr = q_mul(li->ik_rot, li->pre_ik_rot);
@@ -631,6 +662,7 @@ static void solve_ik_chain(const solve_ctx *c, uint32_t b) {
                 lr = euler_to_quat(order, e);
                 li->ik_rot = q_mul(lr, q_inverse(li->pre_ik_rot));
             }
+            if (memcmp(&ik_rot_before, &li->ik_rot, sizeof(quat_t)) != 0) same = 0;
             for (uint32_t k = 0; k <= j; ++k) {
                 const uint32_t bb = (uint32_t)c->ik_link_bone[l0 + j - k];
                 st[bb].total_rot = q_mul(st[bb].ik_rot, st[bb].pre_ik_rot);
@@ -639,8 +671,9 @@ static void solve_ik_chain(const solve_ctx *c, uint32_t b) {
             update_bone(c, target, 1);
             memcpy(tgt_pos, st[target].local + 12, 12);
         }
+        if (same && repro[i >= ikt] == 0xFFFFFFFFu) repro[i >= ikt] = i;
         for (int k = 0; k < 3; ++k) err[k] = ik_pos[k] - tgt_pos[k];
-        if (v3_dot(err, err) < (float)MMDX_EPS_D) return;
+        if (v3_dot(err, err) < (float)MMDX_EPS_D) { ik_trace_emit(c, b, limit, IK_EXIT_REACHED, i + 1, repro); return; }
 #ifdef MMDX_IK_CYCLE_STATS      /* diagnostic build only (tools/archive/probes/ik_cycle_probe.py): when does the chain's state start to repeat? */
         if (limit >= 200) {
             static unsigned long long hist[6];
@@ -661,6 +694,7 @@ static void solve_ik_chain(const solve_ctx *c, uint32_t b) {
         }
 #endif
     }
+    ik_trace_emit(c, b, limit, limit ? IK_EXIT_RAN_OUT : IK_EXIT_LOOP_ZERO, limit, repro);
 }
 
 static void update_bone(const solve_ctx *c, uint32_t b, int solve_ik) {

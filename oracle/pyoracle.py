@@ -227,6 +227,26 @@ class Oracle:
             raise ValueError("libm trace overflow: %d calls" % n)
         return buf[:n].copy()
 
+    IK_TRACE_FIELDS = ("bone", "loop", "exit", "sweeps", "repeat_first_half", "repeat_second_half", "nan", "links")
+    IK_EXITS = ("before_loop", "reached", "ran_out", "loop_zero")
+    IK_NONE = 0xFFFFFFFF
+
+    def trace_ik(self, fn, capacity=1 << 16):
+        """Run fn() with every CCD-IK solve recorded; returns u32 [N, 8] records in the order the solves RETURN (a nested solve
+        before its outer one), columns IK_TRACE_FIELDS: exit is an index into IK_EXITS, the two repeat columns hold the first
+        sweep of that half that reproduced every link's ik_rot byte for byte or IK_NONE -- see mmdx_oracle_trace_ik."""
+        buf = np.zeros((capacity, len(self.IK_TRACE_FIELDS)), np.uint32)
+        self.lib.mmdx_oracle_trace_ik_count.restype = C.c_size_t
+        self.lib.mmdx_oracle_trace_ik(buf.ctypes.data_as(C.c_void_p), C.c_size_t(capacity))
+        try:
+            fn()
+            n = int(self.lib.mmdx_oracle_trace_ik_count())
+        finally:
+            self.lib.mmdx_oracle_trace_ik(None, C.c_size_t(0))
+        if n > capacity:
+            raise ValueError("IK trace overflow: %d solves" % n)
+        return buf[:n].copy()
+
     def time_crowd(self, model, rates, palettes, normalize=True):
         """Seconds for one crowd step (shared morph pass + one skinning pass per palette)."""
         t, ids, w = self.normalize(model) if normalize else (

@@ -147,6 +147,9 @@
             }
             const V3 err = {ik_pos.x - tgt.x, ik_pos.y - tgt.y, ik_pos.z - tgt.z};
             if (v_dot(err, err) < 1e-7f) break;
+            // ccd()'s shortcut: a sweep that reproduced every link's IK rotation bit for bit (bit patterns, so a NaN that keeps its bits
+            // counts as reproduced and -0 for +0 as a change; exact because a sweep is a function of the chain's bits alone) skips the
+            // rest of its half.  All sixteen lanes hold the same rotations, so the group takes the same way out.
             if (!changed) {
                 if (i >= ikt) break;
                 i = ikt - 1;

@@ -862,8 +862,11 @@ __device__ void ccd(const S &st, const SerialParams &p, const float4 *pose, uint
         if (v_dot(err, err) < 1e-7f) return;
         // A sweep that reproduced every link's IK rotation bit for bit left the whole chain as it found it (each link's matrices
         // follow from its rotation and its parent's matrix), so every later sweep with the same `i < ikt` does the same again: the
-        // rest of that half of the iterations is skipped -- the reference would run them and change nothing.  (A NaN never compares
-        // equal, so NaN chains run to the end like the reference's.)  Window chains only: nothing outside the window is involved.
+        // rest of that half of the iterations is skipped -- the reference would run them and change nothing.  `changed` compares bit
+        // patterns (__float_as_uint), not values: a NaN rotation that comes out with the bits it went in with counts as reproduced, so
+        // NaN chains take the shortcut too.  That is still exact: a sweep is a function of the chain's bits alone, NaN operands
+        // included, so the same bits in give the same bits out in every later sweep of that half; and a -0 for a +0 counts as a change.
+        // (tests/test_ik_exits.py steers chains to every exit.)  Window chains only: nothing outside the window is involved.
         if constexpr (kWindow) {
             if (!changed) {
                 if (i >= ikt) return;
