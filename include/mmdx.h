@@ -80,7 +80,9 @@ extern "C" {
  *    mmdx_pose_add and mmdx_rate_add with mmdx_row_add_args and MMDX_REF_NONE (two new entry points and a structure over the
  *    blend's flag bits; nothing existing changes).
  *    mmdx_animator_root_motion_turn with mmdx_root_turn_args and MMDX_ROOT_NORMALIZE, and mmdx_bone_motion_in_place_turn (two new
- *    entry points, a structure and a flag bit no other call accepts; nothing existing changes). */
+ *    entry points, a structure and a flag bit no other call accepts; nothing existing changes).
+ *    mmdx_socket_set_create / _destroy / _get_info and mmdx_palette_sockets with mmdx_socket_set_desc / _info, mmdx_sockets_args and
+ *    MMDX_SOCKET_OFFSET_MATRIX (four new entry points, three structures and a flag of the new desc alone; nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -1176,6 +1178,91 @@ typedef struct mmdx_place_args {
  *  - n_instances == 0 is MMDX_OK and launches nothing.  NULL model / args / pointers, a struct_size mismatch, an unknown flag bit and
  *    reserved0 != 0 are MMDX_ERR_INVALID_ARGUMENT; a MMDX_CREATE_HOST_ONLY model is MMDX_ERR_NO_DEVICE (after validation). */
 MMDX_API mmdx_status mmdx_palette_place(mmdx_model_t model, const mmdx_place_args *args);
+
+/* ---- bone sockets: the frames of chosen bones per instance, on the device -----------------------------------------------------
+ * Where is this character's hand, head or saddle right now?  A skinning matrix is global_offset_matrix_ * local_matrix_
+ * (L/motion/poser_impl.inl:320-326), and libmmd keeps global_offset_matrix_inv_ next to it (:36-37); multiplying it back gives the
+ * bone's frame.  For instance i and socket s, with b = bone[s], p = rest_position[s] and S = palettes[i][b]:
+ *     G   = the identity with row 4 = {p.x, p.y, p.z, 1}                                    (global_offset_matrix_inv_)
+ *     B   = G * S                                                                           (Matrix4x4<float>::operator*)
+ *     out = B            for a socket without an offset
+ *     out = O * B        for a socket with one; O is the attachment's frame inside the bone's frame, row-vector convention
+ * Every product is Matrix4x4<float>::operator* (L/util/math_impl.inl:984-1003): each of the 16 elements is the left-to-right
+ * four-term sum a_r1*b_1c + a_r2*b_2c + a_r3*b_3c + a_r4*b_4c in binary32, unfused -- the rows where G is 0 and 1 included.  There
+ * are no short circuits, exactly as mmdx_palette_place states for itself: a -0 can become +0 and an infinite element of S times a
+ * zero of G is NaN.  O comes from 8 floats {tx, ty, tz, (ignored), qx, qy, qz, qw} exactly as the pose form of mmdx_palette_place
+ * builds W (not normalised), or, with MMDX_SOCKET_OFFSET_MATRIX, is 16 floats used as given; the set expands a pose on the host at
+ * creation, so a pose-form offset and the matrix it expands to give identical results.
+ * What this is and is not:
+ *  - on a model-space palette B is the bone's model-space frame; on a palette that went through mmdx_palette_place it is the bone's
+ *    world frame, because G * (S * W);
+ *  - rows 1-3 of B reproduce the rows 1-3 of libmmd's local_matrix_ bit for bit when S is finite, up to the sign of a zero;
+ *  - row 4 is a recomputation and can differ from libmmd's private local_matrix_ row 4 in the last bits: the contract is the
+ *    formula above, not that private field;
+ *  - the sign and payload of a NaN are not part of the contract, as elsewhere.
+ *
+ * A socket set is created on a MODEL (a host that keeps its own bone solve has no mmdx_skeleton_t): the model supplies the bone
+ * count, the device, the stream and graph recording.  mmdx_socket_set_create copies the desc's arrays.  n_sockets == 0 or above
+ * 65535, a NULL model / desc / bone / rest_position / out_set, a struct_size mismatch, unknown flag bits and reserved0 != 0 are
+ * MMDX_ERR_INVALID_ARGUMENT; bone[s] >= the model's bone count is MMDX_ERR_BAD_INDEX.  On a MMDX_CREATE_HOST_ONLY model the set is
+ * created and validates; mmdx_palette_sockets then answers MMDX_ERR_NO_DEVICE (after validation).  Lifetime follows the graphs':
+ * destroying the model first is allowed and leaves a set that refuses every call (MMDX_ERR_INVALID_ARGUMENT) and can still be
+ * destroyed; a set destroyed while a graph holds its table invalidates the graph, and one destroyed during a recording that used
+ * it poisons that recording. */
+typedef struct mmdx_socket_set_s *mmdx_socket_set_t;
+enum { MMDX_SOCKET_OFFSET_MATRIX = 1u << 0 };     /* offsets are [NS][16] matrices (else [NS][8] poses)                             */
+typedef struct mmdx_socket_set_desc {
+    uint32_t struct_size;            /* = sizeof(mmdx_socket_set_desc)                                                            */
+    uint32_t flags;                  /* MMDX_SOCKET_OFFSET_MATRIX; any other bit: MMDX_ERR_INVALID_ARGUMENT                        */
+    uint32_t n_sockets;              /* NS, 1 .. 65535                                                                            */
+    uint32_t reserved0;              /* must be 0                                                                                 */
+    const uint32_t *bone;            /* [NS] < the model's bone count; repeats allowed                                            */
+    const float *rest_position;      /* [NS][3] the rest position of bone[s] (mmdx_pmx_get_arrays' rest_position row,
+                                        Model::Bone::GetPosition)                                                                 */
+    const float *offset;             /* NULL = no socket has one; else [NS][8] or [NS][16]                                        */
+    const uint8_t *has_offset;       /* NULL = every socket has one when offset is given; else [NS], 0 = socket s has none (its
+                                        row of offset is not read)                                                                */
+} mmdx_socket_set_desc;
+typedef struct mmdx_socket_set_info {
+    uint32_t struct_size;            /* = sizeof(mmdx_socket_set_info), set by the caller                                         */
+    uint32_t n_sockets, n_offsets;   /* sockets; how many of them have an offset                                                  */
+    uint32_t n_bones;                /* the model's bone count: palettes are [NI][n_bones][16]                                    */
+    int32_t device_ordinal;          /* where the table lives; -1 = a host-only model                                             */
+    uint32_t reserved0;
+} mmdx_socket_set_info;
+MMDX_API mmdx_status mmdx_socket_set_create(mmdx_model_t model, const mmdx_socket_set_desc *desc, mmdx_socket_set_t *out_set);
+MMDX_API void mmdx_socket_set_destroy(mmdx_socket_set_t set);
+MMDX_API mmdx_status mmdx_socket_set_get_info(mmdx_socket_set_t set, mmdx_socket_set_info *info);
+
+typedef struct mmdx_sockets_args {
+    uint32_t struct_size;            /* = sizeof(mmdx_sockets_args)                                                               */
+    uint32_t flags;                  /* MMDX_PALETTE_ON_DEVICE | MMDX_OUT_ON_DEVICE; any other bit: MMDX_ERR_INVALID_ARGUMENT      */
+    uint32_t n_instances;
+    uint32_t reserved0;              /* must be 0                                                                                 */
+    const float *palettes;           /* [NI][NB][16], NB = the model's bone count                                                 */
+    float *out_sockets;              /* [NS][NI][16], SOCKET-major                                                                */
+    const mmdx_instance_select *select;   /* NULL = every instance                                                               */
+} mmdx_sockets_args;
+/* out_sockets[s][i] = the 16 floats of socket s of instance i, in libmmd's v[0..15] order (translation in v[12..14]).
+ *  - The output is socket-major on purpose: slab s (out_sockets + s * NI * 16) is byte for byte an [NI][16] placement array for
+ *    mmdx_palette_place(MMDX_PLACE_MATRIX | MMDX_PLACE_ON_DEVICE) of ANOTHER model's crowd -- characters holding props and riders
+ *    on mounts are one more node in a recorded graph.
+ *  - The call is asynchronous on the stream of the set's model (a borrowed one, mmdx_model_set_stream, included), in order with that
+ *    model's solve, place and deform calls, and records into mmdx_graph_begin / _end of that model (both operands, and the list,
+ *    in device memory then); a recorded call reads the palettes afresh at every replay.
+ *  - An operand without its *_ON_DEVICE flag is host memory, copied per call through scratch of the model as mmdx_palette_place
+ *    does, and the call returns when the work is done.
+ *  - select follows mmdx_instance_select as mmdx_deform_batched_select states it: the first min(*count, n_ids) ids are used (count
+ *    NULL: n_ids), a device id >= n_instances is skipped (a host one is MMDX_ERR_INVALID_ARGUMENT before anything is launched), an
+ *    id listed twice writes the same bytes twice, and every row of an unlisted instance keeps every byte; mmdx_cull_bounds' lists go
+ *    in as they are.  With a list, palettes and out_sockets must be in device memory (the staging copies of host operands move
+ *    whole arrays); a host list is copied through scratch of the set and the call returns when the work is done.
+ *  - out_sockets overlapping palettes is MMDX_ERR_INVALID_ARGUMENT; device palettes / out_sockets must be 16-byte aligned.
+ *  - n_instances == 0 is MMDX_OK and launches nothing.  NULL set / args / pointers, a struct_size mismatch, an unknown flag bit and
+ *    reserved0 != 0 are MMDX_ERR_INVALID_ARGUMENT; more than 2^23 instances or list positions is MMDX_ERR_UNSUPPORTED; a set of a
+ *    MMDX_CREATE_HOST_ONLY model is MMDX_ERR_NO_DEVICE (after validation).  Models created with MMDX_CREATE_FAST_MATH run the same,
+ *    uncontracted kernel. */
+MMDX_API mmdx_status mmdx_palette_sockets(mmdx_socket_set_t set, const mmdx_sockets_args *args);
 
 /* ---- a box per instance BEFORE the deform: bone boxes x palette ---------------------------------------------------------------
  * mmdx_deform_batched_bounds gives the box of the vertices it wrote, so a cull that uses it tests last frame's box, and an instance

@@ -83,6 +83,27 @@ class PlaceArgs(C.Structure):
                 ("palettes", C.c_void_p), ("placements", C.c_void_p), ("out_palettes", C.c_void_p)]
 
 
+SOCKET_OFFSET_MATRIX = 1    # mmdx_socket_set_desc.flags: offsets are [NS][16] matrices (else [NS][8] poses)
+
+
+class SocketSetDesc(C.Structure):
+    """mmdx_socket_set_desc: the bones, their rest positions and the local offsets of a socket set (mmdx_socket_set_create)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_sockets", C.c_uint32), ("reserved0", C.c_uint32),
+                ("bone", C.c_void_p), ("rest_position", C.c_void_p), ("offset", C.c_void_p), ("has_offset", C.c_void_p)]
+
+
+class SocketSetInfo(C.Structure):
+    """mmdx_socket_set_info (mmdx_socket_set_get_info)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_sockets", C.c_uint32), ("n_offsets", C.c_uint32), ("n_bones", C.c_uint32),
+                ("device_ordinal", C.c_int32), ("reserved0", C.c_uint32)]
+
+
+class SocketsArgs(C.Structure):
+    """mmdx_sockets_args: palettes in, [NS][NI][16] socket matrices out (mmdx_palette_sockets)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("reserved0", C.c_uint32),
+                ("palettes", C.c_void_p), ("out_sockets", C.c_void_p), ("select", C.POINTER(InstanceSelect))]
+
+
 class RowBlendArgs(C.Structure):
     """mmdx_row_blend_args: two pose or rate arrays, a weight and a mask row per instance (mmdx_pose_blend / mmdx_rate_blend)."""
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("row_items", C.c_uint32),
@@ -191,6 +212,11 @@ SIGNATURES = {
     "mmdx_cull_bounds": (C.c_int32, [C.c_void_p, C.POINTER(CullArgs)]),
     "mmdx_cull_planes_from_matrix": (C.c_int32, [_f32p, C.c_uint32, _f32p]),
     "mmdx_palette_place": (C.c_int32, [C.c_void_p, C.POINTER(PlaceArgs)]),
+    # bone sockets: (model, desc, out_set), (set), (set, info), (set, mmdx_sockets_args*)
+    "mmdx_socket_set_create": (C.c_int32, [C.c_void_p, C.POINTER(SocketSetDesc), C.POINTER(C.c_void_p)]),
+    "mmdx_socket_set_destroy": (None, [C.c_void_p]),
+    "mmdx_socket_set_get_info": (C.c_int32, [C.c_void_p, C.POINTER(SocketSetInfo)]),
+    "mmdx_palette_sockets": (C.c_int32, [C.c_void_p, C.POINTER(SocketsArgs)]),
     "mmdx_model_get_bone_boxes": (C.c_int32, [C.c_void_p, C.POINTER(BoneBoxInfo), _u32p, _f32p]),
     "mmdx_palette_bounds": (C.c_int32, [C.c_void_p, C.POINTER(PaletteBoundsArgs)]),
     "mmdx_sync": (C.c_int32, [C.c_void_p]),

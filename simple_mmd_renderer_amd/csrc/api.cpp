@@ -175,6 +175,7 @@ mmdx_status upload_model(mmdx_model_s *m) {
 
 void free_model(mmdx_model_s *m) {
     graph_drop_handle(&m->pin);              // graphs recorded from this model hold addresses that are about to be freed
+    socket_sets_forget_model(m);             // ... and its socket sets hold the handle itself
     if (m->device >= 0) {
         (void)hipSetDevice(m->device);
         for (DevBuf *b : {&m->tiles, &m->spos, &m->snrm, &m->suv, &m->perm, &m->skin1, &m->skin2_ids,

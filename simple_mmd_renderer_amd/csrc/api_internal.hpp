@@ -42,6 +42,8 @@ struct SetBoneSide {
 SetBoneSide motion_set_bone_side(const mmdx_motion_set_s *set);
 // ... and its bone tables on `device` as a parameter block (clock and output fields empty), the set noted in `model`'s recording
 mmdx_status motion_set_bone_tables(mmdx_motion_set_s *set, mmdx_model_t model, int device, BoneTrackParams *p);
+// socket_api.cpp, the owner of the socket-set handle, for mmdx_model_destroy: the sets created on `m` refuse every call from here on
+void socket_sets_forget_model(mmdx_model_s *m);
 
 }  // namespace mmdx
 

@@ -531,6 +531,102 @@ class DeformModel:
         return int(n.value), float(s.value), float(m.value)
 
 
+class SocketSet:
+    """mmdx_socket_set_t: chosen bones of a model whose frames mmdx_palette_sockets reads out of a crowd's palettes, on the device.
+    Socket s of instance i is O[s] * G[s] * palettes[i][bones[s]] (G: the identity with row 4 = the bone's rest position; O: the
+    socket's optional local offset), 16 floats in libmmd's v[0..15] order; on placed palettes that is the bone's world frame.
+
+    bones: indices into the model's bones [NS].  rest_position: f32 [NS,3], the rest position of bones[s].  offsets: None, [NS,8]
+    poses {tx,ty,tz,_,qx,qy,qz,qw} or [NS,16] / [NS,4,4] matrices.  has_offset: None (every socket has one when offsets is given) or
+    bool [NS]."""
+
+    def __init__(self, model: "DeformModel", bones, rest_position, offsets=None, has_offset=None):
+        bone = np.ascontiguousarray(bones, np.uint32).reshape(-1)
+        ns = bone.size
+        rest = _c(rest_position, np.float32).reshape(ns, 3)
+        d = api.SocketSetDesc()
+        d.struct_size = C.sizeof(api.SocketSetDesc)
+        d.n_sockets = ns
+        d.bone, d.rest_position = bone.ctypes.data, rest.ctypes.data
+        keep = [bone, rest]
+        if offsets is not None:
+            off = _c(offsets, np.float32).reshape(ns, -1)
+            if off.shape[1] not in (api.POSE_FLOATS, 16):
+                raise ValueError("offsets must be [NS,8] poses or [NS,16] matrices")
+            d.flags = api.SOCKET_OFFSET_MATRIX if off.shape[1] == 16 else 0
+            d.offset = off.ctypes.data
+            keep.append(off)
+            if has_offset is not None:
+                has = np.ascontiguousarray(has_offset).astype(np.uint8).reshape(ns)
+                d.has_offset = has.ctypes.data
+                keep.append(has)
+        elif has_offset is not None:
+            raise ValueError("has_offset without offsets")
+        self.h = C.c_void_p()
+        api.check(api.lib().mmdx_socket_set_create(model.h, C.byref(d), C.byref(self.h)))      # copies the arrays
+        info = api.SocketSetInfo()
+        info.struct_size = C.sizeof(api.SocketSetInfo)
+        api.check(api.lib().mmdx_socket_set_get_info(self.h, C.byref(info)))
+        self.info = {k: int(getattr(info, k)) for k, _ in api.SocketSetInfo._fields_}
+        self.ns, self.nb = ns, self.info["n_bones"]
+
+    @classmethod
+    def from_pmx(cls, model: "DeformModel", pmx_model, bones, offsets=None, has_offset=None) -> "SocketSet":
+        """From a loaded .pmx (pmx.PmxModel, the arrays of mmdx_pmx_get_arrays): bones are indices or bone names."""
+        idx = [pmx_model.bone_names.index(b) if isinstance(b, str) else int(b) for b in bones]
+        return cls(model, idx, np.asarray(pmx_model.flat.bone_pos, np.float32)[idx], offsets, has_offset)
+
+    @classmethod
+    def from_skeleton(cls, model: "DeformModel", skeleton, bones, offsets=None, has_offset=None) -> "SocketSet":
+        """From a vmd.Skeleton's rest positions and bone indices."""
+        idx = np.asarray(bones, np.int64).reshape(-1)
+        return cls(model, idx, skeleton.rest_position[idx], offsets, has_offset)
+
+    def sockets_raw(self, n_instances: int, palettes_ptr, out_ptr, flags: int, select=None) -> None:
+        """mmdx_palette_sockets, the raw form.  flags: api.PALETTE_ON_DEVICE | api.OUT_ON_DEVICE say which of the two addresses
+        are device memory; select: an api.InstanceSelect (vmd.instance_select) or None = every instance."""
+        a = api.SocketsArgs()
+        a.struct_size = C.sizeof(api.SocketsArgs)
+        a.flags, a.n_instances = flags, n_instances
+        a.palettes, a.out_sockets = palettes_ptr, out_ptr
+        if select is not None:
+            a.select = C.pointer(select)
+        api.check(api.lib().mmdx_palette_sockets(self.h, C.byref(a)))
+
+    def sockets(self, palettes_dev, out_dev, select=None, n_instances=None) -> None:
+        """Device palettes [NI][NB][16] in, device socket matrices [NS][NI][16] out (socket-major: slab s is an [NI][16] placement
+        array for DeformModel.place_palettes(..., api.PLACE_MATRIX) of another model's crowd).  Asynchronous on the model's stream
+        and recordable.  palettes_dev / out_dev: DeviceBuffers or raw addresses; n_instances defaults to what palettes_dev holds."""
+        if n_instances is None:
+            n_instances = palettes_dev.nbytes // (self.nb * 64)
+        dev = lambda b: getattr(b, "ptr", b)                     # noqa: E731
+        self.sockets_raw(n_instances, dev(palettes_dev), dev(out_dev), api.PALETTE_ON_DEVICE | api.OUT_ON_DEVICE, select)
+
+    def sockets_host(self, palettes) -> np.ndarray:
+        """Host array in, host array out (copies + sync inside the call): palettes [NI,NB,16] -> socket matrices [NS,NI,16]."""
+        pal = _c(palettes, np.float32).reshape(-1, self.nb, 16)
+        out = np.empty((self.ns, pal.shape[0], 16), np.float32)
+        self.sockets_raw(pal.shape[0], pal.ctypes.data, out.ctypes.data, 0)
+        return out
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            api.lib().mmdx_socket_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class PoseImage:
     def __init__(self, nv: int):
         self.coordinates = np.zeros((nv, 3), np.float32)

@@ -79,6 +79,43 @@ int main(int argc, char **argv) {
                 return 2;
             }
         }
+        // A prop in the character's hand (mmdx.h, mmdx_palette_sockets): the frame of bone `hand` out of the last frame's palette --
+        // global_offset_matrix_inv_ * skinning_matrix_ on the reference's side -- with the grip's offset in front of it, used as the
+        // matrix placement of a one-bone prop model.  A crowd does the same with device arrays: slab s of the sockets is the prop
+        // crowd's placement array.
+        const uint32_t hand = 7;
+        const float hand_rest[3] = {1.5f, 12.25f, -0.5f}, grip[8] = {0.f, 0.25f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+        mmdx::SocketSet sockets(poser.handle(), 1, &hand, hand_rest, grip);
+        float socket[16];
+        sockets.Sockets(1, poser.SkinningMatrix(0), socket);
+        mmdx::ModelData pm;
+        pm.n_vertices = 4; pm.n_bones = 1; pm.n_morphs = 0;
+        pm.positions = {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1}; pm.normals = {0, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0, 1}; pm.uvs.assign(8, 0.f);
+        pm.skin_type.assign(4, MMDX_SKIN_BDEF1); pm.bone_ids.assign(16, 0); pm.bone_weights.assign(16, 0.f);
+        for (int v = 0; v < 4; ++v) pm.bone_weights[4 * v] = 1.f;
+        pm.bone_parent.assign(1, -1); pm.morph_offset.assign(1, 0);
+        mmdx::Poser prop(pm);
+        mmdx_place_args pa{};
+        pa.struct_size = sizeof(pa); pa.flags = MMDX_PLACE_MATRIX; pa.n_instances = 1;
+        pa.palettes = prop.SkinningMatrix(0); pa.placements = socket; pa.out_palettes = prop.SkinningMatrix(0);
+        mmdx::check(mmdx_palette_place(prop.handle(), &pa));
+        prop.Deform();
+        // the prop's vertex 0 sits at the model's origin, so it lands on the socket's translation: the grip offset taken through the
+        // hand bone's frame
+        const float *S = poser.SkinningMatrix(hand);
+        float want[3];
+        for (int c = 0; c < 3; ++c) {
+            const float origin = hand_rest[0] * S[c] + hand_rest[1] * S[4 + c] + hand_rest[2] * S[8 + c] + 1.0f * S[12 + c];
+            want[c] = grip[0] * (1.0f * S[c] + 0.0f * S[4 + c] + 0.0f * S[8 + c] + 0.0f * S[12 + c]) +
+                      grip[1] * (0.0f * S[c] + 1.0f * S[4 + c] + 0.0f * S[8 + c] + 0.0f * S[12 + c]) +
+                      grip[2] * (0.0f * S[c] + 0.0f * S[4 + c] + 1.0f * S[8 + c] + 0.0f * S[12 + c]) + 1.0f * origin;
+        }
+        std::printf("prop at the hand socket: %.6f %.6f %.6f\n", prop.pose_image.coordinates[0].x, prop.pose_image.coordinates[0].y,
+                    prop.pose_image.coordinates[0].z);
+        if (std::memcmp(want, socket + 12, sizeof(want)) != 0 || std::memcmp(want, &prop.pose_image.coordinates[0], sizeof(want)) != 0) {
+            std::printf("MISMATCH between the socket, the prop and the host's own product\n");
+            return 2;
+        }
     } catch (const mmdx::Error &e) {
         std::printf("mmdx error %d: %s\n", int(e.status), e.what());
         return 1;

@@ -697,4 +697,46 @@ private:
     mmdx_animator_t anim_ = nullptr;
 };
 
+// Bone sockets (mmdx.h, mmdx_palette_sockets): where a character's hand, head or saddle is, for every instance, on the device.  The
+// reference-side equivalent for one Poser is bone_images_[b].global_offset_matrix_inv_ * bone_images_[b].skinning_matrix_.  A set
+// is created on a model handle: bones [n] index the model's bones, rest_positions [n][3] are those bones' Model::Bone::GetPosition,
+// offsets (NULL = none) are [n][8] poses {tx, ty, tz, 0, qx, qy, qz, qw} or, with offsets_are_matrices, [n][16] matrices: the
+// attachment's frame inside the bone's.  has_offset (NULL = every socket has one) names the sockets that do.
+class SocketSet {
+public:
+    SocketSet(mmdx_model_t model, uint32_t n, const uint32_t *bones, const float *rest_positions, const float *offsets = nullptr,
+              bool offsets_are_matrices = false, const uint8_t *has_offset = nullptr) : n_(n) {
+        mmdx_socket_set_desc d{};
+        d.struct_size = sizeof(d);
+        d.flags = offsets && offsets_are_matrices ? uint32_t(MMDX_SOCKET_OFFSET_MATRIX) : 0u;
+        d.n_sockets = n;
+        d.bone = bones; d.rest_position = rest_positions; d.offset = offsets; d.has_offset = has_offset;
+        check(mmdx_socket_set_create(model, &d, &set_));
+    }
+    ~SocketSet() { mmdx_socket_set_destroy(set_); }
+    SocketSet(const SocketSet &) = delete;
+    SocketSet &operator=(const SocketSet &) = delete;
+
+    // out_sockets [sockets][n][16], socket-major: slab(out_sockets, n, s) is an [n][16] placement array for the PlacePalettes(...,
+    // matrix = true, on_device = true) of another model's crowd.  On palettes that went through PlacePalettes the matrices are world
+    // frames.  Host arrays by default; with on_device = true both are device memory and the call is asynchronous on the model's
+    // stream (and records into its graph).  select (NULL = every instance): what mmdx_cull_bounds wrote, device operands only.
+    void Sockets(uint32_t n_instances, const float *palettes, float *out_sockets, bool on_device = false,
+                 const mmdx_instance_select *select = nullptr) {
+        mmdx_sockets_args a{};
+        a.struct_size = sizeof(a);
+        a.flags = on_device ? uint32_t(MMDX_PALETTE_ON_DEVICE | MMDX_OUT_ON_DEVICE) : 0u;
+        a.n_instances = n_instances;
+        a.palettes = palettes; a.out_sockets = out_sockets; a.select = select;
+        check(mmdx_palette_sockets(set_, &a));
+    }
+    static float *slab(float *out_sockets, uint32_t n_instances, uint32_t socket) { return out_sockets + size_t(socket) * n_instances * 16; }
+    uint32_t size() const { return n_; }
+    mmdx_socket_set_t handle() const { return set_; }
+
+private:
+    uint32_t n_;
+    mmdx_socket_set_t set_ = nullptr;
+};
+
 }  // namespace mmdx

@@ -808,6 +808,7 @@ class Skeleton:
         d = SkeletonDesc(C.sizeof(SkeletonDesc), nb, *[ptr(a) for a in keep], nm, SKELETON_PHYSICS_SEAM if physics_seam else 0,
                          *[ptr(a) for a in mk])
         self._keep = keep + mk
+        self.rest_position = rest                # f32 [NB, 3]: what engine.SocketSet.from_skeleton builds its desc from
         self.nm = nm
         self.h = C.c_void_p()
         api.check(api.lib().mmdx_skeleton_create(C.byref(d), C.byref(self.h)))
