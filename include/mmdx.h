@@ -1132,6 +1132,97 @@ MMDX_API mmdx_status mmdx_animator_root_motion_turn(mmdx_animator_t animator, mm
                                                     const mmdx_root_turn_args *args);
 MMDX_API mmdx_status mmdx_bone_motion_in_place_turn(mmdx_bone_motion_t src, uint32_t bone, uint32_t axes, mmdx_bone_motion_t *out_motion);
 
+/* ---- Clip markers: which events fired during the step, per instance, on the device --------------------------------------------------
+ * A marker is a time in a clip with a channel (0..31): a foot touching the ground, the hit frame of a swing, the end of a one-shot
+ * clip.  mmdx_animator_events reports, for the step that mmdx_animator_advance is ABOUT to take, which channels every instance
+ * passed -- a 32-bit mask per instance -- and, optionally, up to four instance lists in ascending order (mmdx_instance_select with
+ * MMDX_SELECT_ON_DEVICE takes such a list as it is: the sockets of the feet that landed, the deform of those who blinked).  Like root
+ * motion it is called BEFORE advance, with the same dt, on the state advance is about to step; it reads the animator's arrays
+ * (clips_a, clips_b, times_a, times_b, weights, speed, fade_rate) and writes none of them.
+ *
+ * The marker table (mmdx_event_set_t) is made from an animator: it copies the animator's clip count and resolved lengths (the
+ * animator may be destroyed afterwards), and keeps the markers sorted by (clip, time) -- markers of equal clip and time in the order
+ * given -- behind an offset table first[n_clips + 1].  Markers may come in any order, duplicates are allowed, n_markers == 0 is valid
+ * (nothing ever fires).  Creation is host only and refuses, before anything else happens: NULL animator / desc / out or NULL
+ * markers with n_markers > 0 and a struct_size mismatch (MMDX_ERR_INVALID_ARGUMENT); clip >= n_clips (MMDX_ERR_BAD_INDEX);
+ * channel >= 32, a NaN, negative or > L(clip) time, L the length mmdx_animator_get_info reports (MMDX_ERR_INVALID_ARGUMENT).  The
+ * device copy is made by the first call that needs it and stays on that device.
+ *
+ * The arithmetic is part of the contract: comparisons of doubles only, plus the clocks stated above.  For every instance i < NI, with
+ * the state as it stands before advance (L(c), wrap: advance's; near, far, folded: root motion's step 2):
+ *   1. s = double(speed) * dt                                       (step 1 of advance).  A NaN s fires nothing on either side.
+ *   2. a side (c, t0):  raw = t0 + s;  t1 = wrap(c, raw);  it folded: near = L(c), far = 0.0 when raw >= L(c), else near = 0.0,
+ *      far = L(c).  With c >= n_clips (MMDX_CLIP_NONE, an id out of range) nothing fires.
+ *   3. a leg from u to v passes the marker time m:
+ *        u <= v:     (closed ? u <= m : u < m) && m <= v
+ *        otherwise:  v <= m && (closed ? m <= u : m < u)
+ *      The direction is that of the leg's own ends, not the sign of s.
+ *   4. a side that did not fold is one leg t0 -> t1, open at t0.  A folded side is two legs: t0 -> near, open at t0, and far -> t1,
+ *      closed at far: both ends of a seam count.  Further whole laps inside one step are not counted, just as `loops` counts one.
+ *   5. fired(side) = the OR of 1u << channel over the markers of clip c that a leg passes
+ *   6. out_fired[i] = fired(clips_a, times_a) | (fade_rate > 0 ? fired(clips_b, times_b) : 0).  With MMDX_EVENTS_DOMINANT_SIDE:
+ *      fired(clips_b, times_b) alone when fade_rate > 0 && weights[i] > 0.5f, fired(clips_a, times_a) alone otherwise.
+ *   7. list l < n_lists holds, in ascending order, every i with (out_fired[i] & list_mask[l]) != 0 and -- when `levels` is given --
+ *      levels[i] != MMDX_CULLED.  out_counts[l] is its length, out_counts[l] = 0 for n_lists <= l < MMDX_EVENTS_MAX_LISTS; entries
+ *      behind a count keep what they held; an instance may be in several lists.
+ *   8. out_fired[i] is written for every i < NI, whatever `levels` says.
+ *   9. a NaN step (a device NaN dt) fires nothing: out_fired is all 0 and the counts are 0.  Root motion writes nothing then; here a
+ *      stale count would fire last frame's events again on a replay.  A host NaN dt is refused as everywhere.
+ * Consequences:
+ *   - s == 0 fires nothing (a leg from t0 to t0, open at t0).
+ *   - a marker at L of a HOLD clip fires once, in the step that reaches the end: the "clip finished" event.  Sitting on L, nothing.
+ *   - a marker at time 0 does not fire in the step in which a clip is started (the requester knows that event already); it fires
+ *     at every loop seam.
+ *   - after a promotion or a switch in advance's steps 3-4 the new clip starts at its t0: nothing of it fires in that step.
+ *   - the clocks are IEEE: an infinite or NaN clock (advance never makes one from finite values) goes through the lines above as it is.
+ *
+ * mmdx_animator_events.  `model` gives the device, the stream and the recording, as for advance.  The masks cost one launch; with
+ * lists a second one follows (per-chunk counts, then the scatter: no atomics, the order is the instance order).  NULL animator /
+ * set / args / dt / out_fired, a struct_size mismatch, unknown flag bits, n_lists > MMDX_EVENTS_MAX_LISTS, n_lists > 0 with NULL
+ * out_ids / out_counts or list_stride < NI, a misaligned device pointer (dt: 8 bytes, the others: 4), a set whose clip count is not
+ * the animator's and a host NaN dt are MMDX_ERR_INVALID_ARGUMENT, each before the first HIP call.  Device, stream and graph rules are
+ * advance's: asynchronous on `model`'s stream, a model of another device than the animator's (or than the set's copy) is refused,
+ * recordable after one unrecorded run with the same set (a host dt is frozen into the recording), and the animator and the set are
+ * pinned by a graph that holds them.  A set keeps a small scratch for the counts: use one set from one stream at a time. */
+enum { MMDX_EVENTS_DOMINANT_SIDE = (1u << 15) }; /* mmdx_animator_events: only the side with the larger weight fires (step 6) */
+#define MMDX_EVENTS_MAX_LISTS 4
+
+typedef struct mmdx_event_set_s *mmdx_event_set_t;
+
+typedef struct mmdx_event_marker {
+    double time;                   /* seconds, 0 <= time <= L(clip)                                                                */
+    uint32_t clip;                 /* < n_clips                                                                                    */
+    uint32_t channel;              /* < 32: the bit of out_fired                                                                   */
+} mmdx_event_marker;               /* 16 bytes */
+
+typedef struct mmdx_event_set_desc {
+    uint32_t struct_size;          /* = sizeof(mmdx_event_set_desc)                                                                */
+    uint32_t n_markers;            /* 0 allowed                                                                                    */
+    const mmdx_event_marker *markers; /* [n_markers] host, any order; NULL only when n_markers == 0                                */
+} mmdx_event_set_desc;
+
+typedef struct mmdx_event_set_info {
+    uint32_t struct_size;
+    uint32_t n_markers, n_clips;
+    int32_t device_ordinal;        /* where the device copy lives, -1 = not made yet                                               */
+} mmdx_event_set_info;
+
+typedef struct mmdx_events_args {
+    uint32_t struct_size, flags;   /* = sizeof(mmdx_events_args); MMDX_ANIM_DT_ON_DEVICE | MMDX_EVENTS_DOMINANT_SIDE or 0          */
+    const double *dt;              /* as mmdx_animator_advance: a host value, or a device double with the flag                     */
+    uint32_t *out_fired;           /* DEVICE [NI]: bit c set = a marker of channel c was passed during the step                    */
+    uint32_t n_lists, list_stride; /* 0..4 lists; list l = out_ids + l * list_stride; list_stride >= NI when n_lists > 0           */
+    uint32_t list_mask[MMDX_EVENTS_MAX_LISTS];   /* the channels of each list; entries >= n_lists are not read                     */
+    const uint32_t *levels;        /* optional DEVICE [NI]: mmdx_cull_bounds' out_levels; MMDX_CULLED enters no list               */
+    uint32_t *out_ids, *out_counts;/* DEVICE; out_counts[MMDX_EVENTS_MAX_LISTS], entries >= n_lists written 0                      */
+} mmdx_events_args;
+
+MMDX_API mmdx_status mmdx_event_set_create(mmdx_animator_t animator, const mmdx_event_set_desc *desc, mmdx_event_set_t *out_set);
+MMDX_API void mmdx_event_set_destroy(mmdx_event_set_t set);
+MMDX_API mmdx_status mmdx_event_set_get_info(mmdx_event_set_t set, mmdx_event_set_info *info);
+MMDX_API mmdx_status mmdx_animator_events(mmdx_animator_t animator, mmdx_event_set_t set, mmdx_model_t model,
+                                          const mmdx_events_args *args);
+
 /* ---- where every instance stands: palette x world matrix ----------------------------------------------------------------------
  * Every palette the solves above write is in model space.  mmdx_palette_place multiplies each skinning matrix of instance i on the
  * right by that instance's world matrix W[i], so the deform that follows, its bounds and mmdx_cull_bounds are all in world space:

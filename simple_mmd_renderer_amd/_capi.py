@@ -133,6 +133,32 @@ class RootTurnArgs(C.Structure):
     _fields_ = list(RootMotionArgs._fields_)
 
 
+EVENTS_DOMINANT_SIDE = 1 << 15            # MMDX_EVENTS_DOMINANT_SIDE: mmdx_animator_events lets only the heavier side of a fade fire
+EVENTS_MAX_LISTS = 4                      # MMDX_EVENTS_MAX_LISTS
+
+
+class EventMarker(C.Structure):
+    """mmdx_event_marker: a time in a clip and the channel (< 32) it fires."""
+    _fields_ = [("time", C.c_double), ("clip", C.c_uint32), ("channel", C.c_uint32)]
+
+
+class EventSetDesc(C.Structure):
+    """mmdx_event_set_desc: the markers of mmdx_event_set_create, host memory, any order."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_markers", C.c_uint32), ("markers", C.c_void_p)]
+
+
+class EventSetInfo(C.Structure):
+    """mmdx_event_set_info (mmdx_event_set_get_info)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_markers", C.c_uint32), ("n_clips", C.c_uint32), ("device_ordinal", C.c_int32)]
+
+
+class EventsArgs(C.Structure):
+    """mmdx_events_args: the step, the per-instance masks and the instance lists of mmdx_animator_events (all outputs device memory)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("dt", C.c_void_p), ("out_fired", C.c_void_p),
+                ("n_lists", C.c_uint32), ("list_stride", C.c_uint32), ("list_mask", C.c_uint32 * EVENTS_MAX_LISTS),
+                ("levels", C.c_void_p), ("out_ids", C.c_void_p), ("out_counts", C.c_void_p)]
+
+
 class BoneMotionKeys(C.Structure):
     """mmdx_bone_motion_keys: the host key tables of a bound bone motion (mmdx_bone_motion_get_keys)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_bones", C.c_uint32), ("n_keys", C.c_uint32), ("n_curves", C.c_uint32),
@@ -319,6 +345,11 @@ SIGNATURES = {
     "mmdx_bone_motion_in_place": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "mmdx_animator_root_motion_turn": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RootTurnArgs)]),
     "mmdx_bone_motion_in_place_turn": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    # clip markers: (animator, mmdx_event_set_desc*, out_set); (set); (set, info*); (animator, set, model, mmdx_events_args*)
+    "mmdx_event_set_create": (C.c_int32, [C.c_void_p, C.POINTER(EventSetDesc), C.POINTER(C.c_void_p)]),
+    "mmdx_event_set_destroy": (None, [C.c_void_p]),
+    "mmdx_event_set_get_info": (C.c_int32, [C.c_void_p, C.POINTER(EventSetInfo)]),
+    "mmdx_animator_events": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EventsArgs)]),
     "mmdx_bone_motion_get_keys": (C.c_int32, [C.c_void_p, C.POINTER(BoneMotionKeys)]),
     "mmdx_skeleton_solve_morphed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),

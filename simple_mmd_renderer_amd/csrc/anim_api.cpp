@@ -14,6 +14,7 @@
 #include "anim_kernels.hpp"
 #include "api_internal.hpp"
 #include "error.hpp"
+#include "events_kernels.hpp"
 #include "graph_pin.hpp"
 #include "host_runtime.hpp"
 #include "rig_kernels.hpp"
@@ -154,6 +155,19 @@ mmdx_status copy_state(mmdx_animator_t a, mmdx_model_t model, const mmdx_animato
 }
 
 }  // namespace
+
+// events_api.cpp reaches an animator through these two and nothing else
+AnimatorHostTable mmdx::animator_host_table(const mmdx_animator_s *a) {
+    return AnimatorHostTable{a->ni, a->n_clips, a->clips.data()};
+}
+
+mmdx_status mmdx::animator_on_device(mmdx_animator_s *a, int device, AnimArrays *arrays, AnimClips *table, GraphPin **pin) {
+    if (mmdx_status r = state_to_device(a, device)) return r;
+    *arrays = a->arrays;
+    *table = a->table;
+    *pin = &a->pin;
+    return MMDX_OK;
+}
 
 std::vector<uint32_t> mmdx::motion_set_last_frames(const MotionSetHost &h) {
     std::vector<uint32_t> last(h.n_clips, 0);

@@ -598,6 +598,7 @@ private:
 // steps them -- loop wrap, hold, "then" chains, the fade and its hand-over, pending requests (mmdx.h states the arithmetic) -- and
 // operands() is what MotionSet::BlendTimePalettes / BlendTimeMorphRates take.  table: one mmdx_animator_clip per clip of the set
 // (empty = every clip loops over its own length).
+class EventSet;
 class Animator {
 public:
     Animator(MotionSet &set, uint32_t n_instances, const std::vector<mmdx_animator_clip> &table = {}) : set_(set), n_(n_instances) {
@@ -648,6 +649,14 @@ public:
         RootTurn(moving, root_bone, axes, placements_device, dt, normalize);
         Advance(dt);
     }
+    // Clip markers (mmdx.h, mmdx_animator_events): out_fired [n] in device memory receives, per instance, the channels of the markers
+    // of `events` that the step Advance is ABOUT to take passes; call it before Advance with the same dt.  With n_lists > 0, list l
+    // (out_ids + l * list_stride, ascending instance ids, its length in out_counts[l]) holds the instances whose mask meets
+    // list_masks[l] -- and, with levels (mmdx_cull_bounds' out_levels), are not culled -- ready for any select call.  dt_on_device:
+    // dt is a device double (record this form); dominant: MMDX_EVENTS_DOMINANT_SIDE.
+    inline void Events(EventSet &events, uint32_t *out_fired, const double *dt, bool dt_on_device = false, uint32_t n_lists = 0,
+                       const uint32_t *list_masks = nullptr, uint32_t list_stride = 0, uint32_t *out_ids = nullptr,
+                       uint32_t *out_counts = nullptr, const uint32_t *levels = nullptr, bool dominant = false);
     // instance ids[j] fades over fades[j] seconds (NULL: at once) to clips[j], started at start_times[j] (NULL: 0); host lists
     void Request(uint32_t n, const uint32_t *ids, const uint32_t *clips, const float *fades = nullptr, const double *start_times = nullptr,
                  bool on_device = false) {
@@ -696,6 +705,39 @@ private:
     uint32_t n_;
     mmdx_animator_t anim_ = nullptr;
 };
+
+// The markers of an animator's clips (mmdx.h, mmdx_event_set_create): {time in seconds, clip, channel < 32} in any order.  The set
+// copies what it needs of the animator and may outlive it.
+class EventSet {
+public:
+    EventSet(Animator &animator, const std::vector<mmdx_event_marker> &markers) {
+        mmdx_event_set_desc d{};
+        d.struct_size = sizeof(d);
+        d.n_markers = uint32_t(markers.size());
+        d.markers = markers.empty() ? nullptr : markers.data();
+        check(mmdx_event_set_create(animator.handle(), &d, &set_));
+    }
+    ~EventSet() { mmdx_event_set_destroy(set_); }
+    EventSet(const EventSet &) = delete;
+    EventSet &operator=(const EventSet &) = delete;
+    mmdx_event_set_t handle() const { return set_; }
+
+private:
+    mmdx_event_set_t set_ = nullptr;
+};
+
+inline void Animator::Events(EventSet &events, uint32_t *out_fired, const double *dt, bool dt_on_device, uint32_t n_lists,
+                             const uint32_t *list_masks, uint32_t list_stride, uint32_t *out_ids, uint32_t *out_counts,
+                             const uint32_t *levels, bool dominant) {
+    mmdx_events_args a{};
+    a.struct_size = sizeof(a);
+    a.flags = (dt_on_device ? uint32_t(MMDX_ANIM_DT_ON_DEVICE) : 0u) | (dominant ? uint32_t(MMDX_EVENTS_DOMINANT_SIDE) : 0u);
+    a.dt = dt; a.out_fired = out_fired;
+    a.n_lists = n_lists; a.list_stride = list_stride;
+    for (uint32_t l = 0; l < n_lists && l < MMDX_EVENTS_MAX_LISTS; ++l) a.list_mask[l] = list_masks[l];
+    a.levels = levels; a.out_ids = out_ids; a.out_counts = out_counts;
+    check(mmdx_animator_events(anim_, events.handle(), set_.poser().handle(), &a));
+}
 
 // Bone sockets (mmdx.h, mmdx_palette_sockets): where a character's hand, head or saddle is, for every instance, on the device.  The
 // reference-side equivalent for one Poser is bone_images_[b].global_offset_matrix_inv_ * bone_images_[b].skinning_matrix_.  A set

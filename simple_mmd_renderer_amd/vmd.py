@@ -674,6 +674,29 @@ class Animator:
         else:
             self.advance_device_dt(dt_ptr, model)
 
+    def events(self, event_set: "EventSet", out_fired_ptr, dt: Optional[float] = None, dt_ptr=None, lists=None, levels_ptr=None,
+               dominant: bool = False, model=None) -> None:
+        """mmdx_animator_events: out_fired u32[NI] (device memory) receives, per instance, the channels of the markers of `event_set`
+        that the step advance() is ABOUT to take passes -- call it before advance with the same step, dt or dt_ptr as in
+        root_motion.  lists: None, or (masks, list_stride, out_ids_ptr, out_counts_ptr) -- up to four channel masks; list l, at
+        out_ids + l * list_stride words, receives in ascending order the instances whose mask meets masks[l] (and, with levels_ptr,
+        mmdx_cull_bounds' out_levels, are not culled), out_counts u32[4] the lengths.  dominant: only the heavier side of a
+        cross-fade fires (EVENTS_DOMINANT_SIDE).  The animator's arrays are not written."""
+        if (dt is None) == (dt_ptr is None):
+            raise ValueError("give one of dt and dt_ptr")
+        host = C.c_double(dt) if dt is not None else None
+        flags = (0 if dt is not None else ANIM_DT_ON_DEVICE) | (api.EVENTS_DOMINANT_SIDE if dominant else 0)
+        args = EventsArgs(C.sizeof(EventsArgs), flags, C.addressof(host) if dt is not None else dt_ptr, out_fired_ptr)
+        if lists is not None:
+            masks, args.list_stride, args.out_ids, args.out_counts = lists
+            if len(masks) > api.EVENTS_MAX_LISTS:
+                raise ValueError("at most %d lists" % api.EVENTS_MAX_LISTS)
+            args.n_lists = len(masks)
+            for l, m in enumerate(masks):
+                args.list_mask[l] = int(m)
+        args.levels = levels_ptr
+        api.check(api.lib().mmdx_animator_events(self.h, event_set.h, model.h if model is not None else None, C.byref(args)))
+
     def request(self, ids, clips, fades=None, start_times=None, model=None) -> None:
         """Host lists: instance ids[j] fades (fades[j] seconds, default 0 = at once) to clips[j] started at start_times[j]."""
         i, c = np.ascontiguousarray(ids, np.uint32).reshape(-1), np.ascontiguousarray(clips, np.uint32).reshape(-1)
@@ -732,6 +755,38 @@ class Animator:
     def close(self):
         if getattr(self, "h", None):
             api.lib().mmdx_animator_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+EventMarker, EventSetDesc, EventsArgs = api.EventMarker, api.EventSetDesc, api.EventsArgs
+
+
+class EventSet:
+    """The markers of an animator's clips (mmdx_event_set_t): markers = (time seconds, clip, channel < 32) in any order; the set keeps
+    them sorted by (clip, time) and copies what it needs of the animator, which may be closed afterwards."""
+
+    def __init__(self, animator: "Animator", markers):
+        rows = [(float(t), int(c), int(ch)) for t, c, ch in markers]
+        table = (EventMarker * max(len(rows), 1))(*[EventMarker(*r) for r in rows])
+        desc = EventSetDesc(C.sizeof(EventSetDesc), len(rows), C.addressof(table) if rows else None)
+        self.h = C.c_void_p()
+        api.check(api.lib().mmdx_event_set_create(animator.h, C.byref(desc), C.byref(self.h)))
+        self.n_markers = len(rows)
+
+    def info(self) -> dict:
+        i = api.EventSetInfo(C.sizeof(api.EventSetInfo))
+        api.check(api.lib().mmdx_event_set_get_info(self.h, C.byref(i)))
+        return dict(n_markers=i.n_markers, n_clips=i.n_clips, device_ordinal=i.device_ordinal)
+
+    def close(self):
+        if getattr(self, "h", None):
+            api.lib().mmdx_event_set_destroy(self.h)
             self.h = None
 
     def __del__(self):
