@@ -1,7 +1,7 @@
 // tests/anim_math_driver.cpp -- TEST INFRASTRUCTURE ONLY: csrc/anim_math.hpp, the arithmetic of mmdx_animator_advance, compiled for
 // the host.  A stand-alone program: `anim_math_driver in.bin out.bin` reads a crowd's state, the clip table, a dt per step and the
 // requests that arrive before each step, runs the steps and writes every state array after every step.  tests/test_animator.py
-// builds it once plain and once with -fsanitize=address,undefined (both with -ffp-contract=off) and compares the output with
+// builds it once plain and once under the sanitizers (tests/host_program.py: build(..., sanitize=True)) and compares the output with
 // tests/animator_ref.py bit for bit.
 //
 // in.bin   u32 ni, nc, n_steps, n_req

@@ -2,22 +2,21 @@
 
   * fired() / lists_of(): a restatement of the header's steps 1-9 in numpy -- whole arrays at a time, masks instead of branches,
     comparisons of float64 arrays.  It is written from the header's text, not from csrc/events_math.hpp; the clock of a side is
-    animator_ref._wrap, the restatement of advance's wrap.  fired() also reports which of the header's cases every instance went
+    animator_ref.wrap, the restatement of advance's wrap.  fired() also reports which of the header's cases every instance went
     through, so a test can prove its coverage;
   * sort_markers(): the (clip, time) order and the offset table the header describes;
   * case_table(): the generated state table of the CPU and GPU tests, and MARKERS, the marker set it is made for;
   * the stand-alone CPU driver of csrc/events_math.hpp (tests/events_math_driver.cpp): built with g++ at test time, plain and with
-    -fsanitize=address,undefined, into a temporary directory.
+    the sanitizers, by tests/host_program.py.
 """
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import animator_ref as ar
+from tests import host_program as hp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+HERE = hp.TESTS
 NONE, CULLED, MAX_LISTS = ar.NONE, 0xFFFFFFFF, 4
 STATE = (("clips_a", np.uint32), ("clips_b", np.uint32), ("times_a", np.float64), ("times_b", np.float64),
          ("weights", np.float32), ("speed", np.float32), ("fade_rate", np.float32))      # the seven arrays the call reads
@@ -59,7 +58,7 @@ def _side(table, markers, clip, t0, s):
     length, mode = table["length"][row], table["mode"][row]
     with np.errstate(all="ignore"):
         raw = t0 + s
-        t1, fold = ar._wrap(table, clip, raw)
+        t1, fold = ar.wrap(table, clip, raw)
         forwards = raw >= length
         near = np.where(forwards, length, 0.0)
         far = np.where(forwards, 0.0, length)
@@ -189,28 +188,15 @@ def tiled(state, ni, seed=3):
 
 
 # ---- the CPU driver -------------------------------------------------------------------------------------------------------------
-_built = {}
-
-
 def build_driver(sanitize=False):
-    key = "san" if sanitize else "plain"
-    if key not in _built:
-        exe = os.path.join(tempfile.mkdtemp(prefix="mmdx_events_driver_"), "events_math_driver_" + key)
-        cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
-               *(ar.SANITIZE if sanitize else ()), os.path.join(HERE, "events_math_driver.cpp"), "-o", exe]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("building the events driver failed:\n" + r.stdout + r.stderr)
-        _built[key] = exe
-    return _built[key]
+    return hp.build("events_math_driver", [os.path.join(HERE, "events_math_driver.cpp")], sanitize=sanitize)
 
 
 def run_driver(exe, t, markers, state, dts, dominant, masks=(), levels=None):
     """-> (sorted markers, first, per call: (fired, counts, lists [4, ni] with 0xFFFFFFFF behind a count))."""
     ni, nc = state["speed"].size, t["length"].size
-    d = tempfile.mkdtemp(prefix="mmdx_events_run_")
-    fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-    with open(fin, "wb") as f:
+
+    def write(f):
         np.array([ni, nc, markers.size, len(dts), len(masks), levels is not None], np.uint32).tofile(f)
         for k in ("length", "mode", "next", "fade"):
             t[k].tofile(f)
@@ -222,15 +208,10 @@ def run_driver(exe, t, markers, state, dts, dominant, masks=(), levels=None):
         np.array(list(masks) + [0] * (MAX_LISTS - len(masks)), np.uint32).tofile(f)
         if levels is not None:
             np.ascontiguousarray(levels, np.uint32).tofile(f)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("events_math_driver failed (%d):\n%s%s" % (r.returncode, r.stdout, r.stderr))
-    calls = []
-    with open(fout, "rb") as f:
+
+    def read(f):
         s = np.fromfile(f, MARKER, markers.size)
         first = np.fromfile(f, np.uint32, nc + 1)
-        for _ in dts:
-            calls.append((np.fromfile(f, np.uint32, ni), np.fromfile(f, np.uint32, MAX_LISTS),
-                          np.fromfile(f, np.uint32, MAX_LISTS * ni).reshape(MAX_LISTS, ni)))
-        assert f.read() == b""
-    return s, first, calls
+        return s, first, [(np.fromfile(f, np.uint32, ni), np.fromfile(f, np.uint32, MAX_LISTS),
+                           np.fromfile(f, np.uint32, MAX_LISTS * ni).reshape(MAX_LISTS, ni)) for _ in dts]
+    return hp.run_files(exe, write, read)

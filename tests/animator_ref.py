@@ -6,15 +6,15 @@
   * sweep(): the seeded scenario of the CPU and GPU tests -- a clip table with every mode, a crowd with every kind of start, a dt
     per step and the requests that arrive before each step;
   * the stand-alone CPU driver of csrc/anim_math.hpp (tests/anim_math_driver.cpp): built with g++ at test time, plain and with
-    -fsanitize=address,undefined, into a temporary directory.
+    the sanitizers, by tests/host_program.py.
 """
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from tests import host_program as hp
+
+HERE = hp.TESTS
 NONE, NO_REQUEST = 0xFFFFFFFF, 0xFFFFFFFE           # MMDX_CLIP_NONE, MMDX_ANIM_NO_REQUEST
 LOOP, HOLD, THEN = 0, 1, 2                          # MMDX_ANIM_*
 ARRAYS = (("clips_a", np.uint32), ("clips_b", np.uint32), ("times_a", np.float64), ("times_b", np.float64),
@@ -43,7 +43,7 @@ def _clamp(t, length):
     return np.where(t > length, length, np.where(t >= 0.0, t, 0.0))
 
 
-def _wrap(table, clip, t):
+def wrap(table, clip, t):
     """wrap(c, t) of the header for whole arrays -> (new clocks, which of them folded)."""
     nc = table["length"].size
     has = clip < nc
@@ -69,12 +69,12 @@ def advance(state, table, dt):
     nc = table["length"].size
     with np.errstate(all="ignore"):
         step = s["speed"].astype(np.float64) * np.float64(dt)
-        s["times_a"], ev["fold"] = _wrap(table, s["clips_a"], s["times_a"] + step)
+        s["times_a"], ev["fold"] = wrap(table, s["clips_a"], s["times_a"] + step)
         s["loops"] = s["loops"] + ev["fold"].astype(np.uint32)
         fading = s["fade_rate"] > np.float32(0)
         ev["fading"] = fading
         ev["request_waits"] = fading & (s["req_clip"] != NO_REQUEST)
-        tb, _ = _wrap(table, s["clips_b"], s["times_b"] + step)
+        tb, _ = wrap(table, s["clips_b"], s["times_b"] + step)
         s["times_b"] = np.where(fading, tb, s["times_b"])
         w = s["weights"] + np.float32(dt) * s["fade_rate"]
         w = np.where(w >= np.float32(0), w, np.float32(0))
@@ -187,21 +187,8 @@ def run_reference(table, state, dts, requests):
 
 
 # ---- the CPU driver -------------------------------------------------------------------------------------------------------------
-_built = {}
-SANITIZE = ("-fsanitize=address,undefined", "-fno-sanitize-recover=all")
-
-
 def build_driver(sanitize=False):
-    key = "san" if sanitize else "plain"
-    if key not in _built:
-        exe = os.path.join(tempfile.mkdtemp(prefix="mmdx_anim_driver_"), "anim_math_driver_" + key)
-        cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
-               *(SANITIZE if sanitize else ()), os.path.join(HERE, "anim_math_driver.cpp"), "-o", exe]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("building the animator driver failed:\n" + r.stdout + r.stderr)
-        _built[key] = exe
-    return _built[key]
+    return hp.build("anim_math_driver", [os.path.join(HERE, "anim_math_driver.cpp")], sanitize=sanitize)
 
 
 def run_driver(exe, table, state, dts, requests):
@@ -210,9 +197,8 @@ def run_driver(exe, table, state, dts, requests):
     flat = [(np.full(len(r[0]), k, np.uint32),) + tuple(r) for k, r in enumerate(requests)]
     cat = lambda j, t: np.concatenate([f[j] for f in flat]).astype(t) if flat else np.zeros(0, t)      # noqa: E731
     r_step, r_id, r_clip, r_fade, r_time = cat(0, np.uint32), cat(1, np.uint32), cat(2, np.uint32), cat(3, np.float32), cat(4, np.float64)
-    d = tempfile.mkdtemp(prefix="mmdx_anim_run_")
-    fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-    with open(fin, "wb") as f:
+
+    def write(f):
         np.array([ni, nc, len(dts), r_step.size], np.uint32).tofile(f)
         for k in ("length", "mode", "next", "fade"):
             table[k].tofile(f)
@@ -221,15 +207,7 @@ def run_driver(exe, table, state, dts, requests):
         np.ascontiguousarray(dts, np.float64).tofile(f)
         for a in (r_step, r_id, r_clip, r_fade, r_time):
             a.tofile(f)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("anim_math_driver failed (%d):\n%s%s" % (r.returncode, r.stdout, r.stderr))
-    out = []
-    with open(fout, "rb") as f:
-        for _ in dts:
-            out.append({k: np.fromfile(f, t, ni) for k, t in ARRAYS})
-        assert f.read() == b""
-    return out
+    return hp.run_files(exe, write, lambda f: [{k: np.fromfile(f, t, ni) for k, t in ARRAYS} for _ in dts])
 
 
 def assert_states_equal(got, want, what):

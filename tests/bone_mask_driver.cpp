@@ -1,5 +1,5 @@
-// bone_mask_driver.cpp -- csrc/bone_mask.hpp as a stand-alone program, for tests/test_row_blend_cpu.py to build with
-// -fsanitize=address,undefined and run on the cases it gives mmdx_skeleton_subtree_mask:
+// bone_mask_driver.cpp -- csrc/bone_mask.hpp as a stand-alone program, for tests/test_row_blend_cpu.py to build under the sanitizers
+// (tests/host_program.py: build(..., sanitize=True)) and run on the cases it gives mmdx_skeleton_subtree_mask:
 //     bone_mask_driver NB parent[0] .. parent[NB-1] N_ROOTS root[0] .. root[N_ROOTS-1] inside outside
 // prints "BAD k" when roots[k] is no bone (and checks that nothing was written), else the NB mask values, one per line, as the
 // hexadecimal bit pattern of the float.  The arrays are heap allocations of exactly their sizes, so a read or write past either

@@ -1,6 +1,6 @@
 // events_math_driver.cpp -- csrc/events_math.hpp and csrc/events_table.hpp built for the host: the lines the gfx950 kernels compile,
-// run over a state table by a stand-alone program (tests/animator_events_ref.py builds it with g++, plain and with
-// -fsanitize=address,undefined, and compares what it writes with the numpy restatement).
+// run over a state table by a stand-alone program (tests/animator_events_ref.py builds it through tests/host_program.py, plain and
+// under the sanitizers, and compares what it writes with the numpy restatement).
 //
 //   events_math_driver in.bin out.bin
 //

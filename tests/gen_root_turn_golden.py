@@ -82,7 +82,7 @@ def cases():
         place = np.concatenate([rng.uniform(-20, 20, 3), [rng.uniform(-1, 1)], heading(rng, 1)]).astype(F)
         for key, v in zip(cols, (0, NONE, t, 0.0, 0.0, 1.0, 0.0, WALK_DT, 7, place, rt.ROOT_NORMALIZE if k % 2 else 0)):
             cols[key].append(v)
-        t = float(rm.ar._wrap(tab, np.array([0], np.uint32), np.array([t + 1.0 * WALK_DT]))[0][0])
+        t = float(rm.ar.wrap(tab, np.array([0], np.uint32), np.array([t + 1.0 * WALK_DT]))[0][0])
     return {k: np.array(cols[k], t) for k, t in rt.ROW_ARRAYS}
 
 

@@ -294,7 +294,7 @@ def classify(rec):
     return ("nan:" if nan else "") + name
 
 
-def _f(rec):
+def as_fields(rec):
     return dict(zip(Oracle.IK_TRACE_FIELDS, (int(x) for x in rec)))
 
 
@@ -446,7 +446,7 @@ def histogram(cs):
 
 def class_counts(cs):
     """{required / wanted class: DIFFERENT solves of the case that are it} (a candidate that two rows of a chain share counts once)."""
-    recs = {(c, cs.picks[c][i]): (_f(cs.trace[i, c]), cs.chains[c]["name"], cs.tags[i][c]) for i in range(NI) for c in range(len(cs.chains))}
+    recs = {(c, cs.picks[c][i]): (as_fields(cs.trace[i, c]), cs.chains[c]["name"], cs.tags[i][c]) for i in range(NI) for c in range(len(cs.chains))}
     recs = list(recs.values())
     out = {k: sum(1 for r, _, _ in recs if p(r)) for k, p in list(REQUIRED.items()) + list(WANTED.items())}
     for k, names in CHAIN_CLASSES.items():

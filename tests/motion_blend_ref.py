@@ -14,6 +14,7 @@ import os
 import numpy as np
 
 from tests import golden_util as gu
+from tests import host_program as hp
 from tests import motion_time_ref as mt
 
 FIXTURE = os.path.join(gu.GOLDEN_DIR, "motion_blend_expect.npz")
@@ -92,9 +93,8 @@ def check_coverage(z, a_rows, b_rows):
 
 # ---- the real libmmd ------------------------------------------------------------------------------
 def build_driver() -> str:
-    src = os.path.join(mt.HERE, "motion_blend_driver.cpp")
-    return mt._compile("motion_blend_driver", lambda so: [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-ffp-contract=off",
-                                                           "-fPIC", "-shared", "-w", "-I" + mt.REF_INC, "-o", so, src])
+    return hp.build("motion_blend_driver", [os.path.join(hp.TESTS, "motion_blend_driver.cpp")], strict=False, shared=True,
+                    include=[hp.REF_INC])
 
 
 def driver_expect(bone_vmds, bone_names, morph_vmds, morph_names, clips_a, times_a, clips_b, times_b, weights):
@@ -115,8 +115,8 @@ def driver_expect(bone_vmds, bone_names, morph_vmds, morph_names, clips_a, times
         out = np.zeros((n, len(names)) + ((width,) if width > 1 else ()), np.float32)
         one = np.zeros((n, width), np.float32)
         for j, name in enumerate(names):
-            fn(arr, C.c_uint32(len(hs)), name.encode("shift_jis"), C.c_uint32(n), mt._p(ca, C.c_uint32), mt._p(ta, C.c_double),
-               mt._p(cb, C.c_uint32), mt._p(tb, C.c_double), mt._p(w, C.c_float), mt._p(one, C.c_float))
+            fn(arr, C.c_uint32(len(hs)), name.encode("shift_jis"), C.c_uint32(n), mt.ptr(ca, C.c_uint32), mt.ptr(ta, C.c_double),
+               mt.ptr(cb, C.c_uint32), mt.ptr(tb, C.c_double), mt.ptr(w, C.c_float), mt.ptr(one, C.c_float))
             out[:, j] = one if width > 1 else one[:, 0]
         for h in hs:
             lib.mbd_destroy(C.c_void_p(h))

@@ -5,51 +5,29 @@
   * a from-scratch restatement of the same (tests/motion_time_restate.c, gcc at test time), for randomized tests
     anywhere;
   * the fixture tests/golden/motion_time_expect.npz (tests/gen_motion_time_golden.py) and its inputs.
-Nothing compiled here is committed: both libraries are built into a temporary directory per process.
+Nothing compiled here is committed: both libraries are built by tests/host_program.py.
 """
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import golden_util as gu
+from tests import host_program as hp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REF_INC = os.environ.get("REF_INC", "/root/reference/3rd_party/libmmd/include")    # as oracle/Makefile
+HERE, REF_INC, driver_available = hp.TESTS, hp.REF_INC, hp.reference_available          # what callers took from here before
 FIXTURE = os.path.join(gu.GOLDEN_DIR, "motion_time_expect.npz")
 MORPH_VMD = os.path.join(gu.GOLDEN_DIR, "vmd_small.vmd")
 BONE_VMD = os.path.join(gu.GOLDEN_DIR, "rig_small.vmd")
 
-_f32p, _f64p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint32)
-_built = {}
 
-
-def _p(a, t):
+def ptr(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
-def _compile(name, cmd_of):
-    if name not in _built:
-        d = tempfile.mkdtemp(prefix="mmdx_motion_time_")
-        so = os.path.join(d, name + ".so")
-        r = subprocess.run(cmd_of(so), capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("building %s failed:\n%s%s" % (name, r.stdout, r.stderr))
-        _built[name] = so
-    return _built[name]
-
-
 # ---- the real libmmd ------------------------------------------------------------------------------
-def driver_available() -> bool:
-    return os.path.isdir(os.path.join(REF_INC, "mmd"))
-
-
 def build_driver() -> str:
-    src = os.path.join(HERE, "motion_time_driver.cpp")
-    return _compile("motion_time_driver", lambda so: [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-ffp-contract=off",
-                                                       "-fPIC", "-shared", "-w", "-I" + REF_INC, "-o", so, src])
+    return hp.build("motion_time_driver", [os.path.join(HERE, "motion_time_driver.cpp")], strict=False, shared=True, include=[REF_INC])
 
 
 class Driver:
@@ -71,7 +49,7 @@ class Driver:
             sj = name.encode("shift_jis")
         except UnicodeEncodeError:
             return None
-        ok = self.lib.mtd_bone_poses_time(self.h, sj, C.c_uint32(t.size), _p(t, C.c_double), _p(out, C.c_float))
+        ok = self.lib.mtd_bone_poses_time(self.h, sj, C.c_uint32(t.size), ptr(t, C.c_double), ptr(out, C.c_float))
         return out if ok else None
 
     def morph_weights(self, name: str, times):
@@ -82,7 +60,7 @@ class Driver:
             sj = name.encode("shift_jis")
         except UnicodeEncodeError:
             return None
-        ok = self.lib.mtd_morph_weights_time(self.h, sj, C.c_uint32(t.size), _p(t, C.c_double), _p(out, C.c_float))
+        ok = self.lib.mtd_morph_weights_time(self.h, sj, C.c_uint32(t.size), ptr(t, C.c_double), ptr(out, C.c_float))
         return out if ok else None
 
     def close(self):
@@ -115,10 +93,8 @@ def driver_expect(bone_vmd, bone_names, morph_vmd, morph_names, times):
 
 # ---- the restatement ------------------------------------------------------------------------------
 def restatement():
-    src = os.path.join(HERE, "motion_time_restate.c")
-    lib = C.CDLL(_compile("motion_time_restate", lambda so: [os.environ.get("CC", "gcc"), "-std=gnu11", "-O2", "-ffp-contract=off",
-                                                              "-fPIC", "-shared", "-w", "-o", so, src, "-lm"]))
-    return lib
+    return C.CDLL(hp.build("motion_time_restate", [os.path.join(HERE, "motion_time_restate.c")], cxx=False, c_std="gnu11", strict=False,
+                           shared=True, link=["-lm"]))
 
 
 def tracks_of(v):
@@ -158,8 +134,8 @@ def restate_poses(v, bone_names, times):
         nk = 0 if k is None else k[0].size
         fr, tt, rot, ip = [np.ascontiguousarray(a) for a in (k if nk else dummy)]
         for i, x in enumerate(t):
-            lib.mt_bone_pose_time(C.c_uint32(nk), _p(fr, C.c_uint32), _p(tt, C.c_float), _p(rot, C.c_float), _p(ip, C.c_int8),
-                                  C.c_double(float(x)), _p(one, C.c_float))
+            lib.mt_bone_pose_time(C.c_uint32(nk), ptr(fr, C.c_uint32), ptr(tt, C.c_float), ptr(rot, C.c_float), ptr(ip, C.c_int8),
+                                  C.c_double(float(x)), ptr(one, C.c_float))
             out[i, j] = one
     return out
 
@@ -172,8 +148,8 @@ def restate_rates(v, morph_names, times):
         fr, w = np.zeros(1, np.uint32), np.zeros(1, np.float32)
     t = np.ascontiguousarray(times, np.float64).reshape(-1)
     out = np.zeros((t.size, len(morph_names)), np.float32)
-    lib.mt_morph_tracks_time(C.c_uint32(len(morph_names)), _p(off, C.c_uint32), _p(fr, C.c_uint32), _p(w, C.c_float),
-                             C.c_uint32(t.size), _p(t, C.c_double), _p(out, C.c_float))
+    lib.mt_morph_tracks_time(C.c_uint32(len(morph_names)), ptr(off, C.c_uint32), ptr(fr, C.c_uint32), ptr(w, C.c_float),
+                             C.c_uint32(t.size), ptr(t, C.c_double), ptr(out, C.c_float))
     return out
 
 

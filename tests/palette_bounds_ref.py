@@ -7,20 +7,17 @@ Boxes are compared bit for bit, except that a NaN only has to be a NaN (sign and
 Nothing compiled here is committed.
 """
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import golden_util as gu
+from tests import host_program as hp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+HERE, ROOT = hp.TESTS, hp.ROOT
 F = np.float32
 INF = F(np.inf)
 U = 2.0 ** -24
 VERTEX, GROUP = 1, 0
-_built = {}
 
 assert_rows_equal = gu.assert_bits_equal_or_both_nan
 
@@ -164,33 +161,17 @@ def max_pad(table, palettes, pos_scale, morph_scale):
 
 
 # ---- the driver -----------------------------------------------------------------------------------
-SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"]
-
-
 def build_math_driver(sanitize: bool = False) -> str:
-    name = "pbounds_math_driver" + ("_san" if sanitize else "")
-    if name not in _built:
-        exe = os.path.join(tempfile.mkdtemp(prefix="mmdx_palette_bounds_"), name)
-        cmd = ([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"] +
-               (SANITIZE if sanitize else []) + ["-o", exe, os.path.join(HERE, "pbounds_math_driver.cpp")])
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-        if r.returncode != 0:
-            raise RuntimeError("building %s failed:\n%s%s" % (name, r.stdout, r.stderr))
-        _built[name] = exe
-    return _built[name]
+    return hp.build("pbounds_math_driver", [os.path.join(HERE, "pbounds_math_driver.cpp")], sanitize=sanitize)
 
 
 def run_driver(exe, boxes, mats, eps, morph_scale, pos_scale):
     """boxes f32 [n, 9], mats f32 [NI, n, 16] through the driver (text in, text out, floats as hex bit patterns) -> f32 [NI, 6]."""
     boxes, mats = np.asarray(boxes, F).reshape(-1, 9), np.asarray(mats, F)
     ni, n = mats.shape[0], boxes.shape[0]
-    hexes = lambda a: " ".join("%08x" % v for v in gu.bits(a).reshape(-1))          # noqa: E731
-    lines = ["%d %d %s" % (n, ni, hexes(np.array([eps, morph_scale, pos_scale], F)))]
-    lines += [hexes(r) for r in boxes]
-    lines += [hexes(mats[i, r]) for i in range(ni) for r in range(n)]
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=300)
-    if r.returncode != 0:
-        raise RuntimeError("%s failed (%d):\n%s%s" % (os.path.basename(exe), r.returncode, r.stdout[-2000:], r.stderr[-4000:]))
-    out = np.array([[int(v, 16) for v in line.split()] for line in r.stdout.splitlines()], np.uint32).reshape(-1, 6)
+    lines = ["%d %d %s" % (n, ni, hp.hex_words(np.array([eps, morph_scale, pos_scale], F)))]
+    lines += [hp.hex_words(r) for r in boxes]
+    lines += [hp.hex_words(mats[i, r]) for i in range(ni) for r in range(n)]
+    out = hp.parse_hex_rows(hp.run(exe, stdin="\n".join(lines) + "\n").stdout, 6)
     assert out.shape == (ni, 6), out.shape
     return out.view(F)

@@ -9,21 +9,18 @@ Rows are compared bit for bit, except that a NaN only has to be a NaN (golden_ut
 payload of a NaN are not part of the contract.  Nothing compiled here is committed.
 """
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import golden_util as gu
-from tests import motion_time_ref as mt
+from tests import host_program as hp
 
 FIXTURE = os.path.join(gu.GOLDEN_DIR, "palette_place_expect.npz")
-ROOT = os.path.dirname(mt.HERE)
+ROOT = hp.ROOT
 F = np.float32
 ONE, TWO = F(1.0), F(2.0)
 POSE, MATRIX = 0, 1                      # the `form` of a fixture row
 IDENTITY_POSE = np.array([0, 0, 0, 0, 0, 0, 0, 1], F)
-_built = {}
 
 
 # ---- the restatement ------------------------------------------------------------------------------
@@ -77,41 +74,20 @@ assert_rows_equal = gu.assert_bits_equal_or_both_nan
 
 
 # ---- the two drivers ------------------------------------------------------------------------------
-def _compile(name, cmd_of):
-    if name not in _built:
-        exe = os.path.join(tempfile.mkdtemp(prefix="mmdx_palette_place_"), name)
-        r = subprocess.run(cmd_of(exe), capture_output=True, text=True, timeout=300)
-        if r.returncode != 0:
-            raise RuntimeError("building %s failed:\n%s%s" % (name, r.stdout, r.stderr))
-        _built[name] = exe
-    return _built[name]
-
-
 def build_libmmd_driver() -> str:
-    src = os.path.join(mt.HERE, "palette_place_driver.cpp")
-    return _compile("palette_place_driver", lambda exe: [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-ffp-contract=off", "-w",
-                                                          "-I" + mt.REF_INC, "-o", exe, src])
-
-
-SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"]
+    return hp.build("palette_place_driver", [os.path.join(hp.TESTS, "palette_place_driver.cpp")], strict=False, include=[hp.REF_INC])
 
 
 def build_math_driver(sanitize: bool = False) -> str:
-    src = os.path.join(mt.HERE, "place_math_driver.cpp")
-    return _compile("place_math_driver" + ("_san" if sanitize else ""),
-                    lambda exe: [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"] +
-                    (SANITIZE if sanitize else []) + ["-o", exe, src])
+    return hp.build("place_math_driver", [os.path.join(hp.TESTS, "place_math_driver.cpp")], sanitize=sanitize)
 
 
 def run_driver(exe, forms, s, placements):
     """The rows through one of the drivers (text in, text out, floats as hex bit patterns) -> f32 [N, 16]."""
     forms = np.asarray(forms)
     words = np.concatenate([gu.bits(s).reshape(-1, 16), gu.bits(placements).reshape(-1, 16)], axis=1)
-    stdin = "".join("%d %s\n" % (f, " ".join("%08x" % v for v in row)) for f, row in zip(forms, words))
-    r = subprocess.run([exe], input=stdin, capture_output=True, text=True, timeout=300)
-    if r.returncode != 0:
-        raise RuntimeError("%s failed (%d):\n%s%s" % (os.path.basename(exe), r.returncode, r.stdout[-2000:], r.stderr[-4000:]))
-    out = np.array([[int(v, 16) for v in line.split()] for line in r.stdout.splitlines()], np.uint32)
+    stdin = "".join("%d %s\n" % (f, hp.hex_words(row)) for f, row in zip(forms, words))
+    out = hp.parse_hex_rows(hp.run(exe, stdin=stdin).stdout, 16)
     assert out.shape == (forms.size, 16), out.shape
     return out.view(F)
 

@@ -10,16 +10,15 @@ Rows are compared bit for bit, except that a NaN only has to be a NaN (golden_ut
 payload of a NaN are not part of the contract.  Nothing compiled here is committed.
 """
 import os
-import subprocess
 
 import numpy as np
 
 from tests import golden_util as gu
-from tests import motion_time_ref as mt
+from tests import host_program as hp
 from tests import palette_place_ref as pp
 
 FIXTURE = os.path.join(gu.GOLDEN_DIR, "palette_sockets_expect.npz")
-ROOT = pp.ROOT
+ROOT = hp.ROOT
 F = np.float32
 NONE, POSE, MATRIX = 0, 1, 2             # the `form` of a fixture row: what its offset is
 
@@ -72,17 +71,12 @@ assert_rows_equal = gu.assert_bits_equal_or_both_nan
 
 # ---- the two drivers ------------------------------------------------------------------------------
 def build_libmmd_driver() -> str:
-    src = os.path.join(mt.HERE, "palette_sockets_driver.cpp")
-    return pp._compile("palette_sockets_driver", lambda exe: [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-ffp-contract=off", "-w",
-                                                              "-I" + mt.REF_INC, "-o", exe, src])
+    return hp.build("palette_sockets_driver", [os.path.join(hp.TESTS, "palette_sockets_driver.cpp")], strict=False, include=[hp.REF_INC])
 
 
 def build_math_driver(sanitize: bool = False) -> str:
-    src = os.path.join(mt.HERE, "socket_math_driver.cpp")
-    err = os.path.join(ROOT, "simple_mmd_renderer_amd", "csrc", "error.cpp")
-    return pp._compile("socket_math_driver" + ("_san" if sanitize else ""),
-                       lambda exe: [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"] +
-                       (pp.SANITIZE if sanitize else []) + ["-o", exe, src, err])
+    return hp.build("socket_math_driver", [os.path.join(hp.TESTS, "socket_math_driver.cpp"), os.path.join(hp.CSRC, "error.cpp")],
+                    sanitize=sanitize)
 
 
 def run_driver(exe, forms, s, rest, offsets):
@@ -91,11 +85,8 @@ def run_driver(exe, forms, s, rest, offsets):
     rest4 = np.zeros((forms.size, 4), F)
     rest4[:, :3] = rest
     words = np.concatenate([gu.bits(s).reshape(-1, 16), gu.bits(rest4), gu.bits(offsets).reshape(-1, 16)], axis=1)
-    stdin = "".join("%d %s\n" % (f, " ".join("%08x" % v for v in row)) for f, row in zip(forms, words))
-    r = subprocess.run([exe], input=stdin, capture_output=True, text=True, timeout=300)
-    if r.returncode != 0:
-        raise RuntimeError("%s failed (%d):\n%s%s" % (os.path.basename(exe), r.returncode, r.stdout[-2000:], r.stderr[-4000:]))
-    out = np.array([[int(v, 16) for v in line.split()] for line in r.stdout.splitlines()], np.uint32)
+    stdin = "".join("%d %s\n" % (f, hp.hex_words(row)) for f, row in zip(forms, words))
+    out = hp.parse_hex_rows(hp.run(exe, stdin=stdin).stdout, 16)
     assert out.shape == (forms.size, 16), out.shape
     return out.view(F)
 

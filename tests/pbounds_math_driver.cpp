@@ -3,7 +3,7 @@
 // table rows of 9 floats (lo, hi, reach), then ni * n matrices of 16 floats (instance-major: the matrix of each row's bone); every
 // float as the 8 hex digits of its bit pattern.  stdout: ni rows of 6 floats.  Every row goes through heap buffers of exactly the
 // size the header may touch, so an access past them is an AddressSanitizer report.
-// Build: g++ -std=c++17 -O2 -ffp-contract=off [-fsanitize=address,undefined] (tests/palette_bounds_ref.py).
+// Build: tests/host_program.py build(), plain and sanitize=True (called from tests/palette_bounds_ref.py).
 #include <cstdint>
 #include <cstdio>
 #include <cstring>

@@ -3,7 +3,7 @@
 // a line of stdin is the form (0 = pose, 1 = matrix), 16 floats of S and 16 floats of a placement (a pose uses the first 8), each as
 // the 8 hex digits of its bit pattern; a line of stdout is the 16 floats of S * W.  Every row goes through heap buffers of exactly
 // the size the header may touch (16, 8 or 16, 16, 4 floats), so an access past them is an AddressSanitizer report.
-// Build: g++ -std=c++17 -O2 -ffp-contract=off [-fsanitize=address,undefined] (tests/test_palette_place.py).
+// Build: tests/host_program.py build(), plain and sanitize=True (called from tests/palette_place_ref.py).
 #include <cstdint>
 #include <cstdio>
 #include <cstring>

@@ -9,13 +9,11 @@ Nothing compiled here is committed.
 """
 import math
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import golden_util as gu
-from tests import motion_time_ref as mt
+from tests import host_program as hp
 from tests import row_blend_ref as rb
 
 FIXTURE = os.path.join(gu.GOLDEN_DIR, "pose_add_expect.npz")
@@ -182,19 +180,8 @@ def morph_rig(seed=11, nb=20):
 
 
 # ---- the real libmmd ------------------------------------------------------------------------------
-_built = {}
-
-
 def build_driver() -> str:
-    if "exe" not in _built:
-        exe = os.path.join(tempfile.mkdtemp(prefix="mmdx_pose_add_"), "pose_add_driver")
-        cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-ffp-contract=off", "-w", "-I" + mt.REF_INC,
-               os.path.join(mt.HERE, "pose_add_driver.cpp"), "-o", exe]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("building pose_add_driver failed:\n" + r.stdout + r.stderr)
-        _built["exe"] = exe
-    return _built["exe"]
+    return hp.build("pose_add_driver", [os.path.join(hp.TESTS, "pose_add_driver.cpp")], strict=False, include=[hp.REF_INC])
 
 
 def driver_expect(a_poses, b_poses, a_rates, b_rates, weights, bone_masks, morph_masks, mask_ids, pose_refs, rate_refs, ref_ids):
@@ -215,14 +202,8 @@ def driver_expect(a_poses, b_poses, a_rates, b_rates, weights, bone_masks, morph
     pr, rt = np.zeros((n, nb), pose_t), np.zeros((n, nm), rate_t)
     pr["a"], pr["b"], pr["r"], pr["e"], pr["has"] = a_poses, b_poses, rp, ep, has[:, None]
     rt["a"], rt["b"], rt["r"], rt["e"], rt["has"] = a_rates, b_rates, rr, er, has[:, None]
-    with tempfile.TemporaryDirectory(prefix="mmdx_pose_add_io_") as d:
-        src, dst = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(src, "wb") as f:
-            f.write(np.array([n * nb, n * nm], np.uint32).tobytes() + pr.tobytes() + rt.tobytes())
-        r = subprocess.run([build_driver(), src, dst], capture_output=True, text=True, timeout=300)
-        if r.returncode != 0:
-            raise RuntimeError("pose_add_driver failed (%d):\n%s%s" % (r.returncode, r.stdout, r.stderr))
-        out = np.fromfile(dst, np.float32)
+    out = hp.run_files(build_driver(), lambda f: f.write(np.array([n * nb, n * nm], np.uint32).tobytes() + pr.tobytes() + rt.tobytes()),
+                       lambda f: np.fromfile(f, np.float32))
     assert out.size == n * nb * 8 + n * nm
     return out[:n * nb * 8].reshape(n, nb, 8).copy(), out[n * nb * 8:].reshape(n, nm).copy()
 

@@ -2,7 +2,7 @@
 // for the host.  A stand-alone program: `root_math_driver in.bin out.bin` reads rows of animator state, a step and a placement
 // each, plus R -- the root bone's translation at the eight instants of every row, which on the device is eval_bone_pose -- and
 // writes the instants, the fold flags and the placements after the call.  tests/test_root_motion_cpu.py builds it once plain and
-// once with -fsanitize=address,undefined (both with -ffp-contract=off) and compares the output, bit for bit, with the golden rows
+// once under the sanitizers (tests/host_program.py: build(..., sanitize=True)) and compares the output, bit for bit, with the golden rows
 // of the real libmmd and with tests/root_motion_ref.py.
 // The two functions root_math.hpp takes from its caller are motion_blend.hpp's blend_side and blend_rate, which exist for the
 // device only; the host forms below are those two, line for line.

@@ -6,24 +6,23 @@
     carry libmmd's, a GPU test takes it from the pinned MotionSet.eval_bones_time;
   * the clips of the fixture (tests/golden/root_*.vmd, written by vmd.write_vmd) and their clip table;
   * the two stand-alone programs: tests/root_motion_driver.cpp (the REAL libmmd; built where the reference's headers are) and
-    tests/root_math_driver.cpp (csrc/root_math.hpp for the host, plain and with -fsanitize=address,undefined);
+    tests/root_math_driver.cpp (csrc/root_math.hpp for the host, plain and under the sanitizers), both built and run by
+    tests/host_program.py;
   * the fixture tests/golden/root_motion_expect.npz (tests/gen_root_motion_golden.py).
 Nothing compiled here is committed.
 """
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import animator_ref as ar
 from tests import golden_util as gu
+from tests import host_program as hp
 from tests import motion_blend_ref as mb
-from tests import motion_time_ref as mt
 from tests import palette_place_ref as pp
 
 F = np.float32
-HERE = mt.HERE
+HERE = hp.TESTS
 FIXTURE = os.path.join(gu.GOLDEN_DIR, "root_motion_expect.npz")
 NONE = ar.NONE
 ROOT_X, ROOT_Y, ROOT_Z = 1, 2, 4                     # MMDX_ROOT_*
@@ -95,7 +94,7 @@ def _side_times(tab, clips, t0, s):
     """Step 2's clocks for whole arrays -> (instants f64 [N, 4]: t0, t1, near, far; folded bool [N])."""
     nc = tab["length"].size
     raw = t0 + s
-    t1, fold = ar._wrap(tab, clips, raw)
+    t1, fold = ar.wrap(tab, clips, raw)
     length = tab["length"][np.where(clips < nc, clips, 0)]
     forwards = raw >= length
     near = np.where(fold & forwards, length, 0.0)
@@ -164,77 +163,54 @@ def apply(state, tab, dt, r, axes, placements):
 
 
 # ---- the stand-alone programs ---------------------------------------------------------------------------------------------------
-_built = {}
-SANITIZE = ("-fsanitize=address,undefined", "-fno-sanitize-recover=all")
 ROW_ARRAYS = (("clips_a", np.uint32), ("clips_b", np.uint32), ("times_a", np.float64), ("times_b", np.float64), ("weights", F),
               ("speed", F), ("fade_rate", F), ("dt", np.float64), ("axes", np.uint32), ("placements", F))
 
 
-def _build(key, cmd_of):
-    if key not in _built:
-        exe = os.path.join(tempfile.mkdtemp(prefix="mmdx_root_"), key)
-        r = subprocess.run(cmd_of(exe), capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("building %s failed:\n%s%s" % (key, r.stdout, r.stderr))
-        _built[key] = exe
-    return _built[key]
-
-
 def build_math_driver(sanitize=False):
-    return _build("root_math_driver_" + ("san" if sanitize else "plain"), lambda exe: [
-        os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
-        *(SANITIZE if sanitize else ()), os.path.join(HERE, "root_math_driver.cpp"), "-o", exe])
+    return hp.build("root_math_driver", [os.path.join(HERE, "root_math_driver.cpp")], sanitize=sanitize)
 
 
 def build_libmmd_driver():
-    return _build("root_motion_driver", lambda exe: [
-        os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-ffp-contract=off", "-w", "-I" + mt.REF_INC,
-        os.path.join(HERE, "root_motion_driver.cpp"), "-o", exe])
+    return hp.build("root_motion_driver", [os.path.join(HERE, "root_motion_driver.cpp")], strict=False, include=[hp.REF_INC])
 
 
-def _write_rows(f, head, tab, rows):
+def libmmd_driver_args(paths):
+    """What both libmmd drivers take behind their two files: the root's name in Shift-JIS and the clips' paths."""
+    return [ROOT_NAME.encode("shift_jis")] + [p.encode() for p in paths]
+
+
+def write_rows(f, head, tab, rows, row_arrays=ROW_ARRAYS, extra=()):
+    """A driver's input: the head words, the clip table, the row arrays and any float arrays behind them."""
     np.array(head, np.uint32).tofile(f)
     for k in ("length", "mode", "next", "fade"):
         tab[k].tofile(f)
-    for k, t in ROW_ARRAYS:
+    for k, t in row_arrays:
         np.ascontiguousarray(rows[k], t).tofile(f)
+    for a in extra:
+        np.ascontiguousarray(a, F).tofile(f)
 
 
-def _run(cmd, n, with_r_out):
-    d = tempfile.mkdtemp(prefix="mmdx_root_run_")
-    fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-    yield fin
-    r = subprocess.run([cmd[0], fin, fout] + cmd[1:], capture_output=True)
-    if r.returncode != 0:
-        raise RuntimeError("%s failed (%d):\n%s%s" % (os.path.basename(cmd[0]), r.returncode, r.stdout.decode(errors="replace"),
-                                                     r.stderr.decode(errors="replace")))
-    with open(fout, "rb") as f:
+def _run(exe, args, head, tab, rows, extra, with_r_out):
+    n = rows["dt"].size
+
+    def read(f):
         out = dict(times=np.fromfile(f, np.float64, n * 8).reshape(n, 2, 4), folded=np.fromfile(f, np.uint32, n * 2).reshape(n, 2) != 0)
         if with_r_out:
             out["r"] = np.fromfile(f, F, n * 24).reshape(n, 2, 4, 3)
         out["expect"] = np.fromfile(f, F, n * 3).reshape(n, 3)
-        assert f.read() == b""
-    yield out
+        return out
+    return hp.run_files(exe, lambda f: write_rows(f, head, tab, rows, extra=extra), read, args)
 
 
 def run_math_driver(exe, tab, rows, r=None):
     """csrc/root_math.hpp on the host over `rows` (dict of ROW_ARRAYS) with R = r f32 [N, 2, 4, 3] (None: the instants only)."""
-    n = rows["dt"].size
-    steps = _run([exe], n, False)
-    with open(next(steps), "wb") as f:
-        _write_rows(f, [n, tab["length"].size, 0 if r is None else 1], tab, rows)
-        if r is not None:
-            np.ascontiguousarray(r, F).tofile(f)
-    return next(steps)
+    return _run(exe, (), [rows["dt"].size, tab["length"].size, 0 if r is None else 1], tab, rows, () if r is None else (r,), False)
 
 
 def run_libmmd_driver(tab, rows):
     """The real libmmd over `rows` -> times, folded, r (libmmd's R at the sampled instants) and expect."""
-    n = rows["dt"].size
-    steps = _run([build_libmmd_driver(), ROOT_NAME.encode("shift_jis")] + [p.encode() for p in clip_paths()], n, True)
-    with open(next(steps), "wb") as f:
-        _write_rows(f, [n, tab["length"].size], tab, rows)
-    return next(steps)
+    return _run(build_libmmd_driver(), libmmd_driver_args(clip_paths()), [rows["dt"].size, tab["length"].size], tab, rows, (), True)
 
 
 def rows_as_state(rows):

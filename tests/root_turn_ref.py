@@ -8,24 +8,23 @@
   * the clips: tests/root_motion_ref's six and tests/golden/root_q8.vmd, a root whose rotations are drawn from the quaternion group
     {+-1, +-i, +-j, +-k} and whose translations are dyadic, so that every value of its walk is exact;
   * the two stand-alone programs: tests/root_turn_driver.cpp (the REAL libmmd; built where the reference's headers are) and
-    tests/root_turn_math_driver.cpp (csrc/root_math.hpp for the host, plain and with -fsanitize=address,undefined);
+    tests/root_turn_math_driver.cpp (csrc/root_math.hpp for the host, plain and under the sanitizers), both built and run by
+    tests/host_program.py;
   * the fixture tests/golden/root_turn_expect.npz (tests/gen_root_turn_golden.py).
 Nothing compiled here is committed.
 """
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import animator_ref as ar
 from tests import golden_util as gu
+from tests import host_program as hp
 from tests import motion_blend_ref as mb
-from tests import motion_time_ref as mt
 from tests import root_motion_ref as rm
 
 F = np.float32
-HERE = mt.HERE
+HERE = hp.TESTS
 FIXTURE = os.path.join(gu.GOLDEN_DIR, "root_turn_expect.npz")
 Q8_VMD = os.path.join(gu.GOLDEN_DIR, "root_q8.vmd")
 NONE = ar.NONE
@@ -223,52 +222,34 @@ ROW_ARRAYS = rm.ROW_ARRAYS + (("flags", np.uint32),)
 
 
 def build_math_driver(sanitize=False):
-    return rm._build("root_turn_math_driver_" + ("san" if sanitize else "plain"), lambda exe: [
-        os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
-        *(rm.SANITIZE if sanitize else ()), os.path.join(HERE, "root_turn_math_driver.cpp"), "-o", exe])
+    return hp.build("root_turn_math_driver", [os.path.join(HERE, "root_turn_math_driver.cpp")], sanitize=sanitize)
 
 
 def build_libmmd_driver():
-    return rm._build("root_turn_driver", lambda exe: [
-        os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-ffp-contract=off", "-w", "-I" + mt.REF_INC,
-        os.path.join(HERE, "root_turn_driver.cpp"), "-o", exe])
+    return hp.build("root_turn_driver", [os.path.join(HERE, "root_turn_driver.cpp")], strict=False, include=[hp.REF_INC])
 
 
-def _run(cmd, head, tab, rows, extra, with_tq_out):
+def _run(exe, args, tab, rows, extra, with_tq_out):
     n = rows["dt"].size
-    d = tempfile.mkdtemp(prefix="mmdx_root_turn_run_")
-    fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-    with open(fin, "wb") as f:
-        np.array(head, np.uint32).tofile(f)
-        for k in ("length", "mode", "next", "fade"):
-            tab[k].tofile(f)
-        for k, t in ROW_ARRAYS:
-            np.ascontiguousarray(rows[k], t).tofile(f)
-        for a in extra:
-            np.ascontiguousarray(a, F).tofile(f)
-    r = subprocess.run([cmd[0], fin, fout] + cmd[1:], capture_output=True)
-    if r.returncode != 0:
-        raise RuntimeError("%s failed (%d):\n%s%s" % (os.path.basename(cmd[0]), r.returncode, r.stdout.decode(errors="replace"),
-                                                     r.stderr.decode(errors="replace")))
-    with open(fout, "rb") as f:
+
+    def read(f):
         out = dict(times=np.fromfile(f, np.float64, n * 8).reshape(n, 2, 4), folded=np.fromfile(f, np.uint32, n * 2).reshape(n, 2) != 0)
         if with_tq_out:
             out["t"] = np.fromfile(f, F, n * 24).reshape(n, 2, 4, 3)
             out["q"] = np.fromfile(f, F, n * 32).reshape(n, 2, 4, 4)
         out["expect"] = np.fromfile(f, F, n * 8).reshape(n, 8)
-        assert f.read() == b""
-    return out
+        return out
+    return hp.run_files(exe, lambda f: rm.write_rows(f, [n, tab["length"].size], tab, rows, ROW_ARRAYS, extra), read, args)
 
 
 def run_math_driver(exe, tab, rows, t, q):
     """csrc/root_math.hpp on the host over `rows` (dict of ROW_ARRAYS) with (T, Q) = t f32 [N, 2, 4, 3], q f32 [N, 2, 4, 4]."""
-    return _run([exe], [rows["dt"].size, tab["length"].size], tab, rows, (t, q), False)
+    return _run(exe, (), tab, rows, (t, q), False)
 
 
 def run_libmmd_driver(tab, rows):
     """The real libmmd over `rows` -> times, folded, t, q (libmmd's (T, Q) at the sampled instants) and expect."""
-    cmd = [build_libmmd_driver(), ROOT_NAME.encode("shift_jis")] + [p.encode() for p in clip_paths()]
-    return _run(cmd, [rows["dt"].size, tab["length"].size], tab, rows, (), True)
+    return _run(build_libmmd_driver(), rm.libmmd_driver_args(clip_paths()), tab, rows, (), True)
 
 
 rows_as_state = rm.rows_as_state

@@ -82,8 +82,8 @@ def driver_expect(bone_names, morph_names, clips_a, times_a, clips_b, times_b, e
         one = np.zeros((n, width), np.float32)
         for j, name in enumerate(names):
             w = np.ascontiguousarray(e[:, j], np.float32)
-            fn(arr, C.c_uint32(len(hs)), name.encode("shift_jis"), C.c_uint32(n), mt._p(ca, C.c_uint32), mt._p(ta, C.c_double),
-               mt._p(cb, C.c_uint32), mt._p(tb, C.c_double), mt._p(w, C.c_float), mt._p(one, C.c_float))
+            fn(arr, C.c_uint32(len(hs)), name.encode("shift_jis"), C.c_uint32(n), mt.ptr(ca, C.c_uint32), mt.ptr(ta, C.c_double),
+               mt.ptr(cb, C.c_uint32), mt.ptr(tb, C.c_double), mt.ptr(w, C.c_float), mt.ptr(one, C.c_float))
             out[:, j] = one if width > 1 else one[:, 0]
         for h in hs:
             lib.mbd_destroy(C.c_void_p(h))

@@ -5,7 +5,7 @@
 // first 8), each as the 8 hex digits of its bit pattern; a line of stdout is the 16 floats of the socket's matrix.  Every row is a
 // one-socket desc that goes through socket_table_build -- a pose is expanded there, as in the library -- and then through socket_row
 // per output row, all in heap buffers of exactly the size the code may touch, so an access past them is an AddressSanitizer report.
-// Build: g++ -std=c++17 -O2 -ffp-contract=off [-fsanitize=address,undefined] this file + csrc/error.cpp
+// Build: tests/host_program.py build(), plain and sanitize=True, from this file + csrc/error.cpp
 // (tests/palette_sockets_ref.py).
 #include <cstdint>
 #include <cstdio>

@@ -10,7 +10,6 @@ and on the GPU the animator's arrays feed the existing blend calls unchanged.
 import ctypes as C
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -20,6 +19,7 @@ from simple_mmd_renderer_amd import synth, vmd
 from simple_mmd_renderer_amd.engine import DeformModel, DeviceBuffer
 from tests import animator_ref as ar
 from tests import golden_util as gu
+from tests import host_program as hp
 from tests import motion_blend_ref as mb
 from tests import motion_time_ref as mt
 from tests.test_capi_symbols import declared_symbols
@@ -28,7 +28,7 @@ ENTRY_POINTS = ("mmdx_motion_set_clip_frames", "mmdx_animator_create", "mmdx_ani
                 "mmdx_animator_operands", "mmdx_animator_device_arrays", "mmdx_animator_set_state", "mmdx_animator_get_state",
                 "mmdx_animator_request", "mmdx_animator_advance")
 NONE, NO_REQUEST = vmd.CLIP_NONE, vmd.ANIM_NO_REQUEST
-ROOT = os.path.dirname(mt.HERE)
+ROOT = hp.ROOT
 needs_driver = pytest.mark.skipif(not mt.driver_available(), reason="the reference's libmmd headers are not present")
 
 
@@ -37,7 +37,7 @@ def _lib(hip_lib):
     return hip_lib
 
 
-def _close(*xs):
+def close_all(*xs):
     for x in xs:
         for y in (x if isinstance(x, (list, tuple)) else [x]):
             y.free() if isinstance(y, DeviceBuffer) else y.close()
@@ -107,17 +107,14 @@ def test_clip_frames_is_the_largest_key_frame_of_the_bound_tracks():
     an = vmd.Animator(both, 3)
     assert an.clip_table() == [(np.float64(f) / np.float64(30.0), vmd.ANIM_LOOP, NONE, 0.0) for f in both.clip_frames()]
     assert api.lib().mmdx_motion_set_clip_frames(None, None) == 1
-    _close(an, whole, all_b, all_m, s_sub, s_none, sub, none, both, bones, morphs, bms, mms, bvs, mvs)
+    close_all(an, whole, all_b, all_m, s_sub, s_none, sub, none, both, bones, morphs, bms, mms, bvs, mvs)
 
 
 @needs_driver
 def test_clip_frames_equals_get_length_of_libmmd():
     """Motion::GetLength() of the real libmmd over the same bytes, every track of the file bound."""
-    so = os.path.join(tempfile.mkdtemp(prefix="mmdx_anim_len_"), "anim_len.so")
-    r = subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-fPIC", "-shared", "-w", "-DANIM_DRIVER_LIBMMD", "-I" + mt.REF_INC,
-                        "-o", so, os.path.join(mt.HERE, "anim_math_driver.cpp")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    lib = C.CDLL(so)
+    lib = C.CDLL(hp.build("anim_len", [os.path.join(hp.TESTS, "anim_math_driver.cpp")], strict=False, shared=True, include=[hp.REF_INC],
+                          define=["ANIM_DRIVER_LIBMMD"]))
     lib.amd_motion_length.restype, lib.amd_motion_length.argtypes = C.c_longlong, [C.c_char_p]
     for path in sorted(set(mb.BONE_VMDS + mb.MORPH_VMDS)):
         v = vmd.Vmd(path)
@@ -125,10 +122,10 @@ def test_clip_frames_equals_get_length_of_libmmd():
                  [v.bind_morphs(v.morph_track_names)] if v.info["n_morph_tracks"] else None)
         ms = vmd.MotionSet(*sides)
         assert ms.clip_frames().tolist() == [lib.amd_motion_length(path.encode())], path
-        _close(ms, *[s for s in sides if s], v)
+        close_all(ms, *[s for s in sides if s], v)
 
 
-def _count(events, name, where=None):
+def count_events(events, name, where=None):
     return int(sum((ev[name] if where is None else ev[name] & where(ev)).sum() for ev in events))
 
 
@@ -147,7 +144,7 @@ def check_coverage(table, state, dts, requests, states, events):
     assert set(state["speed"].tolist()) == {1.0, 0.5, -1.0, 0.0}
     fades = np.concatenate([r[2] for r in requests])
     assert (fades == 0).any() and ((fades > 0) & (fades < 1 / 144)).any() and (fades > 10 / 60).any()        # at once, < a step, many steps
-    n = {k: _count(events, k) for k in events[0]}
+    n = {k: count_events(events, k) for k in events[0]}
     assert min(n[k] for k in ("fold", "fading", "promote", "request", "request_waits", "then", "then_none", "at_once", "fade_started",
                               "promote_and_go", "on_length")) >= 3, n
     # a step that spans several lengths folds once; a backwards step folds too
@@ -181,12 +178,12 @@ def test_host_build_of_the_arithmetic_equals_the_numpy_restatement():
         ar.assert_states_equal(got[k], want[k], f"NaN dt, step {k}")
 
 
-def _tiny_set():
+def tiny_set():
     names = ["センター", "首"]
     v = vmd.Vmd(vmd.write_vmd(synth.make_bone_keys(names, 1, keys_per=3), [("あ", 0, 0.5), ("あ", 9, 1.0)]))
     bm = v.bind_bones(names)
     ms = vmd.MotionSet([bm, bm])
-    _close(bm, v)
+    close_all(bm, v)
     return ms
 
 
@@ -194,7 +191,7 @@ def test_animator_entry_points_refuse_bad_arguments():
     """Everything that needs no device is decided before the first HIP call, so it is checked here without a GPU."""
     lib = api.lib()
     err = lambda: lib.mmdx_last_error_string().decode()          # noqa: E731
-    ms = _tiny_set()
+    ms = tiny_set()
     h = C.c_void_p()
 
     def desc(ni=4, clips=None, n_clips=None, struct_size=None, reserved0=0):
@@ -285,7 +282,7 @@ def test_animator_entry_points_refuse_bad_arguments():
     lib.mmdx_animator_destroy(h)
     lib.mmdx_animator_destroy(None)
     # the Python face raises the same statuses
-    ms = _tiny_set()
+    ms = tiny_set()
     with pytest.raises(api.MmdxError) as e:
         vmd.Animator(ms, 4, [(0.0, vmd.ANIM_THEN, 9, 0.0), (0.0, vmd.ANIM_LOOP, 0, 0.0)])
     assert e.value.status == 2
@@ -300,18 +297,18 @@ def test_animator_entry_points_refuse_bad_arguments():
         an.request([0, 1], [0])
     with pytest.raises(ValueError):
         an.set_state(speed=[1.0])
-    _close(an, ms)
+    close_all(an, ms)
 
 
 def _tiny_frames():
-    ms = _tiny_set()
+    ms = tiny_set()
     f = int(ms.clip_frames()[0])
     ms.close()
     return f
 
 
 # ---------------------------------------------------------------------------------------- GPU ----
-def _scenario_vmds(bone_names, morph_names=()):
+def scenario_vmds(bone_names, morph_names=()):
     """Seven clips whose last key frames are animator_ref.CLIP_FRAMES (clip 1: a single key at frame 0, length 0)."""
     out = []
     for c, last in enumerate(ar.CLIP_FRAMES):
@@ -327,17 +324,17 @@ def _scenario_vmds(bone_names, morph_names=()):
     return out
 
 
-def _scenario_set(bone_names, morph_names=()):
-    vs = [vmd.Vmd(d) for d in _scenario_vmds(bone_names, morph_names)]
+def scenario_set(bone_names, morph_names=()):
+    vs = [vmd.Vmd(d) for d in scenario_vmds(bone_names, morph_names)]
     bms = [v.bind_bones(bone_names) for v in vs]
     mms = [v.bind_morphs(morph_names) for v in vs] if morph_names else None
     ms = vmd.MotionSet(bms, mms)
-    _close(bms, mms or [], vs)
+    close_all(bms, mms or [], vs)
     assert ms.clip_frames().tolist() == list(ar.CLIP_FRAMES)
     return ms
 
 
-def _rows_for_create():
+def rows_for_create():
     return [(l, m, n, f) for l, m, n, f in ar.CLIP_ROWS]
 
 
@@ -348,8 +345,8 @@ def test_gpu_advance_equals_the_restatement(ni, device_dt):
     """60 steps of the sweep, requests from host lists before the steps that have them: all eleven arrays after every step."""
     table, state, dts, requests = ar.sweep(ni, 60)
     want, _ = ar.run_reference(table, state, dts, requests)
-    ms = _scenario_set(["b0", "b1", "b2"])
-    an = vmd.Animator(ms, ni, _rows_for_create())
+    ms = scenario_set(["b0", "b1", "b2"])
+    an = vmd.Animator(ms, ni, rows_for_create())
     got_table = an.clip_table()
     assert [r[0] for r in got_table] == table["length"].tolist()
     ar.assert_states_equal(an.get_state(), ar.initial_state(ni), "the initial state")
@@ -364,15 +361,15 @@ def test_gpu_advance_equals_the_restatement(ni, device_dt):
         else:
             an.advance(dt)
         ar.assert_states_equal(an.get_state(), want[k], f"NI {ni}, step {k} (dt {dt})")
-    _close(an, ms, d_dt)
+    close_all(an, ms, d_dt)
 
 
 @pytest.mark.gpu
 def test_gpu_nan_device_dt_changes_nothing_and_device_requests_skip_bad_ids():
     ni = 65
     table, state, dts, requests = ar.sweep(ni, 4)
-    ms = _scenario_set(["b0", "b1", "b2"])
-    an = vmd.Animator(ms, ni, _rows_for_create())
+    ms = scenario_set(["b0", "b1", "b2"])
+    an = vmd.Animator(ms, ni, rows_for_create())
     an.set_state(**state)
     d_dt = DeviceBuffer.from_numpy(np.array([np.nan], np.float64))
     an.advance_device_dt(d_dt.ptr)
@@ -396,14 +393,14 @@ def test_gpu_nan_device_dt_changes_nothing_and_device_requests_skip_bad_ids():
     an.advance_device_dt(d_dt.ptr)
     want, _ = ar.advance(want, table, 1 / 60)
     ar.assert_states_equal(an.get_state(), want, "the step after")
-    _close(an, ms, ds, d_dt)
+    close_all(an, ms, ds, d_dt)
 
 
 @pytest.mark.gpu
 def test_gpu_set_state_and_get_state_round_trip_and_partial_updates():
     ni = 65
     _, state, _, _ = ar.sweep(ni, 1)
-    ms = _scenario_set(["b0", "b1", "b2"])
+    ms = scenario_set(["b0", "b1", "b2"])
     an = vmd.Animator(ms, ni)
     an.set_state(**state)
     ar.assert_states_equal(an.get_state(), state, "round trip")
@@ -428,7 +425,7 @@ def test_gpu_set_state_and_get_state_round_trip_and_partial_updates():
     raw = DeviceBuffer.adopt(addr["speed"], ni * 4)
     gu.assert_bits_equal(raw.download((ni,), np.float32), speed, "speed through its device address")
     raw.ptr = None
-    _close(an, ms)
+    close_all(an, ms)
 
 
 def _rig(name):
@@ -449,11 +446,11 @@ def test_gpu_operands_feed_the_blend_calls_unchanged(rig):
     sk, solver = _rig(rig)
     assert sk.info["solver"] == solver
     names, mnames = [f"b{i}" for i in range(sk.nb)], ["m0", "m1", "m2"]
-    ms = _scenario_set(names, mnames)
+    ms = scenario_set(names, mnames)
     table, state, dts, requests = ar.sweep(ni, 20)
     want, events = ar.run_reference(table, state, dts, requests)
     assert sum(int(ev["fading"].sum()) for ev in events) > 100 and sum(int(ev["promote"].sum()) for ev in events) > 5
-    an = vmd.Animator(ms, ni, _rows_for_create())
+    an = vmd.Animator(ms, ni, rows_for_create())
     an.set_state(**state)
     d_pal, d_w = DeviceBuffer(ni * sk.nb * 64), DeviceBuffer(ni * 3 * 4)
     seen = set()
@@ -471,7 +468,7 @@ def test_gpu_operands_feed_the_blend_calls_unchanged(rig):
         gu.assert_bits_equal(d_w.download((ni, 3), np.float32), ms.blend_morphs_time(*host), f"{rig}: rates, step {k}")
         seen.add(pal.tobytes())
     assert len(seen) >= np.count_nonzero(dts) >= 18               # the crowd moved in every step that was not dt == 0
-    _close(an, ms, sk, d_pal, d_w)
+    close_all(an, ms, sk, d_pal, d_w)
 
 
 @pytest.mark.gpu
@@ -483,7 +480,7 @@ def test_gpu_graph_of_advance_blend_solve_morphs_and_deform():
     names, mnames = [f"bone{i}" for i in range(m.nb)], [f"morph{i}" for i in range(m.nm)]
     ni = 5
     sk = vmd.Skeleton(m.bone_pos, np.asarray(m.bone_parent, np.int32))
-    ms = _scenario_set(names, mnames)
+    ms = scenario_set(names, mnames)
     flags = api.PALETTE_ON_DEVICE | api.WEIGHTS_ON_DEVICE | api.OUT_ON_DEVICE
     start = ar.initial_state(ni)
     start["clips_a"][:] = [0, 3, 5, NONE, 2]
@@ -492,7 +489,7 @@ def test_gpu_graph_of_advance_blend_solve_morphs_and_deform():
     dts = [1 / 60, 1 / 30, 0.25, 1 / 144, 1 / 60, 0.5]
     request = (np.array([3, 0], np.uint32), np.array([6, NONE], np.uint32), np.array([0.0, 0.3], np.float32), np.array([0.1, 0.0]))
     with DeformModel(m) as dm:
-        eager, replayed = vmd.Animator(ms, ni, _rows_for_create()), vmd.Animator(ms, ni, _rows_for_create())
+        eager, replayed = vmd.Animator(ms, ni, rows_for_create()), vmd.Animator(ms, ni, rows_for_create())
         d_dt = DeviceBuffer.from_numpy(np.array([0.0], np.float64))
         d_pal, d_w = DeviceBuffer(ni * m.nb * 64), DeviceBuffer(ni * m.nm * 4)
         sa, sb = dm.out_sizes(api.OUT_SOA, ni)
@@ -542,8 +539,8 @@ def test_gpu_graph_of_advance_blend_solve_morphs_and_deform():
         with pytest.raises(api.MmdxError, match="destroyed"):
             g.launch()
         g.close()
-        _close(eager, d_dt, d_pal, d_w, d_a, d_b)
-    _close(ms, sk)
+        close_all(eager, d_dt, d_pal, d_w, d_a, d_b)
+    close_all(ms, sk)
 
 
 @pytest.mark.gpu
@@ -587,4 +584,4 @@ def test_cpp_animator_matches_python_path(tmp_path):
     assert st["loops"][0] >= 1                                    # clips of 24 frames at most: the first instance has wrapped
     want = "animated checksum=%016x clock[0]=%.6f loops[0]=%d" % (h, st["times_a"][0], st["loops"][0])
     assert want in r.stderr, (want, r.stderr)
-    _close(an, ms, sk, bms, mms, vs, d_pal)
+    close_all(an, ms, sk, bms, mms, vs, d_pal)

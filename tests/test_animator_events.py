@@ -33,7 +33,7 @@ SENT = er.SENTINEL
 CALLS = [(dt, dom) for dt in er.DTS for dom in (False, True)]
 MASKS4 = (0xFFFFFFFF, (1 << 1) | (1 << 14) | (1 << 9), 1 << 20, 0x000000FF)      # everything; three channels; a channel no marker
 #                                                                                   has; channels 0-7 (overlaps the first two)
-_close = ta._close
+_close = ta.close_all
 
 
 @pytest.fixture(autouse=True)
@@ -42,8 +42,8 @@ def _lib(hip_lib):
 
 
 def _animator(ni):
-    ms = ta._scenario_set(["b0"])
-    an = vmd.Animator(ms, ni, ta._rows_for_create())
+    ms = ta.scenario_set(["b0"])
+    an = vmd.Animator(ms, ni, ta.rows_for_create())
     assert [r[0] for r in an.clip_table()] == er.table()["length"].tolist()
     return ms, an
 
@@ -123,7 +123,7 @@ def test_animator_events_refuses_bad_arguments_before_any_device_call(hip_lib):
     ni = 5
     ms, an = _animator(ni)
     es = vmd.EventSet(an, er.MARKERS)
-    ms2 = ta._tiny_set()
+    ms2 = ta.tiny_set()
     an2 = vmd.Animator(ms2, ni)                                             # another clip count
     assert an2.n_clips != an.n_clips
     err = lambda: (hip_lib.mmdx_last_error_string() or b"").decode()          # noqa: E731

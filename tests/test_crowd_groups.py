@@ -15,7 +15,6 @@ outputs, bounds, select lists with a bad id inside a group, fast math grouped ag
 the planner picks a group by itself."""
 import collections
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -23,7 +22,7 @@ import pytest
 from simple_mmd_renderer_amd import _capi as api
 from simple_mmd_renderer_amd import synth
 from simple_mmd_renderer_amd.engine import DeformModel, DeviceBuffer, device_count
-from tests.test_sanitizers import ROOT, SAN
+from tests import host_program as hp
 
 BPV = {api.OUT_SOA: (12, 12), api.OUT_VERTEX32: (32, 0), api.OUT_SOA_POS16: (6, 12)}   # bytes per vertex of out_a, out_b
 TAIL = 64                                                                            # sentinel bytes behind the last instance
@@ -151,14 +150,10 @@ def crowd_inputs(m, ni, morph):
 
 # ---- CPU: the table against the planner ---------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def planner(tmp_path_factory):
-    """tests/launch_shape_driver.cpp `eval`, built as tests/test_launch_shape.py builds it."""
-    exe = tmp_path_factory.mktemp("crowd_groups") / "launch_shape_driver"
-    cmd = ["g++", "-std=c++17", "-Wall", "-Wextra"] + SAN + ["-O2", os.path.join(ROOT, "tests", "launch_shape_driver.cpp"),
-                                                            os.path.join(ROOT, "simple_mmd_renderer_amd", "csrc", "launch_shape.cpp"),
-                                                            "-o", str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
+def planner():
+    """tests/launch_shape_driver.cpp `eval`: the program tests/test_launch_shape.py builds, by the same arguments."""
+    exe = hp.build("launch_shape_driver", [os.path.join(hp.TESTS, "launch_shape_driver.cpp"), os.path.join(hp.CSRC, "launch_shape.cpp")],
+                   sanitize=True)
 
     def plan(cases):
         """cases: dicts of the driver's Case fields (missing: the defaults) -> dicts of the planned shapes."""
@@ -167,7 +162,7 @@ def planner(tmp_path_factory):
         dflt = dict(flags=0, bounds=0, select=0, out_dev=1, out_host_mapped=0, out_bytes=1 << 20, threads=0, group=0, lds_target=0,
                     fused_pack=0, store_wt=-1, frame_kernel=1, stagger=0)
         text = "".join(" ".join(str(int(dict(dflt, **c)[k])) for k in order) + "\n" for c in cases)
-        r = subprocess.run([str(exe), "eval"], input=text, capture_output=True, text=True, timeout=300)
+        r = hp.run(exe, ["eval"], stdin=text)
         assert r.returncode == 0, r.stdout + r.stderr
         lines = r.stdout.splitlines()
         assert len(lines) == len(cases)

@@ -25,7 +25,8 @@ import pytest
 from simple_mmd_renderer_amd import _capi as api
 from simple_mmd_renderer_amd import synth
 from simple_mmd_renderer_amd.engine import DeformModel, DeviceBuffer, device_count, make_cull_view, planes_from_matrix
-from tests.test_sanitizers import ROOT, SAN
+from tests import host_program as hp
+from tests.host_program import ROOT
 
 HEADER = os.path.join(ROOT, "include", "mmdx.h")
 BENCH_HEADER = os.path.join(ROOT, "include", "mmdx_bench.h")
@@ -236,14 +237,9 @@ def test_planes_from_matrix_bit_for_bit(hip_lib, zero_to_one):
 
 # ---- CPU: the planner ------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("cull_shape") / "cull_shape_driver"
-    cmd = ["g++", "-std=c++17", "-Wall", "-Wextra"] + SAN + [os.path.join(ROOT, "tests", "cull_shape_driver.cpp"),
-                                                             os.path.join(ROOT, "simple_mmd_renderer_amd", "csrc", "cull_shape.cpp"),
-                                                             "-o", str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+def driver():
+    return hp.build("cull_shape_driver", [os.path.join(hp.TESTS, "cull_shape_driver.cpp"), os.path.join(hp.CSRC, "cull_shape.cpp")],
+                    opt="-O1", sanitize=True)
 
 
 def plan_ref(ni, form, chunk):
@@ -254,7 +250,7 @@ def plan_ref(ni, form, chunk):
 
 
 def test_planner_sweep_under_sanitizers(driver):
-    r = subprocess.run([driver, "sweep"], capture_output=True, text=True, timeout=300)
+    r = hp.run(driver, ["sweep"])
     assert r.returncode == 0, r.stdout + r.stderr
     counts = dict(kv.split("=") for kv in r.stdout.split())
     assert int(counts["failures"]) == 0 and "ERROR" not in r.stderr
@@ -265,7 +261,7 @@ def test_planner_form_chunk_and_chunk_count(driver):
     """Form by NI (the crossover and its neighbours), forced forms, chunk clamping, chunk count: against this file's own statement."""
     nis = [0, 1, 63, 64, 65, 200, 1023, 1025, 2500, CROSSOVER - 1, CROSSOVER, CROSSOVER + 1, 16384, 262144, 2 ** 32 - 1]
     cases = [(ni, form, chunk) for ni in nis for form in (0, 1, 2, 7) for chunk in (0, -3, 1, 64, 100, 128, 1000, 1024, 1025, 99999)]
-    r = subprocess.run([driver, "eval"], input="".join("%d %d %d\n" % c for c in cases), capture_output=True, text=True, timeout=300)
+    r = hp.run(driver, ["eval"], stdin="".join("%d %d %d\n" % c for c in cases))
     assert r.returncode == 0, r.stdout + r.stderr
     lines = r.stdout.splitlines()
     assert len(lines) == len(cases)

@@ -156,7 +156,7 @@ def test_trace_records_say_what_the_solve_did(oracle):
     for ch in cs.chains:
         poses[ch["ik"], 0:3] = (0.3, -0.2, 0.1)
     rec = oracle.trace_ik(lambda: oracle.bone_solve_full(cs.rig[0], cs.rig[1], poses, *cs.rig[2:]))
-    by = {int(r[0]): ix._f(r) for r in rec}
+    by = {int(r[0]): ix.as_fields(r) for r in rec}
     z = by[cs.chains[col["loop0"]]["ik"]]
     assert ix.Oracle.IK_EXITS[z["exit"]] == "loop_zero" and z["sweeps"] == 0
     f = by[cs.chains[col["fixed40"]]["ik"]]

@@ -5,32 +5,27 @@ code's own rules, (2) evaluates the calls of tests/golden/launch_shapes.json, wh
 as it stood before the planner was split out: a change that moves one of them fails here, on any machine."""
 import json
 import os
-import subprocess
 
 import pytest
 
 from simple_mmd_renderer_amd import synth
 from simple_mmd_renderer_amd.engine import DeformModel
-from tests.test_sanitizers import ROOT, SAN
+from tests import host_program as hp
+from tests.host_program import ROOT
 
 TABLE = os.path.join(ROOT, "tests", "golden", "launch_shapes.json")
 KERNELS = ["none", "deform", "pack", "frame"]        # LaunchShape::Kernel
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("launch_shape") / "launch_shape_driver"
-    # -O2 after SAN's -O1: the sweep is 22 million planner calls; about 15 s under the sanitizers on an 8-core build machine
-    cmd = ["g++", "-std=c++17", "-Wall", "-Wextra"] + SAN + ["-O2"] + [os.path.join(ROOT, "tests", "launch_shape_driver.cpp"),
-                                                             os.path.join(ROOT, "simple_mmd_renderer_amd", "csrc", "launch_shape.cpp"),
-                                                             "-o", str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+def driver():
+    # -O2: the sweep is 22 million planner calls; about 15 s under the sanitizers on an 8-core build machine
+    return hp.build("launch_shape_driver", [os.path.join(hp.TESTS, "launch_shape_driver.cpp"), os.path.join(hp.CSRC, "launch_shape.cpp")],
+                    sanitize=True)
 
 
 def test_every_planned_shape_obeys_the_layout_rules(driver):
-    r = subprocess.run([driver, "sweep"], capture_output=True, text=True, timeout=900)
+    r = hp.run(driver, ["sweep"], timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     counts = dict(kv.split("=") for kv in r.stdout.split())
     assert int(counts["failures"]) == 0 and "ERROR" not in r.stderr
@@ -45,7 +40,7 @@ def test_pinned_launch_shapes(driver):
     rows = table["rows"]
     assert 100 <= len(rows) <= 999
     stdin = "".join(" ".join(str(v) for v in row["in"]) + "\n" for row in rows)
-    r = subprocess.run([driver, "eval"], input=stdin, capture_output=True, text=True, timeout=300)
+    r = hp.run(driver, ["eval"], stdin=stdin)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = r.stdout.splitlines()
     assert len(lines) == len(rows)

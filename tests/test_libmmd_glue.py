@@ -8,7 +8,6 @@ the descriptor mmdx_model_create gets, and the palette read through the tap feed
 golden vertices for tests/golden/pmx_small.pmx."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,13 +15,12 @@ import pytest
 from oracle.pyoracle import Reference, reference_available
 from simple_mmd_renderer_amd import _capi as api
 from tests import golden_util as gu
+from tests import host_program as hp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_INC = "/root/reference/3rd_party/libmmd/include"
 PMX = os.path.join(gu.GOLDEN_DIR, "pmx_small.pmx")
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF_INC, "mmd")), reason="needs /root/reference (build container)")
+@pytest.mark.skipif(not hp.reference_available(), reason="needs /root/reference (build container)")
 def test_glue_header_compiles_against_libmmd_and_agrees_with_the_loader(hip_lib, tmp_path):
     from simple_mmd_renderer_amd import pmx, synth, vmd
     # the model of part 2: names written WITH the byte-order mark libmmd's VMD reader leaves in front of converted names on Linux
@@ -37,16 +35,11 @@ def test_glue_header_compiles_against_libmmd_and_agrees_with_the_loader(hip_lib,
     bone_keys = [(bone_names[1], 0, (0, 0, 0), (0, 0, 0, 1), None), (bone_names[1], 90, (0.5, 1, 0), (0, 0.3827, 0, 0.9239), None)]
     vpath = tmp_path / "glue.vmd"
     vpath.write_bytes(vmd.write_vmd(bone_keys, keys))
-    exe = tmp_path / "glue_driver"
-    lib_dir = os.path.join(ROOT, "simple_mmd_renderer_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wno-unused-parameter", os.path.join(ROOT, "tests", "glue_driver.cpp"), "-I" + REF_INC,
-           "-L" + lib_dir, "-lmmdx", "-Wl,-rpath," + lib_dir, "-o", str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    # libmmd's own headers warn (unused variables, sign compares); only OUR header must be clean
-    ours = [ln for ln in r.stderr.splitlines() if "libmmd_glue.hpp" in ln and "warning" in ln]
-    assert r.returncode == 0, r.stderr[-3000:]
-    assert not ours, "\n".join(ours)
-    r = subprocess.run([str(exe), PMX, str(tmp_path / "bom.pmx"), str(vpath)], capture_output=True, text=True)
+    lib_dir = os.path.join(hp.ROOT, "simple_mmd_renderer_amd")
+    # libmmd's own headers warn (unused variables, sign compares) and come in as system headers; OUR header must be clean: -Werror
+    exe = hp.build("glue_driver", [os.path.join(hp.TESTS, "glue_driver.cpp")], opt="-O1", isystem=[hp.REF_INC],
+                   link=["-L" + lib_dir, "-lmmdx", "-Wl,-rpath," + lib_dir])
+    r = hp.run(exe, [PMX, str(tmp_path / "bom.pmx"), str(vpath)])
     assert r.returncode == 0 and "GLUE OK" in r.stdout, r.stdout + r.stderr
 
 

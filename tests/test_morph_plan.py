@@ -10,12 +10,12 @@ before the planner was split out of api.cpp: every morph mode, kernel kind and p
 GPU: (d) the built library reproduces the same file line for line, and every sequence's last outputs are the oracle's bit for bit."""
 import json
 import os
-import subprocess
 
 import pytest
 
+from tests import host_program as hp
 from tests import morph_plan_seq as mps
-from tests.test_sanitizers import ROOT, SAN
+from tests.host_program import ROOT
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "morph_plan_sequences.json")
 KERNELS = ["none", "deform", "pack", "frame"]        # LaunchShape::Kernel
@@ -24,14 +24,9 @@ LENGTH = 6                                           # 216 million sequences: ab
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("morph_plan") / "morph_plan_driver"
-    cmd = ["g++", "-std=c++17", "-Wall", "-Wextra"] + SAN + ["-O2"] + [os.path.join(ROOT, "tests", "morph_plan_driver.cpp"),
-                                                             os.path.join(ROOT, "simple_mmd_renderer_amd", "csrc", "launch_shape.cpp"),
-                                                             "-o", str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+def driver():
+    return hp.build("morph_plan_driver", [os.path.join(hp.TESTS, "morph_plan_driver.cpp"), os.path.join(hp.CSRC, "launch_shape.cpp")],
+                    sanitize=True)
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +44,7 @@ def counts_of(r):
 
 
 def test_every_plan_obeys_the_rules(driver):
-    counts = counts_of(subprocess.run([driver, "sweep"], capture_output=True, text=True, timeout=300))
+    counts = counts_of(hp.run(driver, ["sweep"]))
     # 4 slot counts x 5 crowd sizes x shared x unchanged x host / device rates x (no list + 3 capacities) x 3 shared_fused x autoskip
     # x the record: morphed_valid x host_rates_valid x (no kept rates, the call's, others)
     assert counts["rows"] == 4 * 5 * 2 * 2 * 2 * 4 * 3 * 2 * (2 * 2 * 3)
@@ -58,7 +53,7 @@ def test_every_plan_obeys_the_rules(driver):
 
 
 def test_the_record_is_sound_over_every_short_sequence(driver):
-    counts = counts_of(subprocess.run([driver, "sequences", str(LENGTH)], capture_output=True, text=True, timeout=900))
+    counts = counts_of(hp.run(driver, ["sequences", str(LENGTH)], timeout=900))
     print(counts)
     assert counts["events"] == EVENTS and counts["settings"] == SETTINGS
     assert counts["sequences"] == SETTINGS * sum(EVENTS ** k for k in range(1, LENGTH + 1))
@@ -73,7 +68,7 @@ def expected_rows(seq):
 def test_pinned_sequences(driver, pinned):
     seqs = pinned["sequences"]
     stdin = "".join(line + "\n" for s in seqs for line in mps.driver_lines(s, pinned["models"][s["model"]]))
-    r = subprocess.run([driver, "eval"], input=stdin, capture_output=True, text=True, timeout=300)
+    r = hp.run(driver, ["eval"], stdin=stdin)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = r.stdout.splitlines()
     assert len(lines) == sum(len(s["steps"]) for s in seqs)

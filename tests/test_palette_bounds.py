@@ -19,6 +19,7 @@ from simple_mmd_renderer_amd import _capi as api
 from simple_mmd_renderer_amd import synth
 from simple_mmd_renderer_amd.engine import DeformModel, DeviceBuffer, device_count
 from tests import golden_util as gu
+from tests import host_program as hp
 from tests import palette_bounds_ref as pb
 from tests.test_capi_symbols import declared_symbols
 
@@ -49,17 +50,11 @@ def host_table(m, **kw):
 
 
 # ---------------------------------------------------------------------------------------- CPU ----
-def test_entry_points_are_declared_exported_and_bound(hip_lib, tmp_path):
+def test_entry_points_are_declared_exported_and_bound(hip_lib):
     for name in ("mmdx_palette_bounds", "mmdx_model_get_bone_boxes"):
         assert name in declared_symbols() and hasattr(hip_lib, name) and name in api.SIGNATURES, name
-    inc = os.path.join(pb.ROOT, "include")
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "mmdx.h"\nint main(void) { printf("%zu %zu %zu %u\\n", sizeof(mmdx_palette_bounds_args), '
-                   "sizeof(mmdx_bone_box_info), sizeof(mmdx_model_info), (unsigned)MMDX_ABI_VERSION); return 0; }\n")
-    exe = tmp_path / "size"
-    r = subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + inc, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    args, info, model_info, abi = (int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split())
+    args, info, model_info, abi = hp.c_values(["sizeof(mmdx_palette_bounds_args)", "sizeof(mmdx_bone_box_info)", "sizeof(mmdx_model_info)",
+                                               "MMDX_ABI_VERSION"])
     assert C.sizeof(api.PaletteBoundsArgs) == args == 4 * 4 + 2 * 8 + 2 * 4
     assert C.sizeof(api.BoneBoxInfo) == info == 32
     assert model_info == 80 and abi == 3 and hip_lib.mmdx_abi_version() == 3

@@ -20,6 +20,7 @@ from simple_mmd_renderer_amd import _capi as api
 from simple_mmd_renderer_amd import synth, vmd
 from simple_mmd_renderer_amd.engine import DeformModel, DeviceBuffer, device_count
 from tests import golden_util as gu
+from tests import host_program as hp
 from tests import motion_time_ref as mt
 from tests import palette_place_ref as pp
 from tests.test_capi_symbols import declared_symbols
@@ -38,7 +39,7 @@ def _lib(hip_lib):
 
 
 # ---------------------------------------------------------------------------------------- CPU ----
-def test_place_entry_point_is_declared_exported_and_bound(hip_lib, tmp_path):
+def test_place_entry_point_is_declared_exported_and_bound(hip_lib):
     assert "mmdx_palette_place" in declared_symbols() and hasattr(hip_lib, "mmdx_palette_place")
     assert "mmdx_palette_place" in api.SIGNATURES
     inc = os.path.join(pp.ROOT, "include")
@@ -46,15 +47,8 @@ def test_place_entry_point_is_declared_exported_and_bound(hip_lib, tmp_path):
     assert "typedef struct mmdx_place_args {" in hdr and "#define MMDX_ABI_VERSION 3u" in hdr and "g_state.model_matrix" in hdr
     assert hip_lib.mmdx_abi_version() == 3
     # the struct size and the flag values as the header gives them to a C compiler
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "mmdx.h"\nint main(void) { printf("%zu %u %u %u %u %u %d\\n", sizeof(mmdx_place_args), '
-                   "(unsigned)MMDX_PLACE_ON_DEVICE, (unsigned)MMDX_PLACE_MATRIX, (unsigned)MMDX_PALETTE_ON_DEVICE, "
-                   "(unsigned)MMDX_OUT_ON_DEVICE, (unsigned)MMDX_POSE_FLOATS, 0); return 0; }\n")
-    exe = tmp_path / "size"
-    r = subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + inc, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    size, place_dev, place_matrix, pal_dev, out_dev, pose_floats, _ = (int(v) for v in subprocess.run(
-        [str(exe)], capture_output=True, text=True, check=True).stdout.split())
+    size, place_dev, place_matrix, pal_dev, out_dev, pose_floats = hp.c_values([
+        "sizeof(mmdx_place_args)", "MMDX_PLACE_ON_DEVICE", "MMDX_PLACE_MATRIX", "MMDX_PALETTE_ON_DEVICE", "MMDX_OUT_ON_DEVICE", "MMDX_POSE_FLOATS"])
     assert C.sizeof(api.PlaceArgs) == size == 4 * 4 + 3 * 8
     assert (api.PLACE_ON_DEVICE, api.PLACE_MATRIX, api.PALETTE_ON_DEVICE, api.OUT_ON_DEVICE, api.POSE_FLOATS) == \
         (place_dev, place_matrix, pal_dev, out_dev, pose_floats)

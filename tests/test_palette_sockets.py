@@ -25,6 +25,7 @@ from simple_mmd_renderer_amd import _capi as api
 from simple_mmd_renderer_amd import synth, vmd
 from simple_mmd_renderer_amd.engine import DeformModel, DeviceBuffer, SocketSet, device_count, device_synchronize
 from tests import golden_util as gu
+from tests import host_program as hp
 from tests import motion_time_ref as mt
 from tests import palette_place_ref as pp
 from tests import palette_sockets_ref as ps
@@ -56,7 +57,7 @@ def rig_model(**kw):
 
 
 # ---------------------------------------------------------------------------------------- CPU ----
-def test_socket_entry_points_are_declared_exported_and_bound(hip_lib, tmp_path):
+def test_socket_entry_points_are_declared_exported_and_bound(hip_lib):
     for name in NEW_SYMBOLS:
         assert name in declared_symbols() and hasattr(hip_lib, name) and name in api.SIGNATURES, name
     inc = os.path.join(ps.ROOT, "include")
@@ -64,13 +65,8 @@ def test_socket_entry_points_are_declared_exported_and_bound(hip_lib, tmp_path):
     assert "typedef struct mmdx_sockets_args {" in hdr and "#define MMDX_ABI_VERSION 3u" in hdr and "global_offset_matrix_inv_" in hdr
     assert "SOCKET-major" in hdr and "MMDX_PLACE_MATRIX | MMDX_PLACE_ON_DEVICE" in hdr.split("} mmdx_sockets_args;")[1]
     assert hip_lib.mmdx_abi_version() == 3
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "mmdx.h"\nint main(void) { printf("%zu %zu %zu %u\\n", sizeof(mmdx_socket_set_desc), '
-                   "sizeof(mmdx_socket_set_info), sizeof(mmdx_sockets_args), (unsigned)MMDX_SOCKET_OFFSET_MATRIX); return 0; }\n")
-    exe = tmp_path / "size"
-    r = subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + inc, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    desc, info, args, flag = (int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split())
+    desc, info, args, flag = hp.c_values(["sizeof(mmdx_socket_set_desc)", "sizeof(mmdx_socket_set_info)", "sizeof(mmdx_sockets_args)",
+                                          "MMDX_SOCKET_OFFSET_MATRIX"])
     assert C.sizeof(api.SocketSetDesc) == desc == 4 * 4 + 4 * 8
     assert C.sizeof(api.SocketSetInfo) == info == 6 * 4
     assert C.sizeof(api.SocketsArgs) == args == 4 * 4 + 3 * 8

@@ -28,7 +28,7 @@ def _lib(hip_lib):
     return hip_lib
 
 
-_close = ta._close
+_close = ta.close_all
 
 
 def poke(an, **arrays):
@@ -126,9 +126,9 @@ def test_gpu_sweep_equals_the_restatement(ni):
     against the restatement (R from eval_bones_time), the eleven arrays against animator_ref."""
     table, state, dts, requests = sweep_with_a_walker(ni)
     want_states, events = ar.run_reference(table, state, dts, requests)
-    ms = ta._scenario_set(["b0", "b1", "b2"])
+    ms = ta.scenario_set(["b0", "b1", "b2"])
     root_bone = 1 if ni == 65 else 0
-    an = vmd.Animator(ms, ni, ta._rows_for_create())
+    an = vmd.Animator(ms, ni, ta.rows_for_create())
     an.set_state(**state)
     place = headings(ni, 40 + ni)
     d_place = DeviceBuffer.from_numpy(place)
@@ -153,13 +153,13 @@ def test_gpu_sweep_equals_the_restatement(ni):
     if ni >= 63:
         for name in ("fold_forwards", "fold_backwards", "fold_while_fading", "mix", "row_a", "moved"):
             assert seen[name] >= 3, (name, seen)
-        n = {name: ta._count(events, name) for name in ("promote", "at_once", "request_waits", "then_none")}
+        n = {name: ta.count_events(events, name) for name in ("promote", "at_once", "request_waits", "then_none")}
         assert min(n.values()) >= 3, n                                       # a promotion, a switch at once, a request in a fade, THEN -> rest
     _close(an, ms, d_place)
 
 
 # ---------------------------------------------------------------------------------------- what is not read, what is not written ----
-def _poison_case():
+def poison_case():
     """16 instances mid-fade, all clocks close to a seam so that folds occur; the weights put rows on A, on B and in between."""
     n = 16
     s = ar.initial_state(n)
@@ -174,7 +174,7 @@ def _poison_case():
 
 @pytest.mark.gpu
 def test_gpu_a_side_the_weight_does_not_read_may_hold_anything():
-    s = _poison_case()
+    s = poison_case()
     n = s["loops"].size
     side = rm.mb.side_of(s["weights"])
     assert (side == 0).sum() >= 4 and (side == 1).sum() >= 4 and (side == 2).sum() >= 4
@@ -204,8 +204,8 @@ def test_gpu_a_side_the_weight_does_not_read_may_hold_anything():
 def test_gpu_nothing_else_is_written_and_a_nan_device_dt_writes_nothing():
     ni = 65
     table, state, _, _ = ar.sweep(ni, 1)
-    ms = ta._scenario_set(["b0", "b1", "b2"])
-    an = vmd.Animator(ms, ni, ta._rows_for_create())
+    ms = ta.scenario_set(["b0", "b1", "b2"])
+    an = vmd.Animator(ms, ni, ta.rows_for_create())
     an.set_state(**state)
     place = headings(ni, 9)
     guard = 16
@@ -353,7 +353,7 @@ def test_gpu_graph_of_root_motion_advance_solve_place_and_bounds():
     names = [f"bone{i}" for i in range(m.nb)]
     ni = 9
     sk = vmd.Skeleton(m.bone_pos, np.asarray(m.bone_parent, np.int32))
-    vs = [vmd.Vmd(d) for d in ta._scenario_vmds(names)]
+    vs = [vmd.Vmd(d) for d in ta.scenario_vmds(names)]
     moving = [v.bind_bones(names) for v in vs]
     still = [b.in_place(0, ALL_AXES) for b in moving]
     roots = [v.bind_bones(names[:1]) for v in vs]
@@ -372,7 +372,7 @@ def test_gpu_graph_of_root_motion_advance_solve_place_and_bounds():
     place0 = headings(ni, 77)
     dev = api.PALETTE_ON_DEVICE | api.OUT_ON_DEVICE
     with DeformModel(m) as dm:
-        eager, replayed = (vmd.Animator(in_place_set, ni, ta._rows_for_create()) for _ in range(2))
+        eager, replayed = (vmd.Animator(in_place_set, ni, ta.rows_for_create()) for _ in range(2))
         d_dt = DeviceBuffer.from_numpy(np.array([0.0], np.float64))
         d_place, d_pal, d_box = DeviceBuffer(ni * 32), DeviceBuffer(ni * m.nb * 64), DeviceBuffer(ni * 24)
 

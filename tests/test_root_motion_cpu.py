@@ -28,7 +28,7 @@ def _lib(hip_lib):
     return hip_lib
 
 
-def _close(*xs):
+def close_all(*xs):
     for x in xs:
         for y in (x if isinstance(x, (list, tuple)) else [x]):
             y.close()
@@ -77,7 +77,7 @@ def test_fixture_clips_and_coverage():
     assert full.clip_frames().tolist() == list(rm.CLIP_FRAMES)
     an = vmd.Animator(ms, 2, [tuple(r) for r in rm.CLIP_ROWS])
     assert [r[0] for r in an.clip_table()] == rm.table()["length"].tolist()
-    _close(an, full, whole, ms, list(vs.values()))
+    close_all(an, full, whole, ms, list(vs.values()))
     z = rm.fixture()
     assert 200 <= z["dt"].size <= 600
     rm.check_coverage(z)
@@ -169,7 +169,7 @@ def dyadic_walk(heading):
         pl = rm.plan(state, tab, DYADIC_DT)
         place, ev = rm.apply(state, tab, DYADIC_DT, dyadic_r(pl["times"]), rm.ROOT_Z, place)
         folds += int(ev["fold_forwards"][0])
-        t = rm.ar._wrap(tab, state["clips_a"], state["times_a"] + DYADIC_DT)[0][0]
+        t = rm.ar.wrap(tab, state["clips_a"], state["times_a"] + DYADIC_DT)[0][0]
         out.append(place[0, :3].copy())
     assert folds == 2
     return out, m
@@ -232,10 +232,10 @@ def test_root_motion_refuses_bad_arguments():
         an.root_motion(ms, 0, ALL_AXES, 4096)
     with pytest.raises(ValueError):
         an.root_motion(ms, 0, ALL_AXES, 4096, dt=0.1, dt_ptr=4096)
-    _close(morphs, mms, mv, short, bm, v, an, ms)
+    close_all(morphs, mms, mv, short, bm, v, an, ms)
 
 
-def _oracle_rows(keys, interp_of, names, frames, times):
+def oracle_rows(keys, interp_of, names, frames, times):
     """The CPU oracle path over key tables: per model bone Motion::GetBonePose at whole frames (oracle.pyoracle.Oracle.bone_pose)
     and at times in seconds (tests/motion_time_restate.c) -> f32 [len(frames) + len(times), NB, 8].  The translations and
     rotations are the tables' own; the Bezier control bytes are the file's (the tables hold presampled curves, compared as bytes)."""
@@ -255,8 +255,8 @@ def _oracle_rows(keys, interp_of, names, frames, times):
         if hi == lo:
             fr, tr, rot = np.zeros(1, np.uint32), np.zeros((1, 3), np.float32), np.zeros((1, 4), np.float32)
         for j, t in enumerate(times):
-            lib.mt_bone_pose_time(C.c_uint32(hi - lo), mt._p(fr, C.c_uint32), mt._p(tr, C.c_float), mt._p(rot, C.c_float),
-                                  mt._p(ip, C.c_int8), C.c_double(float(t)), mt._p(one, C.c_float))
+            lib.mt_bone_pose_time(C.c_uint32(hi - lo), mt.ptr(fr, C.c_uint32), mt.ptr(tr, C.c_float), mt.ptr(rot, C.c_float),
+                                  mt.ptr(ip, C.c_int8), C.c_double(float(t)), mt.ptr(one, C.c_float))
             out[len(frames) + j, b] = one
     return out
 
@@ -285,7 +285,7 @@ def test_in_place_tables_byte_for_byte_and_rows_on_the_cpu_oracle_path():
             gu.assert_bits_equal(src["key_tr"][lo:hi, :3], tr, f"{clip}, {name}: translations")
             gu.assert_bits_equal(src["key_rot"][lo:hi], rot, f"{clip}, {name}: rotations")
         interp_of = {n: t[3] for n, t in tracks.items()}
-        src_rows = _oracle_rows(src, interp_of, names, frames, times)
+        src_rows = oracle_rows(src, interp_of, names, frames, times)
         lo, hi = int(src["key_off"][root]), int(src["key_off"][root + 1])
         if clip == "curved":
             assert hi - lo == 4 and (src["key_tr"][lo:hi, :3] != 0).any(0).all() and (src_rows[:, root, :3] != 0).any(0).all()
@@ -301,7 +301,7 @@ def test_in_place_tables_byte_for_byte_and_rows_on_the_cpu_oracle_path():
             assert got["key_tr"].tobytes() == want.tobytes(), (clip, axes)       # +0.0f: all bits clear
             seen_zeroed += int((got["key_tr"].view(np.uint32) != src["key_tr"].view(np.uint32)).sum())
             if axes in (ALL_AXES, api.ROOT_X | api.ROOT_Z, api.ROOT_Y):
-                rows = _oracle_rows(got, interp_of, names, frames, times)
+                rows = oracle_rows(got, interp_of, names, frames, times)
                 want_rows = src_rows.copy()
                 for c in range(3):
                     if axes & (1 << c):
@@ -311,14 +311,14 @@ def test_in_place_tables_byte_for_byte_and_rows_on_the_cpu_oracle_path():
             assert bm.keys()["key_tr"].tobytes() == src["key_tr"].tobytes()
             again = ip.in_place(root, ALL_AXES)
             assert not again.keys()["key_tr"][lo:hi, :3].any()
-            _close(again, ip)
+            close_all(again, ip)
         # another bone: only its keys
         other = bm.in_place(1, ALL_AXES)
         a, b = int(src["key_off"][1]), int(src["key_off"][2])
         want = src["key_tr"].copy()
         want[a:b, :3] = 0.0
         assert other.keys()["key_tr"].tobytes() == want.tobytes(), clip
-        _close(other, bm, v)
+        close_all(other, bm, v)
     assert seen_zeroed >= 12 * 4                                             # curved: 4 keys x 3 channels, over the eight masks
     lib = api.lib()
     k = api.BoneMotionKeys(C.sizeof(api.BoneMotionKeys))
@@ -343,11 +343,11 @@ def test_in_place_refusals_and_shape():
         assert (ip.nb, ip.n_mapped, ip.n_keys, ip.n_curves) == (bm.nb, bm.n_mapped, bm.n_keys, bm.n_curves)
         both = vmd.MotionSet([bm, ip])
         assert both.clip_frames().tolist() == [45, 45]
-        _close(both, ip)
+        close_all(both, ip)
     with pytest.raises(api.MmdxError) as e:
         bm.in_place(len(names), ALL_AXES)
     assert e.value.status == 2
     ip = bm.in_place(root, ALL_AXES)
     bm.close()                                                   # the copy owns its tables
     assert ip.n_keys > 0
-    _close(ip, v)
+    close_all(ip, v)

@@ -23,7 +23,7 @@ F = np.float32
 NONE = rt.NONE
 ALL_AXES = api.ROOT_X | api.ROOT_Y | api.ROOT_Z
 STATE = plain.STATE
-_close = ta._close
+_close = ta.close_all
 poke, headings = plain.poke, plain.headings
 
 
@@ -93,9 +93,9 @@ def test_gpu_sweep_equals_the_restatement(ni):
     animator_ref.  There are guard floats around the array, and placements[i][3] keeps its bits."""
     table, state, dts, requests = plain.sweep_with_a_walker(ni)
     want_states, events = ar.run_reference(table, state, dts, requests)
-    ms = ta._scenario_set(["b0", "b1", "b2"])
+    ms = ta.scenario_set(["b0", "b1", "b2"])
     root_bone = 1 if ni == 65 else 0
-    an = vmd.Animator(ms, ni, ta._rows_for_create())
+    an = vmd.Animator(ms, ni, ta.rows_for_create())
     an.set_state(**state)
     place = headings(ni, 140 + ni)
     fourth = place[:, 3].copy()
@@ -139,7 +139,7 @@ def test_gpu_sweep_equals_the_restatement(ni):
 @pytest.mark.gpu
 def test_gpu_a_side_the_weight_does_not_read_may_hold_anything():
     """Sides and instants that must not be read are poisoned with NaN clocks and out-of-range ids: nothing changes."""
-    s = plain._poison_case()
+    s = plain.poison_case()
     s["clips_a"][:] = np.where(np.arange(16) % 2 == 0, 0, rt.Q8)
     s["clips_b"][:] = np.where(np.arange(16) % 2 == 0, rt.Q8, 0)
     s["times_a"][:] = np.where(s["clips_a"] == 0, 1.49, 1.99)
@@ -315,7 +315,7 @@ def test_gpu_graph_of_root_turn_advance_solve_and_place():
     names = [f"bone{i}" for i in range(m.nb)]
     ni = 9
     sk = vmd.Skeleton(m.bone_pos, np.asarray(m.bone_parent, np.int32))
-    vs = [vmd.Vmd(d) for d in ta._scenario_vmds(names)]
+    vs = [vmd.Vmd(d) for d in ta.scenario_vmds(names)]
     moving = [v.bind_bones(names) for v in vs]
     still = [b.in_place_turn(0, ALL_AXES) for b in moving]
     roots = [v.bind_bones(names[:1]) for v in vs]
@@ -332,7 +332,7 @@ def test_gpu_graph_of_root_turn_advance_solve_and_place():
     place0 = headings(ni, 78)
     dev = api.PALETTE_ON_DEVICE | api.OUT_ON_DEVICE
     with DeformModel(m) as dm:
-        eager, replayed = (vmd.Animator(in_place_set, ni, ta._rows_for_create()) for _ in range(2))
+        eager, replayed = (vmd.Animator(in_place_set, ni, ta.rows_for_create()) for _ in range(2))
         d_dt = DeviceBuffer.from_numpy(np.array([0.0], np.float64))
         d_place, d_pal = DeviceBuffer(ni * 32), DeviceBuffer(ni * m.nb * 64)
 

@@ -25,7 +25,7 @@ F = np.float32
 ROOT = os.path.dirname(mt.HERE)
 needs_driver = pytest.mark.skipif(not mt.driver_available(), reason="the reference's libmmd headers are not present")
 ALL_AXES = api.ROOT_X | api.ROOT_Y | api.ROOT_Z
-_close = plain._close
+_close = plain.close_all
 
 
 @pytest.fixture(autouse=True)
@@ -277,7 +277,7 @@ def test_in_place_turn_tables_byte_for_byte_and_rows_on_the_cpu_oracle_path():
         bm = v.bind_bones(names)
         src = bm.keys()
         interp_of = {n: t[3] for n, t in tracks.items()}
-        src_rows = plain._oracle_rows(src, interp_of, names, frames, times)
+        src_rows = plain.oracle_rows(src, interp_of, names, frames, times)
         lo, hi = int(src["key_off"][root]), int(src["key_off"][root + 1])
         if clip in ("curved", "q8"):
             assert hi - lo >= 4 and (src_rows[:, root, 4:] != ident).any(1).sum() > len(times) // 2
@@ -295,7 +295,7 @@ def test_in_place_turn_tables_byte_for_byte_and_rows_on_the_cpu_oracle_path():
             assert got["key_rot"].tobytes() == want_rot.tobytes(), (clip, axes)   # +0.0f: all bits clear; 1.0f
             turned_keys += int((got["key_rot"].view(np.uint32) != src["key_rot"].view(np.uint32)).any(1).sum())
             if axes in (ALL_AXES, api.ROOT_X | api.ROOT_Z, 0):
-                rows = plain._oracle_rows(got, interp_of, names, frames, times)
+                rows = plain.oracle_rows(got, interp_of, names, frames, times)
                 want_rows = src_rows.copy()
                 for c in range(3):
                     if axes & (1 << c):

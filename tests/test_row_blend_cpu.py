@@ -10,8 +10,6 @@
 """
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -20,12 +18,13 @@ from simple_mmd_renderer_amd import _capi as api
 from simple_mmd_renderer_amd import synth, vmd
 from simple_mmd_renderer_amd.engine import DeformModel
 from tests import golden_util as gu
+from tests import host_program as hp
 from tests import motion_blend_ref as mb
 from tests import motion_time_ref as mt
 from tests import row_blend_ref as rb
 from tests.test_capi_symbols import declared_symbols
 
-ROOT = os.path.dirname(mt.HERE)
+ROOT = hp.ROOT
 INVALID, BAD_INDEX, NO_DEVICE, UNSUPPORTED = 1, 2, 3, 6
 A, B, PARAMS, OUT = api.BLEND_A_ON_DEVICE, api.BLEND_B_ON_DEVICE, api.BLEND_PARAMS_ON_DEVICE, api.OUT_ON_DEVICE
 needs_driver = pytest.mark.skipif(not mt.driver_available(), reason="the reference's libmmd headers are not present")
@@ -156,29 +155,18 @@ def test_subtree_mask_refuses_nulls_and_needs_no_device():
     sk.close()
 
 
-_built = {}
-
-
-def _mask_driver():
-    """tests/bone_mask_driver.cpp (csrc/bone_mask.hpp with its own main) built with -fsanitize=address,undefined."""
-    if "exe" not in _built:
-        exe = os.path.join(tempfile.mkdtemp(prefix="mmdx_bone_mask_"), "bone_mask_driver_san")
-        cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-               "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", os.path.join(mt.HERE, "bone_mask_driver.cpp"), "-o", exe]
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-        if r.returncode != 0:
-            raise RuntimeError("building the bone mask driver failed:\n" + r.stdout + r.stderr)
-        _built["exe"] = exe
-    return _built["exe"]
+def mask_driver():
+    """tests/bone_mask_driver.cpp (csrc/bone_mask.hpp with its own main) under the sanitizers of tests/host_program.py."""
+    return hp.build("bone_mask_driver", [os.path.join(hp.TESTS, "bone_mask_driver.cpp")], opt="-O1", sanitize=True)
 
 
 @pytest.mark.parametrize("case", MASK_CASES, ids=[c[0] for c in MASK_CASES])
 def test_subtree_mask_header_under_asan_ubsan(case):
     """The same cases through the stand-alone program: the walk stays inside its arrays and computes the same masks."""
     _, parent, roots, inside, outside, expected = case
-    argv = [_mask_driver(), str(len(parent))] + [str(p) for p in parent] + [str(len(roots))] + [str(r) for r in roots] + \
+    argv = [str(len(parent))] + [str(p) for p in parent] + [str(len(roots))] + [str(r) for r in roots] + \
         [repr(float(inside)), repr(float(outside))]
-    r = subprocess.run(argv, capture_output=True, text=True, timeout=60)
+    r = hp.run(mask_driver(), argv, timeout=60)
     assert r.returncode == 0 and not r.stderr, (r.returncode, r.stdout, r.stderr)
     if isinstance(expected, int):
         assert r.stdout.split() == ["BAD", str(expected)]

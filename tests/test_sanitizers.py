@@ -3,28 +3,15 @@ has latent UB exactly here: unchecked bone / vertex indices in Deform and the mo
 section 5).  GPU sanitizers are unavailable on the pool, so this covers the host "model compile" and
 the oracle restatement."""
 import os
-import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g", "-O1"]
+from tests import host_program as hp
 
 
-def test_plan_builder_under_asan_ubsan(tmp_path):
-    exe = tmp_path / "plan_san"
-    cmd = ["g++", "-std=c++17"] + SAN + [os.path.join(ROOT, "tests", "plan_sanitizer_driver.cpp"),
-                                         os.path.join(ROOT, "simple_mmd_renderer_amd", "csrc", "plan.cpp"),
-                                         os.path.join(ROOT, "simple_mmd_renderer_amd", "csrc", "pmx.cpp"),
-                                         os.path.join(ROOT, "simple_mmd_renderer_amd", "csrc", "pmd.cpp"),
-                                         os.path.join(ROOT, "simple_mmd_renderer_amd", "csrc", "vmd.cpp"),
-                                         os.path.join(ROOT, "simple_mmd_renderer_amd", "csrc", "rig.cpp"),
-                                         os.path.join(ROOT, "simple_mmd_renderer_amd", "csrc", "error.cpp"),
-                                         "-o", str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+def test_plan_builder_under_asan_ubsan():
+    exe = hp.build("plan_sanitizer_driver", [os.path.join(hp.TESTS, "plan_sanitizer_driver.cpp")] +
+                   [os.path.join(hp.CSRC, f) for f in ("plan.cpp", "pmx.cpp", "pmd.cpp", "vmd.cpp", "rig.cpp", "error.cpp")],
+                   opt="-O1", sanitize=True)
+    r = hp.run(exe, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert r.returncode == 0, r.stdout + r.stderr
     assert "built=" in r.stdout and "pmx fuzz:" in r.stdout and "vmd fuzz:" in r.stdout and "ERROR" not in r.stderr
 
@@ -65,9 +52,7 @@ int main(void) {
   return 0;
 }
 ''')
-    exe = tmp_path / "oracle_san"
-    cmd = ["gcc", "-std=gnu11"] + SAN + [str(drv), os.path.join(ROOT, "oracle", "mmdx_oracle.c"), "-o", str(exe), "-lm"]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    exe = hp.build("oracle_san", [drv, os.path.join(hp.ROOT, "oracle", "mmdx_oracle.c")], cxx=False, c_std="gnu11", opt="-O1",
+                   sanitize=True, link=["-lm"])
+    r = hp.run(exe, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr

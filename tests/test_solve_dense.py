@@ -15,7 +15,6 @@ per rig for 40 instances and shared, never written; the smaller counts take the 
 
 CPU: the decision itself (csrc/solve_shape.hpp plan_solve_dense), swept by tests/solve_shape_driver.cpp under ASan + UBSan."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -24,10 +23,11 @@ from simple_mmd_renderer_amd import _capi as api
 from simple_mmd_renderer_amd import synth, vmd
 from simple_mmd_renderer_amd.engine import DeviceBuffer
 from tests import golden_util as gu
+from tests import host_program as hp
 from tests import test_solve_select as sel
+from tests.host_program import ROOT
 from tests.test_physics_seam import physics_case, random_transforms
 from tests.test_rig import NESTED_CASES, long_chain_rig, many_long_chains_rig, random_poses
-from tests.test_sanitizers import ROOT, SAN
 
 DENSE, COOP = "MMDX_SOLVE_DENSE", "MMDX_IK_COOP"
 NIS = (1, 17, 40)
@@ -42,16 +42,12 @@ def _lib(hip_lib):
 
 # ---- CPU: the decision ---------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("solve_shape") / "solve_shape_driver"
-    cmd = ["g++", "-std=c++17", "-Wall", "-Wextra"] + SAN + [os.path.join(ROOT, "tests", "solve_shape_driver.cpp"), "-o", str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+def driver():
+    return hp.build("solve_shape_driver", [os.path.join(hp.TESTS, "solve_shape_driver.cpp")], opt="-O1", sanitize=True)
 
 
 def test_decision_sweep_under_sanitizers(driver):
-    r = subprocess.run([driver, "sweep"], capture_output=True, text=True, timeout=300)
+    r = hp.run(driver, ["sweep"])
     assert r.returncode == 0, r.stdout + r.stderr
     counts = dict(kv.split("=") for kv in r.stdout.split())
     assert int(counts["failures"]) == 0 and "ERROR" not in r.stderr
@@ -70,8 +66,7 @@ def test_decision_nested_lds_bound_crowd_size_and_env(driver):
                 fits = 2 * (lds + 1024) <= 160 * 1024
                 cases.append((0, lds, wgs, cus, env))
                 want.append(int(fits and (env == 1 or (env == -1 and wgs > cus))))
-    r = subprocess.run([driver, "eval"], input="".join("%d %d %d %d %d\n" % c for c in cases), capture_output=True, text=True,
-                       timeout=300)
+    r = hp.run(driver, ["eval"], stdin="".join("%d %d %d %d %d\n" % c for c in cases))
     assert r.returncode == 0, r.stdout + r.stderr
     got = [int(x) for x in r.stdout.split()]
     assert len(got) == len(cases)
