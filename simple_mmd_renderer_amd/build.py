@@ -26,7 +26,7 @@ SOURCES = ["api.cpp", "bench_api.cpp", "kernels.hip", "kernels_fast.hip", "launc
            "row_blend_api.cpp", "row_blend_kernels.hip", "socket_api.cpp", "socket_kernels.hip",
            "events_api.cpp", "events_kernels.hip"]
 HEADERS = ["kernels.hpp", "plan.hpp", "error.hpp", "vmd.hpp", "rig.hpp", "rig_kernels.hpp", "pmx.hpp", "graph_pin.hpp", "api_internal.hpp", "host_runtime.hpp",
-           "motion_clock.hpp", "motion_blend.hpp", "launch_shape.hpp", "lds_layout.hpp", "cull_shape.hpp", "solve_shape.hpp", "cull_kernels.hpp", "place_kernels.hpp", "place_math.hpp",
+           "motion_clock.hpp", "motion_blend.hpp", "clip_source.hpp", "launch_shape.hpp", "lds_layout.hpp", "cull_shape.hpp", "solve_shape.hpp", "cull_kernels.hpp", "place_kernels.hpp", "place_math.hpp",
            "pbounds_kernels.hpp", "pbounds_math.hpp", "anim_kernels.hpp", "anim_math.hpp", "instance_list.hpp",
            "row_blend_kernels.hpp", "bone_mask.hpp", "root_math.hpp", "socket_kernels.hpp", "socket_math.hpp", "socket_table.hpp",
            "events_kernels.hpp", "events_math.hpp", "events_table.hpp",

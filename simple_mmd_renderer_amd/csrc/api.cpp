@@ -708,7 +708,7 @@ static mmdx_status run_morph_pass(mmdx_model_t m, const mmdx_deform_args *a, con
     f.chain_rate = static_cast<const float *>(m->chain_rate.ptr);
     f.nm = p.nm; f.ns = p.ns; f.niw = pl.niw;
     f.quad = pl.quad ? 1u : 0u;
-    if (pl.select_rows) { f.sel_ids = dp.sel_ids; f.sel_count = dp.sel_count; f.sel_ni = a->n_instances; }
+    if (pl.select_rows) f.list = {dp.sel_ids, dp.sel_count, a->n_instances};
     HIP_TRY(m->wslot.ensure(pl.wslot_rows * (size_t(p.ns) + 1) * 4));
     f.out = static_cast<float *>(m->wslot.ptr);
     uint32_t *seen = static_cast<uint32_t *>(m->seen.ptr);

@@ -20,10 +20,9 @@
 //     class sort), then written out cooperatively as 16-byte coalesced stores.
 //   HBM-bound: ~24-32 B written per vertex-instance against ~100 VALU ops; no MFMA (gather of small
 //   mat x vec, <= 3 flop/B).
+#include "clip_source.hpp"
 #include "instance_list.hpp"
 #include "kernels.hpp"
-#include "motion_blend.hpp"
-#include "motion_clock.hpp"
 
 #include <type_traits>
 #ifdef PK_STAMPS
@@ -1637,143 +1636,60 @@ __global__ __launch_bounds__(kThreads) void morph_apply_kernel(const DeformParam
 
 #ifndef MMDX_FAST_MATH
 // ---- group-morph flattening on the device (UpdateMorphTransform's recursion, per slot) ------------
-__global__ __launch_bounds__(kThreads) void flatten_kernel(const FlattenParams f) {
-    // output rows have ns+1 columns: column ns is the padding slot of the morph table, always 0
-    const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
-    const uint32_t rows = f.quad ? ((f.niw + 3) / 4) * 4 : f.niw, cols = f.ns + 1;
-    if (idx >= size_t(rows) * cols) return;
-    const uint32_t i = uint32_t(idx / cols), s = uint32_t(idx - size_t(i) * cols);
-    float out = 0.f;
-    if (i < f.niw && s < f.ns)
-        out = slot_weight(f.rates + size_t(i) * f.nm, f.slot_top, f.chain_off, f.chain_rate, s);
-    if (f.quad) f.out[(size_t(i / 4) * cols + s) * 4 + (i & 3)] = out;
-    else f.out[idx] = out;
-}
-
-// The same for a select launch (mmdx_deform_batched_select): output row j = the slot weights of instance f.sel_ids[j]; rows behind the
-// live count or with an id >= f.sel_ni are zeros (their instances are never written).  A kernel of its own: flatten_kernel stays as is.
-__global__ __launch_bounds__(kThreads) void flatten_select_kernel(const FlattenParams f) {
+// One thread per (output row, slot); output rows have ns+1 columns: column ns is the padding slot of the morph table, always 0.
+// Row j holds the slot weights of the instance at position j (instance_list.hpp); padding rows of a quad, positions behind a list's
+// count and ids that are no row of the rates are zeros (their instances are never written).
+template <class Instances>
+__device__ __forceinline__ void flatten_body(const FlattenParams &f, const Instances &sel) {
     const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
     const uint32_t rows = f.quad ? ((f.niw + 3) / 4) * 4 : f.niw, cols = f.ns + 1;
     if (idx >= size_t(rows) * cols) return;
     const uint32_t j = uint32_t(idx / cols), s = uint32_t(idx - size_t(j) * cols);
-    const uint32_t live = f.sel_count ? min(*f.sel_count, f.niw) : f.niw;
+    const Lane ln = sel.lane(j, sel.used(f.niw));
     float out = 0.f;
-    if (j < live && s < f.ns) {
-        const uint32_t i = f.sel_ids[j];
-        if (i < f.sel_ni) out = slot_weight(f.rates + size_t(i) * f.nm, f.slot_top, f.chain_off, f.chain_rate, s);
-    }
+    if (ln.live && s < f.ns) out = slot_weight(f.rates + size_t(ln.row) * f.nm, f.slot_top, f.chain_off, f.chain_rate, s);
     if (f.quad) f.out[(size_t(j / 4) * cols + s) * 4 + (j & 3)] = out;
     else f.out[idx] = out;
 }
 
-// ---- VMD morph tracks -> per-instance morph rates (Motion::GetMorphPose, motion_impl.inl:382-424) ---
-// One thread per (instance, model morph): clamp to the first / last key, exact hit, else the linear
-// blend l*(1-t) + r*t with t = float(frame-left)/float(right-left) (IEEE division: hipcc keeps f32
-// division correctly rounded by default).  A morph without a track keeps rate 0, as after ResetPosing.
-// With a TimeClock: GetMorphPose(name, double time), :426-465 (motion_clock.hpp) -- no exact-hit shortcut,
-// so a key hit still goes through the blend (an infinite neighbour gives NaN there).
-template <class Clock>
-__device__ __forceinline__ float eval_morph_rate(const MorphTrackParams &t, uint32_t m, uint32_t i) {
-    const uint32_t b = t.key_off[m], e = t.key_off[m + 1];
-    const Clock clk = clock_of<Clock>(t.frames, t.times, i);
-    float w = 0.f;
-    if (e > b) {
-        if (clk.at_or_before_first(t.key_frames[b])) {
-            w = t.key_weights[b];
-        } else if (clk.at_or_after_last(t.key_frames[e - 1])) {
-            w = t.key_weights[e - 1];
-        } else {
-            const uint32_t frame = clk.search();
-            uint32_t lo = b, hi = e - 1;               // key_frames[lo] <= frame < key_frames[hi]
-            while (hi - lo > 1) {                      // first key whose frame is > `frame`
-                const uint32_t mid = (lo + hi) / 2;
-                if (t.key_frames[mid] > frame) hi = mid; else lo = mid;
-            }
-            const uint32_t lf = t.key_frames[lo], rf = t.key_frames[hi];
-            if (clk.exact(lf)) {
-                w = t.key_weights[lo];
-            } else {
-                const float bary = clk.bary(lf, rf);
-                w = t.key_weights[lo] * (1.0f - bary) + t.key_weights[hi] * bary;
-            }
-        }
-    }
-    return w;
+__global__ __launch_bounds__(kThreads) void flatten_kernel(const FlattenParams f) { flatten_body(f, AllInstances{}); }
+
+// a select launch (mmdx_deform_batched_select): niw = the list's capacity
+__global__ __launch_bounds__(kThreads) void flatten_select_kernel(const FlattenParams f) { flatten_body(f, ListedInstances{f.list}); }
+
+// ---- VMD morph tracks -> per-instance morph rates (Motion::GetMorphPose: eval_morph_rate, clip_source.hpp) ---
+// One thread per (instance, model morph) -- which instance: lane_item (instance_list.hpp), every instance or the listed ones; what it
+// plays: a rate source (clip_source.hpp) built per lane, a wave spans several instances.  Operand rows and the rate row by the
+// instance's row.
+template <class Source, class Instances, class... Operands>
+__device__ __forceinline__ void morph_track_body(const MorphTrackParams &t, const Instances &sel, const Operands &...operands) {
+    LaneItem it;
+    if (!lane_item<kThreads>(sel, t.ni, t.nm, it)) return;
+    t.out[it.at] = Source(t, operands..., it.ln.row).rate(it.item);
 }
 
 template <class Clock>
 __global__ __launch_bounds__(kThreads) void morph_track_eval_kernel(const MorphTrackParams t) {
-    const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (idx >= size_t(t.ni) * t.nm) return;
-    const uint32_t i = uint32_t(idx / t.nm), m = uint32_t(idx - size_t(i) * t.nm);
-    t.out[idx] = eval_morph_rate<Clock>(t, m, i);
+    morph_track_body<MotionRate<Clock>>(t, AllInstances{});
 }
 
-// Motion set (mmdx_motion_set_eval_morphs*): clip c of the bank is the single-motion table with key_off advanced by c * (nm+1), the
-// offsets there being absolute into the concatenated key arrays -- eval_morph_rate itself evaluates it.  The clip id is per lane (a
-// wave spans several instances); an id outside [0, n_clips) (MMDX_CLIP_NONE included) plays nothing: rate 0, no table read.
+// mmdx_motion_set_eval_morphs*
 template <class Clock>
 __global__ __launch_bounds__(kThreads) void morph_track_eval_set_kernel(MorphTrackParams t, const uint32_t *clips, const uint32_t n_clips) {
-    const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (idx >= size_t(t.ni) * t.nm) return;
-    const uint32_t i = uint32_t(idx / t.nm), m = uint32_t(idx - size_t(i) * t.nm);
-    const uint32_t clip = clips[i];
-    float w = 0.f;
-    if (clip < n_clips) {
-        t.key_off += size_t(clip) * (size_t(t.nm) + 1);
-        w = eval_morph_rate<Clock>(t, m, i);
-    }
-    t.out[idx] = w;
+    morph_track_body<ClipRate<Clock>>(t, AllInstances{}, clips, n_clips);
 }
 
-// Cross-fade between two clips of a set (mmdx_motion_set_blend_morphs_time; motion_blend.hpp).  The rate of one (clip, time) of a
-// blend call: what morph_track_eval_set_kernel stores for it -- eval_morph_rate itself on the clip's table and that side's times.
-template <class Clock>
-__device__ __forceinline__ float eval_clip_rate(MorphTrackParams t, uint32_t clip, uint32_t n_clips, const double *times, uint32_t m,
-                                                uint32_t i) {
-    if (clip >= n_clips) return 0.f;
-    t.key_off += size_t(clip) * (size_t(t.nm) + 1);
-    t.times = times;
-    return eval_morph_rate<Clock>(t, m, i);
-}
-
-// One thread per (instance, morph); weight, clip ids and times per lane.  A lane evaluates one clip -- a, or b when the row is B --
-// and only a lane that blends evaluates b as well, so an end-point row reads nothing of the other clip.
+// mmdx_motion_set_blend_morphs_time (motion_blend.hpp)
 template <class Clock>
 __global__ __launch_bounds__(kThreads) void morph_track_blend_set_kernel(const MorphTrackParams t, const BlendOperands o) {
-    const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (idx >= size_t(t.ni) * t.nm) return;
-    const uint32_t i = uint32_t(idx / t.nm), m = uint32_t(idx - size_t(i) * t.nm);
-    const float w = o.weights[i];
-    const uint32_t side = blend_side(w);
-    const bool first_b = side == kBlendB;
-    float r = eval_clip_rate<Clock>(t, (first_b ? o.clips_b : o.clips_a)[i], o.n_clips, first_b ? o.times_b : o.times_a, m, i);
-    if (side == kBlendMix) r = blend_rate(r, eval_clip_rate<Clock>(t, o.clips_b[i], o.n_clips, o.times_b, m, i), w);
-    t.out[idx] = r;
+    morph_track_body<BlendRate<Clock>>(t, AllInstances{}, o);
 }
 
-// The same for the listed instances (mmdx_motion_set_blend_morphs_time_select; instance_list.hpp): one thread per (list position,
-// morph), t.ni = the list's capacity; the id is per lane, operand rows and the rate row are addressed by it.  Workgroups wholly behind
-// the count leave first.
+// mmdx_motion_set_blend_morphs_time_select: t.ni = the list's capacity
 template <class Clock>
 __global__ __launch_bounds__(kThreads) void morph_track_blend_set_select_kernel(const MorphTrackParams t, const BlendOperands o,
                                                                                 const InstanceList list) {
-    const ListedInstances sel = {list};
-    const uint32_t used = sel.used(t.ni);
-    const size_t idx = size_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (size_t(blockIdx.x) * kThreads >= size_t(used) * t.nm) return;
-    if (idx >= size_t(used) * t.nm) return;
-    const uint32_t k = uint32_t(idx / t.nm), m = uint32_t(idx - size_t(k) * t.nm);
-    const Lane ln = sel.lane(k, used);
-    if (!ln.live) return;
-    const uint32_t i = ln.row;
-    const float w = o.weights[i];
-    const uint32_t side = blend_side(w);
-    const bool first_b = side == kBlendB;
-    float r = eval_clip_rate<Clock>(t, (first_b ? o.clips_b : o.clips_a)[i], o.n_clips, first_b ? o.times_b : o.times_a, m, i);
-    if (side == kBlendMix) r = blend_rate(r, eval_clip_rate<Clock>(t, o.clips_b[i], o.n_clips, o.times_b, m, i), w);
-    t.out[size_t(i) * t.nm + m] = r;
+    morph_track_body<BlendRate<Clock>>(t, ListedInstances{list}, o);
 }
 
 // ---- streaming copy / fill: the practical HBM ceiling printed next to the roofline ---------------
@@ -1812,10 +1728,10 @@ __global__ __launch_bounds__(kThreads) void pattern_fill_kernel(float4 *a, float
 }
 
 // ---- per-instance bounds from the partials of deform_kernel<..., BOUNDS>: one wave per instance, out[i][6] -----------------------
-// (min / max only: the same kernel serves fast-math models)
-__global__ __launch_bounds__(64) void bounds_reduce_kernel(const float *part, float *out, uint32_t units) {
+// (min / max only: the same kernel serves fast-math models)  The workgroup's wave reduces the partials of cell ln.cell into row ln.row.
+__device__ __forceinline__ void bounds_reduce_body(const float *part, float *out, uint32_t units, const Lane ln) {
     const uint32_t lane = threadIdx.x;
-    const float *src = part + size_t(blockIdx.x) * units * 6;
+    const float *src = part + size_t(ln.cell) * units * 6;
     float mn[3], mx[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) mn[c] = mx[c] = __builtin_nanf("");
@@ -1827,31 +1743,20 @@ __global__ __launch_bounds__(64) void bounds_reduce_kernel(const float *part, fl
         }
     }
     const float v = wave_bounds6(mn, mx, lane);
-    if (lane < 6) out[size_t(blockIdx.x) * 6 + lane] = v;
+    if (lane < 6) out[size_t(ln.row) * 6 + lane] = v;
 }
 
+__global__ __launch_bounds__(64) void bounds_reduce_kernel(const float *part, float *out, uint32_t units) {
+    bounds_reduce_body(part, out, units, {blockIdx.x, blockIdx.x, true});
+}
 
 // The same behind a select launch: partials by list position, block j writes row ids[j] -- live positions with an id inside the
 // call's arrays only, every other row of `out` keeps what it held.
 __global__ __launch_bounds__(64) void bounds_reduce_select_kernel(const float *part, float *out, uint32_t units, uint32_t ni,
                                                                   const uint32_t *ids, const uint32_t *count, uint32_t n_ids) {
-    const uint32_t lane = threadIdx.x, j = blockIdx.x;
-    if (j >= (count ? min(*count, n_ids) : n_ids)) return;
-    const uint32_t inst = ids[j];
-    if (inst >= ni) return;
-    const float *src = part + size_t(j) * units * 6;
-    float mn[3], mx[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) mn[c] = mx[c] = __builtin_nanf("");
-    for (uint32_t u = lane; u < units; u += 64) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            mn[c] = bound_op<false>(mn[c], src[size_t(u) * 6 + c]);
-            mx[c] = bound_op<true>(mx[c], src[size_t(u) * 6 + 3 + c]);
-        }
-    }
-    const float v = wave_bounds6(mn, mx, lane);
-    if (lane < 6) out[size_t(inst) * 6 + lane] = v;
+    const ListedInstances sel = {{ids, count, ni}};
+    const Lane ln = sel.lane(blockIdx.x, sel.used(n_ids));
+    if (ln.live) bounds_reduce_body(part, out, units, ln);
 }
 
 #endif  // !MMDX_FAST_MATH
@@ -2076,46 +1981,25 @@ hipError_t launch_bounds_reduce_select(const float *partials, uint32_t units, ui
 
 hipError_t launch_flatten(const FlattenParams &f, hipStream_t stream) {
     const uint32_t rows = f.quad ? ((f.niw + 3) / 4) * 4 : f.niw;
-    const size_t n = size_t(rows) * (f.ns + 1);
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(f.sel_ids ? flatten_select_kernel : flatten_kernel, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads),
-                       0, stream, f);
-    return hipGetLastError();
+    return launch_lane_items<kThreads>(f.list.ids ? flatten_select_kernel : flatten_kernel, rows, f.ns + 1, stream, f);
 }
 
+// The per-(instance, morph) kernels: launch_lane_items (instance_list.hpp); the select form is sized from t.ni = the list's capacity.
 hipError_t launch_morph_track_eval(const MorphTrackParams &t, hipStream_t stream) {
-    const size_t n = size_t(t.ni) * t.nm;
-    if (n == 0) return hipSuccess;
-    const dim3 grid(uint32_t((n + kThreads - 1) / kThreads));
-    if (t.times) hipLaunchKernelGGL(morph_track_eval_kernel<TimeClock>, grid, dim3(kThreads), 0, stream, t);
-    else hipLaunchKernelGGL(morph_track_eval_kernel<FrameClock>, grid, dim3(kThreads), 0, stream, t);
-    return hipGetLastError();
+    return launch_lane_items<kThreads>(MMDX_BY_CLOCK(morph_track_eval_kernel, t.times), t.ni, t.nm, stream, t);
 }
 
 hipError_t launch_morph_track_eval_set(const MorphTrackParams &t, const uint32_t *clips, uint32_t n_clips, hipStream_t stream) {
-    const size_t n = size_t(t.ni) * t.nm;
-    if (n == 0) return hipSuccess;
-    const dim3 grid(uint32_t((n + kThreads - 1) / kThreads));
-    if (t.times) hipLaunchKernelGGL(morph_track_eval_set_kernel<TimeClock>, grid, dim3(kThreads), 0, stream, t, clips, n_clips);
-    else hipLaunchKernelGGL(morph_track_eval_set_kernel<FrameClock>, grid, dim3(kThreads), 0, stream, t, clips, n_clips);
-    return hipGetLastError();
+    return launch_lane_items<kThreads>(MMDX_BY_CLOCK(morph_track_eval_set_kernel, t.times), t.ni, t.nm, stream, t, clips, n_clips);
 }
 
 hipError_t launch_morph_track_blend_set(const MorphTrackParams &t, const BlendOperands &o, hipStream_t stream) {
-    const size_t n = size_t(t.ni) * t.nm;
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(morph_track_blend_set_kernel<TimeClock>, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
-                       t, o);
-    return hipGetLastError();
+    return launch_lane_items<kThreads>(morph_track_blend_set_kernel<TimeClock>, t.ni, t.nm, stream, t, o);
 }
 
 hipError_t launch_morph_track_blend_set_select(const MorphTrackParams &t, const BlendOperands &o, const InstanceList &list,
                                                hipStream_t stream) {
-    const size_t n = size_t(t.ni) * t.nm;
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(morph_track_blend_set_select_kernel<TimeClock>, dim3(uint32_t((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                       stream, t, o, list);
-    return hipGetLastError();
+    return launch_lane_items<kThreads>(morph_track_blend_set_select_kernel<TimeClock>, t.ni, t.nm, stream, t, o, list);
 }
 
 hipError_t launch_copy(void *dst, const void *src, size_t bytes, hipStream_t stream) {

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "instance_list.hpp"
 #include "lds_layout.hpp"
 #include "plan.hpp"
 #include "vmd.hpp"
@@ -96,10 +97,9 @@ struct FlattenParams {
     uint32_t nm, ns, niw;
     uint32_t quad;               // 1: write float4 [ceil(NIw/4)][NS] instance quads (pad lanes = 0)
     uint32_t *seen;              // morph_apply with the flatten fused in: the handle's RatesSeen record (nullptr: always walk)
-    // select launches (behind everything the other kernels read): row j of the output comes from rates[sel_ids[j]]; rows behind
-    // the live count and rows whose id is >= sel_ni are written as zeros.  niw = sel_n then.
-    const uint32_t *sel_ids, *sel_count;
-    uint32_t sel_ni;
+    // select launches (behind everything the other kernels read; ids == nullptr: not one): row j of the output comes from
+    // rates[list.ids[j]]; rows behind the live count and rows whose id is no row of the rates are written as zeros.  niw = sel_n then.
+    InstanceList list;
 };
 
 // One variant of deform_kernel: what pick() (kernels.hip) chooses an instantiation by.
@@ -142,7 +142,6 @@ struct BlendOperands;
 hipError_t launch_morph_track_blend_set(const MorphTrackParams &t, const BlendOperands &o, hipStream_t stream);
 // mmdx_motion_set_blend_morphs_time_select: the same for the listed instances (instance_list.hpp); t.ni = the list's capacity,
 // operand rows and rate rows addressed by id
-struct InstanceList;
 hipError_t launch_morph_track_blend_set_select(const MorphTrackParams &t, const BlendOperands &o, const InstanceList &list,
                                                hipStream_t stream);
 hipError_t launch_copy(void *dst, const void *src, size_t bytes, hipStream_t stream);

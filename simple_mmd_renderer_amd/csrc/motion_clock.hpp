@@ -48,4 +48,7 @@ __device__ __forceinline__ TimeClock clock_of<TimeClock>(const uint32_t *, const
     return {times[i] * 30.0};
 }
 
+// the instantiation of a clock-templated kernel that a call launches: seconds when it carries times, else frames
+#define MMDX_BY_CLOCK(kernel, times) ((times) ? kernel<TimeClock> : kernel<FrameClock>)
+
 }  // namespace mmdx

@@ -5,8 +5,7 @@
 // palettes are bit-identical to libmmd's and the deform kernel downstream stays bit-exact end to end.
 #include <hip/hip_runtime.h>
 
-#include "motion_blend.hpp"
-#include "motion_clock.hpp"
+#include "clip_source.hpp"
 #include "rig.hpp"
 #include "rig_kernels.hpp"
 #include "root_math.hpp"
@@ -23,127 +22,36 @@ namespace {
 
 constexpr uint32_t kRigThreads = 256;
 
-// Bezier<float,32>::operator[] (L/util/math_impl.inl:1379-1392): linear lookup in the presampled table.
-__device__ __forceinline__ float curve_at(const float *lut, uint32_t id, float x) {
-    if (id == kLinearCurve) return x;
-    const float *t = lut + size_t(id) * kCurveSamples;
-    x = x * float(kCurveSamples - 1);
-    const uint32_t ix = uint32_t(x);
-    const float r = x - float(ix);
-    if (ix < kCurveSamples - 1) return (1.0f - r) * t[ix] + r * t[ix + 1];
-    return t[kCurveSamples - 1];
-}
-
-// Motion::GetBonePose(name, frame), L/motion/motion_impl.inl:255-319: the local pose (translation, rotation) of one bone at one
-// frame; with a TimeClock GetBonePose(name, time), :321-380 (motion_clock.hpp: the clamps, the search key, no exact-hit shortcut,
-// bary in double).  The curve lookup and the NLerp are the same code for both.
-template <class Clock>
-__device__ __forceinline__ void eval_bone_pose(const BoneTrackParams &p, uint32_t bone, const Clock clk, float4 &t_out, float4 &q_out) {
-    const uint32_t b = p.key_off[bone], e = p.key_off[bone + 1];
-    const float4 *tr = reinterpret_cast<const float4 *>(p.key_tr);
-    const float4 *rot = reinterpret_cast<const float4 *>(p.key_rot);
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f), q = make_float4(0.f, 0.f, 0.f, 1.f);   // Poser::ResetPosing
-    if (e > b) {
-        if (clk.at_or_before_first(p.key_frame[b])) {
-            t = tr[b]; q = rot[b];
-        } else if (clk.at_or_after_last(p.key_frame[e - 1])) {
-            t = tr[e - 1]; q = rot[e - 1];
-        } else {
-            const uint32_t frame = clk.search();
-            uint32_t lo = b, hi = e - 1;                   // key_frame[lo] <= frame < key_frame[hi]
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) / 2;
-                if (p.key_frame[mid] > frame) hi = mid; else lo = mid;
-            }
-            const uint32_t lf = p.key_frame[lo], rf = p.key_frame[hi];
-            if (clk.exact(lf)) {
-                t = tr[lo]; q = rot[lo];
-            } else {
-                const float bary = clk.bary(lf, rf);
-                const uint4 cv = reinterpret_cast<const uint4 *>(p.key_curve)[lo];   // the LEFT key's curves
-                const float4 lt = tr[lo], rt = tr[hi], lq = rot[lo], rq = rot[hi];
-                float lam = curve_at(p.lut, cv.x, bary);
-                t.x = lt.x * (1.0f - lam) + rt.x * lam;
-                lam = curve_at(p.lut, cv.y, bary);
-                t.y = lt.y * (1.0f - lam) + rt.y * lam;
-                lam = curve_at(p.lut, cv.z, bary);
-                t.z = lt.z * (1.0f - lam) + rt.z * lam;
-                lam = curve_at(p.lut, cv.w, bary);
-                // NLerp(l, r)[lam], L/util/math_impl.inl:1260-1282
-                if (lam < 1e-7f) {
-                    q = lq;
-                } else if (lam > 1.0f - 1e-7f) {
-                    q = rq;
-                } else {
-                    const float dot = lq.x * rq.x + lq.y * rq.y + lq.z * rq.z + lq.w * rq.w;
-                    const float a = 1.0f - lam;
-                    float4 v;
-                    if (dot < 0.0f) {
-                        v = make_float4(a * lq.x - lam * rq.x, a * lq.y - lam * rq.y, a * lq.z - lam * rq.z,
-                                        a * lq.w - lam * rq.w);
-                    } else {
-                        v = make_float4(a * lq.x + lam * rq.x, a * lq.y + lam * rq.y, a * lq.z + lam * rq.z,
-                                        a * lq.w + lam * rq.w);
-                    }
-                    // Vector4D::Normalize: 1 / float(sqrt(double(sum))), L/util/math_impl.inl:717-728, math.inl:27-29
-                    const float s = v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-                    const float n = 1.0f / float(sqrt(double(s)));
-                    q = make_float4(v.x * n, v.y * n, v.z * n, v.w * n);
-                }
-            }
-        }
-    }
-    t_out = t;
-    q_out = q;
+// One thread per (instance, bone) -- which instance: lane_item (instance_list.hpp), every instance or the listed ones; what it plays:
+// a pose source (clip_source.hpp) built per lane, since a wave spans instances when nb is not a multiple of 64.  Operand rows and
+// the pose row are addressed by the instance's row, nothing is kept per list position.
+template <class Source, class Instances, class... Operands>
+__device__ __forceinline__ void bone_track_body(const BoneTrackParams &p, const Instances &sel, const Operands &...operands) {
+    LaneItem it;
+    if (!lane_item<kRigThreads>(sel, p.ni, p.nb, it)) return;
+    float4 t, q;
+    Source(p, operands..., it.ln.row).pose(it.item, t, q);
+    float4 *out = reinterpret_cast<float4 *>(p.out) + it.at * 2;
+    out[0] = t;
+    out[1] = q;
 }
 
 template <class Clock>
 __global__ __launch_bounds__(kRigThreads) void bone_track_eval_kernel(const BoneTrackParams p) {
-    const size_t idx = size_t(blockIdx.x) * kRigThreads + threadIdx.x;
-    if (idx >= size_t(p.ni) * p.nb) return;
-    const uint32_t i = uint32_t(idx / p.nb), bone = uint32_t(idx - size_t(i) * p.nb);
-    float4 t, q;
-    eval_bone_pose(p, bone, clock_of<Clock>(p.frames, p.times, i), t, q);
-    float4 *out = reinterpret_cast<float4 *>(p.out) + idx * 2;
-    out[0] = t;
-    out[1] = q;
+    bone_track_body<MotionPose<Clock>>(p, AllInstances{});
 }
 
-// Motion set (mmdx_motion_set_*): clip c of the bank is the single-motion table with key_off advanced by c * (nb+1) -- the offsets
-// stored there are absolute into the concatenated key arrays -- so the clip of an instance goes through eval_bone_pose itself.  A
-// clip id outside [0, n_clips) (MMDX_CLIP_NONE included) plays nothing: the rest pose of Poser::ResetPosing, and no table is read.
-__device__ __forceinline__ BoneTrackParams clip_of(BoneTrackParams p, uint32_t clip) {
-    p.key_off += size_t(clip) * (size_t(p.nb) + 1);
-    return p;
-}
-
-// One thread per (instance, bone), as above.  A wave spans two instances when nb is not a multiple of 64: the clip id is per lane.
+// mmdx_motion_set_eval_bones*: the clip id is per lane
 template <class Clock>
 __global__ __launch_bounds__(kRigThreads) void bone_track_eval_set_kernel(const BoneTrackParams p, const uint32_t *clips,
                                                                           const uint32_t n_clips) {
-    const size_t idx = size_t(blockIdx.x) * kRigThreads + threadIdx.x;
-    if (idx >= size_t(p.ni) * p.nb) return;
-    const uint32_t i = uint32_t(idx / p.nb), bone = uint32_t(idx - size_t(i) * p.nb);
-    const uint32_t clip = clips[i];
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f), q = make_float4(0.f, 0.f, 0.f, 1.f);   // Poser::ResetPosing
-    if (clip < n_clips) eval_bone_pose(clip_of(p, clip), bone, clock_of<Clock>(p.frames, p.times, i), t, q);
-    float4 *out = reinterpret_cast<float4 *>(p.out) + idx * 2;
-    out[0] = t;
-    out[1] = q;
+    bone_track_body<ClipPose<Clock>>(p, AllInstances{}, clips, n_clips);
 }
 
-// Cross-fade between two clips of a set (mmdx_motion_set_blend_bones_time; motion_blend.hpp).  The pose of one (clip, time) of a
-// blend call: what bone_track_eval_set_kernel stores for it -- eval_bone_pose itself, or the rest pose for an id outside the bank.
-template <class Clock>
-__device__ __forceinline__ void eval_clip_pose(const BoneTrackParams &p, uint32_t clip, uint32_t n_clips, const Clock clk, uint32_t bone,
-                                               float4 &t, float4 &q) {
-    t = make_float4(0.f, 0.f, 0.f, 0.f); q = make_float4(0.f, 0.f, 0.f, 1.f);   // Poser::ResetPosing
-    if (clip < n_clips) eval_bone_pose(clip_of(p, clip), bone, clk, t, q);
-}
-
-// One thread per (instance, bone), as above; weight, clip ids and clocks are per lane (a wave spans instances).  A lane evaluates
-// ONE clip -- a, or b when the weight says the row is B -- and only a lane that blends evaluates b as well: an end-point row is the
-// set call's row bit for bit and reads nothing of the other clip, neither its id and time nor its tables.
+// Cross-fade between two clips of a set (mmdx_motion_set_blend_bones_time; motion_blend.hpp): weight, clip ids and clocks per lane.
+// Spelled out, not bone_track_body<BlendPose>: through BlendPose, which reads the second side's id and time ahead of the first
+// evaluation, this kernel measured 0.3-0.8 % behind its parent at 1 024 x 300 bones twice in a row (profiles/clip_source/); here
+// the second side is read where it is used, as BlendRow says it: A, or B when the row is B, and B as well only when mixing.
 template <class Clock>
 __global__ __launch_bounds__(kRigThreads) void bone_track_blend_set_kernel(const BoneTrackParams p, const BlendOperands o) {
     const size_t idx = size_t(blockIdx.x) * kRigThreads + threadIdx.x;
@@ -153,10 +61,10 @@ __global__ __launch_bounds__(kRigThreads) void bone_track_blend_set_kernel(const
     const uint32_t side = blend_side(w);
     const bool first_b = side == kBlendB;
     float4 t, q;
-    eval_clip_pose(p, (first_b ? o.clips_b : o.clips_a)[i], o.n_clips, clock_of<Clock>(nullptr, first_b ? o.times_b : o.times_a, i), bone, t, q);
+    ClipPose<Clock>(p, (first_b ? o.clips_b : o.clips_a)[i], o.n_clips, clock_of<Clock>(nullptr, first_b ? o.times_b : o.times_a, i)).pose(bone, t, q);
     if (side == kBlendMix) {
         float4 tb, qb;
-        eval_clip_pose(p, o.clips_b[i], o.n_clips, clock_of<Clock>(nullptr, o.times_b, i), bone, tb, qb);
+        ClipPose<Clock>(p, o.clips_b[i], o.n_clips, clock_of<Clock>(nullptr, o.times_b, i)).pose(bone, tb, qb);
         blend_pose(t, q, tb, qb, w);
     }
     float4 *out = reinterpret_cast<float4 *>(p.out) + idx * 2;
@@ -245,79 +153,46 @@ __device__ __forceinline__ void fk_bone(const SkeletonParams &p, PoseAt pose_at,
     for (int y = 0; y < 4; ++y) out[y] = make_float4(S.m[y][0], S.m[y][1], S.m[y][2], S.m[y][3]);
 }
 
-__global__ __launch_bounds__(kRigThreads) void skeleton_fk_kernel(const SkeletonParams p) {
-    const size_t idx = size_t(blockIdx.x) * kRigThreads + threadIdx.x;
-    if (idx >= size_t(p.ni) * p.nb) return;
-    const uint32_t i = uint32_t(idx / p.nb), bone = uint32_t(idx - size_t(i) * p.nb);
-    const float4 *pose = reinterpret_cast<const float4 *>(p.poses) + size_t(i) * p.nb * 2;
-    fk_bone(p, [&](uint32_t k) { return pose[k]; }, i, bone, reinterpret_cast<float4 *>(p.out) + idx * 4);
+// One thread per (instance, bone), lane_item as in bone_track_body: the bone morphs' state by cell, the pose and the palette row by
+// the instance's row.
+template <class Instances>
+__device__ __forceinline__ void skeleton_fk_body(const SkeletonParams &p, const Instances &sel) {
+    LaneItem it;
+    if (!lane_item<kRigThreads>(sel, p.ni, p.nb, it)) return;
+    const float4 *pose = reinterpret_cast<const float4 *>(p.poses) + size_t(it.ln.row) * p.nb * 2;
+    fk_bone(p, [&](uint32_t k) { return pose[k]; }, it.ln.cell, it.item, reinterpret_cast<float4 *>(p.out) + it.at * 4);
 }
 
-// ---- which instance a lane works on: Lane / ListedInstances, instance_list.hpp ---------------------------------------------------
+__global__ __launch_bounds__(kRigThreads) void skeleton_fk_kernel(const SkeletonParams p) { skeleton_fk_body(p, AllInstances{}); }
 
-// skeleton_fk_kernel for the listed instances: one thread per (list position, bone); the bone morphs' state by position, the pose
-// and the palette row by id.  Workgroups wholly behind the count leave first.
+// the listed instances (mmdx_skeleton_solve_select): p.ni = the list's capacity, one thread per (list position, bone)
 __global__ __launch_bounds__(kRigThreads) void skeleton_fk_select_kernel(const SkeletonParams p, const InstanceList list) {
-    const ListedInstances sel = {list};
-    const uint32_t used = sel.used(p.ni);
-    const size_t idx = size_t(blockIdx.x) * kRigThreads + threadIdx.x;
-    if (size_t(blockIdx.x) * kRigThreads >= size_t(used) * p.nb) return;
-    if (idx >= size_t(used) * p.nb) return;
-    const uint32_t k = uint32_t(idx / p.nb), bone = uint32_t(idx - size_t(k) * p.nb);
-    const Lane ln = sel.lane(k, used);
-    if (!ln.live) return;
-    const float4 *pose = reinterpret_cast<const float4 *>(p.poses) + size_t(ln.row) * p.nb * 2;
-    fk_bone(p, [&](uint32_t j) { return pose[j]; }, ln.cell, bone, reinterpret_cast<float4 *>(p.out) + (size_t(ln.row) * p.nb + bone) * 4);
+    skeleton_fk_body(p, ListedInstances{list});
 }
 
-// bone_track_blend_set_kernel for the listed instances (mmdx_motion_set_blend_bones_time_select): one thread per (list position,
-// bone), p.ni = the list's capacity.  A wave spans list positions when nb is no multiple of 64, so the id -- and with it weight,
-// clip ids and clocks -- is per lane; operand rows and the pose row are addressed by the id, nothing is kept per position.  The
-// evaluation is the plain kernel's, call for call.  Workgroups wholly behind the count leave first.
+// bone_track_blend_set_kernel for the listed instances (mmdx_motion_set_blend_bones_time_select): p.ni = the list's capacity
 template <class Clock>
 __global__ __launch_bounds__(kRigThreads) void bone_track_blend_set_select_kernel(const BoneTrackParams p, const BlendOperands o,
                                                                                   const InstanceList list) {
-    const ListedInstances sel = {list};
-    const uint32_t used = sel.used(p.ni);
-    const size_t idx = size_t(blockIdx.x) * kRigThreads + threadIdx.x;
-    if (size_t(blockIdx.x) * kRigThreads >= size_t(used) * p.nb) return;
-    if (idx >= size_t(used) * p.nb) return;
-    const uint32_t k = uint32_t(idx / p.nb), bone = uint32_t(idx - size_t(k) * p.nb);
-    const Lane ln = sel.lane(k, used);
-    if (!ln.live) return;
-    const uint32_t i = ln.row;
-    const float w = o.weights[i];
-    const uint32_t side = blend_side(w);
-    const bool first_b = side == kBlendB;
-    float4 t, q;
-    eval_clip_pose(p, (first_b ? o.clips_b : o.clips_a)[i], o.n_clips, clock_of<Clock>(nullptr, first_b ? o.times_b : o.times_a, i), bone, t, q);
-    if (side == kBlendMix) {
-        float4 tb, qb;
-        eval_clip_pose(p, o.clips_b[i], o.n_clips, clock_of<Clock>(nullptr, o.times_b, i), bone, tb, qb);
-        blend_pose(t, q, tb, qb, w);
-    }
-    float4 *out = reinterpret_cast<float4 *>(p.out) + (size_t(i) * p.nb + bone) * 2;
-    out[0] = t;
-    out[1] = q;
+    bone_track_body<BlendPose<Clock>>(p, ListedInstances{list}, o);
 }
 
-// Bone tracks -> palette in ONE launch (mmdx_skeleton_solve_motion on a parallel-FK skeleton): a workgroup is one instance; its
-// threads evaluate the bones' local poses at the instance's frame into LDS (eval_bone_pose: what bone_track_eval_kernel writes to
-// HBM), one barrier, then every thread rebuilds its bones' matrices from those poses (fk_bone: what skeleton_fk_kernel does from
-// HBM).  The same two functions, so the same bits; the [NI][NB][8] pose array never leaves the chip (it is still written out when
-// the caller asks for it: t.out != nullptr).  The instance's clock (frame, or time * 30.0) is read once per workgroup.
-template <class Clock>
-__global__ __launch_bounds__(1024) void motion_fk_kernel(const BoneTrackParams t, const SkeletonParams p) {
+// Bone tracks -> palette in ONE launch (mmdx_skeleton_solve_motion* on a parallel-FK skeleton): a workgroup is one instance, row i
+// of the callers' arrays; its threads evaluate what the instance plays (`src`, built once per workgroup: its operands are
+// workgroup-uniform, scalar loads and uniform branches) into LDS -- what the bone_track_* kernel of the same source writes to HBM --
+// one barrier, then every thread rebuilds its bones' matrices from those poses (fk_bone: what skeleton_fk_kernel does from HBM).
+// The same functions, so the same bits; the [NI][NB][8] pose array never leaves the chip unless the caller asks for it
+// (poses_out != nullptr).  No bone morphs here (p.morph == nullptr), so fk_bone's cell is not read.
+template <class Source>
+__device__ __forceinline__ void motion_fk_body(const Source &src, float *poses_out, const SkeletonParams &p, uint32_t i) {
     extern __shared__ float4 pose_lds[];                 // [nb][2]
-    const uint32_t i = blockIdx.x;
-    const Clock clk = clock_of<Clock>(t.frames, t.times, i);
     for (uint32_t b = threadIdx.x; b < p.nb; b += blockDim.x) {   // one bone per thread up to 1 024 bones: one latency chain, not several
         float4 tr, q;
-        eval_bone_pose(t, b, clk, tr, q);
+        src.pose(b, tr, q);
         pose_lds[2 * b] = tr;
         pose_lds[2 * b + 1] = q;
-        if (t.out) {
-            float4 *o = reinterpret_cast<float4 *>(t.out) + (size_t(i) * p.nb + b) * 2;
+        if (poses_out) {
+            float4 *o = reinterpret_cast<float4 *>(poses_out) + (size_t(i) * p.nb + b) * 2;
             o[0] = tr; o[1] = q;
         }
     }
@@ -326,109 +201,33 @@ __global__ __launch_bounds__(1024) void motion_fk_kernel(const BoneTrackParams t
         fk_bone(p, [&](uint32_t k) { return pose_lds[k]; }, i, bone, reinterpret_cast<float4 *>(p.out) + (size_t(i) * p.nb + bone) * 4);
 }
 
-// The same for a motion set: the instance's clip id is read once per workgroup next to its clock (workgroup-uniform: a scalar load),
-// an id outside the bank puts the rest pose into LDS.  eval_bone_pose, the barrier and fk_bone are the ones above.
+template <class Clock>
+__global__ __launch_bounds__(1024) void motion_fk_kernel(const BoneTrackParams t, const SkeletonParams p) {
+    motion_fk_body(MotionPose<Clock>(t, blockIdx.x), t.out, p, blockIdx.x);
+}
+
 template <class Clock>
 __global__ __launch_bounds__(1024) void motion_fk_set_kernel(const BoneTrackParams t0, const SkeletonParams p, const uint32_t *clips,
                                                              const uint32_t n_clips) {
-    extern __shared__ float4 pose_lds[];                 // [nb][2]
-    const uint32_t i = blockIdx.x;
-    const uint32_t clip = clips[i];
-    const bool plays = clip < n_clips;
-    const BoneTrackParams t = clip_of(t0, plays ? clip : 0u);
-    const Clock clk = clock_of<Clock>(t.frames, t.times, i);
-    for (uint32_t b = threadIdx.x; b < p.nb; b += blockDim.x) {
-        float4 tr = make_float4(0.f, 0.f, 0.f, 0.f), q = make_float4(0.f, 0.f, 0.f, 1.f);   // Poser::ResetPosing
-        if (plays) eval_bone_pose(t, b, clk, tr, q);
-        pose_lds[2 * b] = tr;
-        pose_lds[2 * b + 1] = q;
-        if (t.out) {
-            float4 *o = reinterpret_cast<float4 *>(t.out) + (size_t(i) * p.nb + b) * 2;
-            o[0] = tr; o[1] = q;
-        }
-    }
-    __syncthreads();
-    for (uint32_t bone = threadIdx.x; bone < p.nb; bone += blockDim.x)
-        fk_bone(p, [&](uint32_t k) { return pose_lds[k]; }, i, bone, reinterpret_cast<float4 *>(p.out) + (size_t(i) * p.nb + bone) * 4);
+    motion_fk_body(ClipPose<Clock>(t0, clips, n_clips, blockIdx.x), t0.out, p, blockIdx.x);
 }
 
-// The cross-fade in one launch (mmdx_skeleton_solve_motion_set_blend_time): both clip ids, both clocks and the weight are read once
-// per workgroup (workgroup-uniform: scalar loads, a uniform branch).  The thread that owns a bone evaluates A -- or B when the row
-// is B -- evaluates B as well when the workgroup blends, and blends in registers (blend_pose); LDS holds the one blended pose per
-// bone, [nb][2] float4 as above.  eval_bone_pose, the barrier and fk_bone are the ones above.
+// mmdx_skeleton_solve_motion_set_blend_time: LDS holds the one blended pose per bone
 template <class Clock>
 __global__ __launch_bounds__(1024) void motion_fk_blend_set_kernel(const BoneTrackParams t0, const SkeletonParams p, const BlendOperands o) {
-    extern __shared__ float4 pose_lds[];                 // [nb][2]
-    const uint32_t i = blockIdx.x;
-    const float w = o.weights[i];
-    const uint32_t side = blend_side(w);
-    const bool first_b = side == kBlendB, mix = side == kBlendMix;
-    const uint32_t clip0 = (first_b ? o.clips_b : o.clips_a)[i];
-    const Clock clk0 = clock_of<Clock>(nullptr, first_b ? o.times_b : o.times_a, i);
-    uint32_t clip1 = 0xFFFFFFFFu;
-    Clock clk1 = clk0;
-    if (mix) {
-        clip1 = o.clips_b[i];
-        clk1 = clock_of<Clock>(nullptr, o.times_b, i);
-    }
-    for (uint32_t b = threadIdx.x; b < p.nb; b += blockDim.x) {
-        float4 tr, q;
-        eval_clip_pose(t0, clip0, o.n_clips, clk0, b, tr, q);
-        if (mix) {
-            float4 tb, qb;
-            eval_clip_pose(t0, clip1, o.n_clips, clk1, b, tb, qb);
-            blend_pose(tr, q, tb, qb, w);
-        }
-        pose_lds[2 * b] = tr;
-        pose_lds[2 * b + 1] = q;
-        if (t0.out) {
-            float4 *out = reinterpret_cast<float4 *>(t0.out) + (size_t(i) * p.nb + b) * 2;
-            out[0] = tr; out[1] = q;
-        }
-    }
-    __syncthreads();
-    for (uint32_t bone = threadIdx.x; bone < p.nb; bone += blockDim.x)
-        fk_bone(p, [&](uint32_t k) { return pose_lds[k]; }, i, bone, reinterpret_cast<float4 *>(p.out) + (size_t(i) * p.nb + bone) * 4);
+    motion_fk_body(BlendPose<Clock>(t0, o, blockIdx.x), t0.out, p, blockIdx.x);
 }
 
-// motion_fk_blend_set_kernel for the listed instances (mmdx_skeleton_solve_motion_set_blend_time_select): a workgroup is one LIST
-// POSITION (p.ni = the list's capacity).  *count, the id and the five operands of its row are workgroup-uniform loads (the same
-// address in every lane: scalar loads).  A workgroup behind the count, or whose id is no row, returns BEFORE the barrier: the
-// condition is uniform over the workgroup, so no lane of a live workgroup skips it.  Operands and the palette row by id; the blend in
-// registers, the poses in LDS, eval_clip_pose / blend_pose / fk_bone as in the plain kernel.
+// The same for the listed instances (mmdx_skeleton_solve_motion_set_blend_time_select): a workgroup is one LIST POSITION (p.ni = the
+// list's capacity).  A workgroup behind the count, or whose id is no row, returns BEFORE the barrier: the condition is uniform over
+// the workgroup, so no lane of a live workgroup skips it.  No pose array is written.
 template <class Clock>
 __global__ __launch_bounds__(1024) void motion_fk_blend_set_select_kernel(const BoneTrackParams t0, const SkeletonParams p, const BlendOperands o,
                                                                           const InstanceList list) {
-    extern __shared__ float4 pose_lds[];                 // [nb][2]
     const ListedInstances sel = {list};
     const Lane ln = sel.lane(blockIdx.x, sel.used(p.ni));
     if (!ln.live) return;
-    const uint32_t i = ln.row;
-    const float w = o.weights[i];
-    const uint32_t side = blend_side(w);
-    const bool first_b = side == kBlendB, mix = side == kBlendMix;
-    const uint32_t clip0 = (first_b ? o.clips_b : o.clips_a)[i];
-    const Clock clk0 = clock_of<Clock>(nullptr, first_b ? o.times_b : o.times_a, i);
-    uint32_t clip1 = 0xFFFFFFFFu;
-    Clock clk1 = clk0;
-    if (mix) {
-        clip1 = o.clips_b[i];
-        clk1 = clock_of<Clock>(nullptr, o.times_b, i);
-    }
-    for (uint32_t b = threadIdx.x; b < p.nb; b += blockDim.x) {
-        float4 tr, q;
-        eval_clip_pose(t0, clip0, o.n_clips, clk0, b, tr, q);
-        if (mix) {
-            float4 tb, qb;
-            eval_clip_pose(t0, clip1, o.n_clips, clk1, b, tb, qb);
-            blend_pose(tr, q, tb, qb, w);
-        }
-        pose_lds[2 * b] = tr;
-        pose_lds[2 * b + 1] = q;
-    }
-    __syncthreads();
-    for (uint32_t bone = threadIdx.x; bone < p.nb; bone += blockDim.x)
-        fk_bone(p, [&](uint32_t k) { return pose_lds[k]; }, i, bone, reinterpret_cast<float4 *>(p.out) + (size_t(i) * p.nb + bone) * 4);
+    motion_fk_body(BlendPose<Clock>(t0, o, ln.row), nullptr, p, ln.row);
 }
 
 // ---- ordered solver: append (inherit) bones + CCD-IK -----------------------------------------------
@@ -1421,96 +1220,59 @@ hipError_t launch_physics_override(const PhysicsParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// The per-(instance, bone) kernels: launch_lane_items (instance_list.hpp); a select form is sized from p.ni = the list's capacity.
 hipError_t launch_bone_track_eval(const BoneTrackParams &p, hipStream_t stream) {
-    const size_t n = size_t(p.ni) * p.nb;
-    if (n == 0) return hipSuccess;
-    const dim3 grid(uint32_t((n + kRigThreads - 1) / kRigThreads));
-    if (p.times) hipLaunchKernelGGL(bone_track_eval_kernel<TimeClock>, grid, dim3(kRigThreads), 0, stream, p);
-    else hipLaunchKernelGGL(bone_track_eval_kernel<FrameClock>, grid, dim3(kRigThreads), 0, stream, p);
-    return hipGetLastError();
+    return launch_lane_items<kRigThreads>(MMDX_BY_CLOCK(bone_track_eval_kernel, p.times), p.ni, p.nb, stream, p);
 }
 
 hipError_t launch_bone_track_eval_set(const BoneTrackParams &p, const uint32_t *clips, uint32_t n_clips, hipStream_t stream) {
-    const size_t n = size_t(p.ni) * p.nb;
-    if (n == 0) return hipSuccess;
-    const dim3 grid(uint32_t((n + kRigThreads - 1) / kRigThreads));
-    if (p.times) hipLaunchKernelGGL(bone_track_eval_set_kernel<TimeClock>, grid, dim3(kRigThreads), 0, stream, p, clips, n_clips);
-    else hipLaunchKernelGGL(bone_track_eval_set_kernel<FrameClock>, grid, dim3(kRigThreads), 0, stream, p, clips, n_clips);
-    return hipGetLastError();
+    return launch_lane_items<kRigThreads>(MMDX_BY_CLOCK(bone_track_eval_set_kernel, p.times), p.ni, p.nb, stream, p, clips, n_clips);
+}
+
+hipError_t launch_bone_track_blend_set(const BoneTrackParams &p, const BlendOperands &o, hipStream_t stream) {
+    return launch_lane_items<kRigThreads>(bone_track_blend_set_kernel<TimeClock>, p.ni, p.nb, stream, p, o);
+}
+
+hipError_t launch_bone_track_blend_set_select(const BoneTrackParams &p, const BlendOperands &o, const InstanceList &list, hipStream_t stream) {
+    return launch_lane_items<kRigThreads>(bone_track_blend_set_select_kernel<TimeClock>, p.ni, p.nb, stream, p, o, list);
 }
 
 hipError_t launch_skeleton_fk(const SkeletonParams &p, hipStream_t stream) {
-    const size_t n = size_t(p.ni) * p.nb;
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(skeleton_fk_kernel, dim3(uint32_t((n + kRigThreads - 1) / kRigThreads)),
-                       dim3(kRigThreads), 0, stream, p);
-    return hipGetLastError();
+    return launch_lane_items<kRigThreads>(skeleton_fk_kernel, p.ni, p.nb, stream, p);
 }
 
 hipError_t launch_skeleton_fk_select(const SkeletonParams &p, const InstanceList &list, hipStream_t stream) {
-    const size_t n = size_t(p.ni) * p.nb;                      // p.ni: the list's capacity
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(skeleton_fk_select_kernel, dim3(uint32_t((n + kRigThreads - 1) / kRigThreads)),
-                       dim3(kRigThreads), 0, stream, p, list);
+    return launch_lane_items<kRigThreads>(skeleton_fk_select_kernel, p.ni, p.nb, stream, p, list);
+}
+
+// The one-launch kernels (motion_fk_body): a workgroup per instance -- per list position of a select form, p.ni = the list's
+// capacity -- its poses in nb * 32 bytes of LDS, a thread per bone up to 1 024.
+template <class Kernel, class... Args>
+static hipError_t launch_motion_fk_shape(Kernel kernel, const SkeletonParams &p, hipStream_t stream, const Args &...args) {
+    if (p.ni == 0 || p.nb == 0) return hipSuccess;
+    const size_t lds = size_t(p.nb) * 32;
+    if (lds > kMotionFkMaxLds) return hipErrorInvalidValue;                  // callers check: the two-launch path takes over
+    const uint32_t threads = std::min<uint32_t>(1024u, (p.nb + 63u) / 64u * 64u);
+    hipLaunchKernelGGL(kernel, dim3(p.ni), dim3(threads), lds, stream, args...);
     return hipGetLastError();
 }
 
 hipError_t launch_motion_fk(const BoneTrackParams &t, const SkeletonParams &p, hipStream_t stream) {
-    if (p.ni == 0 || p.nb == 0) return hipSuccess;
-    const size_t lds = size_t(p.nb) * 32;
-    if (lds > kMotionFkMaxLds) return hipErrorInvalidValue;                  // callers check: the two-launch path takes over
-    const uint32_t threads = std::min<uint32_t>(1024u, (p.nb + 63u) / 64u * 64u);
-    if (t.times) hipLaunchKernelGGL(motion_fk_kernel<TimeClock>, dim3(p.ni), dim3(threads), lds, stream, t, p);
-    else hipLaunchKernelGGL(motion_fk_kernel<FrameClock>, dim3(p.ni), dim3(threads), lds, stream, t, p);
-    return hipGetLastError();
+    return launch_motion_fk_shape(MMDX_BY_CLOCK(motion_fk_kernel, t.times), p, stream, t, p);
 }
 
 hipError_t launch_motion_fk_set(const BoneTrackParams &t, const SkeletonParams &p, const uint32_t *clips, uint32_t n_clips,
                                 hipStream_t stream) {
-    if (p.ni == 0 || p.nb == 0) return hipSuccess;
-    const size_t lds = size_t(p.nb) * 32;
-    if (lds > kMotionFkMaxLds) return hipErrorInvalidValue;                  // callers check: the two-launch path takes over
-    const uint32_t threads = std::min<uint32_t>(1024u, (p.nb + 63u) / 64u * 64u);
-    if (t.times) hipLaunchKernelGGL(motion_fk_set_kernel<TimeClock>, dim3(p.ni), dim3(threads), lds, stream, t, p, clips, n_clips);
-    else hipLaunchKernelGGL(motion_fk_set_kernel<FrameClock>, dim3(p.ni), dim3(threads), lds, stream, t, p, clips, n_clips);
-    return hipGetLastError();
-}
-
-hipError_t launch_bone_track_blend_set(const BoneTrackParams &p, const BlendOperands &o, hipStream_t stream) {
-    const size_t n = size_t(p.ni) * p.nb;
-    if (n == 0) return hipSuccess;
-    const dim3 grid(uint32_t((n + kRigThreads - 1) / kRigThreads));
-    hipLaunchKernelGGL(bone_track_blend_set_kernel<TimeClock>, grid, dim3(kRigThreads), 0, stream, p, o);
-    return hipGetLastError();
+    return launch_motion_fk_shape(MMDX_BY_CLOCK(motion_fk_set_kernel, t.times), p, stream, t, p, clips, n_clips);
 }
 
 hipError_t launch_motion_fk_blend_set(const BoneTrackParams &t, const SkeletonParams &p, const BlendOperands &o, hipStream_t stream) {
-    if (p.ni == 0 || p.nb == 0) return hipSuccess;
-    const size_t lds = size_t(p.nb) * 32;
-    if (lds > kMotionFkMaxLds) return hipErrorInvalidValue;                  // callers check: the two-launch path takes over
-    const uint32_t threads = std::min<uint32_t>(1024u, (p.nb + 63u) / 64u * 64u);
-    hipLaunchKernelGGL(motion_fk_blend_set_kernel<TimeClock>, dim3(p.ni), dim3(threads), lds, stream, t, p, o);
-    return hipGetLastError();
-}
-
-// the select forms of the two above: sized from p.ni = the list's capacity, one thread per (list position, bone) / one workgroup per
-// list position
-hipError_t launch_bone_track_blend_set_select(const BoneTrackParams &p, const BlendOperands &o, const InstanceList &list, hipStream_t stream) {
-    const size_t n = size_t(p.ni) * p.nb;
-    if (n == 0) return hipSuccess;
-    const dim3 grid(uint32_t((n + kRigThreads - 1) / kRigThreads));
-    hipLaunchKernelGGL(bone_track_blend_set_select_kernel<TimeClock>, grid, dim3(kRigThreads), 0, stream, p, o, list);
-    return hipGetLastError();
+    return launch_motion_fk_shape(motion_fk_blend_set_kernel<TimeClock>, p, stream, t, p, o);
 }
 
 hipError_t launch_motion_fk_blend_set_select(const BoneTrackParams &t, const SkeletonParams &p, const BlendOperands &o,
                                              const InstanceList &list, hipStream_t stream) {
-    if (p.ni == 0 || p.nb == 0) return hipSuccess;
-    const size_t lds = size_t(p.nb) * 32;
-    if (lds > kMotionFkMaxLds) return hipErrorInvalidValue;                  // callers check: the two-launch path takes over
-    const uint32_t threads = std::min<uint32_t>(1024u, (p.nb + 63u) / 64u * 64u);
-    hipLaunchKernelGGL(motion_fk_blend_set_select_kernel<TimeClock>, dim3(p.ni), dim3(threads), lds, stream, t, p, o, list);
-    return hipGetLastError();
+    return launch_motion_fk_shape(motion_fk_blend_set_select_kernel<TimeClock>, p, stream, t, p, o, list);
 }
 
 hipError_t launch_bone_morph(const BoneMorphParams &p, hipStream_t stream) {

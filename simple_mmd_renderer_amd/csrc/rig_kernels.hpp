@@ -44,7 +44,7 @@ hipError_t launch_skeleton_ordered_select(const SerialParams &p, const uint8_t *
 hipError_t launch_bone_track_blend_set_select(const BoneTrackParams &p, const BlendOperands &o, const InstanceList &list, hipStream_t stream);
 hipError_t launch_motion_fk_blend_set_select(const BoneTrackParams &t, const SkeletonParams &p, const BlendOperands &o,
                                              const InstanceList &list, hipStream_t stream);
-// mmdx_animator_root_motion.  It lives here, not in anim_kernels.hip, because eval_bone_pose is local to rig_kernels.hip.
+// mmdx_animator_root_motion.  It lives here, not in anim_kernels.hip, next to the other kernels that call eval_bone_pose.
 // p: the concatenated bone tables of a set with k.n_clips clips (clock and output fields unused); the seven arrays are the
 // animator's, [ni] each, only read; placements [ni][8], of which [0..2] are updated.  dt / dt_dev as launch_animator_advance.
 struct RootMotionParams {

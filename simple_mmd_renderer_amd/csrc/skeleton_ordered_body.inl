@@ -4,8 +4,12 @@
 //   inst        the lane's state cell (solver scratch and bone-morph state, p.ni cells): the instance, or the list position
 //   row         its row of the caller's arrays (poses, palettes): the instance, or ids[inst]
 //   live        false: the lane skips the work but reaches every barrier
-// Text, not a function: the plain kernel stays, token for token, the kernel it was before there was a select form -- same registers,
-// same instructions (tools/disassembly_diff.py) -- and the select form cannot drift from it.
+// Text, not a function, and tried: as a __forceinline__ function template this body compiles (gfx950, the project's flags) to
+// different code in all six skeleton_ordered*_kernel instantiations, 5-17 of ~11 800 instructions each, and bone_morph_body.inl as a
+// function adds one instruction to both bone-morph kernels.  The solver is register-bound (256 VGPRs dense, spills plain) and takes
+// milliseconds, so a tidy-up would mean re-measuring it; as text the plain kernel stays the kernel it was before there was a select
+// form (tools/disassembly_diff.py) and the select form cannot drift from it.  The track and FK kernels, which are not register-bound,
+// do share their bodies as functions (clip_source.hpp, instance_list.hpp).
     const State st = {p.state + (live ? inst : 0), p.ni};
     extern __shared__ float chain_lds[];   // (windows x instances) lanes x window_floats of state, then the
                                            // windows' link constants

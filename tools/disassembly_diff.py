@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Instruction-level comparison of every gfx950 kernel of two built libraries (no GPU needed):
-    python tools/disassembly_diff.py parent/libmmdx.so [new/libmmdx.so]
+    python tools/disassembly_diff.py [--histogram] parent/libmmdx.so [new/libmmdx.so]
 Unbundles the code object of every translation unit (as tools/kernel_resources.py does), disassembles it with llvm-objdump, drops
 addresses and encodings, and prints: kernels that differ (with a unified diff), the counts, and the kernels only the new library
-has.  Kernels are keyed by (code object index, mangled name)."""
+has.  Kernels are keyed by (code object index, mangled name).
+--histogram: for every kernel that differs, the per-mnemonic instruction counts that changed, instead of the unified diff; register
+moves, waits and no-ops (s_mov*, v_mov*, s_waitcnt, s_nop) are left out, so a kernel whose instructions were only reordered or
+renumbered prints "same mix"."""
+import collections
 import difflib
 import os
 import re
@@ -43,9 +47,17 @@ def kernels_of(so):
     return {k: v for k, v in out.items() if not k[1].startswith("__hip_cuid")}
 
 
+def mix(instructions):
+    """Instructions per mnemonic, without the ones that only move registers or wait."""
+    names = (i.split(" ", 1)[0] for i in instructions)
+    return collections.Counter(n for n in names if not n.startswith(("s_mov", "v_mov", "s_waitcnt", "s_nop")))
+
+
 def main():
-    parent = kernels_of(sys.argv[1])
-    new = kernels_of(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "simple_mmd_renderer_amd", "libmmdx.so"))
+    args = [a for a in sys.argv[1:] if a != "--histogram"]
+    histogram = len(args) != len(sys.argv) - 1
+    parent = kernels_of(args[0])
+    new = kernels_of(args[1] if len(args) > 1 else os.path.join(ROOT, "simple_mmd_renderer_amd", "libmmdx.so"))
     differ = [k for k in parent if k in new and parent[k] != new[k]]
     for k in differ:
         print("DIFF", k, len(parent[k]), len(new[k]))
@@ -59,7 +71,12 @@ def main():
         print(" gone", k, len(parent[k]))
     for k in differ:
         print("=====", k)
-        print("\n".join(difflib.unified_diff(parent[k], new[k], lineterm="", n=1)))
+        if histogram:
+            a, b = mix(parent[k]), mix(new[k])
+            changed = ["%s %d -> %d" % (n, a[n], b[n]) for n in sorted(set(a) | set(b)) if a[n] != b[n]]
+            print("\n".join(changed) if changed else "same mix")
+        else:
+            print("\n".join(difflib.unified_diff(parent[k], new[k], lineterm="", n=1)))
 
 
 if __name__ == "__main__":
