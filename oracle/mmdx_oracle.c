@@ -31,6 +31,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <time.h>
 
@@ -458,6 +459,7 @@ static quat_t q_inverse(quat_t a) {                        /* :474-477 */
     quat_t c = {-a.i, -a.j, -a.k, a.e};
     return q_scale(c, n);
 }
+static uint32_t g_slerp_branch;    /* append trace only: the way the last q_slerp_from_identity went (AP_SLERP_*) */
 static quat_t q_slerp_from_identity(quat_t b, float l) {   /* SLerp(Identity, b)[l], :1312-1337 */
     const quat_t a = q_identity();
     float comega = a.e * b.e + a.i * b.i + a.j * b.j + a.k * b.k;
@@ -469,8 +471,10 @@ static quat_t q_slerp_from_identity(quat_t b, float l) {   /* SLerp(Identity, b)
         const float p = f_sin((1.0f - l) * omega) * rs;
         l = f_sin(l * omega) * rs;
         if (flip) l = -l;
+        g_slerp_branch = flip ? 2u : 1u;
         return q_add(q_scale(a, p), q_scale(b, l));
     }
+    g_slerp_branch = omega != omega ? 4u : 3u;
     return a;
 }
 static void q_to_matrix(quat_t q, float *m) {              /* :540-563 */
@@ -588,7 +592,61 @@ static void ik_trace_emit(const solve_ctx *c, uint32_t b, uint32_t limit, uint32
     ++g_ik_trace_n;
 }
 
-static void solve_ik_chain(const solve_ctx *c, uint32_t b) {
+/* Optional trace of the append (inherit) branch of update_bone (tests/append_cases.py steers rigs to every append topology with
+ * it): one record of MMDX_APPEND_TRACE_WORDS words per execution of that branch, wherever update_bone was called from -- the
+ * bone, its append parent, kind (bit 0 rotation, bit 1 translation), the ratio's bits, context (AP_CTX_*: the top-level sequence,
+ * a solve's first placement of its links and target, the target's re-evaluation inside the CCD loop), the number of solves on
+ * the stack (0 in the sequence, 1 in a top-level solve, 2 in a solve nested in it ...), the append parent's state (AP_PARENT_*:
+ * not yet written since this frame's reset, written, the bone itself), the SLerp branch (AP_SLERP_*: none = translation only,
+ * regular, regular with the flip, identity because omega <= 1e-7, identity because omega is NaN), and whether the resulting
+ * total rotation or translation holds a NaN.  "Written" is a per-bone mark kept for the trace alone (g_ap_written: update_bone
+ * has assigned the bone's totals since bone_solve_impl reset them).  The trace only reads: no result bit depends on it.  Not
+ * thread-safe; off by default. */
+enum { MMDX_APPEND_TRACE_WORDS = 9 };
+enum { AP_CTX_SEQUENCE = 0, AP_CTX_FIRST_PLACEMENT = 1, AP_CTX_LOOP_TARGET = 2 };
+enum { AP_PARENT_UNWRITTEN = 0, AP_PARENT_WRITTEN = 1, AP_PARENT_SELF = 2 };
+enum { AP_SLERP_NONE = 0, AP_SLERP_REGULAR = 1, AP_SLERP_FLIP = 2, AP_SLERP_SMALL = 3, AP_SLERP_NAN = 4 };
+static uint32_t *g_ap_trace;
+static size_t g_ap_trace_cap, g_ap_trace_n;
+static uint32_t g_ap_ctx, g_ap_depth;
+static uint8_t *g_ap_written;
+static size_t g_ap_written_cap;
+void mmdx_oracle_trace_append(uint32_t *records, size_t capacity) { g_ap_trace = records; g_ap_trace_cap = capacity; g_ap_trace_n = 0; }
+size_t mmdx_oracle_trace_append_count(void) { return g_ap_trace_n; }
+static void ap_trace_reset(uint32_t nb) {                   /* this frame's reset: no bone written yet */
+    if (!g_ap_trace) return;
+    if (g_ap_written_cap < nb) {
+        free(g_ap_written);
+        g_ap_written = (uint8_t *)malloc(nb);
+        g_ap_written_cap = g_ap_written ? nb : 0;
+    }
+    if (g_ap_written) memset(g_ap_written, 0, nb);
+}
+static void ap_trace_emit(const solve_ctx *c, uint32_t b, uint32_t kind, uint32_t slerp) {
+    if (!g_ap_trace) return;
+    if (g_ap_trace_n < g_ap_trace_cap) {
+        uint32_t *rec = g_ap_trace + MMDX_APPEND_TRACE_WORDS * g_ap_trace_n;
+        const bone_state_t *s = &c->st[b];
+        const uint32_t ap = (uint32_t)c->append_parent[b];
+        const float v[7] = {s->total_rot.i, s->total_rot.j, s->total_rot.k, s->total_rot.e, s->total_tr[0], s->total_tr[1], s->total_tr[2]};
+        uint32_t nan = 0;
+        for (int k = 0; k < 7; ++k) if (v[k] != v[k]) nan = 1;
+        rec[0] = b; rec[1] = ap; rec[2] = kind;
+        memcpy(rec + 3, &c->append_ratio[b], 4);
+        rec[4] = g_ap_ctx; rec[5] = g_ap_depth;
+        rec[6] = ap == b ? AP_PARENT_SELF : (g_ap_written && g_ap_written[ap]) ? AP_PARENT_WRITTEN : AP_PARENT_UNWRITTEN;
+        rec[7] = slerp; rec[8] = nan;
+    }
+    ++g_ap_trace_n;
+}
+
+static void solve_ik_chain_body(const solve_ctx *c, uint32_t b);
+static void solve_ik_chain(const solve_ctx *c, uint32_t b) {   /* (the depth count is the append trace's) */
+    ++g_ap_depth;
+    solve_ik_chain_body(c, b);
+    --g_ap_depth;
+}
+static void solve_ik_chain_body(const solve_ctx *c, uint32_t b) {
     bone_state_t *st = c->st;
     const uint32_t l0 = c->ik_link_off[b], n = c->ik_link_off[b + 1] - l0;
     const uint32_t target = (uint32_t)c->ik_target[b];
@@ -596,7 +654,8 @@ static void solve_ik_chain(const solve_ctx *c, uint32_t b) {
     float ik_pos[3], tgt_pos[3], err[3];
     for (uint32_t i = 0; i < n; ++i) st[c->ik_link_bone[l0 + i]].ik_rot = q_identity();
     memcpy(ik_pos, st[b].local + 12, 12);
-    for (uint32_t i = 0; i < n; ++i) update_bone(c, (uint32_t)c->ik_link_bone[l0 + n - i - 1], 1);
+    for (uint32_t i = 0; i < n; ++i) { g_ap_ctx = AP_CTX_FIRST_PLACEMENT; update_bone(c, (uint32_t)c->ik_link_bone[l0 + n - i - 1], 1); }
+    g_ap_ctx = AP_CTX_FIRST_PLACEMENT;
     update_bone(c, target, 1);
     memcpy(tgt_pos, st[target].local + 12, 12);
     for (int k = 0; k < 3; ++k) err[k] = ik_pos[k] - tgt_pos[k];
@@ -668,6 +727,7 @@ static void solve_ik_chain(const solve_ctx *c, uint32_t b) {
                 st[bb].total_rot = q_mul(st[bb].ik_rot, st[bb].pre_ik_rot);
                 place(c, bb);
             }
+            g_ap_ctx = AP_CTX_LOOP_TARGET;
             update_bone(c, target, 1);
             memcpy(tgt_pos, st[target].local + 12, 12);
         }
@@ -706,9 +766,12 @@ static void update_bone(const solve_ctx *c, uint32_t b, int solve_ik) {
     for (int k = 0; k < 3; ++k) s->total_tr[k] = s->morph_tr[k] + t[k];
     if ((f & 0x0300) && c->append_parent[b] >= 0 && (uint64_t)c->append_parent[b] < c->nb) {
         const bone_state_t *ap = &c->st[c->append_parent[b]];
+        g_slerp_branch = AP_SLERP_NONE;
         if (f & 0x0100) s->total_rot = q_mul(s->total_rot, q_slerp_from_identity(ap->total_rot, c->append_ratio[b]));
         if (f & 0x0200) for (int k = 0; k < 3; ++k) s->total_tr[k] = s->total_tr[k] + c->append_ratio[b] * ap->total_tr[k];
+        ap_trace_emit(c, b, (uint32_t)(f >> 8) & 3u, g_slerp_branch);
     }
+    if (g_ap_trace && g_ap_written) g_ap_written[b] = 1;    /* trace only */
     if (c->is_ik_link[b]) {
         s->pre_ik_rot = s->total_rot;
         s->total_rot = q_mul(s->ik_rot, s->total_rot);
@@ -908,6 +971,8 @@ static int bone_solve_impl(uint32_t nb, const float *rest, const int64_t *parent
         st[b].morph_tr[0] = st[b].morph_tr[1] = st[b].morph_tr[2] = 0.0f;
         mat_identity(st[b].local);
     }
+    ap_trace_reset(nb);
+    g_ap_depth = 0;
     if (nm) {
         const bmorph_ctx mc = {nm, morph_type, morph_off, morph_index, morph_value, morph_rotation, st};
         for (uint32_t m = 0; m < nm; ++m) apply_bone_morph(&mc, m, rates[m]);
@@ -916,7 +981,7 @@ static int bone_solve_impl(uint32_t nb, const float *rest, const int64_t *parent
                          ik_link_lo, ik_link_hi, ik_loop, ik_link_off, ik_link_limited, is_link, poses, st};
     for (int pass = 0; pass < 2; ++pass) {
         const uint32_t s0 = pass ? n_pre : 0, s1 = pass ? nb : n_pre;
-        for (uint32_t s = s0; s < s1; ++s) update_bone(&c, order[s], 1);
+        for (uint32_t s = s0; s < s1; ++s) { g_ap_ctx = AP_CTX_SEQUENCE; update_bone(&c, order[s], 1); }
         for (uint32_t s = s0; s < s1; ++s) {                /* UpdateBoneSkinningMatrix of this list */
             const uint32_t b = order[s];
             float g[16];

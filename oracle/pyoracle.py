@@ -247,6 +247,28 @@ class Oracle:
             raise ValueError("IK trace overflow: %d solves" % n)
         return buf[:n].copy()
 
+    APPEND_TRACE_FIELDS = ("bone", "parent", "kind", "ratio_bits", "context", "depth", "parent_state", "slerp", "nan")
+    APPEND_KINDS = (None, "rot", "tr", "rot+tr")
+    APPEND_CONTEXTS = ("sequence", "first_placement", "loop_target")
+    APPEND_PARENT_STATES = ("unwritten", "written", "self")
+    APPEND_SLERPS = ("none", "regular", "flip", "small_omega", "nan_omega")
+
+    def trace_append(self, fn, capacity=1 << 16):
+        """Run fn() with every execution of update_bone's append branch recorded; returns u32 [N, 9] records in execution order,
+        columns APPEND_TRACE_FIELDS: kind, context, parent_state and slerp index the APPEND_* tuples, depth counts the solves on
+        the stack (0 in the sequence) -- see mmdx_oracle_trace_append."""
+        buf = np.zeros((capacity, len(self.APPEND_TRACE_FIELDS)), np.uint32)
+        self.lib.mmdx_oracle_trace_append_count.restype = C.c_size_t
+        self.lib.mmdx_oracle_trace_append(buf.ctypes.data_as(C.c_void_p), C.c_size_t(capacity))
+        try:
+            fn()
+            n = int(self.lib.mmdx_oracle_trace_append_count())
+        finally:
+            self.lib.mmdx_oracle_trace_append(None, C.c_size_t(0))
+        if n > capacity:
+            raise ValueError("append trace overflow: %d evaluations" % n)
+        return buf[:n].copy()
+
     def time_crowd(self, model, rates, palettes, normalize=True):
         """Seconds for one crowd step (shared morph pass + one skinning pass per palette)."""
         t, ids, w = self.normalize(model) if normalize else (
