@@ -43,12 +43,12 @@ def hipcc() -> str:
 
 
 def source_sha() -> str:
-    """SHA-1 over everything the library is built from (sources and headers in the order listed, the flags, experiment knobs):
+    """SHA-1 over everything the library is built from (hashed_files(): sources, headers, included pieces; the flags, experiment knobs):
     embedded in the binary (mmdx_build_source_sha) and compared by build(), bench.py and smoke() -- the loaded library is
     provably built from the files in the tree, whatever the timestamps say."""
     import hashlib
     h = hashlib.sha1()
-    for f in SOURCES + HEADERS:
+    for f in hashed_files():
         h.update(os.path.basename(f).encode() + b"\0")
         h.update(open(os.path.join(CSRC, f), "rb").read())
     h.update(" ".join(flags()).encode())
@@ -70,7 +70,25 @@ def library_sha(path: str = None) -> str | None:
 
 
 STAMPED = "bench_api.cpp"      # the one translation unit that carries -DMMDX_SOURCE_SHA (mmdx_build_source_sha lives there)
-INCLUDES = {"kernels_fast.hip": ["kernels.hip"]}      # sources that #include other sources
+# The kernel families kernels.hip is made of, in the order it includes them: part of kernels.hip's and kernels_fast.hip's objects
+# only, so an edit of one rebuilds those two translation units (and the stamped one), not all of them as a header's would.
+KERNEL_PIECES = ["kernels_store.inl", "kernels_skin_math.inl", "kernels_morph_walk.inl", "kernels_setup.inl", "kernels_bounds.inl",
+                 "kernels_deform.inl", "kernels_pack.inl", "kernels_frame.inl", "kernels_morph_pass.inl", "kernels_morph_track.inl",
+                 "kernels_bench.inl", "kernels_bounds_reduce.inl"]
+INCLUDES = {"kernels.hip": KERNEL_PIECES, "kernels_fast.hip": ["kernels.hip"] + KERNEL_PIECES}      # what a source #includes beside the headers
+
+
+def hashed_files() -> list[str]:
+    """Every file the library is built from, once each: what source_sha() hashes (tests/test_build_lists.py holds csrc/ against it)."""
+    out = SOURCES + HEADERS
+    for src in SOURCES:
+        out = out + [f for f in INCLUDES.get(src, []) if f not in out]
+    return out
+
+
+def object_inputs(src: str) -> list[str]:
+    """The files whose content keys the object of translation unit `src`, beside the headers, which key every object."""
+    return [src] + INCLUDES.get(src, [])
 
 
 def flags(stamp: bool = False) -> list[str]:
@@ -115,7 +133,7 @@ def _objects(verbose: bool) -> list[str]:
     for src in SOURCES:
         stamped = src == STAMPED
         h = common.copy()
-        for f in [src] + INCLUDES.get(src, []):
+        for f in object_inputs(src):
             h.update(open(os.path.join(CSRC, f), "rb").read())
         if stamped:
             h.update(source_sha().encode())
