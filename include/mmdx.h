@@ -82,7 +82,10 @@ extern "C" {
  *    mmdx_animator_root_motion_turn with mmdx_root_turn_args and MMDX_ROOT_NORMALIZE, and mmdx_bone_motion_in_place_turn (two new
  *    entry points, a structure and a flag bit no other call accepts; nothing existing changes).
  *    mmdx_socket_set_create / _destroy / _get_info and mmdx_palette_sockets with mmdx_socket_set_desc / _info, mmdx_sockets_args and
- *    MMDX_SOCKET_OFFSET_MATRIX (four new entry points, three structures and a flag of the new desc alone; nothing existing changes). */
+ *    MMDX_SOCKET_OFFSET_MATRIX (four new entry points, three structures and a flag of the new desc alone; nothing existing changes).
+ *    mmdx_spring_set_create / _destroy / _get_info, mmdx_spring_step and mmdx_spring_get_state / _set_state with
+ *    mmdx_spring_set_desc / _info, mmdx_spring_args, MMDX_SPRING_RESET and MMDX_SPRING_DT_ON_DEVICE (six new entry points, three
+ *    structures and two flag bits no other call accepts; nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -1354,6 +1357,130 @@ typedef struct mmdx_sockets_args {
  *    MMDX_CREATE_HOST_ONLY model is MMDX_ERR_NO_DEVICE (after validation).  Models created with MMDX_CREATE_FAST_MATH run the same,
  *    uncontracted kernel. */
 MMDX_API mmdx_status mmdx_palette_sockets(mmdx_socket_set_t set, const mmdx_sockets_args *args);
+
+/* ---- spring bones: hair, skirts and ribbons swing per instance, on the device ---------------------------------------------------
+ * Secondary motion for a crowd.  The reference moves such bones with Bullet on the host, once per Poser (the physics seam below
+ * reproduces that for one hero model); a crowd cannot step a Bullet world per character.  A spring set is CHAINS of bones that
+ * follow their parent with inertia, stiffness, drag, gravity and sphere colliders; mmdx_spring_step advances every chain of every
+ * (listed) instance by one step in ONE launch and rewrites the chains' palette rows IN PLACE.  There is no libmmd counterpart
+ * (Bullet is out of scope): the contract is the arithmetic below, in IEEE binary32 operations in the order written, unfused.
+ *
+ * The step works on palettes alone.  x . S (pt below) is where a rest-space point x carried by a bone with skinning row S stands
+ * now, so the step needs no local matrices and no solver state, runs after any solve form, reads the rows of anchor and collider
+ * bones and overwrites the rows of the chains' joints -- what Synchronize does at the physics seam.  Called AFTER mmdx_palette_place
+ * the simulation is in world space: walking and turning drag the hair and gravity is the world's.  Called BEFORE it the simulation
+ * is in model space.  The call cannot tell the difference and takes no flag for it.  mmdx_palette_bounds after it stays
+ * conservative, because it reads the rewritten rows.  The frame order is solve -> place -> springs -> palette bounds -> cull ->
+ * deform select.
+ *  - A joint ignores its own clip pose: its target is the rigid continuation of its parent (MMD physics bones carry no keys).
+ *  - Bones below a chain that are not joints keep their solved rows; post-physics bones hanging off a joint would need Fix and
+ *    rigid followers, which this call does not do.  Branching chains, capsule or plane colliders, per-instance wind and reading
+ *    PMX rigid-body blocks are out of scope as well.
+ *
+ * Notation.  pt(x, S)[c] = ((x0*S[c] + x1*S[4+c]) + x2*S[8+c]) + 1.0f*S[12+c], c = 0..2 (Matrix4x4 row-vector product, left to
+ * right).  len(d) = float(sqrt(double((d0*d0 + d1*d1) + d2*d2))).  finite(x) is x - x == 0.  Vector lines are per component.
+ * Per instance, chains are independent; within a chain the joints run in order, the root side first.  For the joint with bone b:
+ * h = rest position of b, t = its tail rest point, P = the parent's CURRENT row (the first joint: the row of the chain's anchor, its
+ * skeleton parent, read from the palette; later joints: the row just computed for the previous joint), c and p = the joint's current
+ * and previous tail (3 floats each, device state owned by the set, per instance).  The chain has stiffness, drag, gravity_scale,
+ * radius; the set a gravity vector g.  dt is one float for the call.
+ *   1. H = pt(h, P), T0 = pt(t, P), a = T0 - H, la = len(a).  If !(la > 0) or !finite(la): row = P (all 16 floats), c = p = T0, the
+ *      joint is done.
+ *   2. If MMDX_SPRING_RESET, or any component of c or p is not finite: c = p = T0 (state heals itself after a NaN frame; a new set's
+ *      state is NaN, so its first step is a reset).
+ *   3. If dt > 0: n = c + (c - p)*(1.0f - drag); n = n + (T0 - c)*(stiffness*dt); n = n + g*(gravity_scale*dt).  Else (0, negative,
+ *      NaN): n = c.
+ *   4. constrain(n): if n == T0 in all three components n stays as it is (T0 is at la from H by la's own definition, and
+ *      (a / la)*la need not round back to a); else d = n - H, l = len(d); if !(l > 0) or !finite(l): n = T0; else n = H + (d / l)*la.
+ *   5. For each collider j in order: C = pt(centre[j], S[collider_bone[j]]), rr = r[j] + radius, d = n - C, l = len(d); if l > 0 and
+ *      l < rr: n = C + (d / l)*rr, then constrain(n) again.
+ *   6. p = c, c = n.
+ *   7. If n == T0 in all three components: row = P, every bit (rigid following: a reset crowd equals its parents exactly).  Else
+ *      u = a / la, v = (n - H) / la, k = u x v = {u1*v2 - u2*v1, u2*v0 - u0*v2, u0*v1 - u1*v0}, cs = (u0*v0 + u1*v1) + u2*v2,
+ *      m = 1.0f + cs.  If !(m > 1e-6f) (antiparallel): row = P and c = p = T0.  Else, with q_ij = (k_i*k_j) / m,
+ *          R = { cs + q00,  q01 + k2,  q02 - k1,
+ *                q01 - k2,  cs + q11,  q12 + k0,
+ *                q02 + k1,  q12 - k0,  cs + q22 }          (u . R = v in the row-vector convention)
+ *      row[4i+j] = (P[4i]*R[0][j] + P[4i+1]*R[1][j]) + P[4i+2]*R[2][j] for i, j = 0..2; row[12+j] = H[j] - ((h0*row[j] + h1*row[4+j])
+ *      + h2*row[8+j]); row[3] = row[7] = row[11] = 0, row[15] = 1.
+ * The state of a joint is written in steps 1, 2, 6 and 7 and stored after step 7.  A float32 prototype of exactly this, its parent
+ * swaying for 3 000 steps with a collider: relative length error <= 6.0e-7, |R R^T - I| <= 1.4e-6, pt(t, row) within 1 ulp of c.
+ *
+ * mmdx_spring_set_create validates everything on the host and touches no device.  Rest positions and parents come from the
+ * skeleton.  The tail of a joint defaults to the next joint's rest position, that of a chain's last joint to h + (h - h of its
+ * skeleton parent).  A bone >= the skeleton's count (joint or collider) is MMDX_ERR_BAD_INDEX.  MMDX_ERR_INVALID_ARGUMENT: a joint
+ * whose skeleton parent is not the previous joint of its chain; a first joint without a parent; an anchor (the first joint's parent)
+ * or collider bone that is a joint of any chain (a read after a write between lanes); a bone listed twice; a chain of 0 or more than
+ * MMDX_SPRING_MAX_JOINTS joints; n_chains == 0 or above 65535; more than MMDX_SPRING_MAX_COLLIDERS colliders; NaN in chain_params,
+ * gravity, joint_tail or collider_sphere; drag outside [0, 1]; max_instances == 0; NULL arrays; reserved0 != 0; a struct_size
+ * mismatch. */
+typedef struct mmdx_spring_set_s *mmdx_spring_set_t;
+#define MMDX_SPRING_MAX_JOINTS 32
+#define MMDX_SPRING_MAX_COLLIDERS 16
+enum {
+    MMDX_SPRING_RESET = (1u << 16),          /* mmdx_spring_step: step 2 resets every joint it steps                                */
+    MMDX_SPRING_DT_ON_DEVICE = (1u << 17)    /* mmdx_spring_step: dt is a device pointer, read when the kernel RUNS                 */
+};
+typedef struct mmdx_spring_set_desc {
+    uint32_t struct_size;            /* = sizeof(mmdx_spring_set_desc)                                                            */
+    uint32_t n_chains;               /* >= 1                                                                                      */
+    uint32_t n_colliders;            /* 0 .. MMDX_SPRING_MAX_COLLIDERS                                                            */
+    uint32_t max_instances;          /* the state holds this many instances; >= 1                                                 */
+    const uint32_t *chain_offset;    /* [n_chains + 1], chain c = joints [chain_offset[c], chain_offset[c + 1]); [0] == 0          */
+    const uint32_t *joint_bone;      /* [n_joints], n_joints = chain_offset[n_chains], chain after chain, the root side first      */
+    const float *joint_tail;         /* NULL = the defaults; else [n_joints][3] rest-space tail points                             */
+    const float *chain_params;       /* [n_chains][4] stiffness, drag, gravity scale, radius                                       */
+    const uint32_t *collider_bone;   /* [n_colliders]                                                                             */
+    const float *collider_sphere;    /* [n_colliders][4] rest-space centre xyz, radius                                            */
+    float gravity[3];
+    uint32_t reserved0;              /* must be 0                                                                                 */
+} mmdx_spring_set_desc;
+typedef struct mmdx_spring_set_info {
+    uint32_t struct_size;            /* = sizeof(mmdx_spring_set_info), set by the caller                                         */
+    uint32_t n_chains, n_joints, n_colliders, max_instances;
+    uint32_t n_bones;                /* the skeleton's bone count: palettes are [NI][n_bones][16]                                 */
+    int32_t device_ordinal;          /* where the table and the state live; -1 = nowhere yet (the first step decides)             */
+    uint32_t reserved0;
+} mmdx_spring_set_info;
+MMDX_API mmdx_status mmdx_spring_set_create(mmdx_skeleton_t skeleton, const mmdx_spring_set_desc *desc, mmdx_spring_set_t *out_set);
+MMDX_API void mmdx_spring_set_destroy(mmdx_spring_set_t set);
+MMDX_API mmdx_status mmdx_spring_set_get_info(mmdx_spring_set_t set, mmdx_spring_set_info *info);
+
+typedef struct mmdx_spring_args {
+    uint32_t struct_size;            /* = sizeof(mmdx_spring_args)                                                                */
+    uint32_t flags;                  /* MMDX_PALETTE_ON_DEVICE (required) | MMDX_SPRING_RESET | MMDX_SPRING_DT_ON_DEVICE            */
+    uint32_t n_instances;            /* NI <= the set's max_instances                                                             */
+    uint32_t reserved0;              /* must be 0                                                                                 */
+    float *palettes;                 /* DEVICE [NI][NB][16], 16-byte aligned, rewritten in place                                  */
+    const float *dt;                 /* one float: host memory, or device memory (4-byte aligned) with MMDX_SPRING_DT_ON_DEVICE    */
+    const mmdx_instance_select *select;   /* NULL = every instance                                                               */
+} mmdx_spring_args;
+/* One step of every chain of every instance (of the listed instances) on `model`'s stream (NULL: the selected device's default
+ * stream), as the rig calls take their model.
+ *   1. Only joint rows are written, of the listed instances, or of all instances without a list; every other byte of palettes
+ *      stays as it is.
+ *   2. The state of unlisted instances is untouched.  State belongs to the INSTANCE (ids[k]), not to the list position.
+ *   3. select follows mmdx_instance_select as mmdx_deform_batched_select states it: the first min(*count, n_ids) ids are used (count
+ *      NULL: n_ids); a device id >= n_instances is skipped; a host id >= n_instances is MMDX_ERR_INVALID_ARGUMENT before anything is
+ *      launched.  A host list is copied through scratch of the set and the call returns when the work is done.
+ *   4. The ids of one call must be distinct: an instance listed twice would be stepped by two lanes at once (undefined state, no
+ *      access outside the arrays).
+ *   5. The call is asynchronous on the model's stream (a borrowed one, mmdx_model_set_stream, included), in order with that model's
+ *      solve, place, bounds and deform calls.  A host dt is passed by value when the call is made.
+ *   6. It records into mmdx_graph_begin / _end of `model` with a device dt and a device list (or none); a host dt or a host list is
+ *      MMDX_ERR_INVALID_ARGUMENT while recording, and so is a set that has not run on that device before (its table and state are
+ *      uploaded by the first call).  A recorded call reads dt and the list afresh at every replay.
+ *   7. The set is pinned by the graphs it took part in: destroying it invalidates them, as for every other handle.
+ *   8. Unknown flag bits, a missing MMDX_PALETTE_ON_DEVICE, reserved0 != 0, NULL set / args / palettes / dt, misaligned device
+ *      pointers, n_instances > max_instances and a struct_size mismatch are MMDX_ERR_INVALID_ARGUMENT; a host NaN dt is legal (step
+ *      3: nothing integrates).  More than 2^24 instances or list positions in one call is MMDX_ERR_UNSUPPORTED.  n_instances == 0 is
+ *      MMDX_OK and launches nothing. */
+MMDX_API mmdx_status mmdx_spring_step(mmdx_spring_set_t set, mmdx_model_t model, const mmdx_spring_args *args);
+/* The state of the first n_instances instances, host arrays [n_instances][n_joints][6] = {c xyz, p xyz}, in stream order behind the
+ * work queued on `model`'s stream; both return when the copy is done.  For tests and save / restore.  Before the first step (or
+ * set_state) on a device, get_state answers NaN everywhere.  Refused while a graph is being recorded. */
+MMDX_API mmdx_status mmdx_spring_get_state(mmdx_spring_set_t set, mmdx_model_t model, uint32_t n_instances, float *out_state);
+MMDX_API mmdx_status mmdx_spring_set_state(mmdx_spring_set_t set, mmdx_model_t model, uint32_t n_instances, const float *state);
 
 /* ---- a box per instance BEFORE the deform: bone boxes x palette ---------------------------------------------------------------
  * mmdx_deform_batched_bounds gives the box of the vertices it wrote, so a cull that uses it tests last frame's box, and an instance

@@ -159,6 +159,29 @@ class EventsArgs(C.Structure):
                 ("levels", C.c_void_p), ("out_ids", C.c_void_p), ("out_counts", C.c_void_p)]
 
 
+SPRING_RESET, SPRING_DT_ON_DEVICE = 1 << 16, 1 << 17     # MMDX_SPRING_*: mmdx_spring_args.flags (with PALETTE_ON_DEVICE, required)
+SPRING_MAX_JOINTS, SPRING_MAX_COLLIDERS = 32, 16          # MMDX_SPRING_MAX_*
+
+
+class SpringSetDesc(C.Structure):
+    """mmdx_spring_set_desc: chains of bones, their parameters, the colliders and gravity of a spring set (mmdx_spring_set_create)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_chains", C.c_uint32), ("n_colliders", C.c_uint32), ("max_instances", C.c_uint32),
+                ("chain_offset", C.c_void_p), ("joint_bone", C.c_void_p), ("joint_tail", C.c_void_p), ("chain_params", C.c_void_p),
+                ("collider_bone", C.c_void_p), ("collider_sphere", C.c_void_p), ("gravity", C.c_float * 3), ("reserved0", C.c_uint32)]
+
+
+class SpringSetInfo(C.Structure):
+    """mmdx_spring_set_info (mmdx_spring_set_get_info)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_chains", C.c_uint32), ("n_joints", C.c_uint32), ("n_colliders", C.c_uint32),
+                ("max_instances", C.c_uint32), ("n_bones", C.c_uint32), ("device_ordinal", C.c_int32), ("reserved0", C.c_uint32)]
+
+
+class SpringArgs(C.Structure):
+    """mmdx_spring_args: device palettes rewritten in place, the step and the instance list of mmdx_spring_step."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("reserved0", C.c_uint32),
+                ("palettes", C.c_void_p), ("dt", C.c_void_p), ("select", C.POINTER(InstanceSelect))]
+
+
 class BoneMotionKeys(C.Structure):
     """mmdx_bone_motion_keys: the host key tables of a bound bone motion (mmdx_bone_motion_get_keys)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_bones", C.c_uint32), ("n_keys", C.c_uint32), ("n_curves", C.c_uint32),
@@ -350,6 +373,13 @@ SIGNATURES = {
     "mmdx_event_set_destroy": (None, [C.c_void_p]),
     "mmdx_event_set_get_info": (C.c_int32, [C.c_void_p, C.POINTER(EventSetInfo)]),
     "mmdx_animator_events": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EventsArgs)]),
+    # spring bones: (skeleton, desc, out_set); (set); (set, info*); (set, model, mmdx_spring_args*); (set, model, n, state) x 2
+    "mmdx_spring_set_create": (C.c_int32, [C.c_void_p, C.POINTER(SpringSetDesc), C.POINTER(C.c_void_p)]),
+    "mmdx_spring_set_destroy": (None, [C.c_void_p]),
+    "mmdx_spring_set_get_info": (C.c_int32, [C.c_void_p, C.POINTER(SpringSetInfo)]),
+    "mmdx_spring_step": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(SpringArgs)]),
+    "mmdx_spring_get_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mmdx_spring_set_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "mmdx_bone_motion_get_keys": (C.c_int32, [C.c_void_p, C.POINTER(BoneMotionKeys)]),
     "mmdx_skeleton_solve_morphed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),

@@ -42,6 +42,14 @@ struct SetBoneSide {
 SetBoneSide motion_set_bone_side(const mmdx_motion_set_s *set);
 // ... and its bone tables on `device` as a parameter block (clock and output fields empty), the set noted in `model`'s recording
 mmdx_status motion_set_bone_tables(mmdx_motion_set_s *set, mmdx_model_t model, int device, BoneTrackParams *p);
+// rig_api.cpp, the owner of the skeleton handle, for mmdx_spring_set_create (spring_api.cpp): what a spring set copies of a
+// skeleton at creation, without the device
+struct SkeletonRest {
+    uint32_t nb;
+    const int32_t *parent;                      // [nb] as mmdx_skeleton_desc.parent gave it; the skeleton's own
+    const float *neg_rest;                      // [nb][4] -rest position
+};
+SkeletonRest skeleton_rest(const mmdx_skeleton_s *s);
 // socket_api.cpp, the owner of the socket-set handle, for mmdx_model_destroy: the sets created on `m` refuse every call from here on
 void socket_sets_forget_model(mmdx_model_s *m);
 

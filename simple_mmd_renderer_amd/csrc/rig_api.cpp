@@ -125,6 +125,8 @@ struct mmdx_motion_set_s {
     }
 };
 
+SkeletonRest mmdx::skeleton_rest(const mmdx_skeleton_s *s) { return {s->plan.nb, s->plan.parent.data(), s->plan.neg_rest.data()}; }
+
 const std::vector<uint32_t> &mmdx::motion_set_clip_frames(const mmdx_motion_set_s *set) { return set->clip_frames; }
 
 // ---- static tables of a motion / a skeleton / a set -> the device they are about to run on (once per device) --------------------

@@ -627,6 +627,127 @@ class SocketSet:
         self.close()
 
 
+def chains_below(skeleton, roots) -> list:
+    """Walk the hierarchy below each bone of `roots` into chains for SpringSet: a chain starts at a root and follows single-child
+    runs (a bone with exactly one child continues, any other count ends the chain), cut at 32 joints.  skeleton: anything with
+    .parent (i32 [NB], -1 = none), e.g. a vmd.Skeleton.  -> a list of lists of bone indices, one per root, the root side first."""
+    parent = np.asarray(skeleton.parent, np.int64).reshape(-1)
+    children = {}
+    for b, p in enumerate(parent.tolist()):
+        children.setdefault(p, []).append(b)
+    out = []
+    for r in roots:
+        chain = [int(r)]
+        while len(children.get(chain[-1], [])) == 1 and len(chain) < api.SPRING_MAX_JOINTS:
+            chain.append(children[chain[-1]][0])
+        out.append(chain)
+    return out
+
+
+class SpringSet:
+    """mmdx_spring_set_t: chains of bones of a skeleton that swing behind their parents (hair, skirts, ribbons), per crowd instance,
+    on the device.  step() advances every chain of every (listed) instance by dt in one launch and rewrites the chains' rows of a
+    device palette array [NI][NB][16] in place: after DeformModel.place_palettes the simulation is in world space, before it in
+    model space.  include/mmdx.h states the arithmetic.
+
+    chains: lists of bone indices, the root side first, each bone the skeleton child of the one before it; the first bone's parent
+    is the chain's anchor.  params: [n_chains,4] stiffness, drag, gravity scale, radius (or one row for all).  colliders: (bones
+    [NC], spheres [NC,4] rest-space centre xyz + radius).  tails: None (the defaults) or [n_joints,3]."""
+
+    def __init__(self, skeleton, chains, params, max_instances: int, gravity=(0.0, -9.8, 0.0), colliders=None, tails=None):
+        chains = [np.ascontiguousarray(c, np.uint32).reshape(-1) for c in chains]
+        off = np.zeros(len(chains) + 1, np.uint32)
+        off[1:] = np.cumsum([c.size for c in chains])
+        bones = np.ascontiguousarray(np.concatenate(chains) if chains else np.zeros(0), np.uint32)
+        prm = np.ascontiguousarray(np.broadcast_to(_c(params, np.float32).reshape(-1, 4), (len(chains), 4)), np.float32)
+        d = api.SpringSetDesc()
+        d.struct_size = C.sizeof(api.SpringSetDesc)
+        d.n_chains, d.max_instances = len(chains), max_instances
+        d.chain_offset, d.joint_bone, d.chain_params = off.ctypes.data, bones.ctypes.data, prm.ctypes.data
+        d.gravity[:] = [float(g) for g in gravity]
+        keep = [off, bones, prm]
+        if tails is not None:
+            t = _c(tails, np.float32).reshape(bones.size, 3)
+            d.joint_tail = t.ctypes.data
+            keep.append(t)
+        if colliders is not None and len(colliders[0]):
+            cb = np.ascontiguousarray(colliders[0], np.uint32).reshape(-1)
+            cs = _c(colliders[1], np.float32).reshape(cb.size, 4)
+            d.n_colliders, d.collider_bone, d.collider_sphere = cb.size, cb.ctypes.data, cs.ctypes.data
+            keep += [cb, cs]
+        self.h = C.c_void_p()
+        api.check(api.lib().mmdx_spring_set_create(skeleton.h, C.byref(d), C.byref(self.h)))      # copies the arrays
+        i = self.info()
+        self.n_joints, self.nb, self.max_instances = i["n_joints"], i["n_bones"], i["max_instances"]
+
+    @classmethod
+    def from_skeleton(cls, skeleton, roots, params, max_instances: int, **kw) -> "SpringSet":
+        """Chains found by chains_below(skeleton, roots)."""
+        return cls(skeleton, chains_below(skeleton, roots), params, max_instances, **kw)
+
+    def info(self) -> dict:
+        i = api.SpringSetInfo(C.sizeof(api.SpringSetInfo))
+        api.check(api.lib().mmdx_spring_set_get_info(self.h, C.byref(i)))
+        return {k: int(getattr(i, k)) for k, _ in api.SpringSetInfo._fields_ if k not in ("struct_size", "reserved0")}
+
+    def step_raw(self, n_instances: int, palettes_ptr, dt_ptr, flags: int, select=None, model=None) -> None:
+        """mmdx_spring_step, the raw form: dt_ptr is the address of one float, host memory unless flags has SPRING_DT_ON_DEVICE."""
+        a = api.SpringArgs()
+        a.struct_size = C.sizeof(api.SpringArgs)
+        a.flags, a.n_instances = flags, n_instances
+        a.palettes, a.dt = palettes_ptr, dt_ptr
+        if select is not None:
+            a.select = C.pointer(select)
+        api.check(api.lib().mmdx_spring_step(self.h, model.h if model is not None else None, C.byref(a)))
+
+    def step(self, palettes_dev, dt=None, dt_ptr=None, n_instances=None, select=None, model=None, reset: bool = False) -> None:
+        """One step on device palettes (a DeviceBuffer or a raw address), in place, asynchronous on the model's stream and recordable
+        with dt_ptr (a device float) and a device list.  dt: a host float; exactly one of dt / dt_ptr."""
+        if (dt is None) == (dt_ptr is None):
+            raise ValueError("exactly one of dt and dt_ptr")
+        if n_instances is None:
+            n_instances = palettes_dev.nbytes // (self.nb * 64)
+        flags = api.PALETTE_ON_DEVICE | (api.SPRING_RESET if reset else 0)
+        host = C.c_float(dt if dt is not None else 0.0)
+        if dt_ptr is not None:
+            flags |= api.SPRING_DT_ON_DEVICE
+        self.step_raw(n_instances, getattr(palettes_dev, "ptr", palettes_dev), dt_ptr if dt_ptr is not None else C.addressof(host), flags,
+                      select, model)
+
+    def reset(self, palettes_dev, n_instances=None, select=None, model=None) -> None:
+        """Every joint of the (listed) instances back to the rigid continuation of its parent: a step with MMDX_SPRING_RESET, dt = 0."""
+        self.step(palettes_dev, dt=0.0, n_instances=n_instances, select=select, model=model, reset=True)
+
+    def state(self, n_instances=None, model=None) -> np.ndarray:
+        """mmdx_spring_get_state: f32 [n_instances, n_joints, 6] = current tail xyz, previous tail xyz (NaN before the first step)."""
+        n = self.max_instances if n_instances is None else n_instances
+        out = np.empty((n, self.n_joints, 6), np.float32)
+        api.check(api.lib().mmdx_spring_get_state(self.h, model.h if model is not None else None, n, out.ctypes.data))
+        return out
+
+    def set_state(self, state, model=None) -> None:
+        """mmdx_spring_set_state: f32 [n, n_joints, 6] for the first n instances."""
+        s = _c(state, np.float32).reshape(-1, self.n_joints, 6)
+        api.check(api.lib().mmdx_spring_set_state(self.h, model.h if model is not None else None, s.shape[0], s.ctypes.data))
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            api.lib().mmdx_spring_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class PoseImage:
     def __init__(self, nv: int):
         self.coordinates = np.zeros((nv, 3), np.float32)

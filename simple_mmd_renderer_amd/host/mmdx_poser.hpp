@@ -781,4 +781,51 @@ private:
     mmdx_socket_set_t set_ = nullptr;
 };
 
+// Spring bones (mmdx.h, mmdx_spring_step): chains of bones that swing behind their parents -- hair, skirts, ribbons -- for every
+// instance of a crowd, on the device.  The reference moves such bones with Bullet, once per Poser; this is the crowd's substitute,
+// not a port of it.  A set is created on a skeleton handle from a filled mmdx_spring_set_desc (the arrays are copied); Step rewrites
+// the chains' rows of device palettes [n][bones][16] in place, after PlacePalettes for a simulation in world space, before it for
+// one in model space.
+class SpringSet {
+public:
+    SpringSet(mmdx_skeleton_t skeleton, mmdx_spring_set_desc desc) {
+        desc.struct_size = sizeof(desc);
+        check(mmdx_spring_set_create(skeleton, &desc, &set_));
+    }
+    ~SpringSet() { mmdx_spring_set_destroy(set_); }
+    SpringSet(const SpringSet &) = delete;
+    SpringSet &operator=(const SpringSet &) = delete;
+
+    // One step of every chain of every instance (select: of the listed ones), asynchronous on `model`'s stream.  dt: one float, host
+    // memory, or device memory with dt_on_device (what a recorded frame takes, together with a device list or none).
+    void Step(mmdx_model_t model, uint32_t n_instances, float *device_palettes, const float *dt, bool dt_on_device = false,
+              const mmdx_instance_select *select = nullptr, bool reset = false) {
+        mmdx_spring_args a{};
+        a.struct_size = sizeof(a);
+        a.flags = uint32_t(MMDX_PALETTE_ON_DEVICE) | (dt_on_device ? uint32_t(MMDX_SPRING_DT_ON_DEVICE) : 0u) |
+                  (reset ? uint32_t(MMDX_SPRING_RESET) : 0u);
+        a.n_instances = n_instances;
+        a.palettes = device_palettes; a.dt = dt; a.select = select;
+        check(mmdx_spring_step(set_, model, &a));
+    }
+    // every joint back to the rigid continuation of its parent
+    void Reset(mmdx_model_t model, uint32_t n_instances, float *device_palettes, const mmdx_instance_select *select = nullptr) {
+        const float zero = 0.0f;
+        Step(model, n_instances, device_palettes, &zero, false, select, true);
+    }
+    // [n_instances][joints][6] = {current tail, previous tail}: save and restore
+    void GetState(mmdx_model_t model, uint32_t n_instances, float *out) { check(mmdx_spring_get_state(set_, model, n_instances, out)); }
+    void SetState(mmdx_model_t model, uint32_t n_instances, const float *in) { check(mmdx_spring_set_state(set_, model, n_instances, in)); }
+    mmdx_spring_set_info Info() const {
+        mmdx_spring_set_info i{};
+        i.struct_size = sizeof(i);
+        check(mmdx_spring_set_get_info(set_, &i));
+        return i;
+    }
+    mmdx_spring_set_t handle() const { return set_; }
+
+private:
+    mmdx_spring_set_t set_ = nullptr;
+};
+
 }  // namespace mmdx

@@ -864,6 +864,7 @@ class Skeleton:
                          *[ptr(a) for a in mk])
         self._keep = keep + mk
         self.rest_position = rest                # f32 [NB, 3]: what engine.SocketSet.from_skeleton builds its desc from
+        self.parent = keep[1]                    # i32 [NB]: what engine.chains_below walks
         self.nm = nm
         self.h = C.c_void_p()
         api.check(api.lib().mmdx_skeleton_create(C.byref(d), C.byref(self.h)))
