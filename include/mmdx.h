@@ -85,7 +85,10 @@ extern "C" {
  *    MMDX_SOCKET_OFFSET_MATRIX (four new entry points, three structures and a flag of the new desc alone; nothing existing changes).
  *    mmdx_spring_set_create / _destroy / _get_info, mmdx_spring_step and mmdx_spring_get_state / _set_state with
  *    mmdx_spring_set_desc / _info, mmdx_spring_args, MMDX_SPRING_RESET and MMDX_SPRING_DT_ON_DEVICE (six new entry points, three
- *    structures and two flag bits no other call accepts; nothing existing changes). */
+ *    structures and two flag bits no other call accepts; nothing existing changes).
+ *    mmdx_aim_set_create / _destroy / _get_info and mmdx_palette_aim with mmdx_aim_set_desc / _info, mmdx_aim_args and
+ *    MMDX_AIM_TARGETS_ON_DEVICE (four new entry points, three structures and a flag bit no other call accepts; nothing existing
+ *    changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -1481,6 +1484,123 @@ MMDX_API mmdx_status mmdx_spring_step(mmdx_spring_set_t set, mmdx_model_t model,
  * set_state) on a device, get_state answers NaN everywhere.  Refused while a graph is being recorded. */
 MMDX_API mmdx_status mmdx_spring_get_state(mmdx_spring_set_t set, mmdx_model_t model, uint32_t n_instances, float *out_state);
 MMDX_API mmdx_status mmdx_spring_set_state(mmdx_spring_set_t set, mmdx_model_t model, uint32_t n_instances, const float *state);
+
+/* ---- look-at: heads and eyes of a crowd turn to device-side targets --------------------------------------------------------------
+ * An aim set turns chosen bones of every (listed) instance towards a per-instance target, on finished palettes, in place, in ONE
+ * launch.  A target is four floats, a point and a weight; a slab of mmdx_palette_sockets ("where the hero's head is, per instance")
+ * or a placement array goes in as it is.  There is no libmmd counterpart (the reference has no look-at): the contract is the
+ * arithmetic below, in IEEE binary32 operations in the order written, unfused, as for the springs.
+ *
+ * Rotating a bone of a finished palette about its current pivot is a right-multiplication of its row by a rigid matrix M, and the
+ * same right-multiplication for every skeleton descendant: the call "places" every row of a subtree by a per-instance matrix, as
+ * mmdx_palette_place(MMDX_PLACE_MATRIX) places a whole palette.  The frame order is solve -> place -> aim -> springs -> palette
+ * bounds -> cull -> deform select: aim runs BEFORE the springs, because hair chains anchor on the head row that aim rewrites; after
+ * mmdx_palette_place the targets are world points, before it model-space points.
+ *  - The hierarchy is the skeleton's parent array ONLY.  Append and IK relations are not followed: an aim on the spine moves
+ *    IK-placed hands with it, which is the caller's choice.
+ *  - The aim is by the eye: it is exact only when the eye lies on the pivot of the link; each later link reduces the remainder.
+ *  - Damping and turn-rate limits (which need state), up vectors and roll control, and following append relations are out of scope.
+ *    The weight in tgt[3] is how a caller fades a look in and out.
+ *
+ * An aim is L = 1 .. MMDX_AIM_MAX_LINKS link bones b_0 .. b_{L-1}, the root side first, each a strict skeleton ancestor of the next
+ * (not necessarily its parent: upper body 2, neck, head); an eye bone be, which is b_{L-1} or a descendant of it; a rest-space eye
+ * point e and a rest-space forward vector f, both carried by be; and per link a share in [0, 1] and a cos_limit in [-1, 1], the
+ * cosine of the largest turn the link may add to its animated pose (a cosine, so that no host cos enters the contract).  The call
+ * rewrites the rows of every bone in the subtree of b_0.
+ *
+ * Notation.  pt, len and finite as in the spring section; dir(x, S)[c] = (x0*S[c] + x1*S[4+c]) + x2*S[8+c]; mul(A, B) is
+ * Matrix4x4::operator*, row r of the result = the row product of mmdx_palette_place over A's row r and B, all 16 elements, no short
+ * circuit.  Vector lines are per component.  Per instance i and aim:
+ *   0. tgt = the 4 floats at targets + i*target_stride (at targets when the stride is 0); g = tgt[0..2], w = tgt[3].  If !(w > 0) or
+ *      any of the four is not finite: nothing of this instance is written for this aim, every byte stays.  Else w = min(w, 1.0f).
+ *      The cumulative matrix C is unset.
+ *   1. For each link l = 0 .. L-1: P = the row of b_l, Q = the row of be, as read from the palette; if C is set, P = mul(P, C) and
+ *      Q = mul(Q, C).  H = pt(h_l, P) with h_l the rest position of b_l; E = pt(e, Q); a = dir(f, Q), la = len(a); d = g - E,
+ *      ld = len(d).  The link is SKIPPED (C unchanged) if !(la > 0), !(ld > 0), or either is not finite.  u = a / la, v = d / ld; if
+ *      u == v in all three components: skipped.  t = share_l*w.  If t >= 1.0f: v2 = v.  Else n = u + (v - u)*t, ln = len(n); if
+ *      !(ln > 0): skipped; else v2 = n / ln.
+ *      Limit.  cs = (u0*v2_0 + u1*v2_1) + u2*v2_2.  If cs < cos_limit_l: p = v2 - u*cs, lp = len(p); if !(lp > 0): skipped; else
+ *      v2 = u*cos_limit_l + (p / lp)*sin_limit_l, with sin_limit_l = float(sqrt(double(1.0f - cos_limit_l*cos_limit_l))) from the
+ *      set's table, and cs is computed again from the new v2 by the same line.
+ *      Rotation.  R = the shortest rotation u -> v2 by the formula of spring step 7: k = u x v2, m = 1.0f + cs, q_ij = (k_i*k_j) / m;
+ *      if !(m > 1e-6f) (antiparallel): skipped.
+ *      Link matrix.  Rows 1-3 of M_l are {R[r][0], R[r][1], R[r][2], 0}, row 4 is {T0, T1, T2, 1} with
+ *      T_j = H_j - ((H0*R[0][j] + H1*R[1][j]) + H2*R[2][j]).  C = M_l if C was unset, else C = mul(C, M_l) with its fourth column set
+ *      to {0, 0, 0, 1} afterwards (which the product gives by itself unless C holds a non-finite value: the fourth column of C is a
+ *      constant).  C_l = C.  A skipped link has C_l = C_{l-1}; C_l is unset while no link has been applied.
+ *   2. Every bone s of the subtree has a depth k(s) = the deepest link that is s or an ancestor of s.  If C_{k(s)} is set:
+ *      row'(s) = mul(row(s), C_{k(s)}); else the row is not written.  All reads of step 1 see the rows as they were before the call.
+ * Sign and payload of a NaN are not part of the contract.  A float32 prototype of exactly this, evaluated in float64, over the case
+ * table of the tests and 3 000 steps of a target circling a swaying 41-bone rig: with L = 1, share 1, limit -1 and e = h the new
+ * forward direction is within 4.4e-7 of v per component; |R R^T - I| <= 3.7e-6 / m (u and v2 are unit vectors to a rounding error,
+ * which the formula divides by m, as spring step 7 does); |pt(h_l, row'(b_l)) - H| <= 4.2e-7 * max(1, |H|).
+ *
+ * mmdx_aim_set_create validates everything on the host and touches no device.  Rest positions and parents come from the skeleton.
+ * A bone >= the skeleton's count (link or eye) is MMDX_ERR_BAD_INDEX.  MMDX_ERR_INVALID_ARGUMENT: a link that is not a strict
+ * descendant of the link before it; an eye bone outside the subtree of the last link; an aim of 0 or more than MMDX_AIM_MAX_LINKS
+ * links; n_aims == 0 or above MMDX_AIM_MAX_AIMS; a share outside [0, 1]; a cos_limit outside [-1, 1]; NaN anywhere; a zero or
+ * non-finite forward; subtrees of two aims that intersect (one workgroup owns a subtree: eyes under an aimed head are a second set
+ * and a second call); NULL arrays; reserved0 != 0; a struct_size mismatch.  A skeleton of more than 2^20 bones is
+ * MMDX_ERR_UNSUPPORTED. */
+typedef struct mmdx_aim_set_s *mmdx_aim_set_t;
+#define MMDX_AIM_MAX_AIMS 16
+#define MMDX_AIM_MAX_LINKS 4
+enum { MMDX_AIM_TARGETS_ON_DEVICE = (1u << 18) };   /* mmdx_palette_aim: targets is a device pointer, read when the kernel RUNS    */
+typedef struct mmdx_aim_set_desc {
+    uint32_t struct_size;            /* = sizeof(mmdx_aim_set_desc)                                                               */
+    uint32_t n_aims;                 /* 1 .. MMDX_AIM_MAX_AIMS                                                                    */
+    const uint32_t *link_offset;     /* [n_aims + 1], aim a = links [link_offset[a], link_offset[a + 1]); [0] == 0                 */
+    const uint32_t *link_bone;       /* [n_links], n_links = link_offset[n_aims], aim after aim, the root side first               */
+    const float *link_params;        /* [n_links][2] share, cos_limit                                                             */
+    const uint32_t *eye_bone;        /* [n_aims]                                                                                  */
+    const float *eye_point;          /* [n_aims][3] rest-space                                                                    */
+    const float *forward;            /* [n_aims][3] rest-space, any length but zero                                               */
+    uint32_t reserved0;              /* must be 0                                                                                 */
+} mmdx_aim_set_desc;
+typedef struct mmdx_aim_set_info {
+    uint32_t struct_size;            /* = sizeof(mmdx_aim_set_info), set by the caller                                            */
+    uint32_t n_aims, n_links;
+    uint32_t n_subtree_rows;         /* palette rows one instance has rewritten when every aim applies                            */
+    uint32_t n_bones;                /* the skeleton's bone count: palettes are [NI][n_bones][16]                                 */
+    int32_t device_ordinal;          /* where the table lives; -1 = nowhere yet (the first call decides)                          */
+} mmdx_aim_set_info;
+MMDX_API mmdx_status mmdx_aim_set_create(mmdx_skeleton_t skeleton, const mmdx_aim_set_desc *desc, mmdx_aim_set_t *out_set);
+MMDX_API void mmdx_aim_set_destroy(mmdx_aim_set_t set);
+MMDX_API mmdx_status mmdx_aim_set_get_info(mmdx_aim_set_t set, mmdx_aim_set_info *info);
+
+typedef struct mmdx_aim_args {
+    uint32_t struct_size;            /* = sizeof(mmdx_aim_args)                                                                   */
+    uint32_t flags;                  /* MMDX_PALETTE_ON_DEVICE (required) | MMDX_AIM_TARGETS_ON_DEVICE                             */
+    uint32_t n_instances;            /* NI                                                                                        */
+    uint32_t target_stride;          /* in floats: 0 = one target for everyone, else a multiple of 4 (>= 4)                       */
+    float *palettes;                 /* DEVICE [NI][NB][16], 16-byte aligned, rewritten in place                                  */
+    const float *targets;            /* {x, y, z, weight} per instance: host memory, or device memory (16-byte aligned) with
+                                        MMDX_AIM_TARGETS_ON_DEVICE.  Stride 16 and targets = slab + 12: a slab of
+                                        mmdx_palette_sockets as it is, its v[15] = 1 the weight                                   */
+    const mmdx_instance_select *select;   /* NULL = every instance                                                               */
+} mmdx_aim_args;
+/* Every aim of every instance (of the listed instances) on `model`'s stream (NULL: the selected device's default stream), as the
+ * rig calls and mmdx_spring_step take their model.
+ *   1. Only rows of the aims' subtrees are written, of the listed instances, or of all instances without a list; every other byte of
+ *      palettes stays as it is.
+ *   2. select follows mmdx_instance_select as mmdx_deform_batched_select states it: the first min(*count, n_ids) ids are used (count
+ *      NULL: n_ids); a device id >= n_instances is skipped; a host id >= n_instances is MMDX_ERR_INVALID_ARGUMENT before anything is
+ *      launched.  A host list is copied through scratch of the set and the call returns when the work is done.  The target of a
+ *      listed instance is that of the INSTANCE (ids[k]), not of the list position.
+ *   3. The ids of one call must be distinct: an instance listed twice would be rewritten by two workgroups at once (undefined rows,
+ *      no access outside the arrays).
+ *   4. The call is asynchronous on the model's stream (a borrowed one, mmdx_model_set_stream, included), in order with that model's
+ *      solve, place, spring, bounds and deform calls.  Host targets are copied through scratch of the set and the call returns when
+ *      the work is done.
+ *   5. It records into mmdx_graph_begin / _end of `model` with device targets and a device list (or none); host targets or a host
+ *      list are MMDX_ERR_INVALID_ARGUMENT while recording, and so is a set that has not run on that device before (its table is
+ *      uploaded by the first call).  A recorded call reads targets and list afresh at every replay.
+ *   6. The set is pinned by the graphs it took part in: destroying it invalidates them, as for every other handle.
+ *   7. Unknown flag bits, a missing MMDX_PALETTE_ON_DEVICE, a target_stride that is neither 0 nor a multiple of 4, NULL set / args /
+ *      palettes / targets, misaligned device pointers and a struct_size mismatch are MMDX_ERR_INVALID_ARGUMENT.  More than 2^23
+ *      instances or list positions in one call is MMDX_ERR_UNSUPPORTED.  n_instances == 0 is MMDX_OK and launches nothing.
+ * MMDX_AIM_BLOCK=64 (read per call, for tests and A/B) makes a workgroup own 64 instances instead of 16. */
+MMDX_API mmdx_status mmdx_palette_aim(mmdx_aim_set_t set, mmdx_model_t model, const mmdx_aim_args *args);
 
 /* ---- a box per instance BEFORE the deform: bone boxes x palette ---------------------------------------------------------------
  * mmdx_deform_batched_bounds gives the box of the vertices it wrote, so a cull that uses it tests last frame's box, and an instance

@@ -44,9 +44,13 @@ typedef enum mmdx_debug_kernel {
     MMDX_DEBUG_KERNEL_DEFORM = 1,    /* the tile kernel (deform_kernel) */
     MMDX_DEBUG_KERNEL_PACK = 2,      /* MMDX_FUSED_PACK=1 */
     MMDX_DEBUG_KERNEL_FRAME = 3,     /* one frame of one model, latency-ordered */
-    MMDX_DEBUG_KERNEL_CULL = 4       /* mmdx_cull_bounds was the model's last planned call: threads = lanes per workgroup, group =
+    MMDX_DEBUG_KERNEL_CULL = 4,      /* mmdx_cull_bounds was the model's last planned call: threads = lanes per workgroup, group =
                                         instances per chunk, ngroups = chunks, select = the form (1: one workgroup walks the chunks,
                                         2: a count launch and a scatter launch, one workgroup per chunk); every other field 0 */
+    MMDX_DEBUG_KERNEL_AIM = 5        /* mmdx_palette_aim on this model's stream was its last planned call: threads = lanes per
+                                        workgroup, group = instances (list positions) per workgroup, 16, or 64 under
+                                        MMDX_AIM_BLOCK=64, ngroups = workgroups per aim, lds = bytes of dynamic LDS, select = 1 with a list;
+                                        every other field 0 */
 } mmdx_debug_kernel;
 typedef struct mmdx_debug_launch_shape {
     uint32_t struct_size;            /* sizeof(mmdx_debug_launch_shape), set by the caller */

@@ -182,6 +182,29 @@ class SpringArgs(C.Structure):
                 ("palettes", C.c_void_p), ("dt", C.c_void_p), ("select", C.POINTER(InstanceSelect))]
 
 
+AIM_TARGETS_ON_DEVICE = 1 << 18                           # MMDX_AIM_TARGETS_ON_DEVICE: mmdx_aim_args.flags (with PALETTE_ON_DEVICE, required)
+AIM_MAX_AIMS, AIM_MAX_LINKS = 16, 4                       # MMDX_AIM_MAX_*
+
+
+class AimSetDesc(C.Structure):
+    """mmdx_aim_set_desc: the link bones, their shares and limits, and the eye of every aim of an aim set (mmdx_aim_set_create)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_aims", C.c_uint32), ("link_offset", C.c_void_p), ("link_bone", C.c_void_p),
+                ("link_params", C.c_void_p), ("eye_bone", C.c_void_p), ("eye_point", C.c_void_p), ("forward", C.c_void_p),
+                ("reserved0", C.c_uint32)]
+
+
+class AimSetInfo(C.Structure):
+    """mmdx_aim_set_info (mmdx_aim_set_get_info)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_aims", C.c_uint32), ("n_links", C.c_uint32), ("n_subtree_rows", C.c_uint32),
+                ("n_bones", C.c_uint32), ("device_ordinal", C.c_int32)]
+
+
+class AimArgs(C.Structure):
+    """mmdx_aim_args: device palettes rewritten in place, the targets and the instance list of mmdx_palette_aim."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("target_stride", C.c_uint32),
+                ("palettes", C.c_void_p), ("targets", C.c_void_p), ("select", C.POINTER(InstanceSelect))]
+
+
 class BoneMotionKeys(C.Structure):
     """mmdx_bone_motion_keys: the host key tables of a bound bone motion (mmdx_bone_motion_get_keys)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_bones", C.c_uint32), ("n_keys", C.c_uint32), ("n_curves", C.c_uint32),
@@ -220,7 +243,7 @@ class DebugLaunchShape(C.Structure):
                 ("reserved0", C.c_uint32)]
 
 
-DEBUG_KERNELS = ("none", "deform", "pack", "frame", "cull")      # mmdx_debug_kernel
+DEBUG_KERNELS = ("none", "deform", "pack", "frame", "cull", "aim")      # mmdx_debug_kernel
 
 
 class DebugSolveShape(C.Structure):
@@ -380,6 +403,11 @@ SIGNATURES = {
     "mmdx_spring_step": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(SpringArgs)]),
     "mmdx_spring_get_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "mmdx_spring_set_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    # look-at: (skeleton, desc, out_set); (set); (set, info*); (set, model, mmdx_aim_args*)
+    "mmdx_aim_set_create": (C.c_int32, [C.c_void_p, C.POINTER(AimSetDesc), C.POINTER(C.c_void_p)]),
+    "mmdx_aim_set_destroy": (None, [C.c_void_p]),
+    "mmdx_aim_set_get_info": (C.c_int32, [C.c_void_p, C.POINTER(AimSetInfo)]),
+    "mmdx_palette_aim": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(AimArgs)]),
     "mmdx_bone_motion_get_keys": (C.c_int32, [C.c_void_p, C.POINTER(BoneMotionKeys)]),
     "mmdx_skeleton_solve_morphed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),

@@ -748,6 +748,92 @@ class SpringSet:
         self.close()
 
 
+class AimSet:
+    """mmdx_aim_set_t: look-at for a crowd.  aim() turns the link bones of every aim of every (listed) instance towards the
+    instance's target, in one launch, and rewrites the rows of the links' subtrees of a device palette array [NI][NB][16] in place:
+    after DeformModel.place_palettes the targets are world points, before it model-space points.  It runs before SpringSet.step (hair
+    anchors on the head row).  include/mmdx.h states the arithmetic.
+
+    aims: a list of dicts {links: bone indices, the root side first, each a strict skeleton ancestor of the next; eye_bone (default:
+    the last link); eye_point [3] rest-space (default: the eye bone's rest position); forward [3] rest-space (default (0, 0, -1));
+    shares: per link in [0, 1] (default 1); cos_limits: per link in [-1, 1] (default -1, no limit)}."""
+
+    def __init__(self, skeleton, aims):
+        links = [np.ascontiguousarray(a["links"], np.uint32).reshape(-1) for a in aims]
+        off = np.zeros(len(aims) + 1, np.uint32)
+        off[1:] = np.cumsum([k.size for k in links])
+        bones = np.ascontiguousarray(np.concatenate(links) if links else np.zeros(0), np.uint32)
+        prm = np.ones((bones.size, 2), np.float32)
+        prm[:, 1] = -1.0
+        eye = np.zeros(len(aims), np.uint32)
+        point, fwd = np.zeros((len(aims), 3), np.float32), np.zeros((len(aims), 3), np.float32)
+        for k, a in enumerate(aims):
+            lo, hi = int(off[k]), int(off[k + 1])
+            if "shares" in a:
+                prm[lo:hi, 0] = np.asarray(a["shares"], np.float32).reshape(-1)
+            if "cos_limits" in a:
+                prm[lo:hi, 1] = np.asarray(a["cos_limits"], np.float32).reshape(-1)
+            eye[k] = a.get("eye_bone", links[k][-1] if links[k].size else 0)
+            point[k] = a["eye_point"] if "eye_point" in a else np.asarray(skeleton.rest_position, np.float32).reshape(-1, 3)[eye[k]]
+            fwd[k] = a.get("forward", (0.0, 0.0, -1.0))
+        d = api.AimSetDesc()
+        d.struct_size = C.sizeof(api.AimSetDesc)
+        d.n_aims = len(aims)
+        d.link_offset, d.link_bone, d.link_params = off.ctypes.data, bones.ctypes.data, prm.ctypes.data
+        d.eye_bone, d.eye_point, d.forward = eye.ctypes.data, point.ctypes.data, fwd.ctypes.data
+        self.h = C.c_void_p()
+        api.check(api.lib().mmdx_aim_set_create(skeleton.h, C.byref(d), C.byref(self.h)))      # copies the arrays
+        self.nb = self.info()["n_bones"]
+
+    def info(self) -> dict:
+        i = api.AimSetInfo(C.sizeof(api.AimSetInfo))
+        api.check(api.lib().mmdx_aim_set_get_info(self.h, C.byref(i)))
+        return {k: int(getattr(i, k)) for k, _ in api.AimSetInfo._fields_ if k != "struct_size"}
+
+    def aim_raw(self, n_instances: int, palettes_ptr, targets_ptr, stride: int, flags: int, select=None, model=None) -> None:
+        """mmdx_palette_aim, the raw form: targets_ptr is host memory unless flags has AIM_TARGETS_ON_DEVICE."""
+        a = api.AimArgs()
+        a.struct_size = C.sizeof(api.AimArgs)
+        a.flags, a.n_instances, a.target_stride = flags, n_instances, stride
+        a.palettes, a.targets = palettes_ptr, targets_ptr
+        if select is not None:
+            a.select = C.pointer(select)
+        api.check(api.lib().mmdx_palette_aim(self.h, model.h if model is not None else None, C.byref(a)))
+
+    def aim(self, model, palettes_dev, targets, stride: int = 4, select=None, n_instances=None) -> None:
+        """Device palettes (a DeviceBuffer or a raw address) in place, asynchronous on the model's stream and recordable with device
+        targets and a device list.  targets: a DeviceBuffer or a raw device address ({x, y, z, weight} every `stride` floats; stride 0:
+        one target for everyone; stride 16 and the address of a mmdx_palette_sockets slab + 48 bytes: the slab's translations), or a
+        numpy array [NI,4] / [4] in host memory (copied, and the call returns when the work is done)."""
+        if n_instances is None:
+            n_instances = palettes_dev.nbytes // (self.nb * 64)
+        pal = getattr(palettes_dev, "ptr", palettes_dev)
+        if isinstance(targets, np.ndarray):
+            t = _c(targets, np.float32)
+            stride = 0 if t.size == 4 else t.size // max(n_instances, 1)
+            self.aim_raw(n_instances, pal, t.ctypes.data, stride, api.PALETTE_ON_DEVICE, select, model)
+        else:
+            self.aim_raw(n_instances, pal, getattr(targets, "ptr", targets), stride,
+                         api.PALETTE_ON_DEVICE | api.AIM_TARGETS_ON_DEVICE, select, model)
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            api.lib().mmdx_aim_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class PoseImage:
     def __init__(self, nv: int):
         self.coordinates = np.zeros((nv, 3), np.float32)
