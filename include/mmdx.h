@@ -88,7 +88,10 @@ extern "C" {
  *    structures and two flag bits no other call accepts; nothing existing changes).
  *    mmdx_aim_set_create / _destroy / _get_info and mmdx_palette_aim with mmdx_aim_set_desc / _info, mmdx_aim_args and
  *    MMDX_AIM_TARGETS_ON_DEVICE (four new entry points, three structures and a flag bit no other call accepts; nothing existing
- *    changes). */
+ *    changes).
+ *    mmdx_reach_set_create / _destroy / _get_info and mmdx_palette_reach with mmdx_reach_set_desc / _info, mmdx_reach_args,
+ *    MMDX_REACH_TARGETS_ON_DEVICE and MMDX_REACH_KEEP_END_ROTATION (four new entry points, three structures, a flag bit no other
+ *    call accepts and a flag of the new desc alone; nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -1601,6 +1604,128 @@ typedef struct mmdx_aim_args {
  *      instances or list positions in one call is MMDX_ERR_UNSUPPORTED.  n_instances == 0 is MMDX_OK and launches nothing.
  * MMDX_AIM_BLOCK=64 (read per call, for tests and A/B) makes a workgroup own 64 instances instead of 16. */
 MMDX_API mmdx_status mmdx_palette_aim(mmdx_aim_set_t set, mmdx_model_t model, const mmdx_aim_args *args);
+
+/* ---- reach: two-bone IK moves hands and feet of a crowd to device-side targets ---------------------------------------------------
+ * A reach set puts the tip of a two-bone limb (upper arm - forearm - hand, thigh - shin - foot) of every (listed) instance on a
+ * per-instance target, on finished palettes, in place, in ONE launch.  A target is four floats, a point and a weight, read as
+ * mmdx_palette_aim reads it: a slab of mmdx_palette_sockets ("where the prop's handle is, per instance") or a placement array goes in
+ * as it is.  The solve is analytic (the law of cosines); there is no libmmd counterpart, so the contract is the arithmetic below, in
+ * IEEE binary32 operations in the order written, unfused, lengths by float(sqrt(double(s))), no trigonometry, as for the springs and
+ * the aim.  The skeleton solver's CCD-IK is a different thing: its targets are bones of the clip in model space, inside the solve.
+ *
+ * The frame order is solve -> place -> aim -> reach -> springs -> palette bounds -> cull -> deform select: reach runs AFTER aim,
+ * because an aimed spine carries the arms, and BEFORE the springs, because sleeves and ribbons anchor on rows that reach rewrites.
+ *  - The hierarchy is the skeleton's parent array ONLY.  Append and IK relations are not followed.
+ *  - Joint angle limits and hinge axes, twist distribution, chains longer than two bones, damping (which needs state) and ground
+ *    queries are out of scope: the caller supplies the foot target, and the weight in tgt[3] fades a reach in and out.
+ *
+ * A reach names three bones: a (upper arm, thigh), b (elbow, knee), c (wrist, ankle), each a strict skeleton ancestor of the next
+ * (not necessarily its parent: MMD arms have twist bones in between); a rest-space tip point e carried by c; a rest-space pole
+ * vector carried by a, the bend direction of a straight limb; a max_extension in (0, 1], the share of its length the limb never
+ * stretches past; and flags.  The call rewrites the rows of every bone in the subtree of a.
+ *
+ * Notation.  pt, dir, len, mul and finite as in the aim section; dot(x, y) = (x0*y0 + x1*y1) + x2*y2; h_s the rest position of
+ * bone s.  rot(u, v, H), the shortest rotation from u to v about the pivot H, is aim step 1's "Rotation" and "Link matrix": if u == v
+ * in all three components the identity matrix exactly; else cs = dot(u, v), k = u x v, m = 1.0f + cs, FAILS if !(m > 1e-6f),
+ * q_ij = (k_i*k_j) / m, R = {{cs + q00, q01 + k2, q02 - k1}, {q01 - k2, cs + q11, q12 + k0}, {q02 + k1, q12 - k0, cs + q22}}, rows
+ * 1-3 {R[r][0], R[r][1], R[r][2], 0}, row 4 {T0, T1, T2, 1} with T_j = H_j - ((H0*R[0][j] + H1*R[1][j]) + H2*R[2][j]).  Vector lines
+ * are per component.  Per instance i and reach:
+ *   0. Target.  tgt = the 4 floats at targets + i*target_stride (at targets when the stride is 0); g = tgt[0..2], w = tgt[3].  If
+ *      !(w > 0) or any of the four is not finite: nothing of this instance is written, every byte stays.  Else w = min(w, 1.0f).
+ *   1. Points.  A = pt(h_a, row a), B = pt(h_b, row b), K = pt(h_c, row c), T = pt(e, row c).  With MMDX_REACH_KEEP_END_ROTATION the
+ *      solved point is the end bone's pivot: G = g - (T - K), then T = K; otherwise G = g.  Gw = G if w >= 1.0f, else
+ *      T + (G - T)*w.  l1 = len(B - A), l2 = len(T - B), dv = Gw - A, d = len(dv).  If any of l1, l2, d is not > 0 or not finite:
+ *      nothing is written.
+ *   2. Clamp.  s = l1 + l2, lmax = s*max_extension, lmin = fabs(l1 - l2) + (s - lmax).  If !(lmin <= lmax): nothing is written.
+ *      dc = d < lmin ? lmin : d, then dc = dc > lmax ? lmax : dc.  dh = dv / d, Gc = A + dh*dc.
+ *   3. Elbow.  x = ((l1*l1 - l2*l2) + dc*dc) / (2.0f*dc), y2 = l1*l1 - x*x, y = y2 > 0 ? float(sqrt(double(y2))) : 0.  Bend direction:
+ *      b = B - A, p = b - dh*dot(b, dh), lp = len(p).  If !(lp > 1e-4f*l1) (a straight or target-aligned limb): b = dir(pole, row a),
+ *      p and lp again by the same lines; if then !(lp > 0): nothing is written.  nb = dh*x + (p / lp)*y, v1 = nb / len(nb),
+ *      u1 = (B - A) / l1.  M_a = rot(u1, v1, A).
+ *   4. Forearm.  B1 = pt(h_b, mul(row b, M_a)), T1 = pt(the solved point, mul(row c, M_a)): e, or h_c with the flag.
+ *      u2 = (T1 - B1) / len(T1 - B1), v2 = (Gc - B1) / len(Gc - B1); a length that is not > 0 or not finite: nothing is written.
+ *      M_b = rot(u2, v2, B1).  C_0 = M_a.  C_1 = mul(M_a, M_b) with its fourth column set to {0, 0, 0, 1} afterwards (which the
+ *      product gives by itself for finite values, as for the aim).
+ *   5. End bone.  Without the flag C_2 = C_1.  With it C_2 is the pure translation by pt(h_c, mul(row c, C_1)) - K: rows 1-3 those
+ *      of the identity exactly, so a planted foot keeps its animated orientation, its 3x3 value for value.
+ *   6. Writes.  Every bone s of the subtree of a has a depth k(s) = 0, 1 or 2: the deepest of a, b, c that is s or an ancestor of
+ *      s.  row'(s) = mul(row(s), C_{k(s)}).  All reads see the rows as they were before the call.  A failure in steps 1-4 (a
+ *      "nothing is written", a rot that fails) writes nothing for this (instance, reach): all or nothing, unlike the aim's per-link
+ *      skip.
+ * Sign and payload of a NaN are not part of the contract.  A float32 prototype of exactly this, evaluated in float64, over the case
+ * table of the tests and 3 000 steps of a target circling a swaying 41-bone rig (seven sets, both flag values, 30 067 applied reaches):
+ * the tip (with the flag: the pivot of c) ends within 4.6e-5 * max(1, |Gc|) of Gc (2.8e-6 where both rotations have m > 0.1; the
+ * worst is at m = 1.1e-3 and the error does not grow further towards m = 0); |B' - A| and |T' - B'| keep l1 and l2 to 4.6e-5 relative
+ * (7.0e-6 where m > 0.1); the new elbow leaves the plane of dh and the bend direction by at most 4.4e-6 * l1.  Only the rigidity goes
+ * with 1 / m (u and v of a rot are unit vectors to a rounding error, which the formula divides by m, as the aim's does):
+ * |C C^T - I| <= 1.2e-6 / m for the 3x3 of C_0 (m of M_a) and of C_1 (the smaller m of M_a and M_b); the smallest m met was 6.7e-6.
+ *
+ * mmdx_reach_set_create validates everything on the host and touches no device.  Rest positions and parents come from the skeleton.
+ * A bone >= the skeleton's count is MMDX_ERR_BAD_INDEX.  MMDX_ERR_INVALID_ARGUMENT: b not a strict descendant of a, or c not of b;
+ * max_extension outside (0, 1]; NaN anywhere; a zero or non-finite pole; n_reaches == 0 or above MMDX_REACH_MAX_REACHES; unknown
+ * per-reach flag bits; subtrees of two reaches that intersect (one workgroup owns a subtree: a reach under an aimed spine is a
+ * different set and call); NULL arrays; reserved0 != 0; a struct_size mismatch.  A skeleton of more than 2^20 bones is
+ * MMDX_ERR_UNSUPPORTED. */
+typedef struct mmdx_reach_set_s *mmdx_reach_set_t;
+#define MMDX_REACH_MAX_REACHES 16
+enum { MMDX_REACH_TARGETS_ON_DEVICE = (1u << 19) }; /* mmdx_palette_reach: targets is a device pointer, read when the kernel RUNS  */
+enum { MMDX_REACH_KEEP_END_ROTATION = 1u };         /* mmdx_reach_set_desc.flags[r]: solve for the pivot of c, translate its subtree */
+typedef struct mmdx_reach_set_desc {
+    uint32_t struct_size;            /* = sizeof(mmdx_reach_set_desc)                                                             */
+    uint32_t n_reaches;              /* 1 .. MMDX_REACH_MAX_REACHES                                                               */
+    const uint32_t *bones;           /* [n_reaches][3] a, b, c                                                                    */
+    const float *tip_point;          /* [n_reaches][3] rest-space e                                                               */
+    const float *pole;               /* [n_reaches][3] rest-space, any length but zero                                            */
+    const float *max_extension;      /* [n_reaches] in (0, 1]                                                                     */
+    const uint32_t *flags;           /* [n_reaches] 0 | MMDX_REACH_KEEP_END_ROTATION                                              */
+    uint32_t reserved0;              /* must be 0                                                                                 */
+} mmdx_reach_set_desc;
+typedef struct mmdx_reach_set_info {
+    uint32_t struct_size;            /* = sizeof(mmdx_reach_set_info), set by the caller                                          */
+    uint32_t n_reaches;
+    uint32_t n_subtree_rows;         /* palette rows one instance has rewritten when every reach applies                          */
+    uint32_t n_bones;                /* the skeleton's bone count: palettes are [NI][n_bones][16]                                 */
+    int32_t device_ordinal;          /* where the table lives; -1 = nowhere yet (the first call decides)                          */
+    uint32_t reserved0;
+} mmdx_reach_set_info;
+MMDX_API mmdx_status mmdx_reach_set_create(mmdx_skeleton_t skeleton, const mmdx_reach_set_desc *desc, mmdx_reach_set_t *out_set);
+MMDX_API void mmdx_reach_set_destroy(mmdx_reach_set_t set);
+MMDX_API mmdx_status mmdx_reach_set_get_info(mmdx_reach_set_t set, mmdx_reach_set_info *info);
+
+typedef struct mmdx_reach_args {
+    uint32_t struct_size;            /* = sizeof(mmdx_reach_args)                                                                 */
+    uint32_t flags;                  /* MMDX_PALETTE_ON_DEVICE (required) | MMDX_REACH_TARGETS_ON_DEVICE                           */
+    uint32_t n_instances;            /* NI                                                                                        */
+    uint32_t target_stride;          /* in floats: 0 = one target for everyone, else a multiple of 4 (>= 4)                       */
+    float *palettes;                 /* DEVICE [NI][NB][16], 16-byte aligned, rewritten in place                                  */
+    const float *targets;            /* {x, y, z, weight} per instance, for EVERY reach of the set: host memory, or device memory
+                                        (16-byte aligned) with MMDX_REACH_TARGETS_ON_DEVICE.  Stride 16 and targets = slab + 12: a
+                                        slab of mmdx_palette_sockets as it is, its v[15] = 1 the weight.  Two hands on two
+                                        targets are two sets and two calls                                                        */
+    const mmdx_instance_select *select;   /* NULL = every instance                                                               */
+} mmdx_reach_args;
+/* Every reach of every instance (of the listed instances) on `model`'s stream (NULL: the selected device's default stream), as
+ * mmdx_palette_aim takes its model.
+ *   1. Only rows of the reaches' subtrees are written, of the listed instances, or of all instances without a list; every other byte
+ *      of palettes stays as it is.
+ *   2. select follows mmdx_instance_select as mmdx_deform_batched_select states it: the first min(*count, n_ids) ids are used (count
+ *      NULL: n_ids); a device id >= n_instances is skipped; a host id >= n_instances is MMDX_ERR_INVALID_ARGUMENT before anything is
+ *      launched.  A host list is copied through scratch of the set and the call returns when the work is done.  The target of a
+ *      listed instance is that of the INSTANCE (ids[k]), not of the list position.
+ *   3. The ids of one call must be distinct: an instance listed twice would be rewritten by two workgroups at once (undefined rows,
+ *      no access outside the arrays).
+ *   4. The call is asynchronous on the model's stream (a borrowed one, mmdx_model_set_stream, included), in order with that model's
+ *      solve, place, aim, spring, bounds and deform calls.  Host targets are copied through scratch of the set and the call returns
+ *      when the work is done.
+ *   5. It records into mmdx_graph_begin / _end of `model` with device targets and a device list (or none); host targets or a host
+ *      list are MMDX_ERR_INVALID_ARGUMENT while recording, and so is a set that has not run on that device before (its table is
+ *      uploaded by the first call).  A recorded call reads targets and list afresh at every replay.
+ *   6. The set is pinned by the graphs it took part in: destroying it invalidates them, as for every other handle.
+ *   7. Unknown flag bits, a missing MMDX_PALETTE_ON_DEVICE, a target_stride that is neither 0 nor a multiple of 4, NULL set / args /
+ *      palettes / targets, misaligned device pointers and a struct_size mismatch are MMDX_ERR_INVALID_ARGUMENT.  More than 2^23
+ *      instances or list positions in one call is MMDX_ERR_UNSUPPORTED.  n_instances == 0 is MMDX_OK and launches nothing.
+ * A workgroup owns 16 instances (list positions) of one reach at every crowd size. */
+MMDX_API mmdx_status mmdx_palette_reach(mmdx_reach_set_t set, mmdx_model_t model, const mmdx_reach_args *args);
 
 /* ---- a box per instance BEFORE the deform: bone boxes x palette ---------------------------------------------------------------
  * mmdx_deform_batched_bounds gives the box of the vertices it wrote, so a cull that uses it tests last frame's box, and an instance

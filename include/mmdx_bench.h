@@ -47,10 +47,11 @@ typedef enum mmdx_debug_kernel {
     MMDX_DEBUG_KERNEL_CULL = 4,      /* mmdx_cull_bounds was the model's last planned call: threads = lanes per workgroup, group =
                                         instances per chunk, ngroups = chunks, select = the form (1: one workgroup walks the chunks,
                                         2: a count launch and a scatter launch, one workgroup per chunk); every other field 0 */
-    MMDX_DEBUG_KERNEL_AIM = 5        /* mmdx_palette_aim on this model's stream was its last planned call: threads = lanes per
+    MMDX_DEBUG_KERNEL_AIM = 5,       /* mmdx_palette_aim on this model's stream was its last planned call: threads = lanes per
                                         workgroup, group = instances (list positions) per workgroup, 16, or 64 under
                                         MMDX_AIM_BLOCK=64, ngroups = workgroups per aim, lds = bytes of dynamic LDS, select = 1 with a list;
                                         every other field 0 */
+    MMDX_DEBUG_KERNEL_REACH = 6      /* mmdx_palette_reach likewise: group = 16, ngroups = workgroups per reach */
 } mmdx_debug_kernel;
 typedef struct mmdx_debug_launch_shape {
     uint32_t struct_size;            /* sizeof(mmdx_debug_launch_shape), set by the caller */

@@ -205,6 +205,30 @@ class AimArgs(C.Structure):
                 ("palettes", C.c_void_p), ("targets", C.c_void_p), ("select", C.POINTER(InstanceSelect))]
 
 
+REACH_TARGETS_ON_DEVICE = 1 << 19                         # MMDX_REACH_TARGETS_ON_DEVICE: mmdx_reach_args.flags (with PALETTE_ON_DEVICE, required)
+REACH_MAX_REACHES = 16                                    # MMDX_REACH_MAX_REACHES
+REACH_KEEP_END_ROTATION = 1                               # MMDX_REACH_KEEP_END_ROTATION: mmdx_reach_set_desc.flags[r]
+
+
+class ReachSetDesc(C.Structure):
+    """mmdx_reach_set_desc: the three bones, the tip point, the pole, the extension and the flags of every reach of a reach set
+    (mmdx_reach_set_create)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_reaches", C.c_uint32), ("bones", C.c_void_p), ("tip_point", C.c_void_p),
+                ("pole", C.c_void_p), ("max_extension", C.c_void_p), ("flags", C.c_void_p), ("reserved0", C.c_uint32)]
+
+
+class ReachSetInfo(C.Structure):
+    """mmdx_reach_set_info (mmdx_reach_set_get_info)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_reaches", C.c_uint32), ("n_subtree_rows", C.c_uint32), ("n_bones", C.c_uint32),
+                ("device_ordinal", C.c_int32), ("reserved0", C.c_uint32)]
+
+
+class ReachArgs(C.Structure):
+    """mmdx_reach_args: device palettes rewritten in place, the targets and the instance list of mmdx_palette_reach."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("target_stride", C.c_uint32),
+                ("palettes", C.c_void_p), ("targets", C.c_void_p), ("select", C.POINTER(InstanceSelect))]
+
+
 class BoneMotionKeys(C.Structure):
     """mmdx_bone_motion_keys: the host key tables of a bound bone motion (mmdx_bone_motion_get_keys)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_bones", C.c_uint32), ("n_keys", C.c_uint32), ("n_curves", C.c_uint32),
@@ -243,7 +267,7 @@ class DebugLaunchShape(C.Structure):
                 ("reserved0", C.c_uint32)]
 
 
-DEBUG_KERNELS = ("none", "deform", "pack", "frame", "cull", "aim")      # mmdx_debug_kernel
+DEBUG_KERNELS = ("none", "deform", "pack", "frame", "cull", "aim", "reach")      # mmdx_debug_kernel
 
 
 class DebugSolveShape(C.Structure):
@@ -408,6 +432,11 @@ SIGNATURES = {
     "mmdx_aim_set_destroy": (None, [C.c_void_p]),
     "mmdx_aim_set_get_info": (C.c_int32, [C.c_void_p, C.POINTER(AimSetInfo)]),
     "mmdx_palette_aim": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(AimArgs)]),
+    # reach: (skeleton, desc, out_set); (set); (set, info*); (set, model, mmdx_reach_args*)
+    "mmdx_reach_set_create": (C.c_int32, [C.c_void_p, C.POINTER(ReachSetDesc), C.POINTER(C.c_void_p)]),
+    "mmdx_reach_set_destroy": (None, [C.c_void_p]),
+    "mmdx_reach_set_get_info": (C.c_int32, [C.c_void_p, C.POINTER(ReachSetInfo)]),
+    "mmdx_palette_reach": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(ReachArgs)]),
     "mmdx_bone_motion_get_keys": (C.c_int32, [C.c_void_p, C.POINTER(BoneMotionKeys)]),
     "mmdx_skeleton_solve_morphed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),

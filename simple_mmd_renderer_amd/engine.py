@@ -834,6 +834,85 @@ class AimSet:
         self.close()
 
 
+class ReachSet:
+    """mmdx_reach_set_t: two-bone IK for a crowd.  reach() puts the tip of every reach of every (listed) instance on the instance's
+    target, in one launch, and rewrites the rows of the limbs' subtrees of a device palette array [NI][NB][16] in place: after
+    DeformModel.place_palettes the targets are world points, before it model-space points.  It runs after AimSet.aim (an aimed spine
+    carries the arms) and before SpringSet.step (sleeves anchor on the rows it rewrites).  include/mmdx.h states the arithmetic.
+
+    reaches: a list of dicts {bones: (a, b, c), each a strict skeleton ancestor of the next; tip_point [3] rest-space (default: the
+    rest position of c); pole [3] rest-space (default (0, 0, -1)); max_extension in (0, 1] (default 1); keep_end_rotation (default
+    False): solve for the pivot of c and translate its subtree, so a planted foot keeps its orientation}."""
+
+    def __init__(self, skeleton, reaches):
+        n = len(reaches)
+        bones = np.zeros((n, 3), np.uint32)
+        tip, pole = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+        ext, flags = np.ones(n, np.float32), np.zeros(n, np.uint32)
+        for k, r in enumerate(reaches):
+            bones[k] = np.asarray(r["bones"], np.uint32).reshape(3)
+            tip[k] = r["tip_point"] if "tip_point" in r else np.asarray(skeleton.rest_position, np.float32).reshape(-1, 3)[bones[k, 2]]
+            pole[k] = r.get("pole", (0.0, 0.0, -1.0))
+            ext[k] = r.get("max_extension", 1.0)
+            flags[k] = r.get("flags", api.REACH_KEEP_END_ROTATION if r.get("keep_end_rotation") else 0)
+        d = api.ReachSetDesc()
+        d.struct_size = C.sizeof(api.ReachSetDesc)
+        d.n_reaches = n
+        d.bones, d.tip_point, d.pole = bones.ctypes.data, tip.ctypes.data, pole.ctypes.data
+        d.max_extension, d.flags = ext.ctypes.data, flags.ctypes.data
+        self.h = C.c_void_p()
+        api.check(api.lib().mmdx_reach_set_create(skeleton.h, C.byref(d), C.byref(self.h)))      # copies the arrays
+        self.nb = self.info()["n_bones"]
+
+    def info(self) -> dict:
+        i = api.ReachSetInfo(C.sizeof(api.ReachSetInfo))
+        api.check(api.lib().mmdx_reach_set_get_info(self.h, C.byref(i)))
+        return {k: int(getattr(i, k)) for k, _ in api.ReachSetInfo._fields_ if k not in ("struct_size", "reserved0")}
+
+    def reach_raw(self, n_instances: int, palettes_ptr, targets_ptr, stride: int, flags: int, select=None, model=None) -> None:
+        """mmdx_palette_reach, the raw form: targets_ptr is host memory unless flags has REACH_TARGETS_ON_DEVICE."""
+        a = api.ReachArgs()
+        a.struct_size = C.sizeof(api.ReachArgs)
+        a.flags, a.n_instances, a.target_stride = flags, n_instances, stride
+        a.palettes, a.targets = palettes_ptr, targets_ptr
+        if select is not None:
+            a.select = C.pointer(select)
+        api.check(api.lib().mmdx_palette_reach(self.h, model.h if model is not None else None, C.byref(a)))
+
+    def reach(self, model, palettes_dev, targets, stride: int = 4, select=None, n_instances=None) -> None:
+        """Device palettes (a DeviceBuffer or a raw address) in place, asynchronous on the model's stream and recordable with device
+        targets and a device list.  targets: a DeviceBuffer or a raw device address ({x, y, z, weight} every `stride` floats; stride 0:
+        one target for everyone; stride 16 and the address of a mmdx_palette_sockets slab + 48 bytes: the slab's translations), or a
+        numpy array [NI,4] / [4] in host memory (copied, and the call returns when the work is done)."""
+        if n_instances is None:
+            n_instances = palettes_dev.nbytes // (self.nb * 64)
+        pal = getattr(palettes_dev, "ptr", palettes_dev)
+        if isinstance(targets, np.ndarray):
+            t = _c(targets, np.float32)
+            stride = 0 if t.size == 4 else t.size // max(n_instances, 1)
+            self.reach_raw(n_instances, pal, t.ctypes.data, stride, api.PALETTE_ON_DEVICE, select, model)
+        else:
+            self.reach_raw(n_instances, pal, getattr(targets, "ptr", targets), stride,
+                           api.PALETTE_ON_DEVICE | api.REACH_TARGETS_ON_DEVICE, select, model)
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            api.lib().mmdx_reach_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class PoseImage:
     def __init__(self, nv: int):
         self.coordinates = np.zeros((nv, 3), np.float32)

@@ -867,4 +867,43 @@ private:
     mmdx_aim_set_t set_ = nullptr;
 };
 
+// Reach (mmdx.h, mmdx_palette_reach): two-bone IK puts hands and feet of a crowd on per-instance targets, on the device.  A set is
+// created on a skeleton handle from a filled mmdx_reach_set_desc (the arrays are copied); Reach rewrites the rows of the limbs'
+// subtrees of device palettes [n][bones][16] in place, AFTER AimSet::Aim (an aimed spine carries the arms) and BEFORE
+// SpringSet::Step (sleeves anchor on the rows it rewrites).
+class ReachSet {
+public:
+    ReachSet(mmdx_skeleton_t skeleton, mmdx_reach_set_desc desc) {
+        desc.struct_size = sizeof(desc);
+        check(mmdx_reach_set_create(skeleton, &desc, &set_));
+    }
+    ~ReachSet() { mmdx_reach_set_destroy(set_); }
+    ReachSet(const ReachSet &) = delete;
+    ReachSet &operator=(const ReachSet &) = delete;
+
+    // Every reach of every instance (select: of the listed ones), asynchronous on `model`'s stream.  targets: {x, y, z, weight}
+    // every `stride` floats (0: one for everyone), host memory, or device memory with targets_on_device (what a recorded frame
+    // takes, together with a device list or none).  A slab of SocketSet::Sockets goes in as SocketSet::slab(...) + 12 with stride 16.
+    void Reach(mmdx_model_t model, uint32_t n_instances, float *device_palettes, const float *targets, uint32_t stride = 4,
+               bool targets_on_device = true, const mmdx_instance_select *select = nullptr) {
+        mmdx_reach_args a{};
+        a.struct_size = sizeof(a);
+        a.flags = uint32_t(MMDX_PALETTE_ON_DEVICE) | (targets_on_device ? uint32_t(MMDX_REACH_TARGETS_ON_DEVICE) : 0u);
+        a.n_instances = n_instances;
+        a.target_stride = stride;
+        a.palettes = device_palettes; a.targets = targets; a.select = select;
+        check(mmdx_palette_reach(set_, model, &a));
+    }
+    mmdx_reach_set_info Info() const {
+        mmdx_reach_set_info i{};
+        i.struct_size = sizeof(i);
+        check(mmdx_reach_set_get_info(set_, &i));
+        return i;
+    }
+    mmdx_reach_set_t handle() const { return set_; }
+
+private:
+    mmdx_reach_set_t set_ = nullptr;
+};
+
 }  // namespace mmdx
