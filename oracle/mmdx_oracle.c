@@ -27,6 +27,7 @@
  * Matrix convention: row vector, row-major float[16], translation in elements 12..14
  *   (L/util/math.inl:383-395).
  */
+#include <float.h>
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -813,15 +814,51 @@ static void apply_bone_morph(const bmorph_ctx *c, uint32_t m, float rate) {
 /* Matrix4x4<T>::Inverse(), L/util/math_impl.inl:822-897: Gauss-Jordan on [M | I] with scaled partial pivoting
  * (row i's scale = its largest |element|; a zero row or a zero last pivot gives the ZERO matrix), forward
  * elimination, then the upper triangle is cleared column by column and every row divided by its pivot. */
-void mmdx_oracle_matrix_inverse(const float *in, float *out) {
-    float s[4][8], scale[4];
+/* Optional trace of the inverse (tests/seam_cases.py steers the matrix Fix inverts to every pivot order and exit with it): one record
+ * of MMDX_INV_TRACE_WORDS words per call, written when the call returns -- the 16 input floats as bits; the ORIGINAL index of the
+ * row chosen as pivot at columns 0, 1 and 2 (0xFFFFFFFF where the call left before that column); the exit (INV_EXIT_*); the first
+ * zero row of a zero_row exit (else 0xFFFFFFFF); a mask of the columns 0..2 at which a candidate that was NOT chosen had the chosen
+ * one's |s / scale| exactly (the tie rule decided: the first of them wins); a mask of the columns 0..2 whose chosen pivot element
+ * was zero, so that the elimination divided by zero; bit 0: an input element is not finite, bit 1: an output element is not.
+ * The trace only reads: no result bit depends on it.  Not thread-safe; off by default. */
+enum { MMDX_INV_TRACE_WORDS = 24 };
+enum { INV_EXIT_INVERTED = 0, INV_EXIT_ZERO_ROW = 1, INV_EXIT_ZERO_LAST_PIVOT = 2 };
+static uint32_t *g_inv_trace;
+static size_t g_inv_trace_cap, g_inv_trace_n;
+void mmdx_oracle_trace_inverse(uint32_t *records, size_t capacity) { g_inv_trace = records; g_inv_trace_cap = capacity; g_inv_trace_n = 0; }
+size_t mmdx_oracle_trace_inverse_count(void) { return g_inv_trace_n; }
+static int inv_not_finite(const float *v) {
+    for (int k = 0; k < 16; ++k) if (!(fabsf(v[k]) <= FLT_MAX)) return 1;
+    return 0;
+}
+static void inv_trace_emit(const float *in, const float *out, const uint32_t *pivots, uint32_t kind, uint32_t zero_row,
+                           uint32_t ties, uint32_t zero_pivots) {
+    if (!g_inv_trace) return;
+    if (g_inv_trace_n < g_inv_trace_cap) {
+        uint32_t *rec = g_inv_trace + MMDX_INV_TRACE_WORDS * g_inv_trace_n;
+        memcpy(rec, in, 64);
+        rec[16] = pivots[0]; rec[17] = pivots[1]; rec[18] = pivots[2];
+        rec[19] = kind; rec[20] = zero_row; rec[21] = ties; rec[22] = zero_pivots;
+        rec[23] = (uint32_t)inv_not_finite(in) | (uint32_t)inv_not_finite(out) << 1;
+    }
+    ++g_inv_trace_n;
+}
+
+void mmdx_oracle_matrix_inverse(const float *in_, float *out) {
+    float s[4][8], scale[4], in[16];
     int row[4] = {0, 1, 2, 3};                              /* the reference swaps row pointers */
+    uint32_t t_piv[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, t_ties = 0, t_zero = 0;     /* trace only */
+    memcpy(in, in_, 64);                                    /* (out may be in_: the trace reads the input afterwards) */
     for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 4; ++j) { s[i][j] = in[4 * i + j]; s[i][j + 4] = i == j ? 1.0f : 0.0f; }
     for (int i = 0; i < 4; ++i) {
         scale[i] = fabsf(s[i][0]);
         for (int j = 1; j < 4; ++j) { const float x = fabsf(s[i][j]); if (x > scale[i]) scale[i] = x; }
-        if (scale[i] == 0) { memset(out, 0, 64); return; }
+        if (scale[i] == 0) {
+            memset(out, 0, 64);
+            inv_trace_emit(in, out, t_piv, INV_EXIT_ZERO_ROW, (uint32_t)i, 0, 0);
+            return;
+        }
     }
     for (int i = 0; i < 4; ++i) {
         int pivot = i;
@@ -830,9 +867,17 @@ void mmdx_oracle_matrix_inverse(const float *in, float *out) {
             const float x = fabsf(s[row[p]][i] / scale[p]);
             if (x > best) { best = x; pivot = p; }
         }
+        if (g_inv_trace && i < 3) {                         /* trace only: candidates that tie with the chosen one */
+            for (int p = i; p < 4; ++p)
+                if (p != pivot && fabsf(s[row[p]][i] / scale[p]) == best) t_ties |= 1u << i;
+        }
         if (pivot != i) {
             const int r = row[i]; row[i] = row[pivot]; row[pivot] = r;
             const float c = scale[i]; scale[i] = scale[pivot]; scale[pivot] = c;
+        }
+        if (i < 3) {                                        /* trace only */
+            t_piv[i] = (uint32_t)row[i];
+            if (s[row[i]][i] == 0) t_zero |= 1u << i;
         }
         for (int j = i + 1; j < 4; ++j) {
             const float m = s[row[j]][i] / s[row[i]][i];
@@ -840,7 +885,11 @@ void mmdx_oracle_matrix_inverse(const float *in, float *out) {
             for (int jj = i + 1; jj < 8; ++jj) s[row[j]][jj] -= m * s[row[i]][jj];
         }
     }
-    if (s[row[3]][3] == 0) { memset(out, 0, 64); return; }
+    if (s[row[3]][3] == 0) {
+        memset(out, 0, 64);
+        inv_trace_emit(in, out, t_piv, INV_EXIT_ZERO_LAST_PIVOT, 0xFFFFFFFFu, t_ties, t_zero);
+        return;
+    }
     for (int i = 1; i < 4; ++i)
         for (int j = 0; j < i; ++j) {
             const float m = s[row[j]][i] / s[row[i]][i];
@@ -848,6 +897,7 @@ void mmdx_oracle_matrix_inverse(const float *in, float *out) {
         }
     for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 4; ++j) out[4 * i + j] = s[row[i]][j + 4] / s[row[i]][i];
+    inv_trace_emit(in, out, t_piv, INV_EXIT_INVERTED, 0xFFFFFFFFu, t_ties, t_zero);
 }
 
 /* What BulletPhysicsReactor::React leaves in the poser between the two bone lists

@@ -269,6 +269,29 @@ class Oracle:
             raise ValueError("append trace overflow: %d evaluations" % n)
         return buf[:n].copy()
 
+    INVERSE_TRACE_FIELDS = tuple("m%d" % k for k in range(16)) + ("pivot0", "pivot1", "pivot2", "exit", "zero_row", "ties",
+                                                                  "zero_pivots", "nonfinite")
+    INVERSE_EXITS = ("inverted", "zero_row", "zero_last_pivot")
+    INVERSE_NONE = 0xFFFFFFFF
+
+    def trace_inverse(self, fn, capacity=1 << 16):
+        """Run fn() with every call of the 4x4 inverse recorded; returns u32 [N, 24] records in call order, columns
+        INVERSE_TRACE_FIELDS: the input's bits, the original index of the pivot row chosen at columns 0..2 (INVERSE_NONE where the
+        call left earlier), exit (an index into INVERSE_EXITS), the zero row of a zero_row exit, the columns (bit mask) at which
+        the tie rule decided, the columns whose chosen pivot was zero and was divided by, nonfinite (bit 0 input, bit 1 output)
+        -- see mmdx_oracle_trace_inverse."""
+        buf = np.zeros((capacity, len(self.INVERSE_TRACE_FIELDS)), np.uint32)
+        self.lib.mmdx_oracle_trace_inverse_count.restype = C.c_size_t
+        self.lib.mmdx_oracle_trace_inverse(buf.ctypes.data_as(C.c_void_p), C.c_size_t(capacity))
+        try:
+            fn()
+            n = int(self.lib.mmdx_oracle_trace_inverse_count())
+        finally:
+            self.lib.mmdx_oracle_trace_inverse(None, C.c_size_t(0))
+        if n > capacity:
+            raise ValueError("inverse trace overflow: %d calls" % n)
+        return buf[:n].copy()
+
     def time_crowd(self, model, rates, palettes, normalize=True):
         """Seconds for one crowd step (shared morph pass + one skinning pass per palette)."""
         t, ids, w = self.normalize(model) if normalize else (
