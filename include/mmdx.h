@@ -91,7 +91,9 @@ extern "C" {
  *    changes).
  *    mmdx_reach_set_create / _destroy / _get_info and mmdx_palette_reach with mmdx_reach_set_desc / _info, mmdx_reach_args,
  *    MMDX_REACH_TARGETS_ON_DEVICE and MMDX_REACH_KEEP_END_ROTATION (four new entry points, three structures, a flag bit no other
- *    call accepts and a flag of the new desc alone; nothing existing changes). */
+ *    call accepts and a flag of the new desc alone; nothing existing changes).
+ *    mmdx_ground_create / _destroy / _get_info, mmdx_ground_place and mmdx_ground_targets with mmdx_ground_desc / _info,
+ *    mmdx_ground_place_args and mmdx_ground_targets_args (five new entry points and four structures; nothing existing changes). */
 #define MMDX_ABI_VERSION 3u
 
 typedef int32_t mmdx_status;
@@ -1616,8 +1618,9 @@ MMDX_API mmdx_status mmdx_palette_aim(mmdx_aim_set_t set, mmdx_model_t model, co
  * The frame order is solve -> place -> aim -> reach -> springs -> palette bounds -> cull -> deform select: reach runs AFTER aim,
  * because an aimed spine carries the arms, and BEFORE the springs, because sleeves and ribbons anchor on rows that reach rewrites.
  *  - The hierarchy is the skeleton's parent array ONLY.  Append and IK relations are not followed.
- *  - Joint angle limits and hinge axes, twist distribution, chains longer than two bones, damping (which needs state) and ground
- *    queries are out of scope: the caller supplies the foot target, and the weight in tgt[3] fades a reach in and out.
+ *  - Joint angle limits and hinge axes, twist distribution, chains longer than two bones and damping (which needs state) are out
+ *    of scope.  The caller supplies the target, and the weight in tgt[3] fades a reach in and out; foot targets over a height field
+ *    come from mmdx_ground_targets (the ground section below).
  *
  * A reach names three bones: a (upper arm, thigh), b (elbow, knee), c (wrist, ankle), each a strict skeleton ancestor of the next
  * (not necessarily its parent: MMD arms have twist bones in between); a rest-space tip point e carried by c; a rest-space pole
@@ -1726,6 +1729,133 @@ typedef struct mmdx_reach_args {
  *      instances or list positions in one call is MMDX_ERR_UNSUPPORTED.  n_instances == 0 is MMDX_OK and launches nothing.
  * A workgroup owns 16 instances (list positions) of one reach at every crowd size. */
 MMDX_API mmdx_status mmdx_palette_reach(mmdx_reach_set_t set, mmdx_model_t model, const mmdx_reach_args *args);
+
+/* ---- ground: a height field lifts placements and foot targets on the device ------------------------------------------------------
+ * Root motion walks a placement through the world in x and z; a ground gives it its height and gives the reach sets of the feet
+ * their targets, without the host: one call puts every (listed) placement on the ground, one call turns the feet's world positions
+ * (a mmdx_palette_sockets output) into reach targets that keep each foot's animated height over the ground under that foot, and
+ * writes a hip drop so that the lower foot can reach.  A ground is a regular height field in device memory.  There is no libmmd
+ * counterpart, so the contract is the arithmetic below, in IEEE binary32 operations in the order written, unfused, as for the
+ * springs, the aim and the reach.
+ *
+ * The frame order is animator -> root motion -> GROUND PLACE -> tracks -> solve -> place -> sockets -> GROUND TARGETS -> aim -> reach
+ * -> springs -> palette bounds -> cull -> deform select.  With MMDX_ROOT_X | MMDX_ROOT_Z as root motion's axes the clip keeps its
+ * own vertical motion and mmdx_ground_place owns placements[i][1].
+ *  - Foot alignment to the slope, tilting the placement to the ground normal and geometry that is no height field are out of scope.
+ *
+ * The height function h(x, z) of a field of nx samples per row and nz rows, H[nz][nx], origin (origin_x, origin_z), cells
+ * (cell_x, cell_z):
+ *   Cell and fraction.  u = (x - origin_x) / cell_x.  If u is not finite the sample FAILS.  u = u < 0 ? 0 : u, then
+ *      u = u > float(nx-1) ? float(nx-1) : u.  iu = uint32(u) (truncation); if iu > nx-2 then iu = nx-2.  fu = u - float(iu).
+ *      v, iv, fv from z, origin_z, cell_z, nz by the same lines.  Outside the field the border continues flat: that is the clamp.
+ *   Corners.  h00 = H[iv][iu], h10 = H[iv][iu+1], h01 = H[iv+1][iu], h11 = H[iv+1][iu+1].
+ *   Interpolation.  The cell is two triangles split along the diagonal from corner 10 to corner 01, as a height-field mesh is
+ *      drawn, so feet stand on the rendered surface (which is not the bilinear patch).  If fu + fv <= 1.0f:
+ *         h = (h00*((1.0f - fu) - fv) + h10*fu) + h01*fv
+ *      else
+ *         h = (h11*((fu + fv) - 1.0f) + h10*(1.0f - fv)) + h01*(1.0f - fu)
+ * At a sample point h equals the stored height exactly, up to the sign of a zero, in every cell and at the clamped borders.
+ * Measured on the numpy restatement against a binary64 evaluation of the same formulas from the same binary32 x and z (200 000
+ * random points in and around each field of the tests: 2 x 2, 3 x 2 and 33 x 17 samples, unequal cells, negative origins, steps
+ * between neighbouring samples of up to max|H|): |h - h64| <= 5.7e-7 * max(1, max|H|) = MMDX_GROUND_H_ERROR, rounded up; and h is
+ * continuous across the diagonal and across cell edges to the same bound (points a few ulps on either side).  The error is the
+ * rounding of u and v, half an ulp of a number up to nx - 1, times the step between neighbouring samples: it grows with the sample
+ * count and the steepness, not with the heights themselves.  Heights whose products overflow binary32 are the caller's: nothing is
+ * read or written out of bounds, the values are inf or NaN.
+ *
+ * mmdx_ground_create validates on the host and touches no device.  MMDX_ERR_INVALID_ARGUMENT: a NULL pointer, a struct_size
+ * mismatch, any flag bit, reserved0 != 0, nx or nz outside 2 .. 8192, a cell size that is not finite and > 0, a non-finite origin,
+ * any non-finite height.  The heights are copied at create; the table is uploaded by the first call on a device and stays there. */
+typedef struct mmdx_ground_s *mmdx_ground_t;
+#define MMDX_GROUND_MAX_FEET 8
+#define MMDX_GROUND_MIN_SAMPLES 2
+#define MMDX_GROUND_MAX_SAMPLES 8192
+#define MMDX_GROUND_H_ERROR 6e-7f   /* measured, see above; the tests assert four times it */
+typedef struct mmdx_ground_desc {
+    uint32_t struct_size;            /* = sizeof(mmdx_ground_desc)                                                                */
+    uint32_t flags;                  /* none defined: must be 0                                                                   */
+    uint32_t nx, nz;                 /* samples per row, rows: MMDX_GROUND_MIN_SAMPLES .. MMDX_GROUND_MAX_SAMPLES each            */
+    float origin_x, origin_z;        /* world x, z of H[0][0]                                                                     */
+    float cell_x, cell_z;            /* world distance between samples, > 0                                                       */
+    const float *heights;            /* HOST [nz][nx], copied by the call                                                         */
+    uint32_t reserved0;              /* must be 0                                                                                 */
+} mmdx_ground_desc;
+typedef struct mmdx_ground_info {
+    uint32_t struct_size;            /* = sizeof(mmdx_ground_info), set by the caller                                             */
+    uint32_t nx, nz;
+    float origin_x, origin_z, cell_x, cell_z;
+    float min_height, max_height;
+    int32_t device_ordinal;          /* where the table lives; -1 = nowhere yet (the first call decides)                          */
+    uint32_t reserved0;
+} mmdx_ground_info;
+MMDX_API mmdx_status mmdx_ground_create(const mmdx_ground_desc *desc, mmdx_ground_t *out_ground);
+MMDX_API void mmdx_ground_destroy(mmdx_ground_t ground);
+MMDX_API mmdx_status mmdx_ground_get_info(mmdx_ground_t ground, mmdx_ground_info *info);
+
+typedef struct mmdx_ground_place_args {
+    uint32_t struct_size;            /* = sizeof(mmdx_ground_place_args)                                                          */
+    uint32_t flags;                  /* none defined: must be 0                                                                   */
+    uint32_t n_instances;            /* NI                                                                                        */
+    float y_offset;
+    float *placements;               /* DEVICE [NI][MMDX_POSE_FLOATS], 4-byte aligned: the array root motion and
+                                        mmdx_palette_place share; only placements[i][1] is ever written                           */
+    const float *drop;               /* DEVICE [NI], 4-byte aligned, or NULL: last frame's mmdx_ground_targets out_drop           */
+    const mmdx_instance_select *select;   /* NULL = every instance                                                               */
+} mmdx_ground_place_args;
+/* Per (listed) instance i, p = placements[i]: h0 = h(p[0], p[2]).  If the sample fails, or drop is given and drop[i] is not finite,
+ * nothing of this instance is written.  Otherwise p[1] = (h0 + y_offset) + drop[i]; without drop p[1] = h0 + y_offset.  Called
+ * after root motion and before mmdx_palette_place.  drop may not overlap placements (MMDX_ERR_INVALID_ARGUMENT).  The rules 2, 4,
+ * 5, 6 and 7 below mmdx_ground_targets hold here too. */
+MMDX_API mmdx_status mmdx_ground_place(mmdx_ground_t ground, mmdx_model_t model, const mmdx_ground_place_args *args);
+
+typedef struct mmdx_ground_targets_args {
+    uint32_t struct_size;            /* = sizeof(mmdx_ground_targets_args)                                                        */
+    uint32_t flags;                  /* none defined: must be 0                                                                   */
+    uint32_t n_instances;            /* NI                                                                                        */
+    uint32_t n_feet;                 /* NF: 1 .. MMDX_GROUND_MAX_FEET                                                             */
+    const float *placements;         /* DEVICE [NI][MMDX_POSE_FLOATS], 4-byte aligned, read only                                  */
+    const float *points;             /* DEVICE, 4-byte aligned: foot f of instance i is the three floats at
+                                        points + f*slab_stride + i*point_stride.  points = sockets + 12, point_stride = 16,
+                                        slab_stride = NI*16: a mmdx_palette_sockets output as it is                               */
+    uint32_t point_stride;           /* in floats, >= 3                                                                           */
+    uint32_t slab_stride;            /* in floats, >= 3                                                                           */
+    float *out_targets;              /* DEVICE [NF][NI][4], 16-byte aligned, foot-major: slab f is the target array of the reach
+                                        set of foot f, with target_stride = 4                                                     */
+    float *out_drop;                 /* DEVICE [NI], 4-byte aligned, or NULL                                                      */
+    float max_step;                  /* finite, >= 0: the most a target leaves the foot's animated height, up or down             */
+    float max_drop;                  /* finite, >= 0: the most the hips are lowered                                               */
+    const mmdx_instance_select *select;   /* NULL = every instance                                                               */
+} mmdx_ground_targets_args;
+/* Per (listed) instance i, ty = placements[i][1], and per foot f with P its point:
+ *   hf = h(P.x, P.z).  If that fails, or any of P.x, P.y, P.z, ty is not finite: out_targets[f][i] = {+0, +0, +0, +0} (weight 0: the
+ *   reach writes nothing for that limb).  Otherwise dy = hf - ty; dy = dy < -max_step ? -max_step : dy, then
+ *   dy = dy > max_step ? max_step : dy; out_targets[f][i] = {P.x, P.y + dy, P.z, 1.0f}.
+ * The placement stands at ty, so the clip holds the foot at P.y - ty over it, and the target keeps that height over the ground
+ * under the foot: a swing arc survives, a planted foot lands on the slope.  Use the feet's reach sets with
+ * MMDX_REACH_KEEP_END_ROTATION.  If out_drop is given: h0 = h(placements[i][0], placements[i][2]); m = 0.0f; then, if h0 did not
+ * fail, per foot whose SAMPLE succeeded (whatever P.y and ty are), in foot order: d = hf - h0, m = d < m ? d : m.  So m is the least
+ * hf - h0 where that is below 0, and 0 otherwise, if no foot was sampled or if h0 failed; a d that is a NaN is never taken.
+ * r = m < 0 ? m : 0, then out_drop[i] = r < -max_drop ? -max_drop : r.  The NEXT frame's mmdx_ground_place reads it: the latency
+ * of one frame is deliberate, the call that lowers the hips runs before the solve, the call that knows by how much after it.
+ *   1. Only out_targets[f][i] and out_drop[i] of the listed instances (of all without a list) are written; every other byte stays.
+ *   2. select follows mmdx_instance_select as mmdx_deform_batched_select states it: the first min(*count, n_ids) ids are used (count
+ *      NULL: n_ids); a device id >= n_instances is skipped; a host id >= n_instances is MMDX_ERR_INVALID_ARGUMENT before anything is
+ *      launched.  A host list is copied through scratch of the ground and the call returns when the work is done.
+ *   3. out_targets and out_drop may overlap neither points nor placements nor each other (MMDX_ERR_INVALID_ARGUMENT).
+ *   4. The call is asynchronous on `model`'s stream (NULL: the selected device's default stream; a borrowed stream,
+ *      mmdx_model_set_stream, included), in order with that model's other calls.  A MMDX_CREATE_HOST_ONLY model is
+ *      MMDX_ERR_NO_DEVICE, after validation.
+ *   5. It records into mmdx_graph_begin / _end of `model` with a device list (or none); a host list is MMDX_ERR_INVALID_ARGUMENT
+ *      while recording, and so is a ground that has not run on that device before (its table is uploaded by the first call).  A
+ *      recorded call reads every array afresh at every replay.
+ *   6. The ground is pinned by the graphs it took part in: destroying it invalidates them, as for every other handle.
+ *   7. NULL ground / args / pointers (drop and out_drop excepted), a struct_size mismatch, any flag bit, misaligned pointers, a
+ *      stride below 3, n_feet outside 1 .. MMDX_GROUND_MAX_FEET, a negative or non-finite max_step / max_drop are
+ *      MMDX_ERR_INVALID_ARGUMENT.  More than 2^23 instances or list positions in one call is MMDX_ERR_UNSUPPORTED.
+ *      n_instances == 0 is MMDX_OK and launches nothing; ground, args, struct_size, flags, n_feet, the strides, max_step, max_drop
+ *      and the list's header are checked before that, no pointer of the arrays is.
+ * One lane per instance (list position) loops over the feet: the drop's minimum needs no atomics and is deterministic. */
+MMDX_API mmdx_status mmdx_ground_targets(mmdx_ground_t ground, mmdx_model_t model, const mmdx_ground_targets_args *args);
 
 /* ---- a box per instance BEFORE the deform: bone boxes x palette ---------------------------------------------------------------
  * mmdx_deform_batched_bounds gives the box of the vertices it wrote, so a cull that uses it tests last frame's box, and an instance

@@ -267,6 +267,38 @@ class DebugLaunchShape(C.Structure):
                 ("reserved0", C.c_uint32)]
 
 
+GROUND_MAX_FEET = 8                                       # MMDX_GROUND_MAX_FEET
+GROUND_H_ERROR = 6e-7                                     # MMDX_GROUND_H_ERROR
+
+
+class GroundDesc(C.Structure):
+    """mmdx_ground_desc: a regular height field, heights [nz][nx] in host memory (mmdx_ground_create copies them)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("nx", C.c_uint32), ("nz", C.c_uint32),
+                ("origin_x", C.c_float), ("origin_z", C.c_float), ("cell_x", C.c_float), ("cell_z", C.c_float),
+                ("heights", C.c_void_p), ("reserved0", C.c_uint32)]
+
+
+class GroundInfo(C.Structure):
+    """mmdx_ground_info (mmdx_ground_get_info)."""
+    _fields_ = [("struct_size", C.c_uint32), ("nx", C.c_uint32), ("nz", C.c_uint32),
+                ("origin_x", C.c_float), ("origin_z", C.c_float), ("cell_x", C.c_float), ("cell_z", C.c_float),
+                ("min_height", C.c_float), ("max_height", C.c_float), ("device_ordinal", C.c_int32), ("reserved0", C.c_uint32)]
+
+
+class GroundPlaceArgs(C.Structure):
+    """mmdx_ground_place_args: device placements whose [i][1] is rewritten, the drop and the instance list of mmdx_ground_place."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("y_offset", C.c_float),
+                ("placements", C.c_void_p), ("drop", C.c_void_p), ("select", C.POINTER(InstanceSelect))]
+
+
+class GroundTargetsArgs(C.Structure):
+    """mmdx_ground_targets_args: device placements and foot points in, reach targets and the hip drop out (mmdx_ground_targets)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_instances", C.c_uint32), ("n_feet", C.c_uint32),
+                ("placements", C.c_void_p), ("points", C.c_void_p), ("point_stride", C.c_uint32), ("slab_stride", C.c_uint32),
+                ("out_targets", C.c_void_p), ("out_drop", C.c_void_p), ("max_step", C.c_float), ("max_drop", C.c_float),
+                ("select", C.POINTER(InstanceSelect))]
+
+
 DEBUG_KERNELS = ("none", "deform", "pack", "frame", "cull", "aim", "reach")      # mmdx_debug_kernel
 
 
@@ -437,6 +469,12 @@ SIGNATURES = {
     "mmdx_reach_set_destroy": (None, [C.c_void_p]),
     "mmdx_reach_set_get_info": (C.c_int32, [C.c_void_p, C.POINTER(ReachSetInfo)]),
     "mmdx_palette_reach": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(ReachArgs)]),
+    # ground: (desc, out_ground); (ground); (ground, info*); (ground, model, mmdx_ground_place_args*); (ground, model, mmdx_ground_targets_args*)
+    "mmdx_ground_create": (C.c_int32, [C.POINTER(GroundDesc), C.POINTER(C.c_void_p)]),
+    "mmdx_ground_destroy": (None, [C.c_void_p]),
+    "mmdx_ground_get_info": (C.c_int32, [C.c_void_p, C.POINTER(GroundInfo)]),
+    "mmdx_ground_place": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(GroundPlaceArgs)]),
+    "mmdx_ground_targets": (C.c_int32, [C.c_void_p, C.c_void_p, C.POINTER(GroundTargetsArgs)]),
     "mmdx_bone_motion_get_keys": (C.c_int32, [C.c_void_p, C.POINTER(BoneMotionKeys)]),
     "mmdx_skeleton_solve_morphed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),

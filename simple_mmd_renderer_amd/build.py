@@ -25,13 +25,14 @@ SOURCES = ["api.cpp", "bench_api.cpp", "kernels.hip", "kernels_fast.hip", "launc
            "pbounds_api.cpp", "pbounds_kernels.hip", "anim_api.cpp", "anim_kernels.hip",
            "row_blend_api.cpp", "row_blend_kernels.hip", "socket_api.cpp", "socket_kernels.hip",
            "events_api.cpp", "events_kernels.hip", "spring_api.cpp", "spring_kernels.hip", "aim_api.cpp", "aim_kernels.hip",
-           "reach_api.cpp", "reach_kernels.hip"]
+           "reach_api.cpp", "reach_kernels.hip", "ground_api.cpp", "ground_kernels.hip"]
 HEADERS = ["kernels.hpp", "plan.hpp", "error.hpp", "vmd.hpp", "rig.hpp", "rig_kernels.hpp", "pmx.hpp", "graph_pin.hpp", "api_internal.hpp", "host_runtime.hpp",
            "motion_clock.hpp", "motion_blend.hpp", "clip_source.hpp", "launch_shape.hpp", "lds_layout.hpp", "cull_shape.hpp", "solve_shape.hpp", "cull_kernels.hpp", "place_kernels.hpp", "place_math.hpp",
            "pbounds_kernels.hpp", "pbounds_math.hpp", "anim_kernels.hpp", "anim_math.hpp", "instance_list.hpp",
            "row_blend_kernels.hpp", "bone_mask.hpp", "root_math.hpp", "socket_kernels.hpp", "socket_math.hpp", "socket_table.hpp",
            "events_kernels.hpp", "events_math.hpp", "events_table.hpp", "spring_kernels.hpp", "spring_math.hpp", "spring_table.hpp",
            "aim_kernels.hpp", "aim_math.hpp", "aim_table.hpp", "reach_kernels.hpp", "reach_math.hpp", "reach_table.hpp",
+           "ground_kernels.hpp", "ground_math.hpp", "ground_table.hpp",
            "bone_morph_body.inl", "skeleton_ordered_body.inl", "ik_coop_body.inl",      # kernel bodies rig_kernels.hip includes twice (plain and select form)
            os.path.join("..", "..", "include", "mmdx.h"), os.path.join("..", "..", "include", "mmdx_bench.h")]
 ARCH = "gfx950"

@@ -913,6 +913,80 @@ class ReachSet:
         self.close()
 
 
+class Ground:
+    """mmdx_ground_t: a regular height field in device memory.  place() puts every (listed) placement on it (only placements[i][1]
+    is written), after root motion and before DeformModel.place_palettes; targets() turns the feet's world positions (a
+    SocketSet.sockets output) into reach targets that keep each foot's animated height over the ground under that foot, one slab
+    [NI][4] per foot for that foot's ReachSet (keep_end_rotation), and writes a hip drop that the NEXT frame's place() reads.
+    include/mmdx.h states the arithmetic.
+
+    heights: [nz][nx] floats; origin = (x, z) of heights[0][0]; cell = (x, z) distance between samples."""
+
+    def __init__(self, heights, origin=(0.0, 0.0), cell=(1.0, 1.0)):
+        h = _c(heights, np.float32)
+        d = api.GroundDesc()
+        d.struct_size = C.sizeof(api.GroundDesc)
+        d.nz, d.nx = (h.shape if h.ndim == 2 else (0, 0))
+        d.origin_x, d.origin_z = origin
+        d.cell_x, d.cell_z = cell
+        d.heights = h.ctypes.data
+        self.h = C.c_void_p()
+        api.check(api.lib().mmdx_ground_create(C.byref(d), C.byref(self.h)))      # copies the heights
+
+    def info(self) -> dict:
+        i = api.GroundInfo(C.sizeof(api.GroundInfo))
+        api.check(api.lib().mmdx_ground_get_info(self.h, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in api.GroundInfo._fields_ if k not in ("struct_size", "reserved0")}
+
+    def place(self, model, placements_dev, n_instances: int, drop=None, y_offset: float = 0.0, select=None, flags: int = 0) -> None:
+        """mmdx_ground_place: device placements [NI][8] (a DeviceBuffer or a raw address) in place, asynchronous on the model's
+        stream and recordable; drop: a DeviceBuffer / raw device address [NI] or None."""
+        a = api.GroundPlaceArgs()
+        a.struct_size = C.sizeof(api.GroundPlaceArgs)
+        a.flags, a.n_instances, a.y_offset = flags, n_instances, y_offset
+        a.placements = getattr(placements_dev, "ptr", placements_dev)
+        a.drop = getattr(drop, "ptr", drop)
+        if select is not None:
+            a.select = C.pointer(select)
+        api.check(api.lib().mmdx_ground_place(self.h, model.h if model is not None else None, C.byref(a)))
+
+    def targets(self, model, placements_dev, points, out_targets, n_instances: int, n_feet: int, point_stride: int = 16,
+                slab_stride=None, out_drop=None, max_step: float = 1.0, max_drop: float = 1.0, select=None, flags: int = 0) -> None:
+        """mmdx_ground_targets: every operand a DeviceBuffer or a raw device address.  points: foot f of instance i at
+        f*slab_stride + i*point_stride floats (the defaults and the address of a sockets output + 48 bytes: its translations);
+        out_targets [NF][NI][4]; out_drop [NI] or None."""
+        a = api.GroundTargetsArgs()
+        a.struct_size = C.sizeof(api.GroundTargetsArgs)
+        a.flags, a.n_instances, a.n_feet = flags, n_instances, n_feet
+        a.placements = getattr(placements_dev, "ptr", placements_dev)
+        a.points = getattr(points, "ptr", points)
+        a.point_stride = point_stride
+        a.slab_stride = n_instances * point_stride if slab_stride is None else slab_stride
+        a.out_targets = getattr(out_targets, "ptr", out_targets)
+        a.out_drop = getattr(out_drop, "ptr", out_drop)
+        a.max_step, a.max_drop = max_step, max_drop
+        if select is not None:
+            a.select = C.pointer(select)
+        api.check(api.lib().mmdx_ground_targets(self.h, model.h if model is not None else None, C.byref(a)))
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            api.lib().mmdx_ground_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class PoseImage:
     def __init__(self, nv: int):
         self.coordinates = np.zeros((nv, 3), np.float32)

@@ -906,4 +906,57 @@ private:
     mmdx_reach_set_t set_ = nullptr;
 };
 
+// Ground (mmdx.h, mmdx_ground_place / mmdx_ground_targets): a regular height field lifts placements and the feet's reach targets on
+// the device.  A ground is created from a filled mmdx_ground_desc (the heights are copied).  Place runs AFTER root motion and BEFORE
+// the placement is used; Targets runs AFTER SocketSet::Sockets of the feet and BEFORE the feet's ReachSet::Reach, and its drop is
+// what the NEXT frame's Place reads.
+class Ground {
+public:
+    explicit Ground(mmdx_ground_desc desc) {
+        desc.struct_size = sizeof(desc);
+        check(mmdx_ground_create(&desc, &ground_));
+    }
+    ~Ground() { mmdx_ground_destroy(ground_); }
+    Ground(const Ground &) = delete;
+    Ground &operator=(const Ground &) = delete;
+
+    // placements[i][1] = (h(x, z) + y_offset) + drop[i] of every instance (select: of the listed ones), asynchronous on `model`'s
+    // stream.  device_placements [n][MMDX_POSE_FLOATS]; device_drop [n] or nullptr.
+    void Place(mmdx_model_t model, uint32_t n_instances, float *device_placements, const float *device_drop = nullptr, float y_offset = 0.0f,
+               const mmdx_instance_select *select = nullptr) {
+        mmdx_ground_place_args a{};
+        a.struct_size = sizeof(a);
+        a.n_instances = n_instances;
+        a.y_offset = y_offset;
+        a.placements = device_placements; a.drop = device_drop; a.select = select;
+        check(mmdx_ground_place(ground_, model, &a));
+    }
+    // Reach targets [n_feet][n][4] and the hip drop [n] (or nullptr) from the feet's world points: foot f of instance i at
+    // device_points + f*slab_stride + i*point_stride floats.  A SocketSet::Sockets output goes in as SocketSet::slab(...) + 12 with
+    // the default strides (16 and n*16).
+    void Targets(mmdx_model_t model, uint32_t n_instances, uint32_t n_feet, const float *device_placements, const float *device_points,
+                 float *device_out_targets, float *device_out_drop, float max_step, float max_drop, uint32_t point_stride = 16,
+                 uint32_t slab_stride = 0, const mmdx_instance_select *select = nullptr) {
+        mmdx_ground_targets_args a{};
+        a.struct_size = sizeof(a);
+        a.n_instances = n_instances; a.n_feet = n_feet;
+        a.placements = device_placements; a.points = device_points;
+        a.point_stride = point_stride;
+        a.slab_stride = slab_stride ? slab_stride : n_instances * point_stride;
+        a.out_targets = device_out_targets; a.out_drop = device_out_drop;
+        a.max_step = max_step; a.max_drop = max_drop; a.select = select;
+        check(mmdx_ground_targets(ground_, model, &a));
+    }
+    mmdx_ground_info Info() const {
+        mmdx_ground_info i{};
+        i.struct_size = sizeof(i);
+        check(mmdx_ground_get_info(ground_, &i));
+        return i;
+    }
+    mmdx_ground_t handle() const { return ground_; }
+
+private:
+    mmdx_ground_t ground_ = nullptr;
+};
+
 }  // namespace mmdx
